@@ -11,16 +11,23 @@ net fused").  Each rank owns one independent video stream (the path shards acros
 needs frame i-1's output), so N GPUs = N streams, weak scaling, no data-path collective; the only
 collective is the RCCL broadcast of the packed weight blob from rank 0 before the timed region.
 
-Launch:  python bench.py [--gpus 1] [--steps K] [--warmup W]
+Launch:  python bench.py [--gpus 1] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
                 --master-port P bench.py --gpus N --steps K --warmup W
 Rank 0 prints ONE JSON line.
 
 `value` follows the bench contract (K timed steps after W warm-up steps, inputs resident in HBM, barrier + synchronize on both
-sides, max over ranks).  The FILE -> PNG rate of the product CLI -- BASELINE.json's "end-to-end" -- is in the same line as
+sides, max over ranks).  A plain run does only that: set-up, warm-up, the timed steps (with the roofline of the dominant kernel
+from events inside them), the outputs of the last step if --dump-outputs is given, the line.  Everything else runs with --full:
+the other checker mode, precision and architectures (`extra`), the CPU baselines and the parity against the oracle, the HBM
+kernels' own timings (`roofline_hbm`), and the FILE -> PNG rate of the product CLI -- BASELINE.json's "end-to-end" -- as
 `end_to_end_fps` (top level) and the `e2e` block (bin/fav_stylize over RAM-backed files: decode, H2D, the same GPU work, D2H,
 write; at --gpus N through the product's own launcher `fav_stylize -streams ... -gpus N`), with a sustained leg (>= 3000 frames,
 shader clock sampled) and the host CPU milliseconds per frame.
+
+--dump-outputs DIR (rank 0): what the last timed step computed, as float32 .npy files -- png_bytes.npy (the bytes of the PNG file
+the step leaves in HBM), frame_rgb.npy ([3][H][W] stylised frame, the recurrent state, fav_stream_get_state) and mask.npy ([H][W]
+certainty mask the step used).  The inputs and weights are seeded, so the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -404,6 +411,18 @@ def hbm_kernel_block(dev):
     return res
 
 
+def dump_outputs(d, stream, png_out, png_n):
+    """what the last timed step computed, as float32 .npy files in `d` (about 25 MB at 1280x720): the bytes of its PNG file, the
+    stylised frame (the recurrent state) and the certainty mask it used"""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()                # every queue of the device: the encoder queue of --png-async and the side queues included
+    os.makedirs(d, exist_ok=True)
+    outs = {"png_bytes": png_out[:int(png_n.item())], "frame_rgb": stream.state(), "mask": stream.last_mask()}
+    for name, t in outs.items():
+        np.save(os.path.join(d, name + ".npy"), t.cpu().numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -425,7 +444,12 @@ def main():
                     "instead of on the compute queue in front of it (fav_stream_encode_png, the default: what bin/fav_stylize does)")
     ap.add_argument("--no-extra", action="store_true", help="skip the informational 4-argument-mode pass after the timed region "
                     "(used for the rocprofv3 runs, so that the per-kernel averages cover the timed configuration only)")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also the informational passes, the CPU baselines + parity, "
+                    "roofline_hbm and the file->PNG run (each still switched off by its --no-* option); without it only the headline runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_extra = args.no_cpu_baseline = args.no_e2e = True
 
     import numpy as np
     import torch
@@ -524,6 +548,8 @@ def main():
     net.profile_enable(False)
     prof = net.profile_read()
     dt = shard.max_over_ranks(dt, cdev)
+    if args.dump_outputs and rank == 0:                 # before anything else runs on the stream
+        dump_outputs(args.dump_outputs, stream, png_out, png_n)
 
     # not part of `value`: the same loop with the checker's 4-argument (image-structure) mode, which is what
     # makeOptFlow_deepflow.sh:59 runs in production; its masks are computed two frames ahead on the side queues
@@ -670,7 +696,7 @@ def main():
                       "resident in HBM; file->PNG rate of the product CLI (BASELINE.json's end-to-end) in `end_to_end_fps` / `e2e`, PSNR vs CPU ref in `parity`",
             "value": round(fps, 3), "unit": "frames/s",
             "value_note": "`value` = in-HBM rate of the whole per-frame hot path (contract: inputs resident when the timed region starts); "
-                          "the rate BASELINE.json's end-to-end wording means (files in -> PNG files out through bin/fav_stylize) is `end_to_end_fps`",
+                          "the rate BASELINE.json's end-to-end wording means (files in -> PNG files out through bin/fav_stylize) is `end_to_end_fps` (--full runs)",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "1280x720 fused on-GPU consistency check (%s) + min-filter + warp + assemble + transformer net "

@@ -6,7 +6,7 @@
 #   test[:<pytest -k expression>]    pytest -m gpu (whole suite, or a selection)
 #   testfile:<file>[:<k>]            one test file
 #   smoke                            __graft_entry__.smoke()
-#   bench[:<extra bench.py flags>]   the driver's default command line (+ flags, '+' for spaces)
+#   bench[:<extra bench.py flags>]   bench.py --full (+ flags, '+' for spaces)
 #   quick                            in-HBM rate only (no CPU baseline, no e2e, no extras); quick3: the 3-argument checker mode (--structure 0)
 #   prof                             rocprofv3 --kernel-trace --stats of the timed configuration (4-argument mode since round 6) -> <tag>_kernel_stats.csv
 #   prof4 / prof3                    the same with --structure 1 / --structure 0
@@ -43,7 +43,7 @@ for STEP in "$@"; do
     testfile) F=${A%%:*}; KX=""; [[ "$A" == *:* ]] && KX=${A#*:}
               timeout 3000 python -m pytest tests/$F -m gpu -x -q -s --timeout 900 ${KX:+-k "$KX"} 2>&1 | tee $O/test_${TAG}_${F%.py}.log | tail -25 ;;
     smoke)    timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tee $O/smoke_${TAG}.log | tail -3 ;;
-    bench)    timeout 1500 python bench.py $A > $O/bench_${TAG}.log 2> $O/bench_${TAG}.err; summ bench < $O/bench_${TAG}.log; tail -3 $O/bench_${TAG}.err ;;
+    bench)    timeout 1500 python bench.py --full $A > $O/bench_${TAG}.log 2> $O/bench_${TAG}.err; summ bench < $O/bench_${TAG}.log; tail -3 $O/bench_${TAG}.err ;;
     quick|quick3) X=""; [ $K = quick3 ] && X="--structure 0"
               for i in 1 2; do timeout 300 $QUICK $X $A 2>/dev/null | tee -a $O/${K}_${TAG}.log | summ $K; done ;;
     prof|prof4|prof3)

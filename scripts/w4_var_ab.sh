@@ -19,7 +19,7 @@ for rep in 1 2 3; do
 done
 for V in $VARS; do LAST=$V; done
 echo "--- whole-frame parity against the oracle, FAV_W4_VAR=$LAST (1280x720, 4-argument mode)"
-FAV_AMD_LIB=$D FAV_W4_VAR=$LAST timeout 600 python bench.py --steps 10 --warmup 2 --no-extra --no-e2e 2>/dev/null | line "FAV_W4_VAR=$LAST "
+FAV_AMD_LIB=$D FAV_W4_VAR=$LAST timeout 600 python bench.py --full --steps 10 --warmup 2 --no-extra --no-e2e 2>/dev/null | line "FAV_W4_VAR=$LAST "
 echo "--- in-kernel timelines (launch 25 of each instantiation: whole-unit launches)"
 for V in $VARS; do FAV_AMD_LIB=$D FAV_W4_VAR=$V FAV_WINO_DBG=25 timeout 300 $Q 2>&1 | grep WINO4DBG | sed "s/^/FAV_W4_VAR=$V : /"; done
 } 2>&1 | tee $O/w4_var_ab_${TAG}.log

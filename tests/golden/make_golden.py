@@ -5,6 +5,7 @@ restatement (the reference's Lua/Torch7 stack cannot run offline) -- it cross-ch
 is not a reference output.
 
     python tests/golden/make_golden.py
+    python tests/golden/make_golden.py --live      (only the stored reference-checker cases of tests/test_cpu_oracle.py)
     python tests/golden/make_golden.py --warp --out gpurun_out/golden      (ON THE GPU BOX: warp fixtures)
 
 The warp fixtures (warp_*.npz) are outputs of the reference's OWN warp kernel (stnbdhw/BilinearSamplerBDHW.cu:1-109 compiled for
@@ -39,6 +40,38 @@ def mask_fixture(name, h, w, kind, seed):
     m3, m4 = O.read_pnm(d + "/o3.pgm"), O.read_pnm(d + "/o4.pgm")
     np.savez_compressed(os.path.join(HERE, name), bw=bw, fw=fw, img=img, mask3=m3, mask4=m4)
     print(name, "reliable% 3-arg", (m3 == 255).mean() * 100, "4-arg", (m4 == 255).mean() * 100, "flips", int((m3 != m4).sum()))
+
+
+def _ref_mask(d, bw, fw, img=None):
+    O.write_flo(d + "/a.flo", bw); O.write_flo(d + "/b.flo", fw)
+    args = [O.REF_CHECKER, d + "/a.flo", d + "/b.flo", d + "/o.pgm"]
+    if img is not None:
+        O.write_pnm(d + "/i.ppm", img); args.append(d + "/i.ppm")
+    subprocess.check_call(args, stdout=subprocess.DEVNULL)
+    return O.read_pnm(d + "/o.pgm")
+
+
+def live_mask_fixtures():
+    """inputs + the reference checker's masks of tests/test_cpu_oracle.py's two reference-binary tests, for machines where
+    oracle/_ref/consistencyChecker cannot be built: mask_live_cases.npz (odd sizes, 3- and 4-argument), mask_extreme_flows_24x40.npz"""
+    d = tempfile.mkdtemp()
+    cases = {}
+    for k, (h, w) in enumerate([(33, 47), (72, 128), (2, 9)]):
+        bw = synth.random_flow(h, w, 50 + k, 2.0); fw = synth.random_flow(h, w, 60 + k, 2.0)
+        img = synth.random_frame(h, w, 70 + k)
+        cases.update({f"bw{k}": bw, f"fw{k}": fw, f"img{k}": img, f"mask3_{k}": _ref_mask(d, bw, fw), f"mask4_{k}": _ref_mask(d, bw, fw, img)})
+    np.savez_compressed(os.path.join(HERE, "mask_live_cases.npz"), **cases)
+    # |flow| >= 2^31, +-inf and NaN at seeded positions of the backward flow
+    h, w = 24, 40
+    bw = synth.random_flow(h, w, 7, 2.0); fw = synth.random_flow(h, w, 8, 2.0)
+    vals = [1e10, -1e10, np.inf, -np.inf, np.nan, 2147483648.0, 2147483520.0, -2147483904.0, 3e9]
+    rng = np.random.default_rng(2)
+    hit = []
+    for v in vals * 2:
+        y, x, c = int(rng.integers(0, h)), int(rng.integers(0, w)), int(rng.integers(0, 2))
+        bw[y, x, c] = np.float32(v); hit.append((y, x))
+    np.savez_compressed(os.path.join(HERE, "mask_extreme_flows_24x40.npz"), bw=bw, fw=fw, hit=np.array(hit, dtype=np.int32),
+                        mask3=_ref_mask(d, bw, fw))
 
 
 def net_fixture():
@@ -115,6 +148,9 @@ if __name__ == "__main__":
         sys.exit(0)
     O.build()
     assert os.path.exists(O.REF_CHECKER), "oracle/_ref/consistencyChecker missing (needs /root/reference)"
+    if "--live" in sys.argv:
+        live_mask_fixtures()
+        sys.exit(0)
     mask_fixture("mask_smooth_64x96.npz", 64, 96, "smooth", 100)
     mask_fixture("mask_rand_120x160.npz", 120, 160, "rand", 200)
     mask_fixture("mask_smooth_180x320.npz", 180, 320, "smooth", 300)

@@ -27,38 +27,39 @@ def test_oracle_mask_matches_reference_golden(oracle, golden_dir, name):
     assert (g["mask3"] != g["mask4"]).sum() > 0     # the structure term is exercised
 
 
-def test_oracle_mask_vs_live_reference_binary(oracle, tmp_path):
+def _reference_mask(oracle, tmp_path, stored, bw, fw, img=None):
+    """the reference consistencyChecker's mask of these inputs: the binary oracle/Makefile builds into oracle/_ref when the reference
+    tree was there at build time (and then it must still give the stored mask), else its output stored by tests/golden/make_golden.py"""
     if not os.path.exists(oracle.REF_CHECKER):
-        pytest.skip("oracle/_ref/consistencyChecker not built (reference tree absent)")
-    for seed, (h, w) in enumerate([(33, 47), (72, 128), (2, 9)]):
-        bw = synth.random_flow(h, w, 50 + seed, 2.0); fw = synth.random_flow(h, w, 60 + seed, 2.0)
-        img = synth.random_frame(h, w, 70 + seed)
-        a, b, i, o = (str(tmp_path / n) for n in ("a.flo", "b.flo", "i.ppm", "o.pgm"))
-        oracle.write_flo(a, bw); oracle.write_flo(b, fw); oracle.write_pnm(i, img)
-        subprocess.check_call([oracle.REF_CHECKER, a, b, o], stdout=subprocess.DEVNULL)
-        assert np.array_equal(oracle.read_pnm(o), oracle.consistency(bw, fw))
-        subprocess.check_call([oracle.REF_CHECKER, a, b, o, i], stdout=subprocess.DEVNULL)
-        assert np.array_equal(oracle.read_pnm(o), oracle.consistency(bw, fw, img))
+        return stored
+    a, b, i, o = (str(tmp_path / n) for n in ("a.flo", "b.flo", "i.ppm", "o.pgm"))
+    oracle.write_flo(a, bw); oracle.write_flo(b, fw)
+    args = [oracle.REF_CHECKER, a, b, o]
+    if img is not None:
+        oracle.write_pnm(i, img); args.append(i)
+    subprocess.check_call(args, stdout=subprocess.DEVNULL)
+    live = oracle.read_pnm(o)
+    assert np.array_equal(live, stored), "the reference binary no longer gives the stored mask"
+    return live
 
 
-def test_oracle_mask_extreme_flows_vs_live_reference_binary(oracle, tmp_path):
+def test_oracle_mask_vs_live_reference_binary(oracle, golden_dir, tmp_path):
+    """odd sizes (33x47, 72x128, 2x9), random flows, both modes (tests/golden/mask_live_cases.npz: inputs + the reference's masks)"""
+    g = np.load(os.path.join(golden_dir, "mask_live_cases.npz"))
+    for k in range(3):
+        bw, fw, img = g[f"bw{k}"], g[f"fw{k}"], g[f"img{k}"]
+        assert np.array_equal(_reference_mask(oracle, tmp_path, g[f"mask3_{k}"], bw, fw), oracle.consistency(bw, fw))
+        assert np.array_equal(_reference_mask(oracle, tmp_path, g[f"mask4_{k}"], bw, fw, img), oracle.consistency(bw, fw, img))
+
+
+def test_oracle_mask_extreme_flows_vs_live_reference_binary(oracle, golden_dir, tmp_path):
     """|flow| >= 2^31, +-inf and NaN (the Middlebury 'unknown flow' marker is 1e10): the reference's (int)floor() gives INT_MIN
     on x86 and the pixel is written 0.  Pins the oracle -- and through it the GPU kernel's float-domain range test
-    (tests/test_gpu_parity.py::test_consistency_extreme_flows) -- on the compiled reference for those inputs."""
-    if not os.path.exists(oracle.REF_CHECKER):
-        pytest.skip("oracle/_ref/consistencyChecker not built (reference tree absent)")
-    h, w = 24, 40
-    bw = synth.random_flow(h, w, 7, 2.0); fw = synth.random_flow(h, w, 8, 2.0)
-    vals = [1e10, -1e10, np.inf, -np.inf, np.nan, 2147483648.0, 2147483520.0, -2147483904.0, 3e9]
-    rng = np.random.default_rng(2)
-    hit = []
-    for v in vals * 2:
-        y, x, c = int(rng.integers(0, h)), int(rng.integers(0, w)), int(rng.integers(0, 2))
-        bw[y, x, c] = np.float32(v); hit.append((y, x))
-    a, b, o = (str(tmp_path / n) for n in ("a.flo", "b.flo", "o.pgm"))
-    oracle.write_flo(a, bw); oracle.write_flo(b, fw)
-    subprocess.check_call([oracle.REF_CHECKER, a, b, o], stdout=subprocess.DEVNULL)
-    ref = oracle.read_pnm(o)
+    (tests/test_gpu_parity.py::test_consistency_extreme_flows) -- on the compiled reference for those inputs
+    (tests/golden/mask_extreme_flows_24x40.npz: inputs, the pixels hit, the reference's mask)."""
+    g = np.load(os.path.join(golden_dir, "mask_extreme_flows_24x40.npz"))
+    bw, fw, hit = g["bw"], g["fw"], [tuple(p) for p in g["hit"]]
+    ref = _reference_mask(oracle, tmp_path, g["mask3"], bw, fw)
     with np.errstate(all="ignore"):
         assert np.array_equal(ref, oracle.consistency(bw, fw))
     assert all(ref[y, x] == 0 for y, x in hit)

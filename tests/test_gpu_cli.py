@@ -68,8 +68,10 @@ def test_consistency_checker_resident_helper(oracle, favlib, tmp_path):
     first call leaves a resident helper behind (own session, socket in a 0700 directory), later calls hand it their argv: same bytes,
     same exit codes, relative paths resolved against the CALLER's directory, sizes may change between calls; FAV_CC_DAEMON=0 computes
     in the calling process as before; SIGTERM (or FAV_CC_IDLE_S seconds without a request) ends it and removes the socket."""
-    import time
-    run = tmp_path / "run"; run.mkdir(mode=0o700)
+    import pathlib, shutil, tempfile, time
+    # the helper's socket path has to fit in sun_path (107 characters), which a path under pytest's tmp_path need not: a short runtime
+    # directory of its own (mkdtemp creates it 0700), removed at the end
+    run = pathlib.Path(tempfile.mkdtemp(prefix="fav-cc-", dir="/tmp"))
     env = dict(os.environ, XDG_RUNTIME_DIR=str(run), FAV_CC_IDLE_S="60")
     exe = os.path.join(BIN, "consistencyChecker")
     cases = []
@@ -125,8 +127,10 @@ def test_consistency_checker_resident_helper(oracle, favlib, tmp_path):
         assert not list(d.glob("*.tmp*"))                                   # per-process temporary names are renamed or removed
     finally:
         pid = _stop_helper(str(run))
+        socks = list((run / "fav-cc").glob("gpu0*.sock"))
+        shutil.rmtree(run, ignore_errors=True)
     assert pid is not None
-    assert not list((run / "fav-cc").glob("gpu0*.sock"))                # SIGTERM: the helper removes its socket
+    assert not socks                                                    # SIGTERM: the helper removes its socket
 
 
 def test_consistency_checker_binary(oracle, favlib, tmp_path, monkeypatch):
