@@ -224,6 +224,17 @@ int launch_conv3_halo(const ConvLaunch& p, int* counts, hipStream_t st);
 bool conv3s2_eligible(int cin_pitch, int coutp, int k, int stride, int stages, int ups);
 int conv3s2_tiles(int OH, int OW);
 int launch_conv3s2(const ConvLaunch& p, int* counts, hipStream_t st);
+// One enumerator per launch wrapper above.  fav_net picks one per layer (net.cpp: select_conv) and reports it through
+// fav_net_profile_read_host as a kernel id -- a contract: bench.py, scripts/wide_bench.py and the GPU tests read the ids
+// (N = the padded output channel count COUTp):
+//   CK_GENERIC  launch_conv          32 | 64 | 128 (its N tile)     CK_S2W     launch_conv3s2w     700 + N
+//   CK_FOLD     launch_conv_fold     1                              CK_UP2     launch_conv3_up2    500 + N
+//   CK_C8       launch_conv_c8       8                              CK_WINO    launch_conv3_wino   400 + N  (+ 1: a pending residual join as its input)
+//   CK_C8D      launch_conv_c8d      7                              CK_WINO4   launch_conv3_wino4  600 + N  (+ 1: likewise)
+//   CK_FIRST1D  launch_conv_first    6                              CK_HALO3   launch_conv3_halo   300 + N
+//   CK_FIRST2D  launch_conv_first2d  16                             CK_S2HALO  launch_conv3s2      200 + N
+enum ConvKernel { CK_GENERIC, CK_FOLD, CK_C8, CK_C8D, CK_FIRST1D, CK_FIRST2D, CK_S2W, CK_UP2, CK_WINO, CK_WINO4, CK_HALO3, CK_S2HALO };
+constexpr int CONV_KERNELS = CK_S2HALO + 1;      // (the last enumerator)
 // counts: per-partial pixel counts or null (then block b holds min(block_pixels, M - b*block_pixels) pixels)
 int launch_in_finalize(const float* partials, const int* counts, int mblocks, int M, int block_pixels, int C, int Cpitch,
                        const float* gamma, const float* beta, float eps,

@@ -35,7 +35,11 @@ using namespace fav;
 namespace {
 
 struct DevBuf { void* p = nullptr; size_t bytes = 0; };
-struct DevConvW { float* wgt = nullptr; float* bias = nullptr; float* wfold = nullptr; float* wc8d = nullptr; float* wwino = nullptr; float* wwino4 = nullptr; float* wup2 = nullptr; float* ws2w = nullptr; float* wfirst = nullptr; float* wfirst2d = nullptr; unsigned short* wgt16 = nullptr; int cinp = 0, coutp = 0, kpad = 0; };
+struct DevConvW {
+    float* wgt = nullptr; float* bias = nullptr; unsigned short* wgt16 = nullptr;      // repack_weights() form: the generic, c8 and halo-resident kernels
+    float* packed[CONV_KERNELS] = {};      // by ConvKernel: the form that kernel's own packing gives (upload_layers); null: that kernel cannot be selected
+    int cinp = 0, coutp = 0, kpad = 0;
+};
 struct DevIN { float* gamma = nullptr; float* beta = nullptr; float* scale = nullptr; float* shift = nullptr;
                long long* acc = nullptr; size_t acc_bytes = 0; };      // accumulator form of the statistics (fav_internal.h, Affine::acc1): [2 parities][stat_acc_words(C)], zero between frames
 
@@ -90,13 +94,115 @@ void repack_weights(const Layer& L, int cinp, int coutp, int kpad, std::vector<f
 }
 
 // Tuning / ablation switches (not part of the product contract): read ONCE per process, never on the launch path.
-struct Tuning { bool no_fold, no_c8, no_h3, no_s2, no_c8d, no_wino, no_up2, no_first, no_s2w, wino_f2, no_acc_stats; };
-const Tuning& tuning()
+struct Tuning {
+    // FAV_NO_<kernel>: select_conv() passes that kernel over
+    bool no_fold = diag_env("FAV_NO_FOLD") != nullptr;
+    bool no_c8 = diag_env("FAV_NO_C8") != nullptr;
+    bool no_c8d = diag_env("FAV_NO_C8D") != nullptr;
+    bool no_first = diag_env("FAV_NO_FIRST") != nullptr;
+    bool no_s2w = diag_env("FAV_NO_S2W") != nullptr;
+    bool no_up2 = diag_env("FAV_NO_UP2") != nullptr;
+    bool no_wino = diag_env("FAV_NO_WINO") != nullptr;
+    bool no_h3 = diag_env("FAV_NO_H3") != nullptr;
+    bool no_s2 = diag_env("FAV_NO_S2") != nullptr;
+    bool first_1d = diag_env("FAV_FIRST_1D") != nullptr;              // the 1-D form of the first layer
+    bool wino_f2 = diag_env("FAV_WINO_F2") != nullptr;                // the residual convolutions as F(2x2,3x3) (rounds 2-3) instead of F(4x4,3x3)
+    bool no_acc_stats = diag_env("FAV_NO_ACC_STATS") != nullptr;      // every InstanceNorm through partials + an in_finalize launch (rounds 1-4)
+    bool no_lazy_join = diag_env("FAV_NO_LAZY_JOIN") != nullptr;      // no residual join stays pending | with the F(4x4) kernels too (run(), L_RES)
+    bool lazy_join = diag_env("FAV_LAZY_JOIN") != nullptr;
+    int side_sk = diag_env("FAV_SIDE_SK") ? atoi(diag_env("FAV_SIDE_SK")) : 0;      // 1: stream-K stays next to the side queues, 2: for the stride-2 halo kernel only
+};
+const Tuning& tuning() { static const Tuning t; return t; }
+
+// Which kernel runs convolution L (weights d) on an input with `stages` pending normalisations and a pending x`2^ups` upsampling -- the
+// whole priority list, first match wins.  A kernel whose weights are not packed (d.packed[k] null: upload_layers) is never chosen.
+// is_final: the network's last layer (Tanh epilogue) on an IH x IW logical input.  Also asked about LATER layers (acc_stats_ok,
+// res_block_is_winograd), so it depends on nothing but its arguments.
+ConvKernel select_conv(const Layer& L, const DevConvW& d, int stages, int ups, int precision, bool is_final, int IH, int IW, const Tuning& t)
 {
-    static const Tuning t = {diag_env("FAV_NO_FOLD") != nullptr, diag_env("FAV_NO_C8") != nullptr, diag_env("FAV_NO_H3") != nullptr, diag_env("FAV_NO_S2") != nullptr, diag_env("FAV_NO_C8D") != nullptr, diag_env("FAV_NO_WINO") != nullptr, diag_env("FAV_NO_UP2") != nullptr, diag_env("FAV_NO_FIRST") != nullptr, diag_env("FAV_NO_S2W") != nullptr,
-                             diag_env("FAV_WINO_F2") != nullptr,       // FAV_WINO_F2: the residual convolutions as F(2x2,3x3) (rounds 2-3) instead of F(4x4,3x3)
-                             diag_env("FAV_NO_ACC_STATS") != nullptr}; // FAV_NO_ACC_STATS: every InstanceNorm through partials + an in_finalize launch (rounds 1-4)
-    return t;
+    // only the generic kernel and the row-folded one (few output channels: kx taps folded into N) have the Tanh epilogue
+    if (is_final) return !t.no_fold && d.packed[CK_FOLD] && conv_fold_launchable(d.cinp, L.k, L.pad, ups, IH, IW) ? CK_FOLD : CK_GENERIC;
+    // a transposed convolution runs on the generic kernel, over the zero-stuffed input
+    if (L.transposed) return CK_GENERIC;
+    // The first layer (9x9 on the 8-channel input pixel) by minimal filtering, ahead of its direct forms below: 2-D F(2x2,3x3) over its
+    // nine 3x3 blocks, or 1-D F(2,3) along x on request (FAV_FIRST_1D).  FAV_NO_C8D takes both away together with the dense-K direct
+    // form.  A layer that the c8 kernel does not take (more than 32 filters, FAV_NO_C8) has the 2-D form only, in groups of 32 filters
+    const bool c8 = !t.no_c8 && conv_c8_eligible(d.cinp, d.coutp, L.k, L.stride, stages, ups);
+    if (!t.no_first && !t.no_c8d) {
+        if (c8 && d.packed[CK_FIRST1D] && conv_c8d_eligible(d.cinp, L.cin, d.coutp, L.k, L.stride, stages, ups))
+            return d.packed[CK_FIRST2D] && !t.first_1d ? CK_FIRST2D : CK_FIRST1D;
+        if (!c8 && d.packed[CK_FIRST2D] && conv_first2d_eligible(d.cinp, L.cin, d.coutp, L.k, L.stride, stages, ups)) return CK_FIRST2D;
+    }
+    // 3x3 stride 2 (d64 / d128): the fragment-order kernel, ahead of the stride-2 halo kernel and the generic one that ran them before it
+    if (d.packed[CK_S2W] && !t.no_s2w && conv3s2w_eligible(d.cinp, L.cout, d.coutp, L.k, L.stride, L.pad, stages, ups)) return CK_S2W;
+    // 3x3 on a x2-upsampled input (fp32 only): four 2x2 convolutions on the physical pixels instead of a 3x3 on every logical one
+    if (d.packed[CK_UP2] && precision == 0 && !t.no_up2 &&
+        conv3_up2_eligible(d.cinp, L.cout, d.coutp, L.k, L.stride, L.pad, stages, ups)) return CK_UP2;
+    // unpadded 3x3 stride 1 (the residual blocks; fp32 only): Winograd F(4x4) where it is packed (not under FAV_WINO_F2), else F(2x2)
+    if (precision == 0 && !t.no_wino) {
+        if (d.packed[CK_WINO4] && conv3_wino4_eligible(d.cinp, L.cout, d.coutp, L.k, L.stride, L.pad, stages, ups)) return CK_WINO4;
+        if (d.packed[CK_WINO] && conv3_wino_eligible(d.cinp, L.cout, d.coutp, L.k, L.stride, L.pad, stages, ups)) return CK_WINO;
+    }
+    // the first layer's direct forms: dense K for its 7 (3) real input channels, else all 8
+    if (c8) return !t.no_c8d && d.packed[CK_C8D] && conv_c8d_eligible(d.cinp, L.cin, d.coutp, L.k, L.stride, stages, ups) ? CK_C8D : CK_C8;
+    // the halo-resident implicit GEMMs take what is left of the 3x3 layers (bf16 fast mode, padded layers, FAV_NO_WINO / _UP2 / _S2W)
+    if (!t.no_h3 && conv3_halo_eligible(d.cinp, d.coutp, L.k, L.stride)) return CK_HALO3;
+    if (!t.no_s2 && conv3s2_eligible(d.cinp, d.coutp, L.k, L.stride, stages, ups)) return CK_S2HALO;
+    return CK_GENERIC;
+}
+
+// What run() and timed_conv() need to know about each kernel: how many partial-statistics tiles it writes for an OH x OW output, whether
+// it writes their pixel counts (else every tile but the last holds CONV_BM pixels), and its profile id (fav_internal.h, ConvKernel)
+struct ConvFacts { int tiles; bool counts; int id; };
+ConvFacts conv_facts(ConvKernel k, int OH, int OW, int coutp, int precision, bool join)
+{
+    switch (k) {
+    case CK_GENERIC: return {conv_mblocks(OH, OW), false, coutp % 128 == 0 ? 128 : (coutp % 64 == 0 ? 64 : 32)};
+    case CK_FOLD:    return {0, false, 1};      // (the last layer: nothing normalises its output)
+    case CK_C8:      return {conv_c8_tiles(OH, OW), true, 8};
+    case CK_C8D:     return {conv_c8_tiles(OH, OW), true, 7};
+    case CK_FIRST1D: return {conv_first_tiles(OH, OW), true, 6};
+    case CK_FIRST2D: return {conv_first2d_tiles(OH, OW), true, 16};
+    case CK_S2W:     return {conv3s2w_tiles(OH, OW, coutp), true, 700 + coutp};
+    case CK_UP2:     return {conv3_up2_tiles(OH, OW), true, 500 + coutp};
+    case CK_WINO:    return {conv3_wino_tiles(OH, OW), true, 400 + coutp + (join ? 1 : 0)};
+    case CK_WINO4:   return {conv3_wino4_tiles(OH, OW), true, 600 + coutp + (join ? 1 : 0)};
+    case CK_HALO3:   return {conv3_halo_tiles(OH, OW, precision == 0), true, 300 + coutp};
+    case CK_S2HALO:  return {conv3s2_tiles(OH, OW), true, 200 + coutp};
+    }
+    return {0, false, 0};
+}
+
+// The launch of kernel k with its packed weights.  cs: the full descriptor; cg: the same with no_sk set while look-ahead masks are in
+// flight (timed_conv) -- for the kernels whose blocks hand tiles over to each other
+int launch_selected(ConvKernel k, const ConvLaunch& cs, const ConvLaunch& cg, const DevConvW& d, int cin_real, int* counts, hipStream_t st)
+{
+    const float* w = d.packed[k];
+    switch (k) {
+    case CK_GENERIC: return launch_conv(cg, st);
+    case CK_FOLD:    return launch_conv_fold(cs, w, st);
+    case CK_C8:      return launch_conv_c8(cs, counts, st);
+    case CK_C8D:     return launch_conv_c8d(cs, cin_real, w, counts, st);
+    case CK_FIRST1D: return launch_conv_first(cs, cin_real, w, counts, st);
+    case CK_FIRST2D: return launch_conv_first2d(cs, cin_real, w, counts, st);
+    case CK_S2W:     return launch_conv3s2w(cs, w, counts, st);
+    case CK_UP2:     return launch_conv3_up2(cs, w, counts, st);
+    case CK_WINO:    return launch_conv3_wino(cs, w, counts, st);
+    case CK_WINO4:   return launch_conv3_wino4(cs, w, counts, st);
+    case CK_HALO3:   return launch_conv3_halo(cg, counts, st);
+    case CK_S2HALO:  return launch_conv3s2(tuning().side_sk == 2 ? cs : cg, counts, st);
+    }
+    set_error("internal: unknown convolution kernel %d", (int)k); return FAV_EINVAL;
+}
+
+// one more pending per-channel stage t(x) = relu?(x*scale+shift) on a tensor that carries at most one
+int append_stage(Affine& a, const float* scale, const float* shift, int relu)
+{
+    if (a.stages >= 2) { set_error("network: more than two stacked normalisations on one tensor are unsupported"); return FAV_EUNSUPPORTED; }
+    if (a.stages == 0) { a.scale1 = scale; a.shift1 = shift; a.relu1 = relu; }
+    else { a.scale2 = scale; a.shift2 = shift; a.relu2 = relu; }
+    ++a.stages;
+    return FAV_OK;
 }
 
 bool only_tail(const std::vector<Layer>& ls, size_t from, bool& has_tanh, float& mul);
@@ -200,7 +306,6 @@ struct fav_net {
     bool acc_dirty = false;         // a forward failed half-way (or the precision changed): every accumulator is zeroed before the next forward
     bool branch_tail_acc_ok = false; // set by L_RES around its branch: the join is a plain res_add launch, which takes the last InstanceNorm as accumulators
     int reserve_cus = 0;            // set when a stream uses the look-ahead side queues (they are CU-masked to this many CUs)
-    bool use_c8 = false, use_h3 = false, use_s2 = false, use_wino = false, use_wino4 = false, use_up2 = false, use_first = false, use_first2d = false, use_s2w = false; int* c8_counts = nullptr;                                    // first-layer kernel selection for the next launch
     // activation arena: buffers are created on the first forward for a given (H, W) and reused after
     int curH = 0, curW = 0;
     std::vector<DevBuf> bufs;
@@ -219,7 +324,7 @@ struct fav_net {
     {
         (void)hipSetDevice(device);
         (void)hipFree(stage);
-        for (auto& c : convs) { (void)hipFree(c.wgt); (void)hipFree(c.bias); (void)hipFree(c.wfold); (void)hipFree(c.wc8d); (void)hipFree(c.wwino); (void)hipFree(c.wwino4); (void)hipFree(c.wup2); (void)hipFree(c.ws2w); (void)hipFree(c.wfirst); (void)hipFree(c.wfirst2d); (void)hipFree(c.wgt16); }
+        for (auto& c : convs) { (void)hipFree(c.wgt); (void)hipFree(c.bias); (void)hipFree(c.wgt16); for (float* p : c.packed) (void)hipFree(p); }
         for (auto& i : ins) { (void)hipFree(i.gamma); (void)hipFree(i.beta); (void)hipFree(i.scale); (void)hipFree(i.shift); (void)hipFree(i.acc); }
         for (void* sp : slabs) (void)hipFree(sp);
         (void)hipFree(ones); (void)hipFree(zeros); (void)hipFree(sk_ws); (void)hipFree(sk_flags); (void)hipFree(ks_ws); (void)hipFree(ks_cnt); if (sk_err_host) (void)hipHostFree(sk_err_host);
@@ -227,7 +332,7 @@ struct fav_net {
     int upload_layers(std::vector<Layer>& ls, int& chan_pitch, int& maxc);
     int upload();
     int alloc(size_t bytes, float** out);
-    int timed_conv(const ConvLaunch& c, int conv_index, const Layer& L);
+    int timed_conv(const ConvLaunch& c, int conv_index, const Layer& L, ConvKernel kernel, int* counts);
     int run(std::vector<Layer>& ls, Act& cur, bool top, float* out_planar, float* out_raw);
     bool res_block_is_winograd(const Layer& R, size_t first_conv) const;
     bool acc_stats_ok(const std::vector<Layer>& ls, size_t li) const;
@@ -270,27 +375,27 @@ int fav_net::upload_layers(std::vector<Layer>& ls, int& chan_pitch, int& maxc)
             if (!L.transposed && conv_c8d_eligible(d.cinp, L.cin, d.coutp, L.k, L.stride, 0, 0)) {      // first layer: dense-K pairing
                 std::vector<float> wd;
                 conv_c8d_pack(L.w.data(), L.cin, L.cout, wd);
-                rc = dev_upload(wd, 0, &d.wc8d); if (rc) return rc;
+                rc = dev_upload(wd, 0, &d.packed[CK_C8D]); if (rc) return rc;
                 std::vector<float> wf1;                                            // the same layer with F(2,3) along x (kernels_first.hip)
                 conv_first_pack(L.w.data(), L.cin, L.cout, wf1);
-                rc = dev_upload(wf1, 0, &d.wfirst); if (rc) return rc;
+                rc = dev_upload(wf1, 0, &d.packed[CK_FIRST1D]); if (rc) return rc;
                 std::vector<float> wf2;                                            // ... and with F(2x2,3x3) over its nine 3x3 blocks
                 conv_first2d_pack(L.w.data(), L.cin, L.cout, wf2);
-                rc = dev_upload(wf2, 0, &d.wfirst2d); if (rc) return rc;
+                rc = dev_upload(wf2, 0, &d.packed[CK_FIRST2D]); if (rc) return rc;
             } else if (!L.transposed && conv_first2d_eligible(d.cinp, L.cin, d.coutp, L.k, L.stride, 0, 0)) {      // first layer with more than 32 filters: groups of 32 on the 2-D form
                 std::vector<float> wf2;
                 conv_first2d_pack_groups(L.w.data(), L.cin, L.cout, d.coutp, wf2);
-                rc = dev_upload(wf2, 0, &d.wfirst2d); if (rc) return rc;
+                rc = dev_upload(wf2, 0, &d.packed[CK_FIRST2D]); if (rc) return rc;
             }
             if (!L.transposed && L.cin == d.cinp && conv3_wino_eligible(d.cinp, L.cout, d.coutp, L.k, L.stride, L.pad, 0, 0)) {      // residual 3x3: Winograd
                 std::vector<float> ww;
                 conv_wino_pack(L.w.data(), L.cin, L.cout, ww);
-                rc = dev_upload(ww, 0, &d.wwino); if (rc) return rc;
+                rc = dev_upload(ww, 0, &d.packed[CK_WINO]); if (rc) return rc;
             }
             if (!L.transposed && L.cin == d.cinp && !tuning().wino_f2 && conv3_wino4_eligible(d.cinp, L.cout, d.coutp, L.k, L.stride, L.pad, 0, 0)) {      // ... as F(4x4,3x3) (round 4), any number of 128-filter groups (round 5)
                 std::vector<float> w4;
                 conv_wino4_pack_groups(L.w.data(), L.cin, L.cout, w4);
-                rc = dev_upload(w4, 0, &d.wwino4); if (rc) return rc;
+                rc = dev_upload(w4, 0, &d.packed[CK_WINO4]); if (rc) return rc;
             }
             if (!L.transposed && L.cin == d.cinp && conv3_up2_eligible(d.cinp, L.cout, d.coutp, L.k, L.stride, L.pad, 1, 1)) {      // 3x3 after a x2 upsampling: merged 2x2 taps
                 std::vector<float> wu, wu9;
@@ -299,12 +404,12 @@ int fav_net::upload_layers(std::vector<Layer>& ls, int& chan_pitch, int& maxc)
                     conv_up2w_pack(L.w.data(), L.cin, wu9);                        // the nine-position form follows the phase-merged one
                     wu.insert(wu.end(), wu9.begin(), wu9.end());
                 } else conv_up2w_pack_groups(L.w.data(), L.cin, L.cout, wu);      // more than 64 filters: the nine-position form only, one block per group of 64
-                rc = dev_upload(wu, 0, &d.wup2); if (rc) return rc;
+                rc = dev_upload(wu, 0, &d.packed[CK_UP2]); if (rc) return rc;
             }
             if (!L.transposed && L.cin == d.cinp && conv3s2w_eligible(d.cinp, L.cout, d.coutp, L.k, L.stride, L.pad, 1, 0)) {      // 3x3 stride 2: fragment order
                 std::vector<float> ws;
                 conv_s2w_pack_groups(L.w.data(), L.cin, L.cout, ws);
-                rc = dev_upload(ws, 0, &d.ws2w); if (rc) return rc;
+                rc = dev_upload(ws, 0, &d.packed[CK_S2W]); if (rc) return rc;
             }
             if (!L.transposed && conv_fold_eligible(d.cinp, L.cout, L.k, L.stride)) {
                 // [ky][n = c*k + kx][ci] for the row-folded last-layer kernel
@@ -324,7 +429,7 @@ int fav_net::upload_layers(std::vector<Layer>& ls, int& chan_pitch, int& maxc)
                                 const double a = m >= 1 ? (double)wr[(size_t)(m - 1) * L.k] : 0.0, b = m < L.k ? (double)wr[(size_t)m * L.k] : 0.0;
                                 wf[((size_t)(L.k + m) * 32 + co * L.k + kx) * d.cinp + ci] = (float)(a + b);
                             }
-                rc = dev_upload(wf, 0, &d.wfold); if (rc) return rc;
+                rc = dev_upload(wf, 0, &d.packed[CK_FOLD]); if (rc) return rc;
             }
             chan_pitch = L.cout;
             maxc = std::max(maxc, std::max(d.coutp, d.cinp));
@@ -421,11 +526,9 @@ int fav_net::alloc(size_t bytes, float** out)
     return FAV_OK;
 }
 
-int fav_net::timed_conv(const ConvLaunch& c, int conv_index, const Layer& L)
+int fav_net::timed_conv(const ConvLaunch& c, int conv_index, const Layer& L, ConvKernel kernel, int* counts)
 {
-    const float* wfold = (c.final_mode && !tuning().no_fold && conv_fold_launchable(c.CIN, c.KH, c.pad, c.ups, c.IH, c.IW)) ? convs[conv_index].wfold : nullptr;
-    const float* c8d_w = (use_c8 && !tuning().no_c8d && conv_c8d_eligible(c.CIN, L.cin, c.COUTp, L.k, c.stride, c.pre.stages, c.ups)) ? convs[conv_index].wc8d : nullptr;
-    if (c.pre.acc1 != nullptr && !(use_wino && use_wino4)) { set_error("internal: accumulator-form InstanceNorm in front of a kernel that cannot take it"); return FAV_EINVAL; }
+    if (c.pre.acc1 != nullptr && kernel != CK_WINO4) { set_error("internal: accumulator-form InstanceNorm in front of a kernel that cannot take it"); return FAV_EINVAL; }
     ConvLaunch cs = c;
     cs.reserve_cus = reserve_cus;
     cs.no_sk = shared_device ? 1 : 0;
@@ -438,9 +541,8 @@ int fav_net::timed_conv(const ConvLaunch& c, int conv_index, const Layer& L)
     // profiles/r02p_4arg_kernel_stats.csv).  Data-parallel grids do not wait for anybody.  The halo-resident 3x3 kernel (bf16 fast
     // mode, FAV_NO_WINO) hands tiles over the same way and takes the same descriptor.
     ConvLaunch cg = cs;
-    static const int side_sk_mode = diag_env("FAV_SIDE_SK") ? atoi(diag_env("FAV_SIDE_SK")) : 0;      // (tuning: read once) 1: keep stream-K next to the side queues, 2: for the stride-2 halo kernel only
-    if (reserve_cus > 0 && side_sk_mode != 1) cg.no_sk = 1;
-    auto go = [&]() { return use_first ? (use_first2d ? launch_conv_first2d(cs, L.cin, convs[conv_index].wfirst2d, c8_counts, st) : launch_conv_first(cs, L.cin, convs[conv_index].wfirst, c8_counts, st)) : use_s2w ? launch_conv3s2w(cs, convs[conv_index].ws2w, c8_counts, st) : use_up2 ? launch_conv3_up2(cs, convs[conv_index].wup2, c8_counts, st) : use_wino ? (use_wino4 ? launch_conv3_wino4(cs, convs[conv_index].wwino4, c8_counts, st) : launch_conv3_wino(cs, convs[conv_index].wwino, c8_counts, st)) : wfold ? launch_conv_fold(cs, wfold, st) : (use_c8 ? (c8d_w ? launch_conv_c8d(cs, L.cin, c8d_w, c8_counts, st) : launch_conv_c8(cs, c8_counts, st)) : (use_h3 ? launch_conv3_halo(cg, c8_counts, st) : (use_s2 ? launch_conv3s2(side_sk_mode == 2 ? cs : cg, c8_counts, st) : launch_conv(cg, st)))); };
+    if (reserve_cus > 0 && tuning().side_sk != 1) cg.no_sk = 1;
+    auto go = [&]() { return launch_selected(kernel, cs, cg, convs[conv_index], L.cin, counts, st); };
     char tag[96] = "";
     if (TraceRange::enabled()) snprintf(tag, sizeof tag, "fav:conv%d k%d s%d %d->%d %dx%d", conv_index, L.k, L.stride, L.cin, L.cout, c.OW, c.OH);
     TraceRange tr(tag);
@@ -455,8 +557,7 @@ int fav_net::timed_conv(const ConvLaunch& c, int conv_index, const Layer& L)
     prof_pending.push_back(r);
     if ((int)prof_ms.size() <= conv_index) { prof_ms.resize(conv_index + 1, 0.0); prof_macs.resize(conv_index + 1, 0.0); prof_n.resize(conv_index + 1, 0); prof_tile.resize(conv_index + 1, 0); }
     prof_macs[conv_index] = (double)c.OH * c.OW * L.cout * L.cin * L.k * L.k;      // useful MACs only
-    // kernel id: 16 first layer with F(2x2,3x3) over its nine 3x3 blocks, 6 first layer with F(2,3) along x, 500+N 3x3 on a x2-upsampled input (merged taps), 700+N stride-2 3x3 (fragment-order weights), 400+N Winograd 3x3 (+1: with a pending residual join as its input), 1 row-folded last layer, 8 first layer, 300+N halo 3x3 (N = 64|128), 200+N stride-2 halo 3x3, else the generic kernel's N tile
-    prof_tile[conv_index] = use_first ? (use_first2d ? 16 : 6) : use_s2w ? 700 + c.COUTp : use_up2 ? 500 + c.COUTp : use_wino ? (use_wino4 ? 600 : 400) + c.COUTp + (c.join_skip ? 1 : 0) : wfold ? 1 : (use_c8 ? (c8d_w ? 7 : 8) : (use_h3 ? 300 + c.COUTp : (use_s2 ? 200 + c.COUTp : (c.COUTp % 128 == 0 ? 128 : (c.COUTp % 64 == 0 ? 64 : 32)))));
+    prof_tile[conv_index] = conv_facts(kernel, c.OH, c.OW, c.COUTp, precision, c.join_skip != nullptr).id;
     return rc;
 }
 
@@ -473,22 +574,24 @@ static int count_convs(const std::vector<Layer>& ls)
 // conv_cursor already points at the second one's weights
 bool fav_net::acc_stats_ok(const std::vector<Layer>& ls, size_t li) const
 {
-    if (tuning().no_acc_stats || tuning().no_wino || precision != 0) return false;
+    if (tuning().no_acc_stats) return false;
     if (li + 3 >= ls.size() || ls[li + 1].type != L_IN || ls[li + 2].type != L_RELU || ls[li + 3].type != L_CONV) return false;
     if (conv_cursor >= convs.size()) return false;
     const Layer& c2 = ls[li + 3]; const DevConvW& d2 = convs[conv_cursor];
-    return !c2.transposed && d2.wwino4 != nullptr && conv3_wino4_eligible(d2.cinp, c2.cout, d2.coutp, c2.k, c2.stride, c2.pad, 1, 0);
+    return select_conv(c2, d2, 1, 0, precision, false, 0, 0, tuning()) == CK_WINO4;      // (behind the InstanceNorm + ReLU: one pending stage)
 }
 
 // conv - InstanceNorm - ReLU - conv - InstanceNorm (models_video.lua:10-39) with both convolutions on the Winograd kernel
 bool fav_net::res_block_is_winograd(const Layer& R, size_t first_conv) const
 {
     const std::vector<Layer>& b = R.block;
-    if (tuning().no_wino || b.size() != 5 || b[0].type != L_CONV || b[1].type != L_IN || b[2].type != L_RELU || b[3].type != L_CONV || b[4].type != L_IN) return false;
+    if (b.size() != 5 || b[0].type != L_CONV || b[1].type != L_IN || b[2].type != L_RELU || b[3].type != L_CONV || b[4].type != L_IN) return false;
     if (first_conv + 1 >= convs.size()) return false;
     for (int k = 0; k < 2; ++k) {
         const Layer& c = b[k ? 3 : 0]; const DevConvW& d = convs[first_conv + (size_t)k];
-        if (c.transposed || d.wwino == nullptr || !conv3_wino_eligible(d.cinp, c.cout, d.coutp, c.k, c.stride, c.pad, 1, 0)) return false;
+        const ConvKernel kernel = select_conv(c, d, 1, 0, precision, false, 0, 0, tuning());
+        // (a pending join is for one group of 128 filters, F(4x4) included: the layers that have the F(2x2) weights as well)
+        if ((kernel != CK_WINO && kernel != CK_WINO4) || d.packed[CK_WINO] == nullptr) return false;
     }
     return true;
 }
@@ -532,12 +635,13 @@ int fav_net::run(std::vector<Layer>& ls, Act& cur, bool top, float* out_planar, 
             if (c.IH + 2 * c.pad < L.k || c.IW + 2 * c.pad < L.k) { set_error("network: input too small for the architecture"); return FAV_EINVAL; }
             bool has_tanh = false; float mul = 1.f;
             const bool is_final = top && only_tail(ls, li + 1, has_tanh, mul) && has_tanh && L.cout == 3;
+            const ConvKernel kernel = select_conv(L, d, cur.pre.stages, cur.ups, precision, is_final, c.IH, c.IW, tuning());
             Act nxt;
             nxt.Hp = c.OH; nxt.Wp = c.OW; nxt.C = L.cout;
             if (is_final && L.transposed) { set_error("network: a transposed convolution as the last layer is unsupported"); return FAV_EUNSUPPORTED; }
             if (is_final) {
                 c.final_mode = 1; c.tanh_mul = mul; c.out_planar = out_planar; c.out_raw_nchw = out_raw;
-                int rc = timed_conv(c, (int)conv_cursor - 1, L); if (rc) return rc;
+                int rc = timed_conv(c, (int)conv_cursor - 1, L, kernel, nullptr); if (rc) return rc;
                 cur = nxt;
                 return FAV_OK;        // Tanh / MulConstant / TotalVariation are folded into the epilogue
             }
@@ -552,25 +656,9 @@ int fav_net::run(std::vector<Layer>& ls, Act& cur, bool top, float* out_planar, 
                 nxt.data = base + ((size_t)lazy.shave * lazy.pitch + lazy.shave) * L.cout; nxt.pitch = lazy.pitch; c.OWp = lazy.pitch;
             } else { rc = alloc((size_t)c.OH * c.OW * L.cout * sizeof(float), &nxt.data); if (rc) return rc; }
             const bool want_stats = li + 1 < ls.size() && ls[li + 1].type == L_IN;
-            const bool c8 = !L.transposed && conv_c8_eligible(d.cinp, d.coutp, L.k, L.stride, cur.pre.stages, cur.ups) && !tuning().no_c8;
-            const bool wino4 = !L.transposed && d.wwino4 != nullptr && precision == 0 && !tuning().no_wino &&
-                               conv3_wino4_eligible(d.cinp, L.cout, d.coutp, L.k, L.stride, L.pad, cur.pre.stages, cur.ups);
-            const bool wino = wino4 || (!L.transposed && d.wwino != nullptr && precision == 0 && !tuning().no_wino &&
-                                        conv3_wino_eligible(d.cinp, L.cout, d.coutp, L.k, L.stride, L.pad, cur.pre.stages, cur.ups));
-            // (a first layer with more than 32 filters: the 2-D minimal-filtering kernel in groups of 32; no other special kernel takes it)
-            const bool first_wide = !c8 && !L.transposed && d.wfirst2d != nullptr && !tuning().no_first && !tuning().no_c8d &&
-                                    conv_first2d_eligible(d.cinp, L.cin, d.coutp, L.k, L.stride, cur.pre.stages, cur.ups);
-            const bool first = first_wide || (c8 && d.wfirst != nullptr && !tuning().no_first && !tuning().no_c8d && conv_c8d_eligible(d.cinp, L.cin, d.coutp, L.k, L.stride, cur.pre.stages, cur.ups));
-            const bool up2 = !L.transposed && d.wup2 != nullptr && precision == 0 && !tuning().no_up2 &&
-                             conv3_up2_eligible(d.cinp, L.cout, d.coutp, L.k, L.stride, L.pad, cur.pre.stages, cur.ups);
-            const bool s2w = !L.transposed && d.ws2w != nullptr && !tuning().no_s2w &&
-                             conv3s2w_eligible(d.cinp, L.cout, d.coutp, L.k, L.stride, L.pad, cur.pre.stages, cur.ups);
-            const bool h3 = !wino && !up2 && !s2w && !L.transposed && conv3_halo_eligible(d.cinp, d.coutp, L.k, L.stride) && !tuning().no_h3;
-            const bool s2 = !L.transposed && !s2w && !h3 && !c8 && conv3s2_eligible(d.cinp, d.coutp, L.k, L.stride, cur.pre.stages, cur.ups) && !tuning().no_s2;
-            static const bool first_1d = diag_env("FAV_FIRST_1D") != nullptr;      // (tuning: read once) the 1-D form of the first layer
-            const bool first2d = first_wide || (first && d.wfirst2d != nullptr && !first_1d);
-            nxt.mblocks = first ? (first2d ? conv_first2d_tiles(c.OH, c.OW) : conv_first_tiles(c.OH, c.OW)) : s2w ? conv3s2w_tiles(c.OH, c.OW, d.coutp) : up2 ? conv3_up2_tiles(c.OH, c.OW) : wino ? (wino4 ? conv3_wino4_tiles(c.OH, c.OW) : conv3_wino_tiles(c.OH, c.OW)) : c8 ? conv_c8_tiles(c.OH, c.OW) : (h3 ? conv3_halo_tiles(c.OH, c.OW, precision == 0) : (s2 ? conv3s2_tiles(c.OH, c.OW) : conv_mblocks(c.OH, c.OW))); nxt.ppitch = d.coutp;
-            const bool acc = wino4 && want_stats && !pitched_out && cur.join_skip == nullptr &&
+            const ConvFacts facts = conv_facts(kernel, c.OH, c.OW, d.coutp, precision, cur.join_skip != nullptr);
+            nxt.mblocks = facts.tiles; nxt.ppitch = d.coutp;
+            const bool acc = kernel == CK_WINO4 && want_stats && !pitched_out && cur.join_skip == nullptr &&
                              (acc_stats_ok(ls, li) || (branch_tail_acc_ok && !top && li + 2 == ls.size() && !tuning().no_acc_stats && precision == 0));
             if (acc) {
                 DevIN& din = ins[in_cursor];                   // the InstanceNorm that follows
@@ -578,16 +666,15 @@ int fav_net::run(std::vector<Layer>& ls, Act& cur, bool top, float* out_planar, 
                 c.stat_acc = nxt.acc;
             }
             if (want_stats && !acc) { rc = alloc((size_t)nxt.mblocks * d.coutp * 2 * sizeof(float), &nxt.partials); if (rc) return rc; }
-            if (want_stats && !acc && (c8 || first || h3 || s2 || wino || up2 || s2w)) { float* cp = nullptr; rc = alloc((size_t)nxt.mblocks * sizeof(int), &cp); if (rc) return rc; nxt.counts = reinterpret_cast<int*>(cp); }
+            if (want_stats && !acc && facts.counts) { float* cp = nullptr; rc = alloc((size_t)nxt.mblocks * sizeof(int), &cp); if (rc) return rc; nxt.counts = reinterpret_cast<int*>(cp); }
             c.out = nxt.data; c.partials = nxt.partials;
             if (cur.join_skip != nullptr || pitched_out) {
-                if (!wino) { set_error("internal: a pending residual join next to a convolution that is not the Winograd kernel's"); return FAV_EINVAL; }
+                if (kernel != CK_WINO && kernel != CK_WINO4) { set_error("internal: a pending residual join next to a convolution that is not the Winograd kernel's"); return FAV_EINVAL; }
                 c.join_skip = cur.join_skip; c.join_out = cur.join_out;
             }
-            if (h3 && precision == 1) c.wgt16 = d.wgt16;
-            c8_counts = (c8 || first || h3 || s2 || wino || up2 || s2w) ? (nxt.counts ? nxt.counts : reinterpret_cast<int*>(zeros)) : nullptr; use_c8 = c8; use_h3 = h3; use_s2 = s2; use_wino = wino; use_wino4 = wino4; use_up2 = up2; use_first = first; use_first2d = first2d; use_s2w = s2w;
-            rc = timed_conv(c, (int)conv_cursor - 1, L); if (rc) return rc;
-            use_c8 = false; use_h3 = false; use_s2 = false; use_wino = false; use_wino4 = false; use_up2 = false; use_first = false; use_first2d = false; use_s2w = false;
+            if (kernel == CK_HALO3 && precision == 1) c.wgt16 = d.wgt16;
+            int* counts = facts.counts ? (nxt.counts ? nxt.counts : reinterpret_cast<int*>(zeros)) : nullptr;
+            rc = timed_conv(c, (int)conv_cursor - 1, L, kernel, counts); if (rc) return rc;
             cur = nxt;
             break;
         }
@@ -605,18 +692,18 @@ int fav_net::run(std::vector<Layer>& ls, Act& cur, bool top, float* out_planar, 
                 int rc = launch_in_finalize(cur.partials, cur.counts, cur.mblocks, M, CONV_BM, C, cur.ppitch, d.gamma, d.beta, L.eps,
                                             d.scale, d.shift, st);
                 if (rc) return rc;
-                cur.pre.scale1 = d.scale; cur.pre.shift1 = d.shift; cur.pre.relu1 = 0; cur.pre.stages = 1;
+                rc = append_stage(cur.pre, d.scale, d.shift, 0); if (rc) return rc;
             } else {
-                if (cur.pre.stages >= 2) { set_error("network: more than two stacked normalisations on one tensor are unsupported"); return FAV_EUNSUPPORTED; }
+                Affine normalised = cur.pre;
+                int rc = append_stage(normalised, d.scale, d.shift, 0); if (rc) return rc;
                 // statistics of the pending-transformed tensor (nearest upsampling replicates every
                 // element s*s times and leaves mean and biased variance unchanged)
                 float* part = nullptr;
                 const int mb = (M + 127) / 128;
-                int rc = alloc((size_t)mb * C * 2 * sizeof(float), &part); if (rc) return rc;
+                rc = alloc((size_t)mb * C * 2 * sizeof(float), &part); if (rc) return rc;
                 rc = launch_stats(cur.data, M, C, cur.pre, part, st); if (rc) return rc;
                 rc = launch_in_finalize(part, nullptr, mb, M, 128, C, C, d.gamma, d.beta, L.eps, d.scale, d.shift, st); if (rc) return rc;
-                if (cur.pre.stages == 0) { cur.pre.scale1 = d.scale; cur.pre.shift1 = d.shift; cur.pre.relu1 = 0; cur.pre.stages = 1; }
-                else { cur.pre.scale2 = d.scale; cur.pre.shift2 = d.shift; cur.pre.relu2 = 0; cur.pre.stages = 2; }
+                cur.pre = normalised;
             }
             cur.partials = nullptr; cur.counts = nullptr; cur.acc = nullptr; cur.acc_other = nullptr;
             break;
@@ -624,14 +711,12 @@ int fav_net::run(std::vector<Layer>& ls, Act& cur, bool top, float* out_planar, 
         case L_BN: {
             const DevIN& d = ins[in_cursor++];
             if (cur.data == nullptr || (int)L.mean.size() != cur.C) { set_error("network: misplaced SpatialBatchNormalization"); return FAV_EUNSUPPORTED; }
-            if (cur.pre.stages >= 2) { set_error("network: more than two stacked normalisations on one tensor are unsupported"); return FAV_EUNSUPPORTED; }
-            if (cur.pre.stages == 0) { cur.pre.scale1 = d.scale; cur.pre.shift1 = d.shift; cur.pre.relu1 = 0; cur.pre.stages = 1; }
-            else { cur.pre.scale2 = d.scale; cur.pre.shift2 = d.shift; cur.pre.relu2 = 0; cur.pre.stages = 2; }
+            int rc = append_stage(cur.pre, d.scale, d.shift, 0); if (rc) return rc;
             cur.partials = nullptr; cur.counts = nullptr;
             break;
         }
         case L_RELU:
-            if (cur.pre.stages == 0) { cur.pre.scale1 = ones; cur.pre.shift1 = zeros; cur.pre.relu1 = 1; cur.pre.stages = 1; }
+            if (cur.pre.stages == 0) (void)append_stage(cur.pre, ones, zeros, 1);
             else if (cur.pre.stages == 1) cur.pre.relu1 = 1;
             else cur.pre.relu2 = 1;
             cur.partials = nullptr;
@@ -663,20 +748,19 @@ int fav_net::run(std::vector<Layer>& ls, Act& cur, bool top, float* out_planar, 
             // 16 us launch they replace (639 against 634 frames/s, profiles/r4s_stream_k_and_joins_ab.log).  (The F(4x4) kernel's pending-join
             // instantiation is kept for FAV_LAZY_JOIN and the tests that pin its bits against the launched joins; since the row requests carry
             // their own offsets it spills inside its K loop -- nobody tuned it further)
-            static const bool no_lazy = diag_env("FAV_NO_LAZY_JOIN") != nullptr;      // (tuning: read once)
-            static const bool want_lazy = diag_env("FAV_LAZY_JOIN") != nullptr;
             const int nconv = count_convs(L.block);
-            const bool lazy_out = !no_lazy && (tuning().wino_f2 || want_lazy) && precision == 0 && li + 1 < ls.size() && ls[li + 1].type == L_RES && skip.pre.stages == 0 && skip.ups == 0 &&
+            const bool lazy_out = !tuning().no_lazy_join && (tuning().wino_f2 || tuning().lazy_join) && precision == 0 &&
+                                  li + 1 < ls.size() && ls[li + 1].type == L_RES && skip.pre.stages == 0 && skip.ups == 0 &&
                                   res_block_is_winograd(L, conv_cursor) && res_block_is_winograd(ls[li + 1], conv_cursor + (size_t)nconv);
             if (lazy_out) { lazy.active = true; lazy.pitch = skip.P(); lazy.rows = skip.Hp; lazy.shave = L.shave; lazy.conv_index = (int)conv_cursor + nconv - 1; }
-            // the join below is a plain res_add launch (no statistics of its own, not left pending): it can take the branch's last
-            // InstanceNorm as accumulators (round 5) -- no in_finalize launch between the branch's last convolution and the join
-            {
-                size_t nx0 = li + 1;
-                if (nx0 < ls.size() && ls[nx0].type == L_UP && ls[nx0].scale == 2) ++nx0;
-                const bool join_stats = nx0 < ls.size() && ls[nx0].type == L_IN;
-                branch_tail_acc_ok = !lazy_out && !join_stats;
-            }
+            // the join feeds an InstanceNorm (directly, or through the x2 nearest upsample of models_video.lua:94-98, which leaves
+            // mean and biased variance unchanged): it takes that norm's statistics in the same pass
+            size_t nx = li + 1;
+            if (nx < ls.size() && ls[nx].type == L_UP && ls[nx].scale == 2) ++nx;
+            const bool join_stats = nx < ls.size() && ls[nx].type == L_IN;
+            // else, when the join is a plain res_add launch (not left pending either), it can take the branch's last InstanceNorm as
+            // accumulators (round 5) -- no in_finalize launch between the branch's last convolution and the join
+            branch_tail_acc_ok = !lazy_out && !join_stats;
             rc = run(L.block, br, false, nullptr, nullptr);
             lazy.active = false; branch_tail_acc_ok = false;
             if (rc) return rc;
@@ -694,11 +778,7 @@ int fav_net::run(std::vector<Layer>& ls, Act& cur, bool top, float* out_planar, 
             }
             Act z; z.Hp = br.Hp; z.Wp = br.Wp; z.C = br.C;
             rc = alloc((size_t)z.Hp * z.Wp * z.C * sizeof(float), &z.data); if (rc) return rc;
-            // the join feeds an InstanceNorm (directly, or through the x2 nearest upsample of models_video.lua:94-98, which leaves
-            // mean and biased variance unchanged): take that norm's statistics in the same pass
-            size_t nx = li + 1;
-            if (nx < ls.size() && ls[nx].type == L_UP && ls[nx].scale == 2) ++nx;
-            if (nx < ls.size() && ls[nx].type == L_IN) {
+            if (join_stats) {
                 z.mblocks = res_add_stat_blocks(z.Hp, z.Wp); z.ppitch = z.C;
                 rc = alloc((size_t)z.mblocks * z.C * 2 * sizeof(float), &z.partials); if (rc) return rc;
                 float* cp = nullptr; rc = alloc((size_t)z.mblocks * sizeof(int), &cp); if (rc) return rc; z.counts = reinterpret_cast<int*>(cp);

@@ -464,7 +464,7 @@ def test_f4x4_kernel_on_an_odd_number_of_channel_slices(favlib, oracle, cuda, tm
     x = (np.random.default_rng(31).standard_normal((7, h, w)) * 50).astype(np.float32)
     ref = oracle.net_forward(layers, x)
     net, got, kids = _wide_forward(favlib, cuda, p, x)
-    assert kids[1] in (728, 729), kids                # the F(4x4) kernel (fav_internal.h: conv kernel ids)
+    assert kids[1] in (728, 729), kids                # the F(4x4) kernel (fav_internal.h: the id table at enum ConvKernel)
     assert got.shape == ref.shape == (3, h, w)
     err = np.abs(got - ref).max()
     assert err <= 2e-2 and np.abs(ref).std() > 5, err
