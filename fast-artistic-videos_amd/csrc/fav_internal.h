@@ -166,18 +166,13 @@ struct ConvLaunch {
     float* ks_ws = nullptr; int* ks_cnt = nullptr;
 };
 inline size_t conv3_wino4_ksplit_bytes() { return (size_t)256 * 2 * 256 * 128 * sizeof(float); }
+// kernels_conv.hip: the generic implicit-GEMM kernel (data-parallel or stream-K)
 size_t conv_streamk_workspace_bytes();
 int conv_streamk_grid();
 constexpr int CONV_BM = 128;
 inline int conv_mblocks(int OH, int OW) { return (OH * OW + CONV_BM - 1) / CONV_BM; }
 int launch_conv(const ConvLaunch& p, hipStream_t st);
-// last layer with few output channels: kx taps folded into N (see kernels_conv.hip); wfold = [KH][32][CIN]
-bool conv_fold_eligible(int cin_pitch, int cout, int k, int stride);
-bool conv_fold_launchable(int cin_pitch, int k, int pad, int ups, int IH, int IW);      // 128 / 256 input channels: on a x2-upsampled input only
-int launch_conv_fold(const ConvLaunch& p, const float* wfold, hipStream_t st);
-
-// per-channel finalize of (mean, M2) partials -> scale/shift:  scale = gamma/sqrt(var+eps)
-// first layer (8-channel input pitch, 9x9): LDS-resident halo + weights, persistent blocks; partial statistics are
+// first layer (8-channel input pitch, 9x9), kernels_c8.hip: LDS-resident halo + weights, persistent blocks; partial statistics are
 // per 16x16 tile with explicit counts
 bool conv_c8_eligible(int cin_pitch, int coutp, int k, int stride, int stages, int ups);
 int conv_c8_tiles(int OH, int OW);
@@ -187,6 +182,18 @@ int launch_conv_c8(const ConvLaunch& p, int* counts, hipStream_t st);
 bool conv_c8d_eligible(int cin_pitch, int cin_real, int coutp, int k, int stride, int stages, int ups);
 void conv_c8d_pack(const float* w, int cin, int cout, std::vector<float>& out);
 int launch_conv_c8d(const ConvLaunch& p, int cin_real, const float* wc8d, int* counts, hipStream_t st);
+// 3x3 stride-1 layers, kernels_halo.hip: halo-resident implicit GEMM (stream-K, needs the ConvLaunch sk_* fields); partials per 8x32 tile
+bool conv3_halo_eligible(int cin_pitch, int coutp, int k, int stride);
+int conv3_halo_tiles(int OH, int OW, bool edge_b);      // edge_b: fp32 kernel (16 x 16 tiles on a narrow ragged right edge)
+int launch_conv3_halo(const ConvLaunch& p, int* counts, hipStream_t st);
+// 3x3 stride-2 layers, kernels_halo_s2.hip: halo-resident implicit GEMM with even / odd column planes (stream-K); partials per 4x32 tile
+bool conv3s2_eligible(int cin_pitch, int coutp, int k, int stride, int stages, int ups);
+int conv3s2_tiles(int OH, int OW);
+int launch_conv3s2(const ConvLaunch& p, int* counts, hipStream_t st);
+// last layer with few output channels: kx taps folded into N (kernels_fold.hip); wfold = [KH][32][CIN]
+bool conv_fold_eligible(int cin_pitch, int cout, int k, int stride);
+bool conv_fold_launchable(int cin_pitch, int k, int pad, int ups, int IH, int IW);      // 128 / 256 input channels: on a x2-upsampled input only
+int launch_conv_fold(const ConvLaunch& p, const float* wfold, hipStream_t st);
 // the same first layer with 1-D minimal filtering F(2,3) along x (kernels_first.hip); wpk = conv_first_pack() (first_pack.h);
 // eligibility as conv_c8d_eligible; partials per 8x64 tile with explicit counts
 int conv_first_tiles(int OH, int OW);
@@ -216,14 +223,6 @@ int launch_conv3_up2(const ConvLaunch& p, const float* wpk, int* counts, hipStre
 bool conv3s2w_eligible(int cin_pitch, int cout, int coutp, int k, int stride, int pad, int stages, int ups);
 int conv3s2w_tiles(int OH, int OW, int coutp);
 int launch_conv3s2w(const ConvLaunch& p, const float* wpk, int* counts, hipStream_t st);
-// 3x3 stride-1 layers: halo-resident implicit GEMM (stream-K, needs the ConvLaunch sk_* fields); partials per 8x32 tile
-bool conv3_halo_eligible(int cin_pitch, int coutp, int k, int stride);
-int conv3_halo_tiles(int OH, int OW, bool edge_b);      // edge_b: fp32 kernel (16 x 16 tiles on a narrow ragged right edge)
-int launch_conv3_halo(const ConvLaunch& p, int* counts, hipStream_t st);
-// 3x3 stride-2 layers: halo-resident implicit GEMM with even / odd column planes (stream-K); partials per 4x32 tile
-bool conv3s2_eligible(int cin_pitch, int coutp, int k, int stride, int stages, int ups);
-int conv3s2_tiles(int OH, int OW);
-int launch_conv3s2(const ConvLaunch& p, int* counts, hipStream_t st);
 // One enumerator per launch wrapper above.  fav_net picks one per layer (net.cpp: select_conv) and reports it through
 // fav_net_profile_read_host as a kernel id -- a contract: bench.py, scripts/wide_bench.py and the GPU tests read the ids
 // (N = the padded output channel count COUTp):
@@ -235,6 +234,7 @@ int launch_conv3s2(const ConvLaunch& p, int* counts, hipStream_t st);
 //   CK_FIRST2D  launch_conv_first2d  16                             CK_S2HALO  launch_conv3s2      200 + N
 enum ConvKernel { CK_GENERIC, CK_FOLD, CK_C8, CK_C8D, CK_FIRST1D, CK_FIRST2D, CK_S2W, CK_UP2, CK_WINO, CK_WINO4, CK_HALO3, CK_S2HALO };
 constexpr int CONV_KERNELS = CK_S2HALO + 1;      // (the last enumerator)
+// kernels_elem.hip.  Per-channel finalize of (mean, M2) partials -> scale/shift:  scale = gamma/sqrt(var+eps)
 // counts: per-partial pixel counts or null (then block b holds min(block_pixels, M - b*block_pixels) pixels)
 int launch_in_finalize(const float* partials, const int* counts, int mblocks, int M, int block_pixels, int C, int Cpitch,
                        const float* gamma, const float* beta, float eps,

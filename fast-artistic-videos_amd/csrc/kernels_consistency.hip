@@ -18,6 +18,7 @@
 #include <mutex>
 
 #include "fav_internal.h"
+#include "launch_common.h"
 #include "consistency_pixel.h"
 
 namespace fav {
@@ -48,9 +49,6 @@ __global__ void xcd_probe_kernel(int* out)
     unsigned xcc; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
     if (threadIdx.x == 0) out[blockIdx.x] = (int)(xcc & 15u);
 }
-
-constexpr int MAX_DEVICES = 64;
-inline int cur_dev() { int d = 0; (void)hipGetDevice(&d); return (d >= 0 && d < MAX_DEVICES) ? d : 0; }
 
 __global__ __launch_bounds__(256) void consistency_kernel(const float2* f1, const float2* f2, const float* structure,
                                                           const float* avg_ptr, uint8_t* out, int W, int H)

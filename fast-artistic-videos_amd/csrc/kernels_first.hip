@@ -1,7 +1,7 @@
 // kernels_first.hip -- the first layer (c9s1-32: 9x9, 7 real input channels of the NHWC8 network input -> 32 channels, full
 // resolution; models_video.lua:57-80; 3 channels for first-frame image models) with 1-D minimal filtering along x.
 //
-// The direct form (conv_c8d_kernel, kernels_conv.hip) is a dense-K implicit GEMM at 0.78 of the fp32 MFMA peak: K = 7 x 81,
+// The direct form (conv_c8d_kernel, kernels_c8.hip) is a dense-K implicit GEMM at 0.78 of the fp32 MFMA peak: K = 7 x 81,
 // N = 32 -- too few output channels for a 2-D Winograd transform to pay (its vector-ALU work is per input element).  Along ONE
 // axis it does: the 9 taps of a filter row are three blocks of three, each block a 3-tap correlation computed as F(2,3) -- 4
 // multiplies per output pair instead of 6 (first_pack.h) -- so a tile needs 4 x 95 instead of 2 x 287 matrix instructions
@@ -18,19 +18,14 @@
 #include <vector>
 
 #include "fav_internal.h"
+#include "conv_device.h"
+#include "launch_common.h"
 #include "first_pack.h"
 #include "first2d_pack.h"
 
 namespace fav {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-
 namespace {
-
-constexpr int MAX_DEVICES = 64;
-inline int cur_dev() { int d = 0; (void)hipGetDevice(&d); return (d >= 0 && d < MAX_DEVICES) ? d : 0; }
 
 constexpr int F_TH = 8, F_TW = 64;                 // output tile
 constexpr int F_HR = F_TH + 8, F_HC = F_TW + 8;    // halo 16 x 72
@@ -243,16 +238,10 @@ template <int CR>
 int launch_first_t(const FirstArgs& a, int reserve_cus, hipStream_t st)
 {
     const size_t lds = (size_t)(4 * conv_first_pairs(CR) * 64 + CR * F_CPL + 8 * 64 + 8) * sizeof(float);
-    const int dv = cur_dev();
-    static int nblocks[MAX_DEVICES] = {};
-    if (!nblocks[dv]) {
-        FAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_first_kernel<CR>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        int prop_cus = 0;
-        FAV_HIP(hipDeviceGetAttribute(&prop_cus, hipDeviceAttributeMultiprocessorCount, dv));      // (hipGetDeviceProperties costs a millisecond or two per call)
-        nblocks[dv] = prop_cus;
-    }
+    static PerDevice cache; int cus;
+    FAV_HIP(launch_cus(cache, &cus, conv_first_kernel<CR>));
     const int tiles = a.tiles_x * a.tiles_y;
-    const int grid = std::max(1, nblocks[dv] - reserve_cus);
+    const int grid = persistent_slots(cus, reserve_cus);
     hipLaunchKernelGGL((conv_first_kernel<CR>), dim3(tiles < grid ? tiles : grid), dim3(512), lds, st, a);
     FAV_LAUNCH_CHECK("conv_first_kernel");
     return FAV_OK;
@@ -533,17 +522,11 @@ template <int CR, bool WIDE = false>
 int launch_first2d_t(const FirstArgs& a, int reserve_cus, hipStream_t st)
 {
     const size_t lds = (size_t)(16 * conv_first2d_quads(CR) * 128 + CR * G_CPL + 8 * 64 + 8) * sizeof(float);
-    const int dv = cur_dev();
-    static int nblocks[MAX_DEVICES] = {};
-    if (!nblocks[dv]) {
-        FAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_first2d_kernel<CR, WIDE>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        int prop_cus = 0;
-        FAV_HIP(hipDeviceGetAttribute(&prop_cus, hipDeviceAttributeMultiprocessorCount, dv));      // (hipGetDeviceProperties costs a millisecond or two per call)
-        nblocks[dv] = prop_cus;
-    }
+    static PerDevice cache; int cus;
+    FAV_HIP(launch_cus(cache, &cus, conv_first2d_kernel<CR, WIDE>));
     const int tiles = a.tiles_x * a.tiles_y;
     const int ngrp = WIDE ? a.groups : 1;
-    int grid = std::max(1, nblocks[dv] - reserve_cus);
+    int grid = persistent_slots(cus, reserve_cus);
     grid = std::min(grid, tiles * ngrp);
     if (WIDE) grid = std::max(ngrp, grid / ngrp * ngrp);      // a block keeps one group's weights
 #ifdef FAV_DIAG

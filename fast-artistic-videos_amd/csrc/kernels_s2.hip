@@ -20,17 +20,13 @@
 #include <cstdlib>
 
 #include "fav_internal.h"
+#include "conv_device.h"
+#include "launch_common.h"
 #include "s2_pack.h"
 
 namespace fav {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-
 namespace {
-
-constexpr int MAX_DEVICES = 64;
-inline int cur_dev() { int d = 0; (void)hipGetDevice(&d); return (d >= 0 && d < MAX_DEVICES) ? d : 0; }
 
 constexpr int SW_P = 20;                    // pixel pitch in floats: 16 channels + 4
 constexpr int SW_EW = 33, SW_OW = 32;       // pixels per row of the even / odd column plane
@@ -74,11 +70,7 @@ __global__ __launch_bounds__(64 * NTC * TR, NTC * TR / 4) void conv3s2w_kernel(c
     const int nt = wave % NTC, row = wave / NTC;
     const int m = lane & 31, h = lane >> 5;
     const int CIN = p.CIN, nch = CIN >> 4;
-    int lb;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        lb = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int lb = xcd_linear_block();
     const int ngrp = WIDE ? p.groups : 1, grp = WIDE ? lb % p.groups : 0;      // (gridDim.x % groups == 0: every item of this block is of group grp)
     const int PITCH = WIDE ? p.COUTP : COUT;
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.wpk) + (size_t)grp * (nch * 18 * NTC * 256), 0, nch * 18 * NTC * 1024, 0x00020000);
@@ -322,21 +314,15 @@ int launch_s2w_t(const S2wArgs& a, int reserve_cus, hipStream_t st)
 {
     const auto kern = conv3s2w_kernel<NTC, TR, WIDE>;
     const size_t lds = (size_t)(2 * SwGeo<NTC, TR>::HB + 2 * a.CIN) * sizeof(float) + (size_t)TR * NTC * 32 * sizeof(float2) + 16 * sizeof(int);
-    const int dv = cur_dev();
-    static int cus[MAX_DEVICES] = {};
-    if (!cus[dv]) {
-        FAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        int prop_cus = 0;
-        FAV_HIP(hipDeviceGetAttribute(&prop_cus, hipDeviceAttributeMultiprocessorCount, dv));      // (hipGetDeviceProperties costs a millisecond or two per call)
-        cus[dv] = prop_cus;
-    }
+    static PerDevice cache; int cus;
+    FAV_HIP(launch_cus(cache, &cus, kern));
     const int ngrp = WIDE ? a.groups : 1;
     const int tiles = a.tiles_x * a.tiles_y * ngrp;
     // (Rounds 2-5 launched a layer of many short tiles one tile per block next to the look-ahead queue: a persistent block that shared its
     //  CU with a side-queue kernel fell behind and its statically assigned tiles became the launch's tail.  Since round 6 the mask's
     //  long-lived kernels sit on the CUs this grid leaves free (kernels_consistency.hip, xcd_share) and the persistent form is the
     //  faster one again: d64 100 us against 137 us, profiles/r8l_4arg_cu_filling_ab.log.  FAV_S2W_TILE_GRID restores the old form.)
-    const int slots = std::max(1, cus[dv] - reserve_cus);
+    const int slots = persistent_slots(cus, reserve_cus);
     static const bool tile_grid = diag_env("FAV_S2W_TILE_GRID") != nullptr;      // (tuning: read once)
     int grid = (tile_grid && reserve_cus > 0 && tiles > 4 * slots) ? tiles : std::min(tiles, slots);
     if (WIDE) grid = std::max(ngrp, grid / ngrp * ngrp);      // a block stays with one group

@@ -22,20 +22,15 @@
 #include <cstdlib>
 
 #include "fav_internal.h"
+#include "conv_device.h"
+#include "launch_common.h"
 #include "up2_pack.h"
 
 namespace fav {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-
 namespace {
 
-constexpr int MAX_DEVICES = 64;
-inline int cur_dev() { int d = 0; (void)hipGetDevice(&d); return (d >= 0 && d < MAX_DEVICES) ? d : 0; }
-
-constexpr int LDSS = 36;                     // pixel pitch in floats
+// (LDSS = 36: pixel pitch in floats)
 constexpr int U2_HW = 34, U2_HP = 10 * 34;   // halo: 10 rows x 34 pixels
 constexpr int U2_HPP = 384;                  // padded to 6 pieces x 512 threads / 8 chunks (pixels 340..383 are scratch)
 constexpr int U2_HB = U2_HPP * LDSS;         // floats per halo buffer (55 296 B)
@@ -476,20 +471,12 @@ int launch_conv3_up2(const ConvLaunch& c, const float* wpk, int* counts, hipStre
     a.tiles_x = (a.PW + 31) / 32; a.tiles_y = wg ? (a.PH + 3) / 4 : (a.PH + 7) / 8;
     const size_t lds = wg ? (size_t)(UW_ZS + 2 * c.CIN + 2 * 4 * 64 + 8) * sizeof(float)          // exchange area (the halo buffers live inside it) | affine table | statistics
                           : (size_t)(2 * U2_HB + 2 * c.CIN) * sizeof(float);
-    const int dv = cur_dev();
-    static int cus[MAX_DEVICES] = {};
-    if (!cus[dv]) {
-        FAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_up2_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        FAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_up2w_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        FAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(conv3_up2w_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        int prop_cus = 0;
-        FAV_HIP(hipDeviceGetAttribute(&prop_cus, hipDeviceAttributeMultiprocessorCount, dv));      // (hipGetDeviceProperties costs a millisecond or two per call)
-        cus[dv] = prop_cus;
-    }
+    static PerDevice cache; int cus;
+    FAV_HIP(launch_cus(cache, &cus, conv3_up2_kernel<true>, conv3_up2w_kernel<false>, conv3_up2w_kernel<true>));
     a.COUTP = c.COUTp; a.groups = c.COUTp / 64;
     FAV_REQUIRE((long long)(c.OH + 1) * c.OW * c.COUTp < (1ll << 31), "upsampled 3x3 conv: output too large");
     const int tiles = a.tiles_x * a.tiles_y * a.groups;
-    const int grid = std::min(tiles, std::max(1, cus[dv] - c.reserve_cus));
+    const int grid = std::min(tiles, persistent_slots(cus, c.reserve_cus));
     // (every U2 of the reference's builder is followed by a normalisation: stages == 1)
     if (wg && a.groups > 1) { hipLaunchKernelGGL(conv3_up2w_kernel<true>, dim3(grid), dim3(768), lds, st, a); }      // (wpk: the groups' nine-position blocks only)
     else if (wg) { a.wpk = wpk + conv_up2_packed_floats(c.CIN); hipLaunchKernelGGL(conv3_up2w_kernel<false>, dim3(grid), dim3(768), lds, st, a); }

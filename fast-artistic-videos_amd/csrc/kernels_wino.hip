@@ -2,7 +2,7 @@
 // Winograd F(2x2, 3x3) minimal filtering on the fp32 matrix cores of gfx950.
 //
 // Why: the ten residual convolutions are 56 % of the network's multiply-adds, and the halo-resident implicit GEMM
-// (kernels_conv.hip, conv3_halo_kernel) already runs them at 0.75 of the fp32 MFMA peak with 94 % matrix-pipe efficiency inside
+// (kernels_halo.hip, conv3_halo_kernel) already runs them at 0.75 of the fp32 MFMA peak with 94 % matrix-pipe efficiency inside
 // its K loop -- what is left there is clock and launch ramp.  F(2x2, 3x3) computes every 2x2 output patch from a 4x4 input
 // patch with 16 multiplies per (input channel, output channel) instead of 36: 2.25x fewer matrix instructions for the same
 // result (different rounding: the products are of transformed operands, fp32 throughout, errors of the order of the direct
@@ -32,20 +32,15 @@
 #include <type_traits>
 
 #include "fav_internal.h"
+#include "conv_device.h"
+#include "launch_common.h"
 #include "wino_pack.h"
 
 namespace fav {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-
 namespace {
 
-constexpr int MAX_DEVICES = 64;
-inline int cur_dev() { int d = 0; (void)hipGetDevice(&d); return (d >= 0 && d < MAX_DEVICES) ? d : 0; }
-
-constexpr int LDSS = 36;                               // pixel pitch in floats (32 channels + 4): conflict-free 16-byte fragment reads
+// (LDSS = 36: pixel pitch in floats, 32 channels + 4 -- conflict-free 16-byte fragment reads)
 constexpr int WG_TROW = 18 * LDSS;                     // 648: one row-transformed line = even plane (9 pixels) | odd plane (9 pixels)
 constexpr int WG_TTYP = 4 * WG_TROW;                   // 2592: the four lines i = 0..3 of one tile row; 648 sixteen-byte slots = 8 (mod 16)
 constexpr int WG_TBUF = 4 * WG_TTYP;                   // 10368 floats per halo buffer (4 tile rows)
@@ -62,21 +57,9 @@ struct WinoArgs {
     long long* dbg;          // optional in-kernel timeline (FAV_WINO_DBG), 24 slots per block
 };
 
-// exact merge of NW groups' (mean, M2) with per-group counts (Chan et al.); same as kernels_conv.hip
-__device__ __forceinline__ float2 merge_group_stats(const float2* st, const int* wn, int NW, int pitch, int c, int* n_out)
-{
-    int n = 0; float s = 0.f;
-    for (int w = 0; w < NW; ++w) { n += wn[w]; s += (float)wn[w] * st[w * pitch + c].x; }
-    const float mean = n ? s / (float)n : 0.f;
-    float m2 = 0.f;
-    for (int w = 0; w < NW; ++w) { const float d = st[w * pitch + c].x - mean; m2 += st[w * pitch + c].y + (float)wn[w] * d * d; }
-    *n_out = n;
-    return make_float2(mean, m2);
-}
-
 // MODE 1: the input carries a pending per-channel scale/shift (+ReLU) -- the InstanceNorm of the producing convolution.
 // MODE 2: the input is a pending RESIDUAL JOIN (models_video.lua:41-53): z = skip + scale * y + shift, formed while the halo is staged
-//   (same operations in the same order as res_add_kernel, kernels_conv.hip) and written out once -- every input pixel by the unit whose
+//   (same operations in the same order as res_add_kernel, kernels_elem.hip) and written out once -- every input pixel by the unit whose
 //   8 x 16 outputs start at it -- as the next block's skip.  y and skip share pitch and offsets (net.cpp lays y out under the skip),
 //   the skip rows bypass the register file: buffer_load ... lds into the part of the exchange area the halo buffers leave free, read
 //   back by the thread that requested them when it commits the item (requested BEFORE y's rows: loads return in order, so y's arrival
@@ -98,11 +81,7 @@ __global__ __launch_bounds__(512, 2) void conv3_wino_kernel(const WinoArgs p)
     int dbi = 0;
 #define DBG_T() { if (p.dbg && t == 0 && dbi < 21) p.dbg[blockIdx.x * 24 + dbi++] = wall_clock64(); }
     DBG_T();
-    int lb;
-    {
-        const int nwg = gridDim.x, q = nwg >> 3, r = nwg & 7, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-        lb = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int lb = xcd_linear_block();
     if (AFF) for (int i = t; i < CIN; i += NT) { aff[i] = p.scale1[i]; aff[CIN + i] = p.shift1[i]; }
     const float lo1 = (MODE == 1 && p.relu1) ? 0.f : -INFINITY;
     // landing area of the skip rows (MODE 2): [row a][thread] sixteen bytes each behind the two halo buffers, then wave 0's item B
@@ -411,7 +390,7 @@ __global__ __launch_bounds__(512, 2) void conv3_wino_kernel(const WinoArgs p)
             __syncthreads();
             if (t < NC) {
                 int nn;
-                p.partials[(size_t)u * 128 + nq * 32 + t] = merge_group_stats(st, wn, 4, NC, t, &nn);
+                p.partials[(size_t)u * 128 + nq * 32 + t] = merge_wave_stats(st, wn, 4, NC, t, &nn);
                 if (t == 0) p.counts[u] = nn;          // (the four quarters of a unit write the same count)
             }
             __syncthreads();
@@ -451,18 +430,18 @@ int launch_wino_t(const WinoArgs& a0, int reserve_cus, hipStream_t st)
 {
     const auto kern = conv3_wino_kernel<MODE>;
     const size_t lds = (size_t)(WG_PS + 2 * a0.CIN) * sizeof(float);
+    static PerDevice cache;
     const int dv = cur_dev();
-    static int cus[MAX_DEVICES] = {};
-    if (!cus[dv]) {
-        FAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        int occ = 0; int prop_cus = 0;
-        FAV_HIP(hipDeviceGetAttribute(&prop_cus, hipDeviceAttributeMultiprocessorCount, dv));      // (hipGetDeviceProperties costs a millisecond or two per call)
+    int cus = cache.get(dv);
+    if (!cus) {
+        FAV_HIP(first_launch_setup(dv, &cus, kern));
+        int occ = 0;
         FAV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 512, lds));
         if (occ < 1) { set_error("winograd conv: kernel does not fit on a CU"); return FAV_EHIP; }
-        cus[dv] = prop_cus;          // one block per CU
+        cache.set(dv, cus);          // one block per CU
     }
     const int units = a0.units_x * a0.units_y;
-    const int grid = std::min(units, std::max(1, cus[dv] - reserve_cus));
+    const int grid = std::min(units, persistent_slots(cus, reserve_cus));
     WinoArgs a = a0; a.dbg = nullptr;
     // A CU holds one unit at a time (the accumulators fill the register file), so a launch takes ceil(units / grid) rounds of one
     // unit time.  When the last round has at most grid / 4 units (the first three residual layers at 1280x720: 550, 525, 525 units

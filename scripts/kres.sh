@@ -1,5 +1,5 @@
 #!/bin/bash
-# Per-kernel register / scratch / LDS report of one HIP source (compile-time, no GPU): scripts/kres.sh csrc/kernels_conv.hip
+# Per-kernel register / scratch / LDS report of one HIP source (compile-time, no GPU): scripts/kres.sh csrc/kernels_halo.hip
 cd "$(dirname "$0")/../fast-artistic-videos_amd"
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -fhip-fp32-correctly-rounded-divide-sqrt ${KRES_FLAGS} -Rpass-analysis=kernel-resource-usage -c "$1" -o /tmp/kres.o 2>&1 | python3 -c '
 import re, sys
