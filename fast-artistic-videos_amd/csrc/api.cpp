@@ -120,6 +120,14 @@ extern "C" int fav_min_filter_f32(const float* cert, float* out, int H, int W, i
     return launch_min_filter_f32(cert, out, H, W, r, static_cast<hipStream_t>(stream));
 }
 
+extern "C" int fav_scale_bicubic_f32(const float* src, float* dst, int C, int Hs, int Ws, int Hd, int Wd, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(src && dst, "fav_scale_bicubic_f32: null pointer");
+    FAV_REQUIRE(C > 0 && Hs > 0 && Ws > 0 && Hd > 0 && Wd > 0, "fav_scale_bicubic_f32: non-positive dimension");
+    int rc = ensure_device(); if (rc) return rc;
+    return launch_scale_planar(src, dst, C, Hs, Ws, Hd, Wd, static_cast<hipStream_t>(stream));
+}
+
 // ---- A9 on the GPU: the bytes of the PNG file (kernels_png.hip)
 extern "C" size_t fav_png_capacity(int W, int H) { return (W > 0 && H > 0) ? png_capacity(W, H) : 0; }
 extern "C" size_t fav_png_workspace_bytes(int W, int H) { return (W > 0 && H > 0) ? png_workspace_bytes(W, H) : 0; }

@@ -283,6 +283,12 @@ int launch_prep_input(const uint8_t* frame_hwc, const float* prev_rgb, int Hs, i
                       const float* cert, int border, int H, int W, int pad, float* in8, hipStream_t st,
                       int fill_random = 0, unsigned seed = 0, unsigned index = 0, int* q0_out = nullptr);
 int launch_quantize_rgb8(const float* rgb_planar, uint8_t* out_hwc, int H, int W, hipStream_t st);
+// -scale_factor (kernels_scale.hip): image.scale(.., 'bicubic') [recalled].  launch_scale_prep: launch_prep_input for a frame without a
+// prior, resampled H x W -> Hs x Ws on the way (in8: [Hs+2*pad][Ws+2*pad][8]; the fill is keyed by the scaled grid);
+// launch_scale_planar: [C][Hs][Ws] -> [C][Hd][Wd] fp32
+int launch_scale_prep(const uint8_t* frame_hwc, int H, int W, int Hs, int Ws, int pad, float* in8, hipStream_t st,
+                      int fill_random = 0, unsigned seed = 0, unsigned index = 0);
+int launch_scale_planar(const float* src, float* dst, int C, int Hs, int Ws, int Hd, int Wd, hipStream_t st);
 // Huffman codes of the PNG encoder (png_tables.cpp): PNG_NTABLES model codes with their dynamic-block headers + the fixed code
 constexpr int PNG_NSYM = 277;            // literals 0..255, end of block 256, length symbols 257..276 (runs of 3..66)
 constexpr int PNG_NTABLES = 12;

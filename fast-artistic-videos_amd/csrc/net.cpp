@@ -1107,6 +1107,11 @@ struct fav_stream {
     bool has_state = false;
     unsigned frame_counter = 0;  // 1-based index of the frame being stylised (key of the uniform-random fill)
     float* in8 = nullptr;        // padded NHWC8 network input
+    // -scale_factor (fav_stream_set_single_image_size): frames without a prior run at sHs x sWs (0: unscaled).  The scaled padded input
+    // and the network's planar output at that size (sHo x sWo) live here from the call that sets the size on
+    int sHs = 0, sWs = 0, sHo = 0, sWo = 0;
+    float* scaled_in8 = nullptr; float* scaled_out = nullptr;
+    bool last_scaled = false;    // the last frame ran at the scaled size: in8 does not hold its input
     float* cert_tmp = nullptr; float* cert = nullptr;
     uint8_t* mask = nullptr;     // certainty as the checker writes it (u8 {0,255})
     int* q0_main = nullptr;      // the XCD the caller's queue deals block 0 of a launch to (written by prep_input_kernel, read by the look-ahead mask's long-lived kernels)
@@ -1155,6 +1160,7 @@ struct fav_stream {
         if (done_host) (void)hipHostFree(done_host);       // (retired_host lives in the same allocation)
         for (auto& pf : pref) { if (pf.done) (void)hipEventDestroy(pf.done); (void)hipFree(pf.mask); (void)hipFree(pf.cert); }
         for (int i = 0; i < NSIDE; ++i) (void)hipFree(side_cert_tmp[i]);
+        (void)hipFree(scaled_in8); (void)hipFree(scaled_out);
         (void)hipFree(q0_main); (void)hipFree(state); (void)hipFree(in8); (void)hipFree(cert_tmp); (void)hipFree(cert); (void)hipFree(mask); (void)hipFree(ws); (void)hipFree(png_ws);
     }
 };
@@ -1271,12 +1277,23 @@ extern "C" int fav_stream_first_frame(fav_stream* s, const uint8_t* frame_rgb_hw
     FAV_HIP(hipSetDevice(s->net->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     ++s->frame_counter;
+    fav_net* fn = s->img_net ? s->img_net : s->net;      // image model: 3 content channels (the zero prior / mask planes meet zero weights)
+    if (s->sHs) {      // core.lua:127-130,150-152: resampled before the model, the result resampled back to H x W (= Ho x Wo) into the state
+        int rc = launch_scale_prep(frame_rgb_hwc, s->H, s->W, s->sHs, s->sWs, s->net->pad, s->scaled_in8, st,
+                                   s->img_net ? 0 : s->opts.fill_random, s->opts.seed, s->frame_counter);
+        if (rc) return rc;
+        s->last_st = st; s->ran = true; s->last_scaled = true;
+        rc = state_for_writing(s, st); if (rc) return rc;
+        rc = fn->forward_padded(s->scaled_in8, s->sHs, s->sWs, s->scaled_out, nullptr, st);
+        if (!rc) rc = launch_scale_planar(s->scaled_out, s->state, 3, s->sHo, s->sWo, s->Ho, s->Wo, st);
+        if (rc) { state_writing_failed(s); return rc; }
+        return stream_finish(s, out_rgb_f32, out_rgb8_hwc, st);
+    }
     // the image model sees only the three content channels (core.lua:146): no fill there
     int rc = launch_prep_input(frame_rgb_hwc, nullptr, 0, 0, nullptr, nullptr, s->opts.border_mode, s->H, s->W, s->net->pad, s->in8, st,
                                s->img_net ? 0 : s->opts.fill_random, s->opts.seed, s->frame_counter);
     if (rc) return rc;
-    s->last_st = st; s->ran = true;
-    fav_net* fn = s->img_net ? s->img_net : s->net;      // image model: 3 content channels (the zero prior / mask planes meet zero weights)
+    s->last_st = st; s->ran = true; s->last_scaled = false;
     rc = state_for_writing(s, st); if (rc) return rc;
     rc = fn->forward_padded(s->in8, s->H, s->W, s->state, nullptr, st); if (rc) { state_writing_failed(s); return rc; }
     return stream_finish(s, out_rgb_f32, out_rgb8_hwc, st);
@@ -1290,8 +1307,43 @@ extern "C" int fav_stream_set_image_net(fav_stream* s, fav_net* image_net)
         FAV_REQUIRE(image_net->pad == s->net->pad, "fav_stream_set_image_net: image model pads %d px, video model %d px (both read the same padded input)", image_net->pad, s->net->pad);
         int Ho, Wo; image_net->out_size(s->H, s->W, &Ho, &Wo);
         FAV_REQUIRE(Ho == s->Ho && Wo == s->Wo, "fav_stream_set_image_net: the image model maps %dx%d to %dx%d, the video model to %dx%d", s->W, s->H, Wo, Ho, s->Wo, s->Ho);
+        if (s->sHs) {
+            image_net->out_size(s->sHs, s->sWs, &Ho, &Wo);
+            FAV_REQUIRE(Ho == s->sHo && Wo == s->sWo, "fav_stream_set_image_net: the image model maps the scaled %dx%d to %dx%d, the video model to %dx%d", s->sWs, s->sHs, Wo, Ho, s->sWo, s->sHo);
+        }
     }
     s->img_net = image_net;
+    return FAV_OK;
+}
+
+extern "C" int fav_stream_set_single_image_size(fav_stream* s, int Hs, int Ws)
+{
+    FAV_REQUIRE(s, "fav_stream_set_single_image_size: null stream");
+    FAV_HIP(hipSetDevice(s->net->device));
+    if (Hs == 0 && Ws == 0) {      // back to the unscaled path (hipFree waits for the frames that still read the buffers)
+        (void)hipFree(s->scaled_in8); (void)hipFree(s->scaled_out);
+        s->scaled_in8 = s->scaled_out = nullptr; s->sHs = s->sWs = s->sHo = s->sWo = 0;
+        return FAV_OK;
+    }
+    if (s->Ho != s->H || s->Wo != s->W) {
+        set_error("fav_stream_set_single_image_size: the network maps %dx%d frames to %dx%d; the result is scaled back to the frame's size (core.lua:151), "
+                  "which must therefore be the size of the stylised frames (both sides multiples of 4 for the canonical models)", s->W, s->H, s->Wo, s->Ho);
+        return FAV_EUNSUPPORTED;
+    }
+    const int pad = s->net->pad;
+    FAV_REQUIRE(Hs > 0 && Ws > 0 && pad < Hs && pad < Ws, "fav_stream_set_single_image_size: %dx%d is not larger than the reflection padding %d", Ws, Hs, pad);
+    int Ho, Wo; s->net->out_size(Hs, Ws, &Ho, &Wo);
+    FAV_REQUIRE(Ho >= 1 && Wo >= 1, "fav_stream_set_single_image_size: %dx%d is too small for the architecture", Ws, Hs);
+    if (s->img_net) {
+        int Hi, Wi; s->img_net->out_size(Hs, Ws, &Hi, &Wi);
+        FAV_REQUIRE(Hi == Ho && Wi == Wo, "fav_stream_set_single_image_size: the image model maps %dx%d to %dx%d, the video model to %dx%d", Ws, Hs, Wi, Hi, Wo, Ho);
+    }
+    float* in8 = nullptr; float* out = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&in8), (size_t)(Hs + 2 * pad) * (Ws + 2 * pad) * 32) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&out), (size_t)3 * Ho * Wo * 4) != hipSuccess) {
+        (void)hipFree(in8); return hip_fail(hipErrorOutOfMemory, "hipMalloc(scaled single-image buffers)"); }
+    (void)hipFree(s->scaled_in8); (void)hipFree(s->scaled_out);
+    s->scaled_in8 = in8; s->scaled_out = out; s->sHs = Hs; s->sWs = Ws; s->sHo = Ho; s->sWo = Wo;
     return FAV_OK;
 }
 
@@ -1313,7 +1365,7 @@ static int stream_next(fav_stream* s, const uint8_t* frame, const float* bw, con
                                s->opts.fill_random, s->opts.seed, s->frame_counter, s->q0_main);
         if (rc) return rc;
     }
-    s->last_st = st; s->ran = true;
+    s->last_st = st; s->ran = true; s->last_scaled = false;
     rc = state_for_writing(s, st); if (rc) return rc;       // (the prior was read from the previous state above)
     { TraceRange tr_net("fav:network"); rc = s->net->forward_padded(s->in8, s->H, s->W, s->state, nullptr, st); }
     if (rc) { state_writing_failed(s); return rc; }
@@ -1533,6 +1585,7 @@ extern "C" int fav_stream_output_size(const fav_stream* s, int* Ho, int* Wo)
 extern "C" int fav_stream_get_input_f32(const fav_stream* s, float* in7, fav_hipstream_t stream)
 {
     FAV_REQUIRE(s && in7 && s->frame_counter > 0, "fav_stream_get_input_f32: no frame has been assembled yet");
+    FAV_REQUIRE(!s->last_scaled, "fav_stream_get_input_f32: the last frame ran at the scaled single-image size (this view is the H x W input)");
     FAV_HIP(hipSetDevice(s->net->device));
     return launch_unpad_input(s->in8, s->H, s->W, s->net->pad, in7, static_cast<hipStream_t>(stream));
 }

@@ -45,6 +45,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -562,6 +563,15 @@ void run_stream(const Opt& o, fav_net* net, fav_net* net_img, int nwriters, Stre
             if (!o.s("temporal_eval_file").empty() && (Wo != W || Ho != H))
                 die("-temporal_eval_file: the stylised frames (" + std::to_string(Wo) + "x" + std::to_string(Ho) + ") are larger than the flow; the reference's func_eval fails on such sizes as well (fav.lua:128-151)");
             if (net_img) check(fav_stream_set_image_net(fs, net_img), "fav_stream_set_image_net");
+            if (o.d("scale_factor") != 1.0) {            // img:view(1, 3, H * f, W * f) (core.lua:130) needs whole numbers
+                const double f = o.d("scale_factor"), hs = H * f, ws = W * f;
+                if (std::fabs(hs - std::round(hs)) > 1e-9 * hs || std::fabs(ws - std::round(ws)) > 1e-9 * ws || hs < 0.5 || ws < 0.5 || hs > 1e6 || ws > 1e6) {
+                    char msg[256];
+                    snprintf(msg, sizeof msg, "-scale_factor %s: %dx%d frames would be stylised at %gx%g; both sides must be whole numbers", o.s("scale_factor").c_str(), W, H, ws, hs);
+                    die(msg);
+                }
+                check(fav_stream_set_single_image_size(fs, (int)std::round(hs), (int)std::round(ws)), "-scale_factor");
+            }
             const size_t n = (size_t)W * H, no = (size_t)Wo * Ho;
             if (gpu_png && Wo > 9000) die("-png_encoder gpu encodes rows of up to 9000 pixels (one image row lives in a CU's LDS); pass -png_encoder host for " + std::to_string(Wo) + "-wide frames");
             if (gpu_png) {
@@ -752,7 +762,12 @@ int main(int argc, char** argv)
         die("Must give -flow_pattern and -occlusions_pattern");                                              // fav.lua:180-182
     if (o.i("gpu") < 0) die("-gpu -1: this build has no CPU backend (the CPU restatement lives in oracle/ and is test infrastructure only)");
     if (o.f("evaluate")) die("-evaluate needs the VGG-16 perceptual-loss network: outside the hot-path scope (DESIGN.md)");
-    if (o.d("scale_factor") != 1.0) die("-scale_factor != 1 is not supported");
+    {   // core.lua:127-130,150-152: frames without a prior are stylised at H*f x W*f and scaled back
+        const std::string sf = o.s("scale_factor");
+        char* end = nullptr;
+        const double f = strtod(sf.c_str(), &end);
+        if (sf.empty() || end == sf.c_str() || *end != '\0' || !std::isfinite(f) || f <= 0.0) die("-scale_factor must be a number above 0, not '" + sf + "'");
+    }
     if (o.s("fill_occlusions") != "vgg-mean" && o.s("fill_occlusions") != "uniform-random") die("-fill_occlusions must be vgg-mean or uniform-random");
     if (o.s("png_encoder") != "gpu" && o.s("png_encoder") != "host") die("-png_encoder must be gpu (the file's bytes are produced on the device) or host (zlib, -png_level)");
     if (o.s("precision") != "fp32" && o.s("precision") != "bf16") die("-precision must be fp32 (parity mode) or bf16 (bf16 operands in the 3x3 residual convolutions)");

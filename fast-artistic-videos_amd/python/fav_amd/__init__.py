@@ -72,6 +72,7 @@ EXPORTS = [
     "fav_write_png_rgb8_host", "fav_free_host",
     "fav_vr_create", "fav_vr_destroy", "fav_vr_face", "fav_vr_finish_frame", "fav_vr_output_sizes", "fav_vr_get_f32",
     "fav_vr_map_host", "fav_temporal_loss_host", "fav_sequential_sum_f32", "fav_read_flo_into_host", "fav_read_pnm_into_host", "fav_net_set_precision", "fav_net_check", "fav_net_set_shared_device", "fav_net_forget_stream",
+    "fav_scale_bicubic_f32", "fav_stream_set_single_image_size",
 ]
 
 
@@ -158,6 +159,15 @@ def conv2d(x, weight, bias=None, stride=1, pad=0, gamma=None, beta=None, eps=1e-
     out = torch.empty((cout, oh, ow), dtype=torch.float32, device=x.device)
     _check(lib().fav_conv2d_nchw_f32(_p(x), cin, h, w, _p(weight), _p(bias), cout, k, stride, pad, _p(gamma), _p(beta),
                                      C.c_float(eps), 1 if relu else 0, _p(out), _stream()))
+    return out
+
+
+def scale_bicubic(x, hd: int, wd: int):
+    """image.scale(x, wd, hd, 'bicubic') [recalled] of a float [C][H][W] tensor: the resampling behind -scale_factor."""
+    torch = _torch(); _chk_f32(x, "x")
+    c, h, w = x.shape
+    out = torch.empty((c, hd, wd), dtype=torch.float32, device=x.device)
+    _check(lib().fav_scale_bicubic_f32(_p(x), _p(out), c, h, w, hd, wd, _stream()))
     return out
 
 
@@ -299,6 +309,10 @@ class Stream:
     def set_image_net(self, img_net: Optional[Net]):
         self._img = img_net      # keep alive
         _check(lib().fav_stream_set_image_net(self.h, img_net.h if img_net is not None else None))
+
+    def set_single_image_size(self, hs: int, ws: int):
+        """-scale_factor: frames without a prior run at hs x ws and are scaled back to H x W (0, 0: the unscaled path)"""
+        _check(lib().fav_stream_set_single_image_size(self.h, hs, ws))
 
     def _outs(self, dev, want_f32, want_u8):
         torch = _torch()

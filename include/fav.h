@@ -89,6 +89,15 @@ int fav_consistency_u8(const float* flow1_flo, const float* flow2_flo, const uin
  * 1 - maxpool_{r x r, stride 1, pad r/2}(1 - cert), window truncated at the borders. cert [H][W]. */
 int fav_min_filter_f32(const float* cert, float* out, int H, int W, int r, fav_hipstream_t stream);
 
+/* ---- bicubic resampling ------------------------------------------------------------------------
+ * image.scale(src, Wd, Hd, 'bicubic') on a float tensor [Torch7 `image`, recalled: the package is not vendored], the resampling
+ * behind -scale_factor (fast_artistic_video_core.lua:128,151).  Separable, the width first into an fp32 intermediate; along an axis
+ * scale = (float)(src_len-1)/(float)(dst_len-1), sample di < dst_len-1 is the Catmull-Rom cubic through s[i-1..i+2] at
+ * x = di*scale - i (i = floor), with the missing neighbour at either end extrapolated linearly (2*p1 - p2, 2*p2 - p1); the last sample
+ * is s[src_len-1]; equal lengths copy; a one-sample source is repeated.  No clamping, no antialiasing, any factor.
+ * src [C][Hs][Ws], dst [C][Hd][Wd], contiguous fp32, device pointers. */
+int fav_scale_bicubic_f32(const float* src, float* dst, int C, int Hs, int Ws, int Hd, int Wd, fav_hipstream_t stream);
+
 /* ---- A6/A7: VGG preprocessing + 7-channel input assembly --------------------------------------
  * Replaces run_next_image's input construction (fast_artistic_video_core.lua:161-171) and the first
  * frame's (:133-138) with fill_occlusions = vgg-mean; preprocess.lua:57-62.
@@ -191,6 +200,22 @@ void fav_stream_destroy(fav_stream* s);
  * without a prior (fav_stream_first_frame).  NULL restores 'self' (the video model with an all-occluded prior).  The
  * image model must use the same leading reflection padding as the video model.  Not owned by the stream. */
 int fav_stream_set_image_net(fav_stream* s, fav_net* image_net);
+/* -scale_factor (fast_artistic_video_core.lua:127-130,150-152): frames WITHOUT a prior (fav_stream_first_frame) are resampled to
+ * Hs x Ws (fav_scale_bicubic_f32's arithmetic on the byte / 255 image) before the model, the model runs at that size -- the image
+ * model when one is set, its padding rule unchanged -- and the de-processed result is resampled to the stream's H x W, which is
+ * what is returned, saved and kept as the recurrent state.  0, 0 restores the unscaled path.  fav_stream_next_frame_* are untouched:
+ * the frame after a scaled one runs at H x W on the H x W state.
+ *   - the stylised frames must have the frames' size (Ho == H, Wo == W: H and W multiples of 4 for the canonical models), because
+ *     the reference scales back to W x H exactly: otherwise FAV_EUNSUPPORTED;
+ *   - Hs x Ws must be a size fav_stream_create would accept (larger than the reflection padding, non-empty network output):
+ *     otherwise FAV_EINVAL;
+ *   - the scaled input and the scaled output are buffers of the stream, allocated by this call, not per frame;
+ *   - a fav_net keeps ONE activation arena: when frames at both sizes run through the same network (the video model as its own image
+ *     model without -create_inconsistent) the arena is rebuilt once, when frame 2 arrives at full size;
+ *   - deviation: with model_img == 'self' the reference itself stops in torch.cat (core.lua:135 builds the fill at H x W next to an
+ *     Hs x Ws image).  Here the evident intent is implemented: the prior and mask planes, and the uniform-random fill's (y, x)
+ *     key, are those of the scaled grid. */
+int fav_stream_set_single_image_size(fav_stream* s, int Hs, int Ws);
 /* first frame / -create_inconsistent: core.lua:121-158 with model_img == 'self'.
  * frame_rgb_hwc: P6 payload [H][W][3] u8.  out_rgb_f32 [3][H][W] float RGB (deprocessed, unclamped)
  * and/or out_rgb8_hwc [H][W][3] u8 (image.save quantisation); either may be NULL. */
@@ -227,7 +252,8 @@ int fav_stream_set_host_ordered(fav_stream* s, int on);
 int fav_stream_get_state(fav_stream* s, float* state_rgb_f32, fav_hipstream_t stream);
 int fav_stream_set_state(fav_stream* s, const float* state_rgb_f32, fav_hipstream_t stream);
 /* test view: the 7-channel network input of the LAST frame as run_next_image assembles it (fast_artistic_video_core.lua:161-171:
- * content | masked warped prior + fill | certainty), [7][H][W] fp32, copied out of the fused kernel's padded buffer */
+ * content | masked warped prior + fill | certainty), [7][H][W] fp32, copied out of the fused kernel's padded buffer (FAV_EINVAL
+ * right after a frame that ran at the scaled single-image size) */
 int fav_stream_get_input_f32(const fav_stream* s, float* in7, fav_hipstream_t stream);
 /* device pointer of the last certainty mask used (u8 [H][W], before the min filter) -- tests */
 const uint8_t* fav_stream_last_mask(const fav_stream* s);
