@@ -346,5 +346,7 @@ int net_pad(const fav_net* n);
 int net_in_channels(const fav_net* n);
 void net_out_size(const fav_net* n, int H, int W, int* Ho, int* Wo);
 int net_forward_padded(fav_net* n, const float* in8, int H, int W, float* out_planar, hipStream_t st);
+void net_forget_stream(const fav_net* n, hipStream_t st);      // `st` is about to be destroyed: drain it, never synchronise it again
+void net_reserve_cus(fav_net* n, int cus);                      // the persistent / stream-K grids leave at least `cus` CUs to side queues
 }  // namespace fav
 

@@ -22,6 +22,7 @@ def packs(tmp_path_factory):
 #include "s2_pack.h"
 #include "up2_pack.h"
 #include "first2d_pack.h"
+#include "fold_pack.h"
 #include <cstring>
 static long fin(const std::vector<float>& v, float* out) { if (out) memcpy(out, v.data(), v.size() * 4); return (long)v.size(); }
 extern "C" long w4(const float* w, int cin, int cout, float* out) { std::vector<float> v; fav::conv_wino4_pack(w, cin, cout, v); return fin(v, out); }
@@ -32,6 +33,7 @@ extern "C" long u2(const float* w, int cin, int cout, float* out) { std::vector<
 extern "C" long u2g(const float* w, int cin, int cout, float* out) { std::vector<float> v; fav::conv_up2w_pack_groups(w, cin, cout, v); return fin(v, out); }
 extern "C" long f2(const float* w, int cin, int cout, float* out) { std::vector<float> v; fav::conv_first2d_pack(w, cin, cout, v); return fin(v, out); }
 extern "C" long f2g(const float* w, int cin, int cout, int coutp, float* out) { std::vector<float> v; fav::conv_first2d_pack_groups(w, cin, cout, coutp, v); return fin(v, out); }
+extern "C" long fold(const float* w, int cin, int cout, int cinp, int k, float* out) { std::vector<float> v; fav::conv_fold_pack(w, cin, cinp, cout, k, v); return fin(v, out); }
 ''')
     so = d / "libwidepack.so"
     subprocess.check_call(["g++", "-O2", "-shared", "-fPIC", "-I", CSRC, "-o", str(so), str(src)])
@@ -87,6 +89,30 @@ def test_first_layer_groups_of_32(packs, cin, cout, coutp):
         else:
             assert np.array_equal(blk, packs("f2", sub))
     assert whole.any()
+
+
+@pytest.mark.parametrize("cout,cin,cinp,k", [(3, 32, 32, 9), (3, 16, 16, 3), (3, 12, 16, 9)])
+def test_row_folded_last_layer_packing(packs, cout, cin, cinp, k):
+    """the row-folded last layer (kernels_fold.hip) reads 2 k + 1 blocks of [32 rows n = co * k + kx][cinp channels]: block ky < k holds filter
+    row ky, w[co][ci][ky][kx]; block k + m, m = 0 .. k, the merged row W[m - 1] + W[m] (W[-1] = W[k] = 0) that a x2-upsampled input meets --
+    summed in double and rounded to float once.  Rows >= cout * k and channels >= cin are zero.  Cases: the canonical c9s1-3 behind 32
+    channels, the smallest pitch, and a real channel count below the pitch (the zero columns)."""
+    rng = np.random.default_rng(1000 * cin + k)
+    w = rng.standard_normal((cout, cin, k, k)).astype(np.float32)
+    # neighbouring filter rows of opposite sign and nearby magnitude: their sum cancels most leading bits, so a float sum of anything but
+    # the two exact operands, or a double sum that is not rounded once, would show
+    for co, ci, ky in [(0, 0, 0), (1, cin - 1, k - 2), (2, cin // 2, k // 2)]:
+        w[co, ci, ky + 1] = -w[co, ci, ky] * (1 + rng.uniform(-1e-3, 1e-3, k)).astype(np.float32)
+    w[0, 1, 1] = np.nextafter(-w[0, 1, 0], np.float32(np.inf))
+    got = packs("fold", w, cinp, k)
+    assert got.size == (2 * k + 1) * 32 * cinp
+    want = np.zeros((2 * k + 1, 32, cinp), np.float32)
+    rows = w.transpose(2, 0, 3, 1).reshape(k, cout * k, cin)                   # [ky][co * k + kx][ci]
+    want[:k, :cout * k, :cin] = rows
+    padded = np.zeros((k + 2, cout * k, cin), np.float64); padded[1:k + 1] = rows      # padded[m] = W[m - 1]
+    want[k:, :cout * k, :cin] = (padded[:k + 1] + padded[1:]).astype(np.float32)
+    assert np.array_equal(got, want.ravel())
+    assert not got.reshape(2 * k + 1, 32, cinp)[:, cout * k:].any() and not got.reshape(2 * k + 1, 32, cinp)[:, :, cin:].any()
 
 
 def test_fixed_point_words_of_the_accumulator_statistics():
