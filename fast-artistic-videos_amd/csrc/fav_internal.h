@@ -327,6 +327,9 @@ int launch_vr_rotate(const float* src, float* dst, int H, int W, int mode, hipSt
 int launch_vr_accum(float* acc, const float* w, const float* div, size_t n, int first, hipStream_t st);
 int launch_vr_cert(const uint8_t* cert_u8, const float* m0, const float* m1, const float* m2, const float* m3, float* out, size_t n,
                    hipStream_t st);
+// launch_consistency + launch_vr_cert in one pass: mask_out[i] = consistency_pixel(bw, fw, structure, avg), out = max(mask / 255, m0..m3)
+int launch_vr_check_cert(const float* bw_flo, const float* fw_flo, const float* structure, const float* avg, const float* m0,
+                         const float* m1, const float* m2, const float* m3, uint8_t* mask_out, float* out, int H, int W, hipStream_t st);
 int launch_vr_prior(const float* lfw, const float* border, const float* grad, const float* cert, const float* m, const float* m2,
                     float* out, size_t n, hipStream_t st);
 int launch_vr_blend(const float* seg, const float* borders, const float* g, const float* anti, float* out, size_t n, hipStream_t st);

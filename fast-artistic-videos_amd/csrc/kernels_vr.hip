@@ -7,6 +7,7 @@
 // perspective / equirectangular warps themselves are the A2 kernel (kernels_frame.hip: warp_kernel) fed with static maps.
 // Compiled with -ffp-contract=off: every expression rounds like the CPU restatement (oracle/vr_oracle.py).
 #include "fav_internal.h"
+#include "consistency_pixel.h"
 
 namespace fav {
 namespace {
@@ -59,6 +60,26 @@ __global__ __launch_bounds__(256) void vr_cert_kernel(const uint8_t* cert_u8, co
     if (m2) b = fmaxf(b, m2[i]);
     if (m3) b = fmaxf(b, m3[i]);
     out[i] = cert_u8 ? fmaxf((float)cert_u8[i] / 255.f, b) : b;       // image.load(…, 1): byte / 255
+}
+
+// consistency_kernel (kernels_consistency.hip) + vr_cert_kernel in one pass: the checker's byte of this pixel (consistency_pixel.h,
+// bit-exact with the reference binary; structure / avg_ptr null = its 3-argument mode) goes to mask_out AND, as the same byte / 255,
+// into the max with the border masks -- the certainty file's round trip (write, poll, read, upload) without the file.
+__global__ __launch_bounds__(256) void vr_check_cert_kernel(const float2* bw, const float2* fw, const float* structure, const float* avg_ptr,
+                                                            const float* m0, const float* m1, const float* m2, const float* m3,
+                                                            uint8_t* mask_out, float* out, int W, int H)
+{
+    const int ay = blockIdx.y, ax = blockIdx.x * 256 + threadIdx.x;
+    if (ax >= W) return;
+    const size_t i = (size_t)ay * W + ax;
+    const uint8_t m = consistency_pixel(bw, fw, structure, avg_ptr, ax, ay, W, H);
+    float b = 0.f;
+    if (m0) b = fmaxf(b, m0[i]);
+    if (m1) b = fmaxf(b, m1[i]);
+    if (m2) b = fmaxf(b, m2[i]);
+    if (m3) b = fmaxf(b, m3[i]);
+    mask_out[i] = m;
+    out[i] = fmaxf((float)m / 255.f, b);                               // the conversion of vr_cert_kernel, on the same byte
 }
 
 // :281-293: mask = max(g, ceil(g) * (1 - cert)) * m;  out = warped * (1 - mask) + border * mask
@@ -207,6 +228,16 @@ int launch_vr_cert(const uint8_t* cert_u8, const float* m0, const float* m1, con
 {
     hipLaunchKernelGGL(vr_cert_kernel, grid1(n), dim3(256), 0, st, cert_u8, m0, m1, m2, m3, out, n);
     FAV_LAUNCH_CHECK("vr_cert_kernel");
+    return FAV_OK;
+}
+
+int launch_vr_check_cert(const float* bw_flo, const float* fw_flo, const float* structure, const float* avg, const float* m0,
+                         const float* m1, const float* m2, const float* m3, uint8_t* mask_out, float* out, int H, int W, hipStream_t st)
+{
+    FAV_REQUIRE(H >= 1 && W >= 1 && H <= 65535, "vr_check_cert_kernel: a %dx%d face does not fit the launch grid", W, H);
+    hipLaunchKernelGGL(vr_check_cert_kernel, dim3((W + 255) / 256, H), dim3(256), 0, st, reinterpret_cast<const float2*>(bw_flo),
+                       reinterpret_cast<const float2*>(fw_flo), structure, avg, m0, m1, m2, m3, mask_out, out, W, H);
+    FAV_LAUNCH_CHECK("vr_check_cert_kernel");
     return FAV_OK;
 }
 

@@ -5,6 +5,9 @@
 //                         vr_helper.lua:3-96), optional cube->equirectangular map (vr_helper.lua:99-184)
 //   fav_vr_face         : one cube face = func_load_cert (:204-237) -> min filter (core.lua:207) -> func_make_last_frame_warped
 //                         (:239-302) -> input assembly + network (core.lua:121-180) -> last_segments[mode] (:525)
+//   fav_vr_face_flow    : the same face with the certainty computed here from the two flows (the checker's arithmetic, consistency_pixel.h)
+//                         instead of read from the file stylizeVRVideo_deepflow.sh:59-64 has six makeOptFlow.sh pipelines write;
+//                         fav_vr_prefetch_mask starts that mask ahead of time on a side stream
 //   fav_vr_finish_frame : blend_other_sides (:454-509) -> prev_last_segments, median filter (utils.lua:151-159), equirectangular
 //                         image and cube-map strip (:527-557)
 // Faces are planar fp32 [3][hplus][wplus] on the device; six faces per frame in processing order (file ids 6,1,2,5,3,4 =
@@ -161,9 +164,26 @@ struct fav_vr {
     float* strip = nullptr; float* equi = nullptr; float* cube = nullptr;
     int FH = 0, FW = 0;                   // filtered face size
     int cube_h = 0, cube_w = 0;
+    // the consistency check on the device (fav_vr_face_flow): mask of a check made on the caller's stream, the mask the last face used
+    // (that one or a look-ahead slot's), and the structure workspaces of the checker's 4-argument mode -- one per queue, each allocated
+    // by the first structure-mode face that runs on it
+    uint8_t* mask_u8 = nullptr; const uint8_t* last_mask = nullptr;
+    void* ws = nullptr; void* side_ws = nullptr;
+    // look-ahead (fav_vr_prefetch_mask): one side stream, one slot per face of a frame (slot = mode); everything here is created by the
+    // first look-ahead
+    hipStream_t side = nullptr; hipEvent_t ev_in = nullptr;
+    struct Pending {
+        uint8_t* mask = nullptr; float* cert_tmp = nullptr; hipEvent_t done = nullptr;
+        bool valid = false; int i = 0; const uint8_t* frame = nullptr; const float* bw = nullptr; const float* fw = nullptr; bool structure = false;
+    };
+    Pending pend[6];
     ~fav_vr()
     {
         if (vid) (void)hipSetDevice(net_device(vid));
+        if (side) { (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); }
+        if (ev_in) (void)hipEventDestroy(ev_in);
+        for (auto& p : pend) { if (p.done) (void)hipEventDestroy(p.done); (void)hipFree(p.mask); (void)hipFree(p.cert_tmp); }
+        (void)hipFree(mask_u8); (void)hipFree(ws); (void)hipFree(side_ws);
         for (auto p : map) (void)hipFree(p);
         for (auto p : mask) (void)hipFree(p);
         for (auto p : grad) (void)hipFree(p);
@@ -265,6 +285,7 @@ extern "C" int fav_vr_create(fav_net* video_net, fav_net* image_net_or_null, int
     ok = ok && dmalloc(&v->tmp_rot, 3 * n) && dmalloc(&v->tmp_warp, 3 * n) && dmalloc(&v->border, 3 * n) && dmalloc(&v->lfw, 3 * n) &&
          dmalloc(&v->prior, 3 * n) && dmalloc(&v->flow_lua, 2 * n) && dmalloc(&v->cert_tmp, n) && dmalloc(&v->cert, n) &&
          dmalloc(&v->in8, (size_t)(hplus + 2 * pad) * (wplus + 2 * pad) * 8);
+    ok = ok && hipMalloc(reinterpret_cast<void**>(&v->mask_u8), n) == hipSuccess;
     if (v->cube_w) ok = ok && dmalloc(&v->cube, 3 * (size_t)v->cube_h * v->cube_w);
     if (o.out_equi_w > 0 && o.out_equi_h > 0) {
         std::vector<float> m;
@@ -292,34 +313,89 @@ static int add_border(fav_vr* v, const float* src, int rot, int map_k, bool divi
     return launch_vr_accum(v->border, v->tmp_warp, divide ? v->mask_all_div : nullptr, v->n, first ? 1 : 0, st);
 }
 
-extern "C" int fav_vr_face(fav_vr* v, int i, const uint8_t* frame_rgb_hwc, const float* backward_flo, const uint8_t* cert_pgm,
-                           float* out_rgb_f32, fav_hipstream_t stream)
+static bool vr_temporal(const fav_vr* v, int i) { return i >= 7 && !v->o.create_inconsistent; }
+
+// the masks of the already stylised neighbours that enter face `mode`'s border certainty (:210-231), null where none does
+static void border_masks(const fav_vr* v, int mode, const float* m[4])
 {
-    FAV_REQUIRE(v && frame_rgb_hwc && i >= 1, "fav_vr_face: bad argument");
+    enum { L = 0, R = 1, T = 2, B = 3 };
+    const bool bd = !v->o.create_inconsistent_border;
+    m[0] = bd && (mode == 1 || mode >= 3) ? v->mask[L] : nullptr;
+    m[1] = bd && (mode >= 2) ? v->mask[R] : nullptr;
+    m[2] = bd && (mode >= 4) ? v->mask[T] : nullptr;
+    m[3] = bd && (mode >= 4) ? v->mask[B] : nullptr;
+}
+
+// the checker on queue `q`: makeOptFlow_deepflow.sh:59 `consistencyChecker backward forward reliable [frame]` -> mask, and
+// cert_tmp = max(mask / 255, border masks).  The structure plane is launch_structure in its stand-alone operator form (as
+// fav_consistency_u8 calls it) on `*ws`, the workspace of this queue.
+static int check_cert(fav_vr* v, int mode, const uint8_t* frame, const float* bw, const float* fw, bool use_structure, void** ws,
+                      uint8_t* mask, float* cert_tmp, hipStream_t q)
+{
+    const float* structure = nullptr; const float* avg = nullptr;
+    if (use_structure) {
+        const size_t ws_bytes = fav_consistency_workspace_bytes(v->W, v->H, 1);
+        if (!*ws) FAV_HIP(hipMalloc(ws, ws_bytes));
+        int rc = launch_structure(frame, v->W, v->H, *ws, ws_bytes, &structure, &avg, q); if (rc) return rc;
+    }
+    const float* m[4]; border_masks(v, mode, m);
+    return launch_vr_check_cert(bw, fw, structure, avg, m[0], m[1], m[2], m[3], mask, cert_tmp, v->H, v->W, q);
+}
+
+// The look-ahead slot that holds exactly this face's mask, or null.  Whatever else is pending for this face or an earlier one is
+// dropped: its kernels run to their end on the side stream and nobody reads what they wrote.
+static fav_vr::Pending* take_pending(fav_vr* v, int i, const uint8_t* frame, const float* bw, const float* fw, bool flow, bool structure)
+{
+    fav_vr::Pending* hit = nullptr;
+    for (auto& p : v->pend) {
+        if (!p.valid || p.i > i) continue;
+        p.valid = false;
+        if (flow && p.i == i && p.frame == frame && p.bw == bw && p.fw == fw && p.structure == structure) hit = &p;
+    }
+    return hit;
+}
+
+// where a temporal face's certainty comes from: the file's bytes (fav_vr_face) or the two flows (fav_vr_face_flow)
+struct CertSource { const char* who; const uint8_t* cert_pgm; bool flow; const float* fw; bool structure; };
+
+static int vr_face(fav_vr* v, int i, const uint8_t* frame_rgb_hwc, const float* backward_flo, const CertSource& cs, float* out_rgb_f32,
+                   fav_hipstream_t stream)
+{
+    FAV_REQUIRE(v && frame_rgb_hwc && i >= 1, "%s: bad argument", cs.who);
     FAV_HIP(hipSetDevice(net_device(v->vid)));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int mode = (i - 1) % 6, H = v->H, W = v->W, pad = net_pad(v->vid);
     const size_t n = v->n;
     const bool single = v->o.create_inconsistent ? (i % 6 == 1) : (i == 1);      // fast_artistic_video_vr.lua:304-310
-    const bool temporal = i >= 7 && !v->o.create_inconsistent;
+    const bool temporal = vr_temporal(v, i);
     enum { L = 0, R = 1, T = 2, B = 3 };
     int rc;
+    if (temporal && cs.flow) FAV_REQUIRE(cs.fw, "%s: face %d needs the forward flow (forward_flo is NULL)", cs.who, i);
+    fav_vr::Pending* ahead = take_pending(v, i, frame_rgb_hwc, backward_flo, cs.fw, temporal && cs.flow, cs.structure);
     if (single) {
         rc = launch_vr_prep(frame_rgb_hwc, nullptr, nullptr, v->img ? 0 : v->o.fill_random, v->o.seed, (unsigned)i, H, W, pad, v->in8, st);
         if (rc) return rc;
         rc = net_forward_padded(v->img ? v->img : v->vid, v->in8, H, W, v->last[mode], st); if (rc) return rc;
     } else {
-        if (temporal) FAV_REQUIRE(backward_flo && cert_pgm && v->have_prev, "fav_vr_face: face %d needs the flow, the certainty and a finished previous frame", i);
+        if (temporal) FAV_REQUIRE(backward_flo && (cs.flow || cs.cert_pgm) && v->have_prev, "%s: face %d needs the flow, the certainty and a finished previous frame", cs.who, i);
         for (int k = 0; k < mode && !v->o.create_inconsistent_border; ++k)
-            FAV_REQUIRE(v->have_last[k], "fav_vr_face: faces must be processed in order (face %d of this frame is missing)", k);
+            FAV_REQUIRE(v->have_last[k], "%s: faces must be processed in order (face %d of this frame is missing)", cs.who, k);
         // ---- func_load_cert (:204-237) + min filter (core.lua:207)
         const bool bd = !v->o.create_inconsistent_border;
-        const float* ml = bd && (mode == 1 || mode >= 3) ? v->mask[L] : nullptr;
-        const float* mr = bd && (mode >= 2) ? v->mask[R] : nullptr;
-        const float* mt = bd && (mode >= 4) ? v->mask[T] : nullptr;
-        const float* mb = bd && (mode >= 4) ? v->mask[B] : nullptr;
-        rc = launch_vr_cert(temporal ? cert_pgm : nullptr, ml, mr, mt, mb, v->cert_tmp, n, st); if (rc) return rc;
-        rc = launch_min_filter_f32(v->cert_tmp, v->cert, H, W, v->o.occlusions_min_filter, st); if (rc) return rc;
+        const float* cert_tmp = v->cert_tmp;
+        if (temporal && cs.flow) {
+            if (ahead) {                                                          // computed ahead of time on the side stream
+                FAV_HIP(hipStreamWaitEvent(st, ahead->done, 0));
+                cert_tmp = ahead->cert_tmp; v->last_mask = ahead->mask;
+            } else {
+                rc = check_cert(v, mode, frame_rgb_hwc, backward_flo, cs.fw, cs.structure, &v->ws, v->mask_u8, v->cert_tmp, st); if (rc) return rc;
+                v->last_mask = v->mask_u8;
+            }
+        } else {
+            const float* m[4]; border_masks(v, mode, m);
+            rc = launch_vr_cert(temporal ? cs.cert_pgm : nullptr, m[0], m[1], m[2], m[3], v->cert_tmp, n, st); if (rc) return rc;
+        }
+        rc = launch_min_filter_f32(cert_tmp, v->cert, H, W, v->o.occlusions_min_filter, st); if (rc) return rc;
         // ---- func_make_last_frame_warped (:239-302)
         bool have_border = false;
         if (bd) {
@@ -364,6 +440,51 @@ extern "C" int fav_vr_face(fav_vr* v, int i, const uint8_t* frame_rgb_hwc, const
     if (out_rgb_f32) FAV_HIP(hipMemcpyAsync(out_rgb_f32, v->last[mode], 3 * n * sizeof(float), hipMemcpyDeviceToDevice, st));
     return FAV_OK;
 }
+
+extern "C" int fav_vr_face(fav_vr* v, int i, const uint8_t* frame_rgb_hwc, const float* backward_flo, const uint8_t* cert_pgm,
+                           float* out_rgb_f32, fav_hipstream_t stream)
+{
+    const CertSource cs = {"fav_vr_face", cert_pgm, false, nullptr, false};
+    return vr_face(v, i, frame_rgb_hwc, backward_flo, cs, out_rgb_f32, stream);
+}
+
+extern "C" int fav_vr_face_flow(fav_vr* v, int i, const uint8_t* frame_rgb_hwc, const float* backward_flo, const float* forward_flo,
+                                int use_structure, float* out_rgb_f32, fav_hipstream_t stream)
+{
+    const CertSource cs = {"fav_vr_face_flow", nullptr, true, forward_flo, use_structure != 0};
+    return vr_face(v, i, frame_rgb_hwc, backward_flo, cs, out_rgb_f32, stream);
+}
+
+// Event-ordered: the side stream starts behind everything `stream` holds now (the inputs are complete there; the last reader of this
+// slot's buffers, a face enqueued earlier, is through), and the face that consumes the mask waits for the slot's event.  Two queues in
+// all.  The masks of one frame run one after the other on the one side stream, so they share one structure workspace.
+extern "C" int fav_vr_prefetch_mask(fav_vr* v, int i, const uint8_t* frame_rgb_hwc, const float* backward_flo, const float* forward_flo,
+                                    int use_structure, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(v && i >= 1, "fav_vr_prefetch_mask: bad argument");
+    if (!vr_temporal(v, i)) return FAV_OK;                                       // this face reads no mask
+    FAV_REQUIRE(frame_rgb_hwc && backward_flo && forward_flo, "fav_vr_prefetch_mask: face %d needs its frame and both flows", i);
+    FAV_HIP(hipSetDevice(net_device(v->vid)));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const unsigned ef = hipEventDisableTiming | hipEventDisableSystemFence;
+    if (!v->side) FAV_HIP(hipStreamCreateWithFlags(&v->side, hipStreamNonBlocking));
+    if (!v->ev_in) FAV_HIP(hipEventCreateWithFlags(&v->ev_in, ef));
+    const int mode = (i - 1) % 6;
+    fav_vr::Pending& p = v->pend[mode];
+    p.valid = false;
+    if (!p.mask) FAV_HIP(hipMalloc(reinterpret_cast<void**>(&p.mask), v->n));
+    if (!p.cert_tmp) FAV_HIP(hipMalloc(reinterpret_cast<void**>(&p.cert_tmp), v->n * sizeof(float)));
+    if (!p.done) FAV_HIP(hipEventCreateWithFlags(&p.done, ef));
+    FAV_HIP(hipEventRecord(v->ev_in, st));
+    FAV_HIP(hipStreamWaitEvent(v->side, v->ev_in, 0));                           // (work enqueued on `stream` after this call is not waited for)
+    int rc = check_cert(v, mode, frame_rgb_hwc, backward_flo, forward_flo, use_structure != 0, &v->side_ws, p.mask, p.cert_tmp, v->side);
+    if (rc) return rc;
+    FAV_HIP(hipEventRecord(p.done, v->side));
+    p.valid = true; p.i = i; p.frame = frame_rgb_hwc; p.bw = backward_flo; p.fw = forward_flo; p.structure = use_structure != 0;
+    return FAV_OK;
+}
+
+extern "C" const uint8_t* fav_vr_last_mask(const fav_vr* v) { return v ? v->last_mask : nullptr; }
 
 extern "C" int fav_vr_finish_frame(fav_vr* v, uint8_t* equi_rgb8_hwc, uint8_t* cubemap_rgb8_hwc, fav_hipstream_t stream)
 {
@@ -427,7 +548,8 @@ extern "C" int fav_vr_output_sizes(const fav_vr* v, int* equi_w, int* equi_h, in
 }
 
 // which: 0 last_segments[k] (this frame's raw faces), 1 prev_last_segments[k] (blended faces of the finished frame),
-//        2 median-filtered faces ([3][filt_h][filt_w]), 3 equirectangular float image, 4 cube-map float strip
+//        2 median-filtered faces ([3][filt_h][filt_w]), 3 equirectangular float image, 4 cube-map float strip,
+//        5 the last face's certainty plane after border max and erosion ([H][W])
 extern "C" int fav_vr_get_f32(const fav_vr* v, int which, int k, float* out_dev, fav_hipstream_t stream)
 {
     FAV_REQUIRE(v && out_dev && k >= 0 && k < 6, "fav_vr_get_f32: bad argument");
@@ -438,6 +560,7 @@ extern "C" int fav_vr_get_f32(const fav_vr* v, int which, int k, float* out_dev,
     else if (which == 2) { src = v->filt[k]; cnt = 3 * (size_t)v->FH * v->FW; }
     else if (which == 3) { src = v->equi; cnt = v->equi ? 3 * (size_t)v->o.out_equi_w * v->o.out_equi_h : 0; }
     else if (which == 4) { src = v->cube; cnt = v->cube ? 3 * (size_t)v->cube_h * v->cube_w : 0; }
+    else if (which == 5) { src = v->cert; cnt = v->n; }
     FAV_REQUIRE(src && cnt, "fav_vr_get_f32: nothing of kind %d", which);
     FAV_HIP(hipMemcpyAsync(out_dev, src, cnt * sizeof(float), hipMemcpyDeviceToDevice, st));
     return FAV_OK;

@@ -5,10 +5,15 @@
 // "<prefix>-%05d_equi.png" / "<prefix>-%05d_cubemap.png" (:541,552).  All compute goes through libfav's C ABI (fav_vr_*);
 // there is no CPU backend.  Not provided (rejected with a message): -evaluate, -backward, -smooth_certainty and
 // -continue_with > 1 (in the reference that option reloads per-face PNGs which func_save_image no longer writes, :521-523).
+// -forward_flow_pattern <pat> (additive; same {..} / [..] / %d tokens as -flow_pattern, e.g. flow-%d/forward_{%d}_[%d].flo): the
+// forward-backward consistency check runs on the GPU from the two flows (fav_vr_face_flow) and no certainty file is read;
+// -occlusions_pattern is then not required, and if both are given the forward flow wins.  -structure <0|1> (default 1, as
+// makeOptFlow_deepflow.sh:59 calls the checker) selects the checker's 4-argument mode on the face's frame.  At the first face of a
+// frame the masks of the faces whose files are complete already are started ahead of the faces (fav_vr_prefetch_mask).
 // Additive flags: -precision <fp32|bf16>, -warp_border <stn|cpu>, -poll_timeout <sec>, -poll_settle <sec> (host/fav_poll.h), -png_level <0..9>, -seed <n> (uniform-random fill), -timing <0|1>,
 // and -- several 360-degree videos on several GPUs (BASELINE config 5; the faces of one frame depend on each other through the
 // border priors, so the unit of sharding is the video) -- -streams <a,b,...> / -gpus <n> / -force_dist / -dry_run exactly as in
-// fav_stylize (host/fav_launcher.h): %S in -input_pattern, -flow_pattern, -occlusions_pattern and -output_prefix is the stream's
+// fav_stylize (host/fav_launcher.h): %S in -input_pattern, -flow_pattern, -forward_flow_pattern, -occlusions_pattern and -output_prefix is the stream's
 // name, stream s -> worker process s mod n, rank 0 parses the checkpoints and ncclBroadcast (RCCL) hands the packed blobs on.
 #include <hip/hip_runtime.h>
 #include <sys/stat.h>
@@ -62,6 +67,13 @@ void read_polled(const std::string& path, const favp::Poll& p, const char* what,
     check(rc, what);
 }
 
+// a finished input: there, not empty and not modified for -poll_settle seconds (what wait_for_file accepts at its first look)
+bool ready_now(const std::string& path, double settle_s)
+{
+    struct stat st;
+    return stat(path.c_str(), &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0 && favp::wall_age_seconds(st) >= settle_s;
+}
+
 void mkdirs_for(const std::string& path)
 {
     for (size_t p = 1; p < path.size(); ++p) if (path[p] == '/') mkdir(path.substr(0, p).c_str(), 0777);
@@ -76,7 +88,13 @@ int run_video(std::map<std::string, std::string>& v, std::map<std::string, bool>
     hipStream_t st; hipc(hipStreamCreate(&st), "hipStreamCreate");
     fav_vr* vr = nullptr;
     int W = 0, H = 0, ew = 0, eh = 0, cw = 0, ch = 0;
-    uint8_t *d_frame = nullptr, *d_cert = nullptr, *d_equi = nullptr, *d_cube = nullptr; float* d_flow = nullptr;
+    // -forward_flow_pattern: the check runs on the device; the six faces of a frame then have their own input buffers (a mask started
+    // ahead of its face reads them until that face is through), otherwise set 0 serves every face
+    const bool fused = !v["forward_flow_pattern"].empty(); const int use_structure = I("structure");
+    const int nset = fused ? 6 : 1;
+    uint8_t* d_frame6[6] = {}; float* d_bw6[6] = {}; float* d_fw6[6] = {}; bool loaded[6] = {};
+    uint8_t *d_cert = nullptr, *d_equi = nullptr, *d_cube = nullptr;
+    favp::Poll poll; poll.timeout_s = atof(v["poll_timeout"].c_str()); poll.settle_s = std::max(0.0, atof(v["poll_settle"].c_str()));
     std::vector<uint8_t> h_equi, h_cube;
     // -png_encoder gpu (default): the two output images leave the device as finished PNG files (fav_png_encode_rgb8); host: zlib, -png_level
     const bool gpu_png = v["png_encoder"] == "gpu";
@@ -89,8 +107,35 @@ int run_video(std::map<std::string, std::string>& v, std::map<std::string, bool>
         const int mode = (i - 1) % 6, file_idx = (i - 1) / 6 + start, face = proc_order[mode];                     // :155-156
         const std::string img_path = fmt2(v["input_pattern"], file_idx, face);
         if (!file_exists(img_path)) break;                                                                          // :160
-        uint8_t* rgb = nullptr; int w = 0, h = 0, c = 0;
-        check(fav_read_pnm_host(img_path.c_str(), &rgb, &w, &h, &c), "reading the face image");
+        const bool temporal = i >= 7 && !b["create_inconsistent"];
+        const int set = fused ? mode : 0;
+        if (fused && temporal && mode == 0) {
+            // look-ahead: the faces of this frame whose three files are complete already go to the device now and their masks start on
+            // the library's side stream; a face that is not ready yet (or does not read) is loaded in its turn, polled as ever
+            std::vector<void*> held;
+            for (int k = 0; k < 6; ++k) {
+                loaded[k] = false;
+                const std::string ip = fmt2(v["input_pattern"], file_idx, proc_order[k]);
+                const std::string bp = flow_name(v["flow_pattern"], file_idx - 1, file_idx, proc_order[k]);
+                const std::string fp = flow_name(v["forward_flow_pattern"], file_idx - 1, file_idx, proc_order[k]);
+                if (!ready_now(ip, poll.settle_s) || !ready_now(bp, poll.settle_s) || !ready_now(fp, poll.settle_s)) continue;
+                uint8_t* r8 = nullptr; float *bf = nullptr, *ff = nullptr; int iw = 0, ih = 0, ic = 0, bw_ = 0, bh_ = 0, fw_ = 0, fh_ = 0;
+                const bool ok = fav_read_pnm_host(ip.c_str(), &r8, &iw, &ih, &ic) == 0 && fav_read_flo_host(bp.c_str(), &bf, &bw_, &bh_) == 0 &&
+                                fav_read_flo_host(fp.c_str(), &ff, &fw_, &fh_) == 0 && ic == 3 && iw == W && ih == H && bw_ == W && bh_ == H && fw_ == W && fh_ == H;
+                held.push_back(r8); held.push_back(bf); held.push_back(ff);
+                if (!ok) continue;                                               // (its own turn reports what is wrong with it)
+                hipc(hipMemcpyAsync(d_frame6[k], r8, (size_t)W * H * 3, hipMemcpyHostToDevice, st), "H2D frame");
+                hipc(hipMemcpyAsync(d_bw6[k], bf, (size_t)W * H * 8, hipMemcpyHostToDevice, st), "H2D flow");
+                hipc(hipMemcpyAsync(d_fw6[k], ff, (size_t)W * H * 8, hipMemcpyHostToDevice, st), "H2D forward flow");
+                check(fav_vr_prefetch_mask(vr, i + k, d_frame6[k], d_bw6[k], d_fw6[k], use_structure, st), "fav_vr_prefetch_mask");
+                loaded[k] = true;
+            }
+            hipc(hipStreamSynchronize(st), "sync");                              // the copies have left the host buffers
+            for (void* hp : held) fav_free_host(hp);
+        }
+        const bool have = fused && temporal && loaded[mode];                     // this face's inputs are on the device already
+        uint8_t* rgb = nullptr; int w = W, h = H, c = 3;
+        if (!have) check(fav_read_pnm_host(img_path.c_str(), &rgb, &w, &h, &c), "reading the face image");
         if (c != 3) die(img_path + ": not a P6 image");
         if (!vr) {
             W = w; H = h;
@@ -103,9 +148,12 @@ int run_video(std::map<std::string, std::string>& v, std::map<std::string, bool>
             check(fav_vr_create(vid, img, H, W, &o, &vr), "fav_vr_create");
             check(fav_vr_output_sizes(vr, &ew, &eh, &cw, &ch, nullptr, nullptr), "fav_vr_output_sizes");
             if (b["out_cubemap"] && !cw) die("-out_cubemap needs square cropped faces");
-            hipc(hipMalloc(reinterpret_cast<void**>(&d_frame), (size_t)W * H * 3), "hipMalloc");
-            hipc(hipMalloc(reinterpret_cast<void**>(&d_cert), (size_t)W * H), "hipMalloc");
-            hipc(hipMalloc(reinterpret_cast<void**>(&d_flow), (size_t)W * H * 8), "hipMalloc");
+            for (int k = 0; k < nset; ++k) {
+                hipc(hipMalloc(reinterpret_cast<void**>(&d_frame6[k]), (size_t)W * H * 3), "hipMalloc");
+                hipc(hipMalloc(reinterpret_cast<void**>(&d_bw6[k]), (size_t)W * H * 8), "hipMalloc");
+                if (fused) hipc(hipMalloc(reinterpret_cast<void**>(&d_fw6[k]), (size_t)W * H * 8), "hipMalloc");
+            }
+            if (!fused) hipc(hipMalloc(reinterpret_cast<void**>(&d_cert), (size_t)W * H), "hipMalloc");
             if (ew) { hipc(hipMalloc(reinterpret_cast<void**>(&d_equi), (size_t)ew * eh * 3), "hipMalloc"); h_equi.resize((size_t)ew * eh * 3); }
             if (b["out_cubemap"]) { hipc(hipMalloc(reinterpret_cast<void**>(&d_cube), (size_t)cw * ch * 3), "hipMalloc"); h_cube.resize((size_t)cw * ch * 3); }
             if (gpu_png && (ew > 9000 || (b["out_cubemap"] && cw > 9000))) die("-png_encoder gpu encodes rows of up to 9000 pixels; pass -png_encoder host for these output sizes");
@@ -113,32 +161,39 @@ int run_video(std::map<std::string, std::string>& v, std::map<std::string, bool>
                 if (ew) { cap_e = fav_png_capacity(ew, eh); hipc(hipMalloc(reinterpret_cast<void**>(&d_png_e), cap_e), "hipMalloc"); h_equi.resize(cap_e); png_ws_bytes = std::max(png_ws_bytes, fav_png_workspace_bytes(ew, eh)); }
                 if (b["out_cubemap"]) { cap_c = fav_png_capacity(cw, ch); hipc(hipMalloc(reinterpret_cast<void**>(&d_png_c), cap_c), "hipMalloc"); h_cube.resize(cap_c); png_ws_bytes = std::max(png_ws_bytes, fav_png_workspace_bytes(cw, ch)); }
                 hipc(hipMalloc(reinterpret_cast<void**>(&d_png_n), 16), "hipMalloc");
+                hipc(hipMemset(d_png_n, 0, 16), "hipMemset");      // (the size word of an output that is not asked for is read back too)
                 if (png_ws_bytes) hipc(hipMalloc(&d_png_ws, png_ws_bytes), "hipMalloc");
             }
         } else if (w != W || h != H) die(img_path + ": face size changed");
-        hipc(hipMemcpyAsync(d_frame, rgb, (size_t)W * H * 3, hipMemcpyHostToDevice, st), "H2D frame");
-        const bool temporal = i >= 7 && !b["create_inconsistent"];
-        float* flo = nullptr; uint8_t* cert = nullptr;
-        if (temporal) {                                                                                             // :225-229, :274-278
-            const std::string cp = flow_name(v["occlusions_pattern"], file_idx - 1, file_idx, face);
+        uint8_t* d_frame = d_frame6[set]; float* d_flow = d_bw6[set]; float* d_fwd = d_fw6[set];
+        if (!have) hipc(hipMemcpyAsync(d_frame, rgb, (size_t)W * H * 3, hipMemcpyHostToDevice, st), "H2D frame");
+        float* flo = nullptr; float* fwd = nullptr; uint8_t* cert = nullptr;
+        if (temporal && !have) {                                                                                    // :225-229, :274-278
             const std::string fp = flow_name(v["flow_pattern"], file_idx - 1, file_idx, face);
-            favp::Poll poll; poll.timeout_s = atof(v["poll_timeout"].c_str()); poll.settle_s = std::max(0.0, atof(v["poll_settle"].c_str()));
-            int cw_ = 0, ch_ = 0, cc = 0, fw = 0, fh = 0;
-            read_polled(cp, poll, "reading the certainty", [&] { return fav_read_pnm_host(cp.c_str(), &cert, &cw_, &ch_, &cc); });
+            int cw_ = W, ch_ = H, cc = 1, fw = 0, fh = 0, gw = W, gh = H;
+            if (fused) {                                                         // the forward flow is waited for like the backward flow
+                const std::string gp = flow_name(v["forward_flow_pattern"], file_idx - 1, file_idx, face);
+                read_polled(gp, poll, "reading the forward flow", [&] { return fav_read_flo_host(gp.c_str(), &fwd, &gw, &gh); });
+            } else {
+                const std::string cp = flow_name(v["occlusions_pattern"], file_idx - 1, file_idx, face);
+                read_polled(cp, poll, "reading the certainty", [&] { return fav_read_pnm_host(cp.c_str(), &cert, &cw_, &ch_, &cc); });
+            }
             read_polled(fp, poll, "reading the flow", [&] { return fav_read_flo_host(fp.c_str(), &flo, &fw, &fh); });
-            if (cc != 1 || cw_ != W || ch_ != H || fw != W || fh != H) die("flow / certainty size does not match the face: " + fp);
-            hipc(hipMemcpyAsync(d_cert, cert, (size_t)W * H, hipMemcpyHostToDevice, st), "H2D cert");
+            if (cc != 1 || cw_ != W || ch_ != H || fw != W || fh != H || gw != W || gh != H) die("flow / certainty size does not match the face: " + fp);
+            if (cert) hipc(hipMemcpyAsync(d_cert, cert, (size_t)W * H, hipMemcpyHostToDevice, st), "H2D cert");
+            if (fwd) hipc(hipMemcpyAsync(d_fwd, fwd, (size_t)W * H * 8, hipMemcpyHostToDevice, st), "H2D forward flow");
             hipc(hipMemcpyAsync(d_flow, flo, (size_t)W * H * 8, hipMemcpyHostToDevice, st), "H2D flow");
         }
         const auto t0 = std::chrono::steady_clock::now();
-        check(fav_vr_face(vr, i, d_frame, temporal ? d_flow : nullptr, temporal ? d_cert : nullptr, nullptr, st), "fav_vr_face");
+        if (fused) check(fav_vr_face_flow(vr, i, d_frame, temporal ? d_flow : nullptr, temporal ? d_fwd : nullptr, use_structure, nullptr, st), "fav_vr_face_flow");
+        else check(fav_vr_face(vr, i, d_frame, temporal ? d_flow : nullptr, temporal ? d_cert : nullptr, nullptr, st), "fav_vr_face");
         hipc(hipStreamSynchronize(st), "sync");
         // a stream-K hand-off that timed out: fail at THIS face, before any output derived from it is written (fav.h: the check
         // comes before a PNG is queued); the image model stylises the faces without a prior
         check(fav_net_check(vid), "stylising a face");
         if (img) check(fav_net_check(img), "stylising a face (image model)");
         if (timing) printf("Elapsed time for stylizing face %d of frame %d: %.4f\n", face, file_idx, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
-        fav_free_host(rgb); fav_free_host(flo); fav_free_host(cert);
+        fav_free_host(rgb); fav_free_host(flo); fav_free_host(fwd); fav_free_host(cert);
         if (mode == 5) {                                                                                            // :527-557
             if (writer.valid()) writer.get();
             check(fav_vr_finish_frame(vr, d_equi, b["out_cubemap"] ? d_cube : nullptr, st), "fav_vr_finish_frame");
@@ -189,7 +244,8 @@ int run_video(std::map<std::string, std::string>& v, std::map<std::string, bool>
     if (vr) fav_vr_destroy(vr);
     check(fav_net_check(vid), "stylising the video");
     if (img) check(fav_net_check(img), "stylising the video (image model)");
-    (void)hipFree(d_frame); (void)hipFree(d_cert); (void)hipFree(d_flow); (void)hipFree(d_equi); (void)hipFree(d_cube);
+    for (int k = 0; k < 6; ++k) { (void)hipFree(d_frame6[k]); (void)hipFree(d_bw6[k]); (void)hipFree(d_fw6[k]); }
+    (void)hipFree(d_cert); (void)hipFree(d_equi); (void)hipFree(d_cube);
     (void)hipFree(d_png_e); (void)hipFree(d_png_c); (void)hipFree(d_png_n); (void)hipFree(d_png_ws);
     (void)fav_net_forget_stream(vid, st);      // the library must not wait on this handle before the next video's first forward
     hipStreamDestroy(st);
@@ -202,7 +258,7 @@ int run_video(std::map<std::string, std::string>& v, std::map<std::string, bool>
 int main(int argc, char** argv)
 {
     std::map<std::string, std::string> v = {
-        {"input_pattern", ""}, {"flow_pattern", ""}, {"occlusions_pattern", ""}, {"model_img", ""}, {"model_vid", ""},
+        {"input_pattern", ""}, {"flow_pattern", ""}, {"occlusions_pattern", ""}, {"forward_flow_pattern", ""}, {"structure", "1"}, {"model_img", ""}, {"model_vid", ""},
         {"start_frame", "1"}, {"continue_with", "1"}, {"num_frames", "9999"}, {"occlusions_min_filter", "7"},
         {"fill_occlusions", "vgg-mean"}, {"overlap_pixel_w", "20"}, {"overlap_pixel_h", "20"}, {"output_prefix", "out"},
         {"out_equi_w", "768"}, {"out_equi_h", "768"}, {"median_filter", "3"}, {"gpu", "-1"}, {"backend", "cuda"}, {"use_cudnn", "1"},
@@ -226,8 +282,12 @@ int main(int argc, char** argv)
     }
     auto I = [&](const char* k) { return atoi(v[k].c_str()); };
     if (v["input_pattern"].empty()) die("Must give -input_pattern");                                               // :564-566
-    if (!b["create_inconsistent"] && (v["flow_pattern"].empty() || v["occlusions_pattern"].empty()))
+    // (-forward_flow_pattern: the certainty is computed from the two flows, -occlusions_pattern is not needed -- and not read if given)
+    if (!b["create_inconsistent"] && (v["flow_pattern"].empty() || (v["occlusions_pattern"].empty() && v["forward_flow_pattern"].empty())))
         die("Must give -flow_pattern and -occlusions_pattern");                                                     // :567-569
+    if (v["structure"] != "0" && v["structure"] != "1") die("-structure must be 0 or 1");
+    if (!v["forward_flow_pattern"].empty() && !v["occlusions_pattern"].empty() && atoi(v["worker_rank"].c_str()) < 0)
+        fprintf(stderr, "fav_stylize_vr: -forward_flow_pattern and -occlusions_pattern both given: the forward flow wins (the check runs on the GPU, no certainty file is read)\n");
     if (I("gpu") < 0) die("-gpu -1: this build has no CPU backend (the CPU restatement under oracle/ is test infrastructure); pass -gpu <id>");
     if (b["evaluate"]) die("-evaluate (perceptual / edge losses) is outside the hot-path scope");
     if (b["backward"]) die("-backward is not provided for the cube-map pipeline");
@@ -243,7 +303,7 @@ int main(int argc, char** argv)
     if (!named) streams.push_back("");
     int world = std::max(1, I("gpus"));
     const int rank = I("worker_rank");
-    static const char* const path_opts[] = {"input_pattern", "flow_pattern", "occlusions_pattern", "output_prefix"};
+    static const char* const path_opts[] = {"input_pattern", "flow_pattern", "occlusions_pattern", "forward_flow_pattern", "output_prefix"};
     if (named && streams.size() > 1 && v["output_prefix"].find("%S") == std::string::npos)
         die("-streams: -output_prefix must contain %S (the videos would overwrite each other's frames)");
     if (rank < 0 && (world > 1 || I("force_dist"))) {                                   // launcher: one worker process per GPU

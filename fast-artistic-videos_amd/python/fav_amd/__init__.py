@@ -54,6 +54,8 @@ def lib() -> C.CDLL:
     for f in (L.fav_png_capacity, L.fav_png_workspace_bytes):
         f.restype = C.c_size_t; f.argtypes = [C.c_int, C.c_int]
     L.fav_vr_destroy.argtypes = [C.c_void_p]; L.fav_vr_destroy.restype = None
+    L.fav_vr_last_mask.restype = C.c_void_p
+    L.fav_vr_last_mask.argtypes = [C.c_void_p]
     L.fav_png_crc32_combine_host.restype = C.c_uint32; L.fav_png_crc32_combine_host.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
     _lib = L
     return L
@@ -73,6 +75,7 @@ EXPORTS = [
     "fav_vr_create", "fav_vr_destroy", "fav_vr_face", "fav_vr_finish_frame", "fav_vr_output_sizes", "fav_vr_get_f32",
     "fav_vr_map_host", "fav_temporal_loss_host", "fav_sequential_sum_f32", "fav_read_flo_into_host", "fav_read_pnm_into_host", "fav_net_set_precision", "fav_net_check", "fav_net_set_shared_device", "fav_net_forget_stream",
     "fav_scale_bicubic_f32", "fav_stream_set_single_image_size",
+    "fav_vr_face_flow", "fav_vr_prefetch_mask", "fav_vr_last_mask",
 ]
 
 
@@ -501,6 +504,29 @@ class VR:
         _check(lib().fav_vr_face(self.h, i, _p(frame_u8_hwc), _p(backward_flo), _p(cert_u8), _p(out), _stream()))
         return out
 
+    def face_flow(self, i: int, frame_u8_hwc, backward_flo=None, forward_flo=None, use_structure=False):
+        """fav_vr_face_flow: the face with the consistency check made on the device from the two flows (no certainty file)"""
+        torch = _torch()
+        out = torch.empty((3, self.H, self.W), dtype=torch.float32, device=frame_u8_hwc.device)
+        _check(lib().fav_vr_face_flow(self.h, i, _p(frame_u8_hwc), _p(backward_flo), _p(forward_flo), 1 if use_structure else 0,
+                                      _p(out), _stream()))
+        return out
+
+    def prefetch_mask(self, i: int, frame_u8_hwc, backward_flo=None, forward_flo=None, use_structure=False):
+        """fav_vr_prefetch_mask: start face i's mask on the VR object's side stream; the matching face_flow consumes it"""
+        _check(lib().fav_vr_prefetch_mask(self.h, i, _p(frame_u8_hwc), _p(backward_flo), _p(forward_flo), 1 if use_structure else 0,
+                                          _stream()))
+
+    def last_mask(self):
+        """copy of the u8 mask the last face_flow computed (before the border max and the min filter)"""
+        torch = _torch()
+        ptr = lib().fav_vr_last_mask(self.h)
+        if not ptr:
+            raise FavError("fav_vr_last_mask: no face has been checked on the device yet")
+        out = torch.empty((self.H, self.W), dtype=torch.uint8, device=f"cuda:{self.net.device}")
+        out.view(-1).copy_(_from_ptr_u8(ptr, self.H * self.W, self.net.device))
+        return out
+
     def finish_frame(self, want_equi: bool = True, want_cube: bool = True):
         torch = _torch()
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -512,7 +538,7 @@ class VR:
     def get(self, which: int, k: int = 0):
         torch = _torch()
         shape = {0: (3, self.H, self.W), 1: (3, self.H, self.W), 2: (3, self.filt_h, self.filt_w),
-                 3: (3, self.equi_h, self.equi_w), 4: (3, self.cube_h, self.cube_w)}[which]
+                 3: (3, self.equi_h, self.equi_w), 4: (3, self.cube_h, self.cube_w), 5: (self.H, self.W)}[which]
         out = torch.empty(shape, dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
         _check(lib().fav_vr_get_f32(self.h, which, k, _p(out), _stream()))
         return out

@@ -296,12 +296,26 @@ void fav_vr_destroy(fav_vr* v);
  * from the second frame on (i >= 7) and ignored before; out_rgb_f32 ([3][H][W], may be NULL) receives the stylised face */
 int fav_vr_face(fav_vr* v, int i, const uint8_t* frame_rgb_hwc, const float* backward_flo, const uint8_t* cert_pgm,
                 float* out_rgb_f32, fav_hipstream_t stream);
+/* one cube face with the consistency check on the GPU: forward_flo = forward_{i-1}_[i].flo of this face; use_structure != 0 selects the
+ * checker's 4-argument mode on this face's frame.  Faces that need no temporal certainty (i < 7, -create_inconsistent) ignore both flows
+ * and behave exactly as fav_vr_face. */
+int fav_vr_face_flow(fav_vr* v, int i, const uint8_t* frame_rgb_hwc, const float* backward_flo, const float* forward_flo,
+                     int use_structure, float* out_rgb_f32, fav_hipstream_t stream);
+/* optional look-ahead, event-ordered: start face i's mask on a side stream owned by the fav_vr (a mask depends on that face's frame and
+ * flows only).  The next fav_vr_face_flow with the same i, pointers and mode consumes it; anything else discards it.  At most six
+ * masks are pending, one per face of a frame (a second look-ahead for the same position of the frame replaces the first); the inputs
+ * must stay unchanged until the face that consumes the mask has been enqueued.  A face that needs no temporal certainty: no-op. */
+int fav_vr_prefetch_mask(fav_vr* v, int i, const uint8_t* frame_rgb_hwc, const float* backward_flo, const float* forward_flo,
+                         int use_structure, fav_hipstream_t stream);
+/* device pointer of the last mask fav_vr_face_flow computed (u8 [hplus][wplus], before the border max and the min filter) -- tests */
+const uint8_t* fav_vr_last_mask(const fav_vr* v);
 /* after the sixth face of a frame: post-blend (the blended faces become the next frame's warp sources), median filter,
  * equirectangular image (u8 [out_equi_h][out_equi_w][3]) and / or cube-map strip (u8 [cube_h][cube_w][3]); either may be NULL */
 int fav_vr_finish_frame(fav_vr* v, uint8_t* equi_rgb8_hwc, uint8_t* cubemap_rgb8_hwc, fav_hipstream_t stream);
 int fav_vr_output_sizes(const fav_vr* v, int* equi_w, int* equi_h, int* cube_w, int* cube_h, int* filtered_w, int* filtered_h);
 /* float views for tests: which = 0 this frame's raw face k, 1 blended face k, 2 median-filtered face k, 3 equirectangular
- * image, 4 cube-map strip (device to device copy) */
+ * image, 4 cube-map strip, 5 the certainty plane of the last face after border max and erosion ([hplus][wplus]; k ignored)
+ * (device to device copy) */
 int fav_vr_get_f32(const fav_vr* v, int which, int k, float* out_dev, fav_hipstream_t stream);
 /* the static maps, computed on the host (no device needed): kind 0..3 = perspective map left/right/top/bottom
  * ([2][hplus][wplus], `overlap` = the crop along that axis), 4 = cube->equirectangular map ([2][out_h][out_w]) */
