@@ -223,6 +223,12 @@ int launch_conv3_up2(const ConvLaunch& p, const float* wpk, int* counts, hipStre
 bool conv3s2w_eligible(int cin_pitch, int cout, int coutp, int k, int stride, int pad, int stages, int ups);
 int conv3s2w_tiles(int OH, int OW, int coutp);
 int launch_conv3s2w(const ConvLaunch& p, const float* wpk, int* counts, hipStream_t st);
+// nn.SpatialFullConvolution with stride 2..4 (`u<n>`, `f<k>s<s>-<n>`) by output phase on the physical input (kernels_tconv.hip); p = the
+// PHYSICAL input with the module's own k / stride / pad; wpk = conv_tconv_pack() of the [cin][cout][k][k] weights (tconv_pack.h); partials
+// per (8 x 32 input-pixel tile, phase) with explicit counts
+bool conv_tconv_eligible(int cin_pitch, int coutp, int k, int stride, int pad, int adj, int ups);
+int conv_tconv_tiles(int OH, int OW, int stride);
+int launch_conv_tconv(const ConvLaunch& p, const float* wpk, int* counts, hipStream_t st);
 // One enumerator per launch wrapper above.  fav_net picks one per layer (net.cpp: select_conv) and reports it through
 // fav_net_profile_read_host as a kernel id -- a contract: bench.py, scripts/wide_bench.py and the GPU tests read the ids
 // (N = the padded output channel count COUTp):
@@ -232,8 +238,9 @@ int launch_conv3s2w(const ConvLaunch& p, const float* wpk, int* counts, hipStrea
 //   CK_C8D      launch_conv_c8d      7                              CK_WINO4   launch_conv3_wino4  600 + N  (+ 1: likewise)
 //   CK_FIRST1D  launch_conv_first    6                              CK_HALO3   launch_conv3_halo   300 + N
 //   CK_FIRST2D  launch_conv_first2d  16                             CK_S2HALO  launch_conv3s2      200 + N
-enum ConvKernel { CK_GENERIC, CK_FOLD, CK_C8, CK_C8D, CK_FIRST1D, CK_FIRST2D, CK_S2W, CK_UP2, CK_WINO, CK_WINO4, CK_HALO3, CK_S2HALO };
-constexpr int CONV_KERNELS = CK_S2HALO + 1;      // (the last enumerator)
+//                                                                   CK_TCONV   launch_conv_tconv   800 + N
+enum ConvKernel { CK_GENERIC, CK_FOLD, CK_C8, CK_C8D, CK_FIRST1D, CK_FIRST2D, CK_S2W, CK_UP2, CK_WINO, CK_WINO4, CK_HALO3, CK_S2HALO, CK_TCONV };
+constexpr int CONV_KERNELS = CK_TCONV + 1;      // (the last enumerator)
 // kernels_elem.hip.  Per-channel finalize of (mean, M2) partials -> scale/shift:  scale = gamma/sqrt(var+eps)
 // counts: per-partial pixel counts or null (then block b holds min(block_pixels, M - b*block_pixels) pixels)
 int launch_in_finalize(const float* partials, const int* counts, int mblocks, int M, int block_pixels, int C, int Cpitch,

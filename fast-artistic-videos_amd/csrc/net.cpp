@@ -24,6 +24,7 @@
 #include "wino4_pack.h"
 #include "up2_pack.h"
 #include "s2_pack.h"
+#include "tconv_pack.h"
 #include "first_pack.h"
 #include "first2d_pack.h"
 #include "fold_pack.h"
@@ -103,6 +104,7 @@ struct Tuning {
     bool no_wino = diag_env("FAV_NO_WINO") != nullptr;
     bool no_h3 = diag_env("FAV_NO_H3") != nullptr;
     bool no_s2 = diag_env("FAV_NO_S2") != nullptr;
+    bool no_tconv = diag_env("FAV_NO_TCONV") != nullptr;              // transposed convolutions on the generic kernel, over the zero-stuffed input (stride 2, adj 1 only)
     bool first_1d = diag_env("FAV_FIRST_1D") != nullptr;              // the 1-D form of the first layer
     bool wino_f2 = diag_env("FAV_WINO_F2") != nullptr;                // the residual convolutions as F(2x2,3x3) (rounds 2-3) instead of F(4x4,3x3)
     bool no_acc_stats = diag_env("FAV_NO_ACC_STATS") != nullptr;      // every InstanceNorm through partials + an in_finalize launch (rounds 1-4)
@@ -120,8 +122,9 @@ ConvKernel select_conv(const Layer& L, const DevConvW& d, int stages, int ups, i
 {
     // only the generic kernel and the row-folded one (few output channels: kx taps folded into N) have the Tanh epilogue
     if (is_final) return !t.no_fold && d.packed[CK_FOLD] && conv_fold_launchable(d.cinp, L.k, L.pad, ups, IH, IW) ? CK_FOLD : CK_GENERIC;
-    // a transposed convolution runs on the generic kernel, over the zero-stuffed input
-    if (L.transposed) return CK_GENERIC;
+    // a transposed convolution (stride >= 2: upload() turns stride 1 into an ordinary convolution) by output phase on the physical input;
+    // FAV_NO_TCONV: on the generic kernel, over the zero-stuffed input
+    if (L.transposed) return !t.no_tconv && d.packed[CK_TCONV] && conv_tconv_eligible(d.cinp, d.coutp, L.k, L.stride, L.pad, L.adj, ups) ? CK_TCONV : CK_GENERIC;
     // The first layer (9x9 on the 8-channel input pixel) by minimal filtering, ahead of its direct forms below: 2-D F(2x2,3x3) over its
     // nine 3x3 blocks, or 1-D F(2,3) along x on request (FAV_FIRST_1D).  FAV_NO_C8D takes both away together with the dense-K direct
     // form.  A layer that the c8 kernel does not take (more than 32 filters, FAV_NO_C8) has the 2-D form only, in groups of 32 filters
@@ -152,7 +155,7 @@ ConvKernel select_conv(const Layer& L, const DevConvW& d, int stages, int ups, i
 // What run() and timed_conv() need to know about each kernel: how many partial-statistics tiles it writes for an OH x OW output, whether
 // it writes their pixel counts (else every tile but the last holds CONV_BM pixels), and its profile id (fav_internal.h, ConvKernel)
 struct ConvFacts { int tiles; bool counts; int id; };
-ConvFacts conv_facts(ConvKernel k, int OH, int OW, int coutp, int precision, bool join)
+ConvFacts conv_facts(ConvKernel k, int OH, int OW, int coutp, int precision, bool join, int stride)
 {
     switch (k) {
     case CK_GENERIC: return {conv_mblocks(OH, OW), false, coutp % 128 == 0 ? 128 : (coutp % 64 == 0 ? 64 : 32)};
@@ -167,6 +170,7 @@ ConvFacts conv_facts(ConvKernel k, int OH, int OW, int coutp, int precision, boo
     case CK_WINO4:   return {conv3_wino4_tiles(OH, OW), true, 600 + coutp + (join ? 1 : 0)};
     case CK_HALO3:   return {conv3_halo_tiles(OH, OW, precision == 0), true, 300 + coutp};
     case CK_S2HALO:  return {conv3s2_tiles(OH, OW), true, 200 + coutp};
+    case CK_TCONV:   return {conv_tconv_tiles(OH, OW, stride), true, 800 + coutp};
     }
     return {0, false, 0};
 }
@@ -189,6 +193,7 @@ int launch_selected(ConvKernel k, const ConvLaunch& cs, const ConvLaunch& cg, co
     case CK_WINO4:   return launch_conv3_wino4(cs, w, counts, st);
     case CK_HALO3:   return launch_conv3_halo(cg, counts, st);
     case CK_S2HALO:  return launch_conv3s2(tuning().side_sk == 2 ? cs : cg, counts, st);
+    case CK_TCONV:   return launch_conv_tconv(cs, w, counts, st);
     }
     set_error("internal: unknown convolution kernel %d", (int)k); return FAV_EINVAL;
 }
@@ -203,8 +208,11 @@ constexpr InputState IN_NORM_UP2{1, 1};     // one pending norm behind a x2 upsa
 // true: `out` is kernel k's packed form of layer L; false: k cannot run L (or runs on the repack_weights() form) and d.packed[k] stays null
 bool pack_weights(ConvKernel k, const Layer& L, const DevConvW& d, std::vector<float>& out)
 {
-    if (L.transposed) return false;      // (the generic kernel, over the zero-stuffed input)
     const float* w = L.w.data();
+    if (L.transposed) {                  // [cin][cout][k][k]: the phase kernel's form, or (FAV_NO_TCONV) the generic kernel's flipped repack_weights() form
+        if (k != CK_TCONV || !conv_tconv_eligible(d.cinp, d.coutp, L.k, L.stride, L.pad, L.adj, IN_PLAIN.ups)) return false;
+        conv_tconv_pack(w, L.cin, L.cout, d.cinp, d.coutp, L.k, L.stride, L.pad, out); return true;
+    }
     const bool first = conv_c8d_eligible(d.cinp, L.cin, d.coutp, L.k, L.stride, IN_PLAIN.stages, IN_PLAIN.ups);      // the first layer with at most 32 filters
     const bool full_k = L.cin == d.cinp;      // every channel of the input pitch is a real one (not the 7 | 3 network inputs in their 8-channel pixel)
     switch (k) {
@@ -241,6 +249,8 @@ bool pack_weights(ConvKernel k, const Layer& L, const DevConvW& d, std::vector<f
     case CK_FOLD:          // the row-folded last layer
         if (!conv_fold_eligible(d.cinp, L.cout, L.k, L.stride)) return false;
         conv_fold_pack(w, L.cin, d.cinp, L.cout, L.k, out); return true;
+    case CK_TCONV:         // (transposed layers only: above)
+        return false;
     }
     return false;
 }
@@ -305,6 +315,24 @@ int pad_channel_counts(std::vector<Layer>& ls, int& chan, int& real, bool& seen_
             int rc = pad_channel_counts(L.block, c, r, seen_conv, false); if (rc) return rc;
             if (c != chan || r != real) { set_error("network: residual branch changes the channel count"); return FAV_EUNSUPPORTED; }
         }
+    }
+    return FAV_OK;
+}
+
+// A stride-1 nn.SpatialFullConvolution (`f<k>s1-<n>`) IS an ordinary convolution: weights flipped and transposed to [cout][cin], zero
+// padding k - 1 - p.  Rewritten in the executed copy of the network, so that it gets the ordinary kernels, the Tanh epilogue and the
+// upsampled-input handling; describe / output size keep the module as the file has it
+int rewrite_stride1_transposed(std::vector<Layer>& ls)
+{
+    for (Layer& L : ls) {
+        if (L.type == L_RES) { int rc = rewrite_stride1_transposed(L.block); if (rc) return rc; }
+        if (L.type != L_CONV || !L.transposed || L.stride != 1) continue;
+        if (L.k < 1 || L.pad < 0 || L.pad > L.k - 1 || L.adj != 0) {
+            set_error("network: SpatialFullConvolution with stride 1 needs pad <= k - 1 and adj 0, got k=%d pad=%d adj=%d", L.k, L.pad, L.adj);
+            return FAV_EUNSUPPORTED; }
+        std::vector<float> w;
+        conv_tconv_as_conv(L.w.data(), L.cin, L.cout, L.k, w);
+        L.w.swap(w); L.pad = L.k - 1 - L.pad; L.transposed = 0;
     }
     return FAV_OK;
 }
@@ -409,9 +437,19 @@ int fav_net::upload_layers(std::vector<Layer>& ls, int& chan_pitch, int& maxc)
                 return FAV_EUNSUPPORTED; }
             d.coutp = (L.cout + 31) / 32 * 32;
             d.kpad = (L.k * L.k * d.cinp + 31) / 32 * 32;
+            // a transposed layer runs by output phase (CK_TCONV); the zero-stuffed form on the generic kernel -- a x2 index map: stride 2,
+            // adj 1 ONLY -- is what is left for a layer the phase kernel does not take (a 4-channel input pitch), and for FAV_NO_TCONV
+            const bool phase = L.transposed && !tuning().no_tconv && conv_tconv_eligible(d.cinp, d.coutp, L.k, L.stride, L.pad, L.adj, IN_PLAIN.ups);
+            if (L.transposed && !phase && (L.stride != 2 || L.adj != 1) && L.stride >= 2 && L.stride <= TCONV_MAX_S && L.k <= TCONV_MAX_K && L.pad <= L.k - 1 && L.adj >= 0 && L.adj < L.stride) {
+                if (tuning().no_tconv) set_error("network: the zero-stuffed form of SpatialFullConvolution (diagnostic switch) is stride 2, adj 1 only, got s=%d adj=%d", L.stride, L.adj);
+                else set_error("network: SpatialFullConvolution with s=%d adj=%d behind %d input channels is unsupported (other than stride 2, adj 1 it needs a multiple of 8)", L.stride, L.adj, d.cinp);
+                return FAV_EUNSUPPORTED; }
             std::vector<float> w;
-            repack_weights(L, d.cinp, d.coutp, d.kpad, w);
-            int rc = dev_upload(w, 0, &d.wgt); if (rc) return rc;
+            int rc = FAV_OK;
+            if (!phase) {                   // (the phase kernel reads its own packing only: no generic weight matrix for it)
+                repack_weights(L, d.cinp, d.coutp, d.kpad, w);
+                rc = dev_upload(w, 0, &d.wgt); if (rc) return rc;
+            }
             rc = dev_upload(L.b, (size_t)d.coutp, &d.bias); if (rc) return rc;
             if (!L.transposed && conv3_halo_eligible(d.cinp, d.coutp, L.k, L.stride)) {      // bf16 copy for the fast mode (round to nearest even)
                 std::vector<unsigned short> w16(w.size());
@@ -419,8 +457,9 @@ int fav_net::upload_layers(std::vector<Layer>& ls, int& chan_pitch, int& maxc)
                 FAV_HIP(hipMalloc(reinterpret_cast<void**>(&d.wgt16), w16.size() * 2));
                 FAV_HIP(hipMemcpy(d.wgt16, w16.data(), w16.size() * 2, hipMemcpyHostToDevice));
             }
-            if (L.transposed && (L.stride != 2 || L.adj != 1 || L.pad > L.k - 1)) {
-                set_error("network: SpatialFullConvolution is supported for stride 2, adj 1 (models_video.lua:99-102), got s=%d adj=%d", L.stride, L.adj);
+            if (L.transposed && (L.k > TCONV_MAX_K || L.stride < 2 || L.stride > TCONV_MAX_S || L.pad > L.k - 1 || L.adj < 0 || L.adj >= L.stride)) {
+                set_error("network: SpatialFullConvolution is supported for k <= %d, stride <= %d, pad <= k - 1, adj < stride (models_video.lua:81-89,99-102), got k=%d s=%d pad=%d adj=%d",
+                          TCONV_MAX_K, TCONV_MAX_S, L.k, L.stride, L.pad, L.adj);
                 return FAV_EUNSUPPORTED; }
             std::vector<float> wk;      // every kernel's own form of the weights: null where pack_weights() has none
             for (int k = 0; k < CONV_KERNELS; ++k)
@@ -478,9 +517,10 @@ int fav_net::upload()
         set_error("network: first convolution has %d input channels; video models take 7 (models_video.lua:57), image models 3", in_channels);
         return FAV_EUNSUPPORTED; }
     exec = layers;
+    int rc = rewrite_stride1_transposed(exec); if (rc) return rc;
     int chan0 = 8;
     int real0 = in_channels; bool seen_conv = false;
-    int rc = pad_channel_counts(exec, chan0, real0, seen_conv, true); if (rc) return rc;
+    rc = pad_channel_counts(exec, chan0, real0, seen_conv, true); if (rc) return rc;
     int chan = 8, maxc = 8;
     rc = upload_layers(exec, chan, maxc); if (rc) return rc;
     params = count_params(layers);
@@ -551,7 +591,8 @@ int fav_net::timed_conv(const ConvLaunch& c, int conv_index, const Layer& L, Con
     prof_pending.push_back(r);
     if ((int)prof_ms.size() <= conv_index) { prof_ms.resize(conv_index + 1, 0.0); prof_macs.resize(conv_index + 1, 0.0); prof_n.resize(conv_index + 1, 0); prof_tile.resize(conv_index + 1, 0); }
     prof_macs[conv_index] = (double)c.OH * c.OW * L.cout * L.cin * L.k * L.k;      // useful MACs only
-    prof_tile[conv_index] = conv_facts(kernel, c.OH, c.OW, c.COUTp, precision, c.join_skip != nullptr).id;
+    if (L.transposed) prof_macs[conv_index] /= (double)(L.stride * L.stride);       // (every output pixel meets k^2 / s^2 taps)
+    prof_tile[conv_index] = conv_facts(kernel, c.OH, c.OW, c.COUTp, precision, c.join_skip != nullptr, L.stride).id;
     return rc;
 }
 
@@ -617,22 +658,30 @@ int fav_net::run(std::vector<Layer>& ls, Act& cur, bool top, float* out_planar, 
             c.pre = cur.pre;
             c.wgt = d.wgt; c.bias = d.bias; c.COUT = L.cout; c.COUTp = d.coutp; c.KH = c.KW = L.k; c.stride = L.stride;
             c.pad = L.pad; c.Kpad = d.kpad;
+            bool has_tanh = false; float mul = 1.f;
+            const bool is_final = top && only_tail(ls, li + 1, has_tanh, mul) && has_tanh && L.cout == 3;
             if (L.transposed) {
-                // stride-2 transposed convolution = stride-1 convolution over the zero-stuffed input (size 2*in with adj 1)
                 if (cur.ups != 0) { set_error("network: SpatialFullConvolution directly after an upsampling is unsupported"); return FAV_EUNSUPPORTED; }
+                if (is_final) { set_error("network: a transposed convolution as the last layer is unsupported"); return FAV_EUNSUPPORTED; }
+            }
+            const ConvKernel kernel = select_conv(L, d, cur.pre.stages, cur.ups, precision, is_final, c.IH, c.IW, tuning());
+            if (L.transposed && kernel == CK_TCONV) {
+                // by output phase on the physical input (kernels_tconv.hip): the module's own geometry
+                c.OH = (c.IH - 1) * L.stride - 2 * L.pad + L.k + L.adj; c.OW = (c.IW - 1) * L.stride - 2 * L.pad + L.k + L.adj;
+                if (c.OH < 1 || c.OW < 1) { set_error("network: input too small for the architecture"); return FAV_EINVAL; }
+            } else if (L.transposed) {
+                // stride-2 transposed convolution = stride-1 convolution over the zero-stuffed input (size 2*in with adj 1): FAV_NO_TCONV, or
+                // a layer the phase kernel does not take (upload_layers lets nothing else through)
+                if (L.stride != 2 || L.adj != 1 || d.wgt == nullptr) { set_error("internal: zero-stuffed SpatialFullConvolution with s=%d adj=%d", L.stride, L.adj); return FAV_EINVAL; }
                 c.ups = 1; c.stuff = 1; c.IH = 2 * cur.Hp; c.IW = 2 * cur.Wp; c.stride = 1; c.pad = L.k - 1 - L.pad;
                 c.OH = c.IH + 2 * c.pad - L.k + 1; c.OW = c.IW + 2 * c.pad - L.k + 1;
             } else {
                 c.OH = (c.IH + 2 * L.pad - L.k) / L.stride + 1;
                 c.OW = (c.IW + 2 * L.pad - L.k) / L.stride + 1;
             }
-            if (c.IH + 2 * c.pad < L.k || c.IW + 2 * c.pad < L.k) { set_error("network: input too small for the architecture"); return FAV_EINVAL; }
-            bool has_tanh = false; float mul = 1.f;
-            const bool is_final = top && only_tail(ls, li + 1, has_tanh, mul) && has_tanh && L.cout == 3;
-            const ConvKernel kernel = select_conv(L, d, cur.pre.stages, cur.ups, precision, is_final, c.IH, c.IW, tuning());
+            if (kernel != CK_TCONV && (c.IH + 2 * c.pad < L.k || c.IW + 2 * c.pad < L.k)) { set_error("network: input too small for the architecture"); return FAV_EINVAL; }
             Act nxt;
             nxt.Hp = c.OH; nxt.Wp = c.OW; nxt.C = L.cout;
-            if (is_final && L.transposed) { set_error("network: a transposed convolution as the last layer is unsupported"); return FAV_EUNSUPPORTED; }
             if (is_final) {
                 c.final_mode = 1; c.tanh_mul = mul; c.out_planar = out_planar; c.out_raw_nchw = out_raw;
                 int rc = timed_conv(c, (int)conv_cursor - 1, L, kernel, nullptr); if (rc) return rc;
@@ -650,7 +699,7 @@ int fav_net::run(std::vector<Layer>& ls, Act& cur, bool top, float* out_planar, 
                 nxt.data = base + ((size_t)lazy.shave * lazy.pitch + lazy.shave) * L.cout; nxt.pitch = lazy.pitch; c.OWp = lazy.pitch;
             } else { rc = alloc((size_t)c.OH * c.OW * L.cout * sizeof(float), &nxt.data); if (rc) return rc; }
             const bool want_stats = li + 1 < ls.size() && ls[li + 1].type == L_IN;
-            const ConvFacts facts = conv_facts(kernel, c.OH, c.OW, d.coutp, precision, cur.join_skip != nullptr);
+            const ConvFacts facts = conv_facts(kernel, c.OH, c.OW, d.coutp, precision, cur.join_skip != nullptr, L.stride);
             nxt.mblocks = facts.tiles; nxt.ppitch = d.coutp;
             const bool acc = kernel == CK_WINO4 && want_stats && !pitched_out && cur.join_skip == nullptr &&
                              (acc_stats_ok(ls, li) || (branch_tail_acc_ok && !top && li + 2 == ls.size() && !tuning().no_acc_stats && precision == 0));
@@ -1082,6 +1131,63 @@ extern "C" int fav_conv2d_nchw_f32(const float* in, int Cin, int H, int W, const
     }
     if (!rc) rc = launch_nhwc_to_nchw(dout, M, Cout, t, out, st);
     if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = hip_fail(hipGetLastError(), "fav_conv2d_nchw_f32");
+    cleanup();
+    return rc;
+}
+
+// nn.SpatialFullConvolution [+ nn.InstanceNormalization [+ nn.ReLU]] as a stand-alone operator: stride >= 2 on the phase kernel
+// (kernels_tconv.hip), stride 1 as the ordinary convolution it is
+extern "C" int fav_conv_transpose2d_nchw_f32(const float* in, int Cin, int H, int W, const float* weight, const float* bias, int Cout,
+                                             int k, int stride, int pad, int adj, const float* gamma, const float* beta, float eps, int relu,
+                                             float* out, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(in && weight && out && Cin > 0 && Cout > 0 && H > 0 && W > 0, "fav_conv_transpose2d_nchw_f32: bad argument");
+    FAV_REQUIRE(k >= 1 && k <= TCONV_MAX_K && stride >= 1 && stride <= TCONV_MAX_S && pad >= 0 && pad <= k - 1 && adj >= 0 && adj < stride,
+                "fav_conv_transpose2d_nchw_f32: supported for k <= %d, stride <= %d, pad <= k - 1, adj < stride, got k=%d s=%d pad=%d adj=%d",
+                TCONV_MAX_K, TCONV_MAX_S, k, stride, pad, adj);
+    int rc = ensure_device(); if (rc) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    std::vector<float> hw((size_t)Cin * Cout * k * k);
+    FAV_HIP(hipMemcpy(hw.data(), weight, hw.size() * sizeof(float), hipMemcpyDeviceToHost));
+    if (stride == 1) {
+        std::vector<float> wc;
+        conv_tconv_as_conv(hw.data(), Cin, Cout, k, wc);
+        float* dwc = nullptr;
+        rc = dev_upload(wc, 0, &dwc);
+        if (!rc) rc = fav_conv2d_nchw_f32(in, Cin, H, W, dwc, bias, Cout, k, 1, k - 1 - pad, gamma, beta, eps, relu, out, stream);
+        (void)hipFree(dwc);
+        return rc;
+    }
+    const int cinp = (Cin + 7) / 8 * 8, coutp = (Cout + 31) / 32 * 32;
+    const int OH = (H - 1) * stride - 2 * pad + k + adj, OW = (W - 1) * stride - 2 * pad + k + adj;
+    FAV_REQUIRE(OH > 0 && OW > 0, "fav_conv_transpose2d_nchw_f32: empty output");
+    const int M = OH * OW, mb = conv_tconv_tiles(OH, OW, stride);
+    std::vector<float> wpk, hb((size_t)coutp, 0.f);
+    conv_tconv_pack(hw.data(), Cin, Cout, cinp, coutp, k, stride, pad, wpk);
+    if (bias) FAV_HIP(hipMemcpy(hb.data(), bias, (size_t)Cout * sizeof(float), hipMemcpyDeviceToHost));      // (nothing is allocated yet)
+    float *dw = nullptr, *db = nullptr, *din = nullptr, *dout = nullptr, *dpart = nullptr, *dsc = nullptr, *dsh = nullptr; int* dcnt = nullptr;
+    auto cleanup = [&]() { (void)hipFree(dw); (void)hipFree(db); (void)hipFree(din); (void)hipFree(dout); (void)hipFree(dpart); (void)hipFree(dsc); (void)hipFree(dsh); (void)hipFree(dcnt); };
+    rc = dev_upload(wpk, 0, &dw); if (rc) { cleanup(); return rc; }
+    rc = dev_upload(hb, 0, &db); if (rc) { cleanup(); return rc; }
+    if (hipMalloc(reinterpret_cast<void**>(&din), (size_t)H * W * cinp * 4) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&dout), (size_t)M * Cout * 4) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&dpart), (size_t)mb * coutp * 8) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&dcnt), (size_t)mb * 4) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&dsc), (size_t)coutp * 4) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&dsh), (size_t)coutp * 4) != hipSuccess) { cleanup(); return hip_fail(hipErrorOutOfMemory, "hipMalloc"); }
+    rc = launch_nchw_to_nhwc_pad(in, Cin, H, W, 0, cinp, din, st); if (rc) { cleanup(); return rc; }
+    ConvLaunch c;
+    c.in = din; c.IH = H; c.IW = W; c.IWp = W; c.CIN = cinp; c.bias = db; c.COUT = Cout; c.COUTp = coutp;
+    c.KH = c.KW = k; c.stride = stride; c.pad = pad; c.OH = OH; c.OW = OW; c.out = dout;
+    c.partials = gamma ? dpart : nullptr;
+    if (!rc) rc = launch_conv_tconv(c, dw, dcnt, st);
+    Affine t;
+    if (!rc && gamma) {
+        rc = launch_in_finalize(dpart, dcnt, mb, M, CONV_BM, Cout, coutp, gamma, beta, eps, dsc, dsh, st);
+        t.scale1 = dsc; t.shift1 = dsh; t.relu1 = relu; t.stages = 1;
+    }
+    if (!rc) rc = launch_nhwc_to_nchw(dout, M, Cout, t, out, st);
+    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = hip_fail(hipGetLastError(), "fav_conv_transpose2d_nchw_f32");
     cleanup();
     return rc;
 }

@@ -66,7 +66,7 @@ EXPORTS = [
     "fav_consistency_u8", "fav_min_filter_f32", "fav_assemble_input_f32", "fav_net_create", "fav_net_pack_host",
     "fav_net_create_from_blob", "fav_net_destroy", "fav_net_describe_host", "fav_t7_describe_host", "fav_net_param_count",
     "fav_net_output_size", "fav_net_forward", "fav_net_profile_enable", "fav_net_profile_read_host",
-    "fav_conv2d_nchw_f32", "fav_stream_create", "fav_stream_destroy",
+    "fav_conv2d_nchw_f32", "fav_conv_transpose2d_nchw_f32", "fav_stream_create", "fav_stream_destroy",
     "fav_stream_set_image_net", "fav_stream_first_frame", "fav_stream_next_frame_cert", "fav_stream_next_frame_flow", "fav_stream_prefetch_mask",
     "fav_stream_get_state",
     "fav_stream_set_state", "fav_stream_last_mask", "fav_stream_get_input_f32", "fav_stream_output_size", "fav_stream_set_host_ordered",
@@ -162,6 +162,18 @@ def conv2d(x, weight, bias=None, stride=1, pad=0, gamma=None, beta=None, eps=1e-
     out = torch.empty((cout, oh, ow), dtype=torch.float32, device=x.device)
     _check(lib().fav_conv2d_nchw_f32(_p(x), cin, h, w, _p(weight), _p(bias), cout, k, stride, pad, _p(gamma), _p(beta),
                                      C.c_float(eps), 1 if relu else 0, _p(out), _stream()))
+    return out
+
+
+def conv_transpose2d(x, weight, bias=None, stride=2, pad=0, adj=0, gamma=None, beta=None, eps=1e-5, relu=False):
+    """nn.SpatialFullConvolution(cin, cout, k, k, stride, stride, pad, pad, adj, adj) [+ InstanceNormalization [+ ReLU]] of a [Cin][H][W]
+    tensor; weight [Cin][Cout][k][k] (torch.nn.functional.conv_transpose2d's layout)."""
+    torch = _torch(); _chk_f32(x, "x"); _chk_f32(weight, "weight")
+    cin, h, w = x.shape; _, cout, k, _ = weight.shape
+    oh, ow = (h - 1) * stride - 2 * pad + k + adj, (w - 1) * stride - 2 * pad + k + adj
+    out = torch.empty((cout, oh, ow), dtype=torch.float32, device=x.device)
+    _check(lib().fav_conv_transpose2d_nchw_f32(_p(x), cin, h, w, _p(weight), _p(bias), cout, k, stride, pad, adj, _p(gamma), _p(beta),
+                                               C.c_float(eps), 1 if relu else 0, _p(out), _stream()))
     return out
 
 

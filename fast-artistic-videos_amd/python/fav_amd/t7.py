@@ -315,7 +315,12 @@ def build_model(arch: str = CANONICAL_ARCH, seed: int = 0, in_channels: int = 7,
       'reflect' / 'replicate'   a padding layer of (f-1)/2 in front of every c-convolution (which then has padW = 0) and of 1 in front of
                                 both convolutions of every residual block; nn.Identity on the skip;
       'zero'                    residual-block convolutions with padW = 1, nn.Identity on the skip.
-    The d / u layers always carry their own zero padding (:90-93,99-102).
+    The d / u / f layers always carry their own zero padding (:81-93,99-102).  `f<k>s<s>-<n>` is nn.SpatialFullConvolution with pad
+    (k - 1) / 2 and adj s - 1 (k odd: Lua's (f - 1) / 2 is not an integer otherwise); `C<n>` is the non-residual conv block (:10-39,103-108:
+    a nested nn.Sequential of [pad] conv norm ReLU [pad] conv norm, followed by a ReLU and no further norm) -- unpadded it loses as many
+    pixels as an R block, so it counts like one for the lazily inserted front pad.  That pad (train_video.lua:319-325: half of what the
+    unpadded network loses) is summed per block at the block's own resolution -- `d`, strided `c`, `u`, `f` and `U` items move it -- which is
+    2 * blocks * downsampling, as before, whenever all blocks sit at one resolution.
 
     recurrent_gain scales the first convolution's weights on input channels 4-7 (1-based: the warped, masked previous output and the
     certainty plane, fast_artistic_video_core.lua:166-171).  Random-init weights make frame -> frame an expanding map (any perturbation
@@ -326,7 +331,7 @@ def build_model(arch: str = CANONICAL_ARCH, seed: int = 0, in_channels: int = 7,
     mods = []
     prev = in_channels
     items = arch.split(",")
-    n_res, down, res_down = 0, 1, 1
+    n_res, down, lost = 0, 1, 0             # lost: what the unpadded blocks shave off per side, in pixels of the full-resolution grid
     for i, v in enumerate(items):
         needs_bn = needs_relu = True
         c0 = v[0]
@@ -336,25 +341,36 @@ def build_model(arch: str = CANONICAL_ARCH, seed: int = 0, in_channels: int = 7,
             if padding_type in ("reflect", "replicate"):                    # :70-75
                 mods.append(_padlayer(padding_type, p)); p = 0
             mods.append(_conv(rng, prev, nxt, f, s, p))                     # :65-80 (otherwise the zero pad stays)
+            down *= s
             if i == 0 and recurrent_gain != 1.0 and prev == 7:
                 mods[-1].fields["weight"][:, 3:7] *= np.float32(recurrent_gain)
         elif c0 == "d":
             nxt = int(v[1:]); mods.append(_conv(rng, prev, nxt, 3, 2, 1)); down *= 2   # :90-93
         elif c0 == "U":
-            nxt = prev; mods.append(_simple("nn.SpatialUpSamplingNearest", scale_factor=int(v[1:])))  # :94-98
+            nxt = prev; mods.append(_simple("nn.SpatialUpSamplingNearest", scale_factor=int(v[1:]))); down = max(down // int(v[1:]), 1)  # :94-98
         elif c0 == "u":
             nxt = int(v[1:]); mods.append(_fullconv(rng, prev, nxt, 3, 2, 1, 1)); down //= 2          # :99-102
-        elif c0 == "R":
-            nxt = int(v[1:]); n_res += 1; res_down = down
+        elif c0 == "f":
+            f, st, nxt = int(v[1]), int(v[3]), int(v[5:])
+            if f % 2 == 0:
+                raise ValueError(f"arch item {v!r}: the f item needs an odd filter size (its padding is (k - 1) / 2, models_video.lua:84)")
+            mods.append(_fullconv(rng, prev, nxt, f, st, (f - 1) // 2, st - 1))                  # :81-89
+            down = max(down // st, 1)
+        elif c0 in "RC":
+            nxt = int(v[1:]); n_res += 1; lost += 2 * down
             norm = _inorm if use_instance_norm else _bnorm
             padded = padding_type in ("reflect", "replicate")
             pc = 1 if padding_type == "zero" else 0
             block = ([_padlayer(padding_type, 1)] if padded else []) + [_conv(rng, nxt, nxt, 3, 1, pc), norm(rng, nxt), _simple("nn.ReLU", inplace=True)] + \
                     ([_padlayer(padding_type, 1)] if padded else []) + [_conv(rng, nxt, nxt, 3, 1, pc), norm(rng, nxt)]       # :10-39
-            skip = _simple("nn.ShaveImage", size=2) if padding_type in ("none", "reflect-start") else _simple("nn.Identity")      # :45-49
-            concat = TorchObject("nn.ConcatTable", {"modules": [_sequential(block), skip]})
-            mods.append(_sequential([concat, _simple("nn.CAddTable", inplace=False)]))            # :41-53
-            needs_bn = needs_relu = False
+            if c0 == "C":
+                mods.append(_sequential(block))                                                   # :103-108
+                needs_bn = False
+            else:
+                skip = _simple("nn.ShaveImage", size=2) if padding_type in ("none", "reflect-start") else _simple("nn.Identity")      # :45-49
+                concat = TorchObject("nn.ConcatTable", {"modules": [_sequential(block), skip]})
+                mods.append(_sequential([concat, _simple("nn.CAddTable", inplace=False)]))        # :41-53
+                needs_bn = needs_relu = False
         else:
             raise ValueError(f"arch item {v!r} is outside the hot-path scope")
         if i == len(items) - 1:
@@ -366,7 +382,7 @@ def build_model(arch: str = CANONICAL_ARCH, seed: int = 0, in_channels: int = 7,
     mods.append(_simple("nn.MulConstant", constant_scalar=float(tanh_constant), inplace=False))
     mods.append(_simple("nn.TotalVariation", strength=1e-6))
     if insert_pad and n_res and padding_type == "reflect-start":
-        p = 2 * n_res * res_down  # train_video.lua:319-325: 2 px/side/block at 1/res_down res (40 for 5 blocks at 1/4)
+        p = lost                  # train_video.lua:319-325: 2 px/side/block at the block's resolution (40 for 5 blocks at 1/4)
         mods.insert(0, TorchObject("nn.SpatialReflectionPadding",
                                    {"pad_l": p, "pad_r": p, "pad_t": p, "pad_b": p,
                                     "_type": "torch.FloatTensor", "train": False}))

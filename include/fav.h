@@ -150,7 +150,8 @@ int fav_net_forward(fav_net* net, const float* in7, float* out3, int H, int W, f
  * enable: every later forward records one event pair per convolution launch.  read: synchronises the
  * recorded events and returns, per convolution in network order, the summed milliseconds, the number of
  * launches, the useful MACs of one launch (no padding) and an id of the kernel instance that ran it (1 = row-folded
- * last layer, 8 = first-layer kernel, 300+N = halo-resident 3x3 kernel with N output channels, otherwise the N tile
+ * last layer, 8 = first-layer kernel, 300+N = halo-resident 3x3 kernel with N output channels, 800+N = transposed-convolution
+ * kernel, otherwise the N tile
  * 128/64/32 of the generic implicit-GEMM kernel); then clears the accumulators.  Arrays hold up to `capacity` entries. */
 int fav_net_profile_enable(fav_net* net, int on);
 int fav_net_profile_read_host(fav_net* net, int capacity, int* count, double* ms_sum, int* launches,
@@ -163,6 +164,15 @@ int fav_conv2d_nchw_f32(const float* in, int Cin, int H, int W,
                         const float* weight, const float* bias, int Cout, int k, int stride, int pad,
                         const float* gamma, const float* beta, float eps, int relu,
                         float* out, fav_hipstream_t stream);
+
+/* operator-level entry (nn.SpatialFullConvolution [+ nn.InstanceNormalization [+ nn.ReLU]]), NCHW fp32, same conventions;
+ * weight [Cin][Cout][k][k]; output (H - 1) * stride - 2 * pad + k + adj per axis.  k <= 9, stride <= 4, pad <= k - 1, adj < stride.
+ * Stride >= 2 runs the phase-decomposed MFMA kernel the network uses for `u<n>` / `f<k>s<s>-<n>` layers, stride 1 the ordinary
+ * convolution it is.  Allocates temporaries: test/ops use. */
+int fav_conv_transpose2d_nchw_f32(const float* in, int Cin, int H, int W,
+                                  const float* weight, const float* bias, int Cout, int k, int stride, int pad, int adj,
+                                  const float* gamma, const float* beta, float eps, int relu,
+                                  float* out, fav_hipstream_t stream);
 
 /* ---- the fused per-frame pipeline (A1..A10 minus file I/O) -------------------------------------
  * Replaces one iteration of run_fast_neural_video's loop (fast_artistic_video_core.lua:194-211)
