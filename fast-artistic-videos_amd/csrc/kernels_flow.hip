@@ -1,0 +1,218 @@
+// kernels_flow.hip -- dense optical flow for gfx950: Horn-Schunck with warping, coarse to fine, Jacobi sweeps ("fav_flow";
+// restated in numpy by tests/util/flow_model.py, which these kernels follow bit for bit in fp32).
+//
+// Flow "from A to B" is w with B(p + w(p)) ~ A(p); flows are the .flo payload [H][W][2] (u, v).
+//   grey          g = (0.299 R + 0.587 G) + 0.114 B on the bytes
+//   down          [1 2 1]/4 along x, then along y (borders replicated, each pass rounded), then the 2x2 mean -> ceil(w/2) x ceil(h/2)
+//   up_flow       bilinear at ((x + 0.5) / 2 - 0.5, (y + 0.5) / 2 - 0.5) clamped to the coarse grid; u * (w / wc), v * (h / hc)
+//   coefficients  Bw = B(p + w0) bilinear with clamped coordinates; a = Ix, b = Iy central differences of Bw * 0.5 (borders replicated);
+//                 c = (Bw - A) - a u0 - b v0;  r = 1 / (alpha^2 + a^2 + b^2)  -> float4 (a, b, c, r) per pixel
+//   sweep         u_bar, v_bar = 4-neighbour means (borders replicated); t = (a u_bar + b v_bar + c) r;  u = u_bar - a t, v = v_bar - b t
+//
+// The sweeps are the hot path: iters x warps x levels x 2 directions of them per frame.  One sweep per launch is a pass over HBM of
+// 32 bytes per pixel; flow_sweep_kernel runs up to K sweeps per launch on a tile that lives in LDS (temporal blocking).  Jacobi reads
+// the previous sweep only, so the result does not depend on K or on the tiling.
+// Compiled with -ffp-contract=off: every operation rounds like the CPU restatement.
+#include "fav_internal.h"
+
+namespace fav {
+namespace {
+
+// img [h][w] at (px, py), coordinates clamped to the image: lerp along x in both rows, then along y
+__device__ __forceinline__ float bilinear(const float* __restrict__ img, int w, int h, float px, float py)
+{
+    px = fminf(fmaxf(px, 0.f), (float)(w - 1));
+    py = fminf(fmaxf(py, 0.f), (float)(h - 1));
+    const float flx = floorf(px), fly = floorf(py);
+    const int x0 = (int)flx, y0 = (int)fly;
+    const int x1 = min(x0 + 1, w - 1), y1 = min(y0 + 1, h - 1);
+    const float fx = px - flx, fy = py - fly;
+    const float* r0 = img + (size_t)y0 * w;
+    const float* r1 = img + (size_t)y1 * w;
+    const float a00 = r0[x0], a01 = r0[x1], a10 = r1[x0], a11 = r1[x1];
+    const float top = a00 + fx * (a01 - a00);
+    const float bot = a10 + fx * (a11 - a10);
+    return top + fy * (bot - top);
+}
+
+__global__ __launch_bounds__(256) void flow_grey_kernel(const uint8_t* __restrict__ rgb, float* __restrict__ g, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float r = (float)rgb[i * 3], gr = (float)rgb[i * 3 + 1], b = (float)rgb[i * 3 + 2];
+    g[i] = (0.299f * r + 0.587f * gr) + 0.114f * b;
+}
+
+// one lane per destination sample: the four blurred samples under it, each from its 3 x 3 neighbourhood (a 4 x 4 gather the L1 serves)
+__global__ __launch_bounds__(256) void flow_down_kernel(const float* __restrict__ src, int w, int h, float* __restrict__ dst, int wd, int hd)
+{
+    const int ox = blockIdx.x * 64 + (threadIdx.x & 63), oy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (ox >= wd || oy >= hd) return;
+    auto blur_x = [&](int y, int x) {      // y, x inside the image
+        const float* row = src + (size_t)y * w;
+        return ((row[max(x - 1, 0)] + 2.f * row[x]) + row[min(x + 1, w - 1)]) * 0.25f;
+    };
+    auto blur = [&](int y, int x) { return ((blur_x(max(y - 1, 0), x) + 2.f * blur_x(y, x)) + blur_x(min(y + 1, h - 1), x)) * 0.25f; };
+    const int x0 = 2 * ox, x1 = min(2 * ox + 1, w - 1), y0 = 2 * oy, y1 = min(2 * oy + 1, h - 1);
+    dst[(size_t)oy * wd + ox] = ((blur(y0, x0) + blur(y0, x1)) + (blur(y1, x0) + blur(y1, x1))) * 0.25f;
+}
+
+__global__ __launch_bounds__(256) void flow_up_kernel(const float2* __restrict__ coarse, int wc, int hc, float2* __restrict__ fine, int w, int h,
+                                                      float sx, float sy)
+{
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= w || y >= h) return;
+    float px = ((float)x + 0.5f) * 0.5f - 0.5f, py = ((float)y + 0.5f) * 0.5f - 0.5f;
+    px = fminf(fmaxf(px, 0.f), (float)(wc - 1));
+    py = fminf(fmaxf(py, 0.f), (float)(hc - 1));
+    const float flx = floorf(px), fly = floorf(py);
+    const int x0 = (int)flx, y0 = (int)fly;
+    const int x1 = min(x0 + 1, wc - 1), y1 = min(y0 + 1, hc - 1);
+    const float fx = px - flx, fy = py - fly;
+    const float2 a00 = coarse[(size_t)y0 * wc + x0], a01 = coarse[(size_t)y0 * wc + x1];
+    const float2 a10 = coarse[(size_t)y1 * wc + x0], a11 = coarse[(size_t)y1 * wc + x1];
+    const float tu = a00.x + fx * (a01.x - a00.x), bu = a10.x + fx * (a11.x - a10.x);
+    const float tv = a00.y + fx * (a01.y - a00.y), bv = a10.y + fx * (a11.y - a10.y);
+    fine[(size_t)y * w + x] = make_float2((tu + fy * (bu - tu)) * sx, (tv + fy * (bv - tv)) * sy);
+}
+
+// warp + derivatives + coefficients in one launch: a lane forms Bw at its pixel and at its four (replicated) neighbours -- each with that
+// pixel's own flow -- instead of a second pass over a stored Bw
+__global__ __launch_bounds__(256) void flow_coef_kernel(const float* __restrict__ A, const float* __restrict__ B, const float2* __restrict__ flow0,
+                                                        float alpha2, float4* __restrict__ coef, int w, int h)
+{
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= w || y >= h) return;
+    auto bw = [&](int yy, int xx) {
+        const float2 f = flow0[(size_t)yy * w + xx];
+        return bilinear(B, w, h, (float)xx + f.x, (float)yy + f.y);
+    };
+    const float2 f0 = flow0[(size_t)y * w + x];
+    const float bc = bilinear(B, w, h, (float)x + f0.x, (float)y + f0.y);
+    const float a = (bw(y, min(x + 1, w - 1)) - bw(y, max(x - 1, 0))) * 0.5f;
+    const float b = (bw(min(y + 1, h - 1), x) - bw(max(y - 1, 0), x)) * 0.5f;
+    const float it = bc - A[(size_t)y * w + x];
+    const float c = (it - a * f0.x) - b * f0.y;
+    const float r = 1.f / ((alpha2 + a * a) + b * b);      // one correctly rounded division (-fhip-fp32-correctly-rounded-divide-sqrt)
+    coef[(size_t)y * w + x] = make_float4(a, b, c, r);
+}
+
+// ---- the sweeps, temporally blocked.
+// A block owns a REGION of 64 x 64 cells: an interior of (64 - 2K)^2 cells and a halo of K cells around it.  It loads the region's (u, v)
+// into LDS (float2, 32 KB) and its coefficients into registers (a lane keeps one column position and 16 rows, ty + 4 j: 64 VGPRs), runs
+// n <= K sweeps there and writes the interior.  After sweep s the cells nearer than s to the region's edge are stale; they are never
+// written back, and the interior stays s <= K cells away from them.
+// Image borders: a neighbour index is clamped to the IMAGE first (then to the region), at every sweep, so the edge cell of the image is
+// its own neighbour exactly as in the one-sweep form; region cells outside the image are loaded from clamped addresses, are read by no
+// cell inside it and are never stored.
+// LDS traffic: a wave reads rows of 64 float2 -- 32 lanes x 8 B = one 256-B bank row per half wave, conflict-free for the centre, left /
+// right (shifted by one lane) and up / down (another row) taps alike.  Two barriers per sweep (all new values are formed in registers
+// before any is stored), one buffer: 32 KB per block leave four 256-thread blocks per CU next to ~110 VGPRs per lane.
+constexpr int SW_R = 64;           // region side
+constexpr int SW_ROWS = 16;        // rows per lane (256 lanes: 64 columns x 4)
+
+__global__ __launch_bounds__(256) void flow_sweep_kernel(const float2* __restrict__ fin, const float4* __restrict__ coef, float2* __restrict__ fout,
+                                                         int W, int H, int K, int n)
+{
+    __shared__ float2 s[SW_R][SW_R];
+    const int lx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int TI = SW_R - 2 * K;
+    const int x0 = (int)blockIdx.x * TI - K, y0 = (int)blockIdx.y * TI - K;
+    const int gx = x0 + lx;
+    const int cx = min(max(gx, 0), W - 1);
+    const int lxl = (gx > 0 && lx > 0) ? lx - 1 : lx;
+    const int lxr = (gx < W - 1 && lx < SW_R - 1) ? lx + 1 : lx;
+    float4 cf[SW_ROWS];
+    float2 nv[SW_ROWS];
+#pragma unroll
+    for (int j = 0; j < SW_ROWS; ++j) {
+        const int ly = ty + 4 * j;
+        const int cy = min(max(y0 + ly, 0), H - 1);
+        const size_t idx = (size_t)cy * W + cx;
+        cf[j] = coef[idx];
+        s[ly][lx] = fin[idx];
+    }
+    __syncthreads();
+    for (int sweep = 0; sweep < n; ++sweep) {
+#pragma unroll
+        for (int j = 0; j < SW_ROWS; ++j) {
+            const int ly = ty + 4 * j, gy = y0 + ly;
+            const int lyu = (gy > 0 && ly > 0) ? ly - 1 : ly;
+            const int lyd = (gy < H - 1 && ly < SW_R - 1) ? ly + 1 : ly;
+            const float2 L = s[ly][lxl], R = s[ly][lxr], U = s[lyu][lx], D = s[lyd][lx];
+            const float ub = ((L.x + R.x) + (U.x + D.x)) * 0.25f;
+            const float vb = ((L.y + R.y) + (U.y + D.y)) * 0.25f;
+            const float t = ((cf[j].x * ub + cf[j].y * vb) + cf[j].z) * cf[j].w;
+            nv[j] = make_float2(ub - cf[j].x * t, vb - cf[j].y * t);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < SW_ROWS; ++j) s[ty + 4 * j][lx] = nv[j];
+        __syncthreads();
+    }
+    if (lx < K || lx >= SW_R - K || gx >= W) return;      // (gx >= 0 here: lx >= K)
+#pragma unroll
+    for (int j = 0; j < SW_ROWS; ++j) {
+        const int ly = ty + 4 * j, gy = y0 + ly;
+        if (ly >= K && ly < SW_R - K && gy < H) fout[(size_t)gy * W + gx] = s[ly][lx];
+    }
+}
+
+inline dim3 grid_64x4(int w, int h) { return dim3((w + 63) / 64, (h + 3) / 4); }
+inline bool size_ok(int w, int h) { return w > 0 && h > 0 && (long long)w * h <= (1ll << 28) && (h + 3) / 4 <= 65535; }
+
+}  // namespace
+
+int launch_flow_grey(const uint8_t* rgb_hwc, float* grey, int W, int H, hipStream_t st)
+{
+    FAV_REQUIRE(size_ok(W, H), "flow grey: bad size %dx%d", W, H);
+    const size_t n = (size_t)W * H;
+    hipLaunchKernelGGL(flow_grey_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rgb_hwc, grey, n);
+    FAV_LAUNCH_CHECK("flow_grey_kernel");
+    return FAV_OK;
+}
+
+int launch_flow_down(const float* src, int W, int H, float* dst, hipStream_t st)
+{
+    FAV_REQUIRE(size_ok(W, H), "flow down: bad size %dx%d", W, H);
+    const int wd = (W + 1) / 2, hd = (H + 1) / 2;
+    hipLaunchKernelGGL(flow_down_kernel, grid_64x4(wd, hd), dim3(256), 0, st, src, W, H, dst, wd, hd);
+    FAV_LAUNCH_CHECK("flow_down_kernel");
+    return FAV_OK;
+}
+
+int launch_flow_up(const float* coarse, int Wc, int Hc, float* fine, int W, int H, hipStream_t st)
+{
+    FAV_REQUIRE(size_ok(W, H) && size_ok(Wc, Hc), "flow up: bad size %dx%d -> %dx%d", Wc, Hc, W, H);
+    hipLaunchKernelGGL(flow_up_kernel, grid_64x4(W, H), dim3(256), 0, st, reinterpret_cast<const float2*>(coarse), Wc, Hc,
+                       reinterpret_cast<float2*>(fine), W, H, (float)W / (float)Wc, (float)H / (float)Hc);
+    FAV_LAUNCH_CHECK("flow_up_kernel");
+    return FAV_OK;
+}
+
+int launch_flow_coef(const float* A, const float* B, const float* flow0, float alpha, float* coef, int W, int H, hipStream_t st)
+{
+    FAV_REQUIRE(size_ok(W, H), "flow coefficients: bad size %dx%d", W, H);
+    hipLaunchKernelGGL(flow_coef_kernel, grid_64x4(W, H), dim3(256), 0, st, A, B, reinterpret_cast<const float2*>(flow0), alpha * alpha,
+                       reinterpret_cast<float4*>(coef), W, H);
+    FAV_LAUNCH_CHECK("flow_coef_kernel");
+    return FAV_OK;
+}
+
+// `iters` sweeps from *cur, ceil(iters / K) launches between *cur and *other; on return *cur holds the result
+int launch_flow_sweeps(float** cur, float** other, const float* coef, int iters, int K, int W, int H, hipStream_t st)
+{
+    FAV_REQUIRE(size_ok(W, H) && iters >= 1 && K >= 1 && K <= FLOW_MAX_SWEEPS_PER_LAUNCH, "flow sweeps: bad argument (%dx%d, %d sweeps, %d per launch)", W, H, iters, K);
+    const int ti = SW_R - 2 * K;
+    const dim3 grid((W + ti - 1) / ti, (H + ti - 1) / ti);
+    FAV_REQUIRE(grid.y <= 65535, "flow sweeps: %d rows are too many", H);
+    for (int done = 0; done < iters; done += K) {
+        hipLaunchKernelGGL(flow_sweep_kernel, grid, dim3(256), 0, st, reinterpret_cast<const float2*>(*cur), reinterpret_cast<const float4*>(coef),
+                           reinterpret_cast<float2*>(*other), W, H, K, std::min(K, iters - done));
+        FAV_LAUNCH_CHECK("flow_sweep_kernel");
+        std::swap(*cur, *other);
+    }
+    return FAV_OK;
+}
+
+}  // namespace fav

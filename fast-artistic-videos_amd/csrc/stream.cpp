@@ -344,6 +344,22 @@ extern "C" int fav_stream_next_frame_flow(fav_stream* s, const uint8_t* frame_rg
     return stream_next(s, frame_rgb_hwc, backward_flo, s->mask, out_rgb_f32, out_rgb8_hwc, st, true);
 }
 
+// -estimate_flow: both flows from the two frames on the caller's queue, then the frame as above (never prefetched: the flows do not exist
+// before this call)
+extern "C" int fav_stream_next_frame_estimate(fav_stream* s, const uint8_t* frame_rgb_hwc, const uint8_t* prev_frame_rgb_hwc,
+                                              const fav_flow_opts* flow_opts_host, int use_structure, float* backward_flo, float* forward_flo,
+                                              void* workspace, size_t workspace_bytes, float* out_rgb_f32, uint8_t* out_rgb8_hwc,
+                                              fav_hipstream_t stream)
+{
+    FAV_REQUIRE(s && frame_rgb_hwc && prev_frame_rgb_hwc && backward_flo && forward_flo, "fav_stream_next_frame_estimate: null argument");
+    FAV_HIP(hipSetDevice(net_device(s->net)));
+    int rc = fav_flow_rgb8(frame_rgb_hwc, prev_frame_rgb_hwc, s->W, s->H, flow_opts_host, backward_flo, workspace, workspace_bytes, stream);
+    if (rc) return rc;
+    rc = fav_flow_rgb8(prev_frame_rgb_hwc, frame_rgb_hwc, s->W, s->H, flow_opts_host, forward_flo, workspace, workspace_bytes, stream);
+    if (rc) return rc;
+    return fav_stream_next_frame_flow(s, frame_rgb_hwc, backward_flo, forward_flo, use_structure, out_rgb_f32, out_rgb8_hwc, stream);
+}
+
 extern "C" int fav_stream_prefetch_mask(fav_stream* s, const uint8_t* frame_rgb_hwc, const float* backward_flo,
                                         const float* forward_flo, int use_structure, fav_hipstream_t stream)
 {

@@ -20,7 +20,13 @@
 // -precision <fp32|bf16> (fp32 = parity mode, default; bf16 = optional fast mode, see include/fav.h),
 // -seed <n> (key of the documented RNG behind -fill_occlusions uniform-random, unseeded in the reference),
 // -writers <n>, -timing <0|1>, -temporal_eval_file <path> (the temporal-consistency number of -evaluate, fav.lua:128-151,
-// with the frame's own flow and certainty: one line of ';'-separated per-frame values, one line with their mean).
+// with the frame's own flow and certainty: one line of ';'-separated per-frame values, one line with their mean),
+// -estimate_flow <0|1> (0, default; 1: frames in, stylised PNGs out, no .flo / .pgm on disk -- both flows of a frame are estimated on the
+//   device from frame i and the frame before it in processing order, which stays on the device (fav_stream_next_frame_estimate), and go
+//   through the fused consistency check, -structure as usual.  Needs -input_pattern only; -flow_pattern, -forward_flow_pattern and
+//   -occlusions_pattern are refused next to it, and so is a -scale_factor other than 1.  -continue_with reads frame i-1's file as well.
+//   The 4-argument look-ahead is OFF in this mode: a mask needs the flows, and those do not exist before the frame is enqueued),
+// -flow_alpha <x>, -flow_iters <n>, -flow_warps <n>, -flow_levels <n> (fav_flow_opts; 0 = default, each).
 //
 // Several videos on several GPUs (BASELINE config 4; the reference runs one `th` process per video, stylizeVideo_deepflow.sh:87-96,
 // and its only device hook is utils.setup_gpu, fast_artistic_video/utils.lua:43-66):
@@ -296,6 +302,7 @@ struct Pinned { uint8_t* frame = nullptr; float* bw = nullptr; float* fw = nullp
 // pd != null: decode straight into that pinned staging set of pin_px pixels (no allocation, no second copy)
 FrameIn load_frame_inputs(const Opt& o, const favp::Poll& poll, int i, bool first_of_run, const Pinned* pd, size_t pin_px)
 {
+    const bool estimate = o.i("estimate_flow") != 0;
     const bool fused_check = !o.s("forward_flow_pattern").empty();
     FrameIn in; in.index = pd ? -i - 1 : i;              // negative index marks "pinned, do not free"
     const std::string fp = fmt_int(o.s("input_pattern"), i);
@@ -305,7 +312,7 @@ FrameIn load_frame_inputs(const Opt& o, const favp::Poll& poll, int i, bool firs
     else check(fav_read_pnm_host(fp.c_str(), &in.frame, &in.W, &in.H, &ch), fp.c_str());
     if (ch != 3) die(fp + ": expected a colour (P6) frame");
     in.single = (i == 1) || o.f("create_inconsistent") || first_of_run;                                 // fav.lua:172
-    if (!in.single) {
+    if (!in.single && !estimate) {
         const std::string fl = flow_name(o.s("flow_pattern"), i - 1, i);                               // fav.lua:100,154
         int w, h;
         if (fused_check) {
@@ -332,7 +339,10 @@ FrameIn load_frame_inputs(const Opt& o, const favp::Poll& poll, int i, bool firs
 // `net` / `net_img` live on the current device; `nwriters` PNG threads.
 void run_stream(const Opt& o, fav_net* net, fav_net* net_img, int nwriters, StreamResult* res)   // nwriters: the budget; adjusted below
 {
-    const bool fused_check = !o.s("forward_flow_pattern").empty();
+    const bool estimate = o.i("estimate_flow") != 0;       // the flows come from the frames (and go through the fused check)
+    const bool fused_check = estimate || !o.s("forward_flow_pattern").empty();
+    const fav_flow_opts flow_opts{o.i("flow_levels"), o.i("flow_warps"), o.i("flow_iters"), (float)o.d("flow_alpha"), 0};
+    void* d_flow_ws = nullptr; size_t flow_ws_bytes = 0;
     const int border = o.s("warp_border") == "cpu" ? FAV_BORDER_CPU : FAV_BORDER_STN;
     const int num_frames = o.i("num_frames");
     const bool backward = o.f("backward");
@@ -431,7 +441,8 @@ void run_stream(const Opt& o, fav_net* net, fav_net* net_img, int nwriters, Stre
     auto load_pinned = [&](int i, bool first_of_run, int set) {
         if (pinned_ready && !pin[set].frame) {           // first use of this staging set: pinned here, by the loader thread that owns it
             Pinned& p = pin[set];
-            if (hipHostMalloc((void**)&p.frame, pin_px * 3, hipHostMallocDefault) || hipHostMalloc((void**)&p.bw, pin_px * 8, hipHostMallocDefault) ||
+            if (estimate) { if (hipHostMalloc((void**)&p.frame, pin_px * 3, hipHostMallocDefault)) die("hipHostMalloc failed"); }      // frames only
+            else if (hipHostMalloc((void**)&p.frame, pin_px * 3, hipHostMallocDefault) || hipHostMalloc((void**)&p.bw, pin_px * 8, hipHostMallocDefault) ||
                 (fused_check ? hipHostMalloc((void**)&p.fw, pin_px * 8, hipHostMallocDefault) : hipHostMalloc((void**)&p.cert, pin_px, hipHostMallocDefault))) die("hipHostMalloc failed");
         }
         return load(i, first_of_run, pinned_ready ? &pin[set] : nullptr);
@@ -546,7 +557,7 @@ void run_stream(const Opt& o, fav_net* net, fav_net* net_img, int nwriters, Stre
     // masks are under way on the side queues while frame i is enqueued.  That mode needs TWO frames: a mask takes 1.5 ms behind a
     // 0.45 ms upload, a frame 1.9 ms -- one frame ahead, every frame waited 0.1 ms for its mask (period 2.05 ms: 460 frames/s;
     // profiles/r03z_cli_4arg_trace.txt)
-    const int LA = (fused_check && o.i("structure") != 0) ? 2 : 1;
+    const int LA = (fused_check && !estimate && o.i("structure") != 0) ? 2 : 1;
     std::deque<FrameIn> ahead;
     bool drained = false;
     next_to_issue = start + inc;
@@ -594,6 +605,19 @@ void run_stream(const Opt& o, fav_net* net, fav_net* net_img, int nwriters, Stre
                 check(fav_stream_set_state(fs, d_state, st), "fav_stream_set_state");
                 hipStreamSynchronize(st); hipFree(d_state);
             }
+            if (estimate) {
+                flow_ws_bytes = fav_flow_workspace_bytes(W, H, &flow_opts);
+                if (!flow_ws_bytes) die(std::string("-estimate_flow: ") + fav_last_error());
+                if (hipMalloc(&d_flow_ws, flow_ws_bytes) != hipSuccess) die("hipMalloc failed");
+                if (!cur.single) {                       // -continue_with: the frame before the first one is read as well, into the set "before" dset
+                    const std::string pp = fmt_int(o.s("input_pattern"), i - inc);
+                    uint8_t* pf = nullptr; int pw, ph, pch;
+                    check(fav_read_pnm_host(pp.c_str(), &pf, &pw, &ph, &pch), pp.c_str());
+                    if (pch != 3 || pw != W || ph != H) die(pp + ": expected a colour (P6) frame of the sequence's size");
+                    if (hipMemcpy(dev[(dset + NDEV - 1) % NDEV].frame, pf, n * 3, hipMemcpyHostToDevice) != hipSuccess) die("upload failed");
+                    fav_free_host(pf);
+                }
+            }
             upload(cur, dset);
             hipStreamSynchronize(st_copy);               // the first frame's host buffers are malloc'ed: release them now
             first = false;
@@ -615,7 +639,7 @@ void run_stream(const Opt& o, fav_net* net, fav_net* net_img, int nwriters, Stre
             const int nset = (dset + 1 + (int)ahead.size()) % NDEV;
             const Dev& dn = dev[nset];
             upload(nxt, nset);
-            if (fused_check && !nxt.single && (!quiet || o.i("structure") != 0)) {
+            if (fused_check && !estimate && !nxt.single && (!quiet || o.i("structure") != 0)) {
                 // quiet: the look-ahead may only start on inputs the host has seen arrive (0.35 ms of DMA; the GPU is busy with frame i-1)
                 if (quiet && wait_event_sleeping(ev_up[nset], 50) != hipSuccess) die("GPU error while uploading a frame");
                 check(fav_stream_prefetch_mask(fs, dn.frame, dn.bw, dn.fw, o.i("structure"), st), "fav_stream_prefetch_mask");
@@ -632,6 +656,11 @@ void run_stream(const Opt& o, fav_net* net, fav_net* net_img, int nwriters, Stre
         if (teval && !cur.single) check(fav_stream_get_state(fs, d_prev, st), "fav_stream_get_state");
         if (cur.single) {
             check(fav_stream_first_frame(fs, dc.frame, nullptr, d_out8, st), "fav_stream_first_frame");       // core:203-204
+        } else if (estimate) {
+            // the previous frame in processing order is still in the device set before this one: with one frame of look-ahead the
+            // uploads only ever touch the set after it
+            check(fav_stream_next_frame_estimate(fs, dc.frame, dev[(dset + NDEV - 1) % NDEV].frame, &flow_opts, o.i("structure"), dc.bw, dc.fw,
+                                                 d_flow_ws, flow_ws_bytes, nullptr, d_out8, st), "fav_stream_next_frame_estimate");
         } else if (fused_check) {
             check(fav_stream_next_frame_flow(fs, dc.frame, dc.bw, dc.fw, o.i("structure"), nullptr, d_out8, st), "fav_stream_next_frame_flow");
         } else {
@@ -713,7 +742,7 @@ void run_stream(const Opt& o, fav_net* net, fav_net* net_img, int nwriters, Stre
     if (h_png_size) hipHostFree(h_png_size);
     for (auto& kv : slot_ev) hipEventDestroy(kv.second);
     fav_stream_destroy(fs);
-    hipFree(d_prev); hipFree(d_cur);
+    hipFree(d_prev); hipFree(d_cur); hipFree(d_flow_ws);
     hipFree(d_out8s[0]); hipFree(d_out8s[1]); for (auto& dv : dev) { hipFree(dv.frame); hipFree(dv.cert); hipFree(dv.bw); hipFree(dv.fw); }
     for (auto p : h_out) hipHostFree(p);
     for (auto& p : pin) { hipHostFree(p.frame); hipHostFree(p.bw); hipHostFree(p.fw); hipHostFree(p.cert); }
@@ -740,6 +769,7 @@ int main(int argc, char** argv)
            // additive
            {"forward_flow_pattern", ""}, {"structure", "1"}, {"warp_border", "stn"}, {"poll_timeout", "3600"}, {"poll_settle", "1.0"},
            {"png_level", "1"}, {"png_encoder", "gpu"}, {"png_overlap", "0"}, {"writers", "0"}, {"timing", "0"}, {"temporal_eval_file", ""}, {"seed", "1"}, {"precision", "fp32"},
+           {"estimate_flow", "0"}, {"flow_alpha", "0"}, {"flow_iters", "0"}, {"flow_warps", "0"}, {"flow_levels", "0"},
            {"streams", ""}, {"gpus", "1"}, {"force_dist", "0"}, {"dry_run", "0"}, {"shared_gpu", "0"}, {"pin_workers", "1"},
            // internal (set by the launcher for its workers)
            {"worker_rank", "-1"}, {"worker_world", "0"}, {"rccl_id_file", ""},
@@ -757,8 +787,17 @@ int main(int argc, char** argv)
         o.v[k] = argv[++a];
     }
     if (o.s("input_pattern").empty()) die("Must give -input_pattern");                                      // fav.lua:177-179
+    if (o.s("estimate_flow") != "0" && o.s("estimate_flow") != "1") die("-estimate_flow must be 0 or 1, not '" + o.s("estimate_flow") + "'");
+    const bool estimate = o.i("estimate_flow") != 0;
+    if (estimate) {
+        for (const char* k : {"flow_pattern", "forward_flow_pattern", "occlusions_pattern"})
+            if (!o.s(k).empty()) die(std::string("-estimate_flow 1 computes both flows and the certainty from the frames: it cannot be combined with -") + k);
+        if (atof(o.s("scale_factor").c_str()) != 1.0) die("-estimate_flow 1 cannot be combined with a -scale_factor other than 1");
+        const fav_flow_opts fo{o.i("flow_levels"), o.i("flow_warps"), o.i("flow_iters"), (float)o.d("flow_alpha"), 0};
+        if (fav_flow_workspace_bytes(16, 16, &fo) == 0) die(std::string("-flow_alpha / -flow_iters / -flow_warps / -flow_levels: ") + fav_last_error());
+    }
     const bool fused_check = !o.s("forward_flow_pattern").empty();
-    if (!o.f("create_inconsistent") && (o.s("flow_pattern").empty() || (o.s("occlusions_pattern").empty() && !fused_check)))
+    if (!estimate && !o.f("create_inconsistent") && (o.s("flow_pattern").empty() || (o.s("occlusions_pattern").empty() && !fused_check)))
         die("Must give -flow_pattern and -occlusions_pattern");                                              // fav.lua:180-182
     if (o.i("gpu") < 0) die("-gpu -1: this build has no CPU backend (the CPU restatement lives in oracle/ and is test infrastructure only)");
     if (o.f("evaluate")) die("-evaluate needs the VGG-16 perceptual-loss network: outside the hot-path scope (DESIGN.md)");

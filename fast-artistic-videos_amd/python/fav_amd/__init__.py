@@ -57,6 +57,8 @@ def lib() -> C.CDLL:
     L.fav_vr_last_mask.restype = C.c_void_p
     L.fav_vr_last_mask.argtypes = [C.c_void_p]
     L.fav_png_crc32_combine_host.restype = C.c_uint32; L.fav_png_crc32_combine_host.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+    L.fav_flow_workspace_bytes.restype = C.c_size_t
+    L.fav_flow_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_void_p]
     _lib = L
     return L
 
@@ -76,6 +78,8 @@ EXPORTS = [
     "fav_vr_map_host", "fav_temporal_loss_host", "fav_sequential_sum_f32", "fav_read_flo_into_host", "fav_read_pnm_into_host", "fav_net_set_precision", "fav_net_check", "fav_net_set_shared_device", "fav_net_forget_stream",
     "fav_scale_bicubic_f32", "fav_stream_set_single_image_size",
     "fav_vr_face_flow", "fav_vr_prefetch_mask", "fav_vr_last_mask",
+    "fav_flow_workspace_bytes", "fav_flow_rgb8", "fav_flow_grey_f32", "fav_flow_down_f32", "fav_flow_up_f32", "fav_flow_coefficients_f32",
+    "fav_flow_sweeps_f32", "fav_stream_next_frame_estimate",
 ]
 
 
@@ -183,6 +187,83 @@ def scale_bicubic(x, hd: int, wd: int):
     c, h, w = x.shape
     out = torch.empty((c, hd, wd), dtype=torch.float32, device=x.device)
     _check(lib().fav_scale_bicubic_f32(_p(x), _p(out), c, h, w, hd, wd, _stream()))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ optical flow
+class _FlowOpts(C.Structure):
+    _fields_ = [("levels", C.c_int), ("warps", C.c_int), ("iters", C.c_int), ("alpha", C.c_float), ("sweeps_per_launch", C.c_int)]
+
+
+def _flow_opts(opts) -> "_FlowOpts":
+    unknown = set(opts) - {f for f, _ in _FlowOpts._fields_}
+    if unknown:
+        raise FavError(f"unknown flow option(s) {sorted(unknown)}")
+    return _FlowOpts(int(opts.get("levels", 0)), int(opts.get("warps", 0)), int(opts.get("iters", 0)), float(opts.get("alpha", 0.0)),
+                     int(opts.get("sweeps_per_launch", 0)))
+
+
+def flow_workspace_bytes(w: int, h: int, **opts) -> int:
+    """fav_flow_workspace_bytes (host only); raises on a bad size or option"""
+    o = _flow_opts(opts)
+    n = lib().fav_flow_workspace_bytes(w, h, C.cast(C.pointer(o), C.c_void_p))
+    if n == 0:
+        _check(-1)
+    return n
+
+
+def flow_rgb8(a, b, **opts):
+    """fav_flow_rgb8: the flow w "from a to b", b(p + w(p)) ~ a(p), of two u8 [H][W][3] frames -> .flo payload [H][W][2] (u, v).
+    opts: levels, warps, iters, alpha, sweeps_per_launch (0 / absent = default)."""
+    torch = _torch()
+    if not (a.is_cuda and b.is_cuda and a.dtype == torch.uint8 and b.dtype == torch.uint8 and a.is_contiguous() and b.is_contiguous() and
+            a.dim() == 3 and a.shape[2] == 3 and a.shape == b.shape):
+        raise FavError("flow_rgb8: a and b must be contiguous uint8 CUDA tensors [H][W][3] of one size")
+    h, w = a.shape[0], a.shape[1]
+    o = _flow_opts(opts)
+    nb = flow_workspace_bytes(w, h, **opts)
+    ws = torch.empty(nb, dtype=torch.uint8, device=a.device)
+    out = torch.empty((h, w, 2), dtype=torch.float32, device=a.device)
+    _check(lib().fav_flow_rgb8(_p(a), _p(b), w, h, C.byref(o), _p(out), _p(ws), C.c_size_t(nb), _stream()))
+    return out
+
+
+def flow_grey(rgb_hwc):
+    torch = _torch()
+    h, w = rgb_hwc.shape[0], rgb_hwc.shape[1]
+    out = torch.empty((h, w), dtype=torch.float32, device=rgb_hwc.device)
+    _check(lib().fav_flow_grey_f32(_p(rgb_hwc), _p(out), w, h, _stream()))
+    return out
+
+
+def flow_down(img):
+    torch = _torch(); _chk_f32(img, "img")
+    h, w = img.shape
+    out = torch.empty(((h + 1) // 2, (w + 1) // 2), dtype=torch.float32, device=img.device)
+    _check(lib().fav_flow_down_f32(_p(img), _p(out), w, h, _stream()))
+    return out
+
+
+def flow_up(coarse, h: int, w: int):
+    torch = _torch(); _chk_f32(coarse, "coarse")
+    out = torch.empty((h, w, 2), dtype=torch.float32, device=coarse.device)
+    _check(lib().fav_flow_up_f32(_p(coarse), coarse.shape[1], coarse.shape[0], _p(out), w, h, _stream()))
+    return out
+
+
+def flow_coefficients(a_grey, b_grey, flow0, alpha: float = 15.0):
+    torch = _torch(); _chk_f32(a_grey, "a_grey"); _chk_f32(b_grey, "b_grey"); _chk_f32(flow0, "flow0")
+    h, w = a_grey.shape
+    out = torch.empty((h, w, 4), dtype=torch.float32, device=a_grey.device)
+    _check(lib().fav_flow_coefficients_f32(_p(a_grey), _p(b_grey), _p(flow0), C.c_float(alpha), _p(out), w, h, _stream()))
+    return out
+
+
+def flow_sweeps(flow0, coef, iters: int, sweeps_per_launch: int = 0):
+    torch = _torch(); _chk_f32(flow0, "flow0"); _chk_f32(coef, "coef")
+    h, w, _ = flow0.shape
+    out, scratch = torch.empty_like(flow0), torch.empty_like(flow0)
+    _check(lib().fav_flow_sweeps_f32(_p(flow0), _p(coef), iters, sweeps_per_launch, _p(out), _p(scratch), w, h, _stream()))
     return out
 
 
@@ -354,6 +435,20 @@ class Stream:
         _check(lib().fav_stream_next_frame_flow(self.h, _p(frame_u8_hwc), _p(backward_flo), _p(forward_flo),
                                                 1 if use_structure else 0, _p(f), _p(u), _stream()))
         return f, u
+
+    def next_frame_estimate(self, frame_u8_hwc, prev_frame_u8_hwc, use_structure=False, want_f32=True, want_u8=False, **flow_opts):
+        """fav_stream_next_frame_estimate (the -estimate_flow path): both flows from the two frames, then next_frame_flow.
+        Returns (f32, u8, backward_flo, forward_flo)."""
+        torch = _torch()
+        f, u = self._outs(frame_u8_hwc.device, want_f32, want_u8)
+        o = _flow_opts(flow_opts)
+        nb = flow_workspace_bytes(self.W, self.H, **flow_opts)
+        ws = torch.empty(nb, dtype=torch.uint8, device=frame_u8_hwc.device)
+        bw = torch.empty((self.H, self.W, 2), dtype=torch.float32, device=frame_u8_hwc.device)
+        fw = torch.empty_like(bw)
+        _check(lib().fav_stream_next_frame_estimate(self.h, _p(frame_u8_hwc), _p(prev_frame_u8_hwc), C.byref(o), 1 if use_structure else 0,
+                                                    _p(bw), _p(fw), _p(ws), C.c_size_t(nb), _p(f), _p(u), _stream()))
+        return f, u, bw, fw
 
     def prefetch_mask(self, frame_u8_hwc, backward_flo, forward_flo, use_structure=False):
         _check(lib().fav_stream_prefetch_mask(self.h, _p(frame_u8_hwc), _p(backward_flo), _p(forward_flo),

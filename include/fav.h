@@ -98,6 +98,35 @@ int fav_min_filter_f32(const float* cert, float* out, int H, int W, int r, fav_h
  * src [C][Hs][Ws], dst [C][Hd][Wd], contiguous fp32, device pointers. */
 int fav_scale_bicubic_f32(const float* src, float* dst, int C, int Hs, int Ws, int Hd, int Wd, fav_hipstream_t stream);
 
+/* ---- dense optical flow ------------------------------------------------------------------------
+ * Stands in for `run-deepflow.sh <img1> <img2> <out.flo>` (makeOptFlow_deepflow.sh:46-49: two closed CPU binaries) with a variational
+ * estimator WITHOUT descriptor matching: Horn-Schunck with warping, coarse to fine, Jacobi sweeps, all in fp32 (the algorithm is stated
+ * in DESIGN.md, "fav_flow", and restated in numpy by tests/util/flow_model.py).  It recovers the small and medium motions of consecutive
+ * video frames; motions much larger than the coarsest level represents (about 2^levels pixels) are not recovered, and its quality
+ * against DeepFlow is unmeasured.
+ * The flow "from A to B" is w with B(p + w(p)) ~ A(p): flow_out is the .flo payload [H][W][2] (u, v), what fav_stream_next_frame_flow
+ * takes.  a_rgb_hwc / b_rgb_hwc: P6 payloads [H][W][3] u8.  Every field of fav_flow_opts may be 0 = default (levels: while the smaller
+ * side is still >= 16, at most 6; warps 3; iters 30; alpha 15 grey levels; sweeps_per_launch 6 -- the number of Jacobi sweeps a launch
+ * runs on a tile in LDS, 1..16: the result is bit-identical for every value); opts_host may be NULL.
+ * workspace: fav_flow_workspace_bytes(W, H, opts) bytes of device memory, 16-byte aligned, owned by the caller, private to the call until
+ * the stream has passed it (0 with a message: bad size or options).  The call allocates nothing and does not synchronise.
+ * W, H >= 16; anything else, or an option out of range, is FAV_EINVAL. */
+typedef struct fav_flow_opts { int levels; int warps; int iters; float alpha; int sweeps_per_launch; } fav_flow_opts;
+size_t fav_flow_workspace_bytes(int W, int H, const fav_flow_opts* opts_host);
+int fav_flow_rgb8(const uint8_t* a_rgb_hwc, const uint8_t* b_rgb_hwc, int W, int H, const fav_flow_opts* opts_host,
+                  float* flow_out, void* workspace, size_t workspace_bytes, fav_hipstream_t stream);
+/* the estimator's stages on their own (operator-level entries, as fav_scale_bicubic_f32 is one): the grey image [H][W]; one pyramid step
+ * to ceil(W/2) x ceil(H/2); the x2 flow upsampling between two level sizes; the coefficients (a, b, c, r) of one warp around flow0,
+ * [H][W][4], 16-byte aligned; `iters` Jacobi sweeps from flow0 into flow_out (scratch: a second flow buffer [H][W][2]; flow0 is not
+ * written and must be neither of the two). */
+int fav_flow_grey_f32(const uint8_t* rgb_hwc, float* grey, int W, int H, fav_hipstream_t stream);
+int fav_flow_down_f32(const float* src, float* dst, int W, int H, fav_hipstream_t stream);
+int fav_flow_up_f32(const float* coarse_flow, int Wc, int Hc, float* fine_flow, int W, int H, fav_hipstream_t stream);
+int fav_flow_coefficients_f32(const float* a_grey, const float* b_grey, const float* flow0, float alpha, float* coef, int W, int H,
+                              fav_hipstream_t stream);
+int fav_flow_sweeps_f32(const float* flow0, const float* coef, int iters, int sweeps_per_launch, float* flow_out, float* scratch,
+                        int W, int H, fav_hipstream_t stream);
+
 /* ---- A6/A7: VGG preprocessing + 7-channel input assembly --------------------------------------
  * Replaces run_next_image's input construction (fast_artistic_video_core.lua:161-171) and the first
  * frame's (:133-138) with fill_occlusions = vgg-mean; preprocess.lua:57-62.
@@ -241,6 +270,13 @@ int fav_stream_next_frame_cert(fav_stream* s, const uint8_t* frame_rgb_hwc, cons
 int fav_stream_next_frame_flow(fav_stream* s, const uint8_t* frame_rgb_hwc, const float* backward_flo,
                                const float* forward_flo, int use_structure,
                                float* out_rgb_f32, uint8_t* out_rgb8_hwc, fav_hipstream_t stream);
+/* next frame from the frames alone (fav_stylize -estimate_flow 1): the backward flow (A = this frame, B = the previous one) and the
+ * forward flow (A = the previous frame, B = this one) are estimated with fav_flow_rgb8 into the caller's buffers backward_flo /
+ * forward_flo ([H][W][2] each) on `stream`, then the frame runs as fav_stream_next_frame_flow with them.  workspace: as fav_flow_rgb8. */
+int fav_stream_next_frame_estimate(fav_stream* s, const uint8_t* frame_rgb_hwc, const uint8_t* prev_frame_rgb_hwc,
+                                   const fav_flow_opts* flow_opts_host, int use_structure, float* backward_flo, float* forward_flo,
+                                   void* workspace, size_t workspace_bytes, float* out_rgb_f32, uint8_t* out_rgb8_hwc,
+                                   fav_hipstream_t stream);
 /* optional look-ahead: start computing the consistency mask of a FUTURE frame on an internal side stream (the mask
  * depends only on that frame and its two flows, not on the recurrent state), so the order-preserving 4-argument
  * structure pass overlaps the network of the current frame.  The inputs must already be complete on `stream`.  The next

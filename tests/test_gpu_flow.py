@@ -1,0 +1,249 @@
+"""The optical-flow estimator on the GPU (csrc/kernels_flow.hip, csrc/flow.cpp) against its numpy restatement
+(tests/util/flow_model.py), the temporally blocked sweep kernel against its one-sweep-per-launch form, and the two executables that use
+it: bin/fav_flow (run-deepflow.sh's argument list) and fav_stylize -estimate_flow 1.
+
+Gate of everything that is not bit-equal (the rule of test_gpu_scale.py): with e32 = max|M32 - M64| of the two CPU models on the same
+input, max|GPU - M64| <= max(4 e32, 2^-20 max(1, max|M64|)).  Nothing is measured against the code under test.
+Measured e32 of the whole estimator on the pairs below (flow_model.warped_pair(h, w, seed 11), default options), in pixels:
+17x23 2.2e-06, 64x64 2.9e-06, 150x203 3.7e-06 (max|M64| 4.5, 5.0, 6.1) -- 4 e32 is far below the 0.02 px the issue allows."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "util"))
+import flow_model as M  # noqa: E402
+
+from fav_amd import synth  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "fast-artistic-videos_amd", "bin")
+VID = os.path.join(ROOT, "tests", "golden", "tiny_model.t7")
+K = 6                    # the default sweeps_per_launch
+SEED = 11
+
+
+def _dev(a, cuda):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
+
+
+def _gate(gpu, m32, m64, what):
+    e32 = float(np.abs(m32.astype(np.float64) - m64).max())
+    bound = max(4 * e32, 2.0 ** -20 * max(1.0, float(np.abs(m64).max())))
+    err = float(np.abs(gpu.astype(np.float64) - m64).max())
+    print(f"{what}: e32 {e32:.3e}  max|GPU - M64| {err:.3e}  bound {bound:.3e}")
+    assert 4 * e32 <= 0.02, (what, e32)
+    assert err <= bound, (what, err, bound)
+
+
+_pairs = {}
+
+
+def _pair(h, w):
+    """the frame pair of a size with both models' flows, computed once"""
+    if (h, w) not in _pairs:
+        A, B = M.warped_pair(h, w, SEED)
+        _pairs[(h, w)] = (A, B, M.flow(A, B, dtype=np.float32), M.flow(A, B, dtype=np.float64))
+    return _pairs[(h, w)]
+
+
+# ------------------------------------------------------------------------------------------------ 4. the stages
+@pytest.mark.parametrize("h,w", M.SIZES)
+def test_grey_down_up_are_bit_equal_to_the_model(favlib, cuda, h, w):
+    for frame in (synth.smooth_frame(h, w, 3), synth.random_frame(h, w, 4)):
+        g = favlib.flow_grey(_dev(frame, cuda))
+        assert np.array_equal(g.cpu().numpy(), M.grey(frame))
+        level = g
+        want = M.grey(frame)
+        for _ in range(4 if min(h, w) > 32 else 1):              # odd sizes at every level of 150x203
+            level, want = favlib.flow_down(level), M.down(want)
+            assert level.shape == want.shape and np.array_equal(level.cpu().numpy(), want)
+    for (hf, wf), (hc, wc) in zip(M.level_sizes(h, w, 4)[:-1], M.level_sizes(h, w, 4)[1:]):
+        coarse = synth.random_flow(hc, wc, 7)
+        got = favlib.flow_up(_dev(coarse, cuda), hf, wf).cpu().numpy()
+        assert np.array_equal(got, M.up_flow(coarse, hf, wf))
+
+
+@pytest.mark.parametrize("h,w", M.SIZES)
+def test_coefficients_match_the_model(favlib, cuda, h, w):
+    A, B = M.grey(synth.smooth_frame(h, w, 5)), M.grey(synth.smooth_frame(h, w, 6))
+    f0 = synth.backward_flow(h, w, 8)
+    got = favlib.flow_coefficients(_dev(A, cuda), _dev(B, cuda), _dev(f0, cuda), 15.0).cpu().numpy()
+    _gate(got, M.coefficients(A, B, f0), M.coefficients(A.astype(np.float64), B.astype(np.float64), f0, dtype=np.float64), f"coefficients {h}x{w}")
+
+
+# ------------------------------------------------------------------------------------------------ 5. tiling invariance
+_sweep_inputs = {}
+
+
+def _sweep_case():
+    if not _sweep_inputs:
+        h, w = 150, 203
+        rng = np.random.default_rng(21)
+        a, b = (rng.standard_normal((2, h, w)) * 6).astype(np.float32)
+        c = (rng.standard_normal((h, w)) * 10).astype(np.float32)
+        r = (np.float32(1) / ((np.float32(225) + a * a) + b * b)).astype(np.float32)
+        _sweep_inputs["x"] = (synth.random_flow(h, w, 22), np.stack([a, b, c, r], -1))
+    return _sweep_inputs["x"]
+
+
+@pytest.mark.parametrize("iters", [1, K, K + 1, 2 * K + 3])
+def test_sweeps_do_not_depend_on_the_temporal_blocking(favlib, cuda, iters):
+    """random (u0, v0) and coefficients at 150x203 (3 x 4 tiles of 52 with ragged last tiles): default sweeps_per_launch against 1, bit
+    for bit over the whole image -- and both against the model, which knows no tiles at all"""
+    f0, coef = _sweep_case()
+    d0, dc = _dev(f0, cuda), _dev(coef, cuda)
+    blocked = favlib.flow_sweeps(d0, dc, iters).cpu().numpy()
+    single = favlib.flow_sweeps(d0, dc, iters, sweeps_per_launch=1).cpu().numpy()
+    assert np.array_equal(d0.cpu().numpy(), f0)                   # the input is not written
+    assert np.array_equal(blocked, single)
+    for k in (4, 16):
+        assert np.array_equal(favlib.flow_sweeps(d0, dc, iters, sweeps_per_launch=k).cpu().numpy(), single), k
+    assert np.array_equal(single, M.sweeps(f0, coef, iters))
+
+
+# ------------------------------------------------------------------------------------------------ 6. the whole estimator
+@pytest.mark.parametrize("h,w", M.SIZES)
+def test_flow_matches_the_model(favlib, cuda, h, w):
+    A, B, m32, m64 = _pair(h, w)
+    got = favlib.flow_rgb8(_dev(A, cuda), _dev(B, cuda)).cpu().numpy()
+    assert got.shape == (h, w, 2)
+    _gate(got, m32, m64, f"flow {h}x{w}")
+    assert np.array_equal(got, favlib.flow_rgb8(_dev(A, cuda), _dev(B, cuda), sweeps_per_launch=1).cpu().numpy())
+
+
+# ------------------------------------------------------------------------------------------------ 7. recovery on the device
+def test_flow_recovers_the_known_shift(favlib, cuda):
+    A, B, w = M.shifted_pair(1)
+    model = M.interior_epe(M.flow(A, B, dtype=np.float64), w)
+    gpu = M.interior_epe(favlib.flow_rgb8(_dev(A, cuda), _dev(B, cuda)).cpu().numpy(), w)
+    print(f"mean interior endpoint error: fp64 model {model:.4f} px, GPU {gpu:.4f} px")
+    assert gpu <= model + 0.01
+
+
+# ------------------------------------------------------------------------------------------------ 8. poisoned state
+def test_flow_after_nan_poison(favlib, cuda, poison):
+    import torch
+    h, w = 150, 203
+    A, B, m32, m64 = _pair(h, w)
+    before = favlib.flow_rgb8(_dev(A, cuda), _dev(B, cuda)).cpu().numpy()
+    torch.cuda.synchronize(); torch.cuda.empty_cache()
+    poison()
+    a, b = _dev(A, cuda), _dev(B, cuda)
+    nb = favlib.flow_workspace_bytes(w, h)
+    ws = torch.full(((nb + 3) // 4,), float("nan"), dtype=torch.float32, device=cuda)      # the workspace itself, too
+    out = torch.full((h, w, 2), float("nan"), dtype=torch.float32, device=cuda)
+    import ctypes as C
+    favlib._check(favlib.lib().fav_flow_rgb8(favlib._p(a), favlib._p(b), w, h, None, favlib._p(out), favlib._p(ws), C.c_size_t(nb), favlib._stream()))
+    after = out.cpu().numpy()
+    assert np.isfinite(after).all() and np.array_equal(after, before)
+    _gate(after, m32, m64, "flow 150x203 after poison")
+
+
+# ------------------------------------------------------------------------------------------------ 9. the stream, in process
+def test_stream_estimate_equals_flows_by_hand(favlib, cuda):
+    import torch
+    h, w = 64, 96
+    frames = [_dev(f, cuda) for f in _frames(3, h, w)]
+    net = favlib.Net(VID, 0)
+    results = []
+    for path in ("hand", "estimate"):
+        st = favlib.Stream(net, h, w)
+        st.first_frame(frames[0])
+        pngs = [favlib.png_encode(None, from_stream=st)]
+        for i in (1, 2):
+            if path == "hand":
+                bw = favlib.flow_rgb8(frames[i], frames[i - 1]); fw = favlib.flow_rgb8(frames[i - 1], frames[i])
+                st.next_frame_flow(frames[i], bw, fw, use_structure=True)
+            else:
+                _, _, bw, fw = st.next_frame_estimate(frames[i], frames[i - 1], use_structure=True)
+            pngs.append(favlib.png_encode(None, from_stream=st))
+        results.append((st.state().cpu().numpy(), pngs, bw.cpu().numpy(), fw.cpu().numpy(), st.last_mask().cpu().numpy()))
+        st.close()
+    torch.cuda.synchronize()
+    (s0, p0, b0, f0, m0), (s1, p1, b1, f1, m1) = results
+    assert np.array_equal(b0, b1) and np.array_equal(f0, f1) and np.array_equal(m0, m1)
+    assert np.array_equal(s0, s1) and p0 == p1 and len(p0) == 3
+    assert 0 < (m0 == 255).mean()                                   # the estimated flows are consistent somewhere: the prior is used
+
+
+# ------------------------------------------------------------------------------------------------ 10, 11. the executables
+def _write_ppm(path, a):
+    with open(path, "wb") as f:
+        f.write(b"P6\n%d %d\n255\n" % (a.shape[1], a.shape[0])); f.write(np.ascontiguousarray(a).tobytes())
+
+
+def _frames(n, h, w):
+    """n frames of one smooth scene moving by a constant (1.5, -1) px per frame"""
+    big = synth.smooth_frame(h + 16, w + 16, 77).astype(np.float64)
+    ys, xs = np.mgrid[0:h, 0:w].astype(np.float64)
+    return [np.clip(np.rint(np.stack([M.bilinear(big[..., c], xs + 8 - 1.5 * i, ys + 8 + 1.0 * i, np.float64) for c in range(3)], -1)), 0, 255).astype(np.uint8)
+            for i in range(n)]
+
+
+def _clip(d, n, h, w):
+    frames = _frames(n, h, w)
+    for i, f in enumerate(frames):
+        _write_ppm(str(d / f"frame_{i + 1:05d}.ppm"), f)
+    return frames
+
+
+def _run(cmd):
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (cmd, r.stdout[-2000:], r.stderr[-2000:])
+    return r
+
+
+@pytest.mark.parametrize("structure,backward", [("1", False), ("0", False), ("1", True)])
+def test_cli_estimate_flow_equals_fav_flow_files(favlib, tmp_path, structure, backward):
+    """fav_flow -batch writes the two flows of every frame, fav_stylize reads them; fav_stylize -estimate_flow 1 sees the frames alone:
+    the PNG files are byte-equal.  -backward walks the frames downwards: the frame before frame i in processing order is i + 1."""
+    n, h, w = 4, 64, 96
+    _clip(tmp_path, n, h, w)
+    os.makedirs(tmp_path / "flow")
+    step = 1 if backward else -1                                       # the previous frame in processing order
+    lines = []
+    for i in range(1, n + 1):
+        if 1 <= i + step <= n:
+            cur, prev = tmp_path / f"frame_{i:05d}.ppm", tmp_path / f"frame_{i + step:05d}.ppm"
+            lines += [f"{cur} {prev} {tmp_path}/flow/backward_{i}.flo", f"{prev} {cur} {tmp_path}/flow/forward_{i}.flo"]
+    (tmp_path / "list.txt").write_text("\n".join(lines) + "\n")
+    _run([os.path.join(BIN, "fav_flow"), "-batch", str(tmp_path / "list.txt")])
+    common = [os.path.join(BIN, "fav_stylize"), "-input_pattern", str(tmp_path / "frame_%05d.ppm"), "-model_vid", VID, "-model_img", "self",
+              "-structure", structure, "-poll_settle", "0", "-poll_timeout", "20"] + (["-backward", "-num_frames", str(n + 1)] if backward else [])
+    _run(common + ["-output_prefix", str(tmp_path / "files" / "out"), "-flow_pattern", str(tmp_path / "flow" / "backward_[%d].flo"),
+                   "-forward_flow_pattern", str(tmp_path / "flow" / "forward_[%d].flo")])
+    r = _run(common + ["-output_prefix", str(tmp_path / "est" / "out"), "-estimate_flow", "1"])
+    assert r.stdout.count("Writing output image to") == n
+    for i in range(1, n + 1):
+        a, b = (open(tmp_path / k / f"out-{i:05d}.png", "rb").read() for k in ("files", "est"))
+        assert len(a) > 100 and a == b, i
+    assert sorted(os.listdir(tmp_path / "est")) == [f"out-{i:05d}.png" for i in range(1, n + 1)]      # nothing else on disk
+    if not backward and structure == "1":
+        # -continue_with 3 reads frame 2's file for the flows and out-00002.png for the state; the file-based run does the same: equal again
+        for k, extra in (("files", ["-flow_pattern", str(tmp_path / "flow" / "backward_[%d].flo"), "-forward_flow_pattern", str(tmp_path / "flow" / "forward_[%d].flo")]),
+                         ("est", ["-estimate_flow", "1"])):
+            os.remove(tmp_path / k / "out-00003.png"); os.remove(tmp_path / k / "out-00004.png")
+            _run(common + ["-output_prefix", str(tmp_path / k / "out"), "-continue_with", "3"] + extra)
+        for i in (3, 4):
+            a, b = (open(tmp_path / k / f"out-{i:05d}.png", "rb").read() for k in ("files", "est"))
+            assert len(a) > 100 and a == b, i
+
+
+def test_fav_flow_as_run_deepflow(favlib, cuda, tmp_path):
+    """makeOptFlow_deepflow.sh:46-49 calls `<flow command> img1 img2 out.flo <downscale>`: four positional arguments"""
+    h, w = 64, 96
+    frames = _clip(tmp_path, 2, h, w)
+    out = tmp_path / "forward_1_2.flo"
+    _run([os.path.join(BIN, "fav_flow"), str(tmp_path / "frame_00001.ppm"), str(tmp_path / "frame_00002.ppm"), str(out), "2"])
+    got = favlib.read_flo(str(out))
+    assert got.shape == (h, w, 2) and os.path.getsize(out) == 12 + h * w * 8
+    assert open(out, "rb").read(4) == b"PIEH"
+    assert np.array_equal(got, favlib.flow_rgb8(_dev(frames[0], cuda), _dev(frames[1], cuda)).cpu().numpy())
+    assert [p for p in os.listdir(tmp_path) if ".tmp." in p] == []
+    # the scene moves by (1.5, -1) px per frame: frame 2 shows at p what frame 1 shows at p - (1.5, -1), so the flow 1 -> 2 is (+1.5, -1)
+    assert M.interior_epe(got, (1.5, -1.0)) < 0.25
