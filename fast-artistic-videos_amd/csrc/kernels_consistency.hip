@@ -173,6 +173,9 @@ __device__ __forceinline__ void iir_col(float* mb, float* vb, int lane, size_t p
     const F4 zero = {f2{0.f, 0.f}, f2{0.f, 0.f}};
     auto request = [&](const float* src, float4* slot) {         // one DMA: 64 lanes x 16 bytes -> slot[0..63]
         __builtin_amdgcn_global_load_lds(src + 4 * lane, (lds_vptr_t)slot, 16, 0, 0);
+        // the counted waits below assume the ISSUE ORDER request(s), then the step's store: a compiler barrier keeps the scheduler from
+        // putting the store first (the request would then have one younger operation less than vmcnt(2 D - 5) counts on)
+        asm volatile("" ::: "memory");
     };
     auto put = [&](float* dst, const F4& v) {
         v4f t = {v.lo.x, v.lo.y, v.hi.x, v.hi.y};

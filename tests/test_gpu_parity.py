@@ -5,7 +5,9 @@ committed outputs of the reference's own consistencyChecker.
 Tolerances (fp32 path, stated once):
   * occlusion mask: bit-exact (integer output);
   * warp / min-filter / assembly: 1e-5 relative to the operand scale (exact min/max);
-  * single convolution (+InstanceNorm): 2e-4 * output scale;
+  * single convolution: 2e-4 * output scale, convolution + InstanceNorm: 5e-4 * output scale.  The operator entry point
+    (test_conv_matches_oracle) runs the GENERIC kernel only, whatever the geometry: the kernels the networks run on are
+    held to the same two bounds one by one in test_gpu_layer_parity.py;
   * network output in the reference's 150*tanh space: max-abs <= 5e-2, i.e.
     <= 2e-4 after de-processing to [0,1]; 8-bit PSNR >= 50 dB.
 """
@@ -145,19 +147,45 @@ def test_mask_bit_exact_vs_reference_golden(favlib, cuda, golden_dir, name):
     assert np.array_equal(m4, g["mask4"]), f"{(m4 != g['mask4']).sum()} bytes differ from the reference binary (4-arg)"
 
 
+@pytest.fixture(scope="module")
+def mask_case(oracle):
+    """inputs and oracle masks of one size, computed once per size (the 3840x2160 oracle takes ten seconds) and dropped with the module"""
+    cases = {}
+
+    def get(h, w):
+        if (h, w) not in cases:
+            bw = synth.backward_flow(h, w, 5) if h > 8 else synth.random_flow(h, w, 5, 0.5)
+            fw = synth.forward_flow_from_backward(bw, 6) if h > 8 else synth.random_flow(h, w, 6, 0.5)
+            img = synth.smooth_frame(h, w, 7) if h > 8 else synth.random_frame(h, w, 7)
+            cases[(h, w)] = (bw, fw, img, oracle.consistency(bw, fw), oracle.consistency(bw, fw, img))
+        return cases[(h, w)]
+    yield get
+    cases.clear()
+
+
 @pytest.mark.parametrize("size", [(360, 640), (720, 1280), (5, 3), (130, 1029), (2, 2), (17, 18), (98, 33), (53, 71), (480, 854), (9, 300), (2160, 3840)])
-def test_mask_bit_exact_vs_oracle(favlib, oracle, cuda, size):
+def test_mask_bit_exact_vs_oracle(favlib, cuda, mask_case, size):
     h, w = size
-    bw = synth.backward_flow(h, w, 5) if h > 8 else synth.random_flow(h, w, 5, 0.5)
-    fw = synth.forward_flow_from_backward(bw, 6) if h > 8 else synth.random_flow(h, w, 6, 0.5)
-    img = synth.smooth_frame(h, w, 7) if h > 8 else synth.random_frame(h, w, 7)
+    bw, fw, img, ref3, ref4 = mask_case(h, w)
     m3 = favlib.consistency(T(bw, cuda), T(fw, cuda)).cpu().numpy()
-    assert np.array_equal(m3, oracle.consistency(bw, fw))
+    assert np.array_equal(m3, ref3)
     m4 = favlib.consistency(T(bw, cuda), T(fw, cuda), T(img, cuda)).cpu().numpy()
-    ref4 = oracle.consistency(bw, fw, img)
     assert np.array_equal(m4, ref4), f"{(m4 != ref4).sum()} of {m4.size} bytes differ (4-arg)"
     if h >= 100:
         assert 0.2 < (m3 == 255).mean() < 0.98          # the fixture exercises both outcomes
+
+
+def test_mask_four_argument_mode_repeats_at_3840x2160(favlib, cuda, mask_case):
+    """the recursive smoothing passes wait for their LDS-DMA ring with COUNTED s_waitcnt vmcnt(N): the count holds only for the issue
+    order request, then store.  The compiler once put one store of the unrolled round first: that step's sample could be read before it
+    had landed -- only when a DMA took ~20 steps, i.e. at this size (long lines, 15 KB pitch), and then in about every second call: a
+    patch of ~100 x 240 structure values was off by up to 8e-2 and 0-10 mask bytes with it (35 % of the calls had a wrong byte).
+    Twelve calls on the same inputs, every one bit-exact: an unfixed build passes this with probability 0.65^12 < 1 %."""
+    h, w = 2160, 3840
+    bw, fw, img, _, ref4 = mask_case(h, w)          # shared with test_mask_bit_exact_vs_oracle[size10]
+    tb, tf, ti = T(bw, cuda), T(fw, cuda), T(img, cuda)
+    wrong = [int((favlib.consistency(tb, tf, ti).cpu().numpy() != ref4).sum()) for _ in range(12)]
+    assert wrong == [0] * 12, f"bytes that differ from the oracle, call by call: {wrong}"
 
 
 @pytest.mark.parametrize("kind", ["black", "constant", "half-black"])
@@ -192,7 +220,8 @@ def test_min_filter_and_assemble(favlib, oracle, cuda):
 
 # ---------------------------------------------------------------------------------------------- A8 layers
 CONV_CASES = [
-    # cin, cout, k, stride, pad, H, W        (the canonical net's layer geometries at small spatial size)
+    # cin, cout, k, stride, pad, H, W        (the canonical net's layer geometries at small spatial size -- on the generic kernel:
+    #                                         fav_conv2d_nchw_f32 always calls launch_conv, none of the kernels select_conv picks for them)
     (7, 32, 9, 1, 4, 40, 56),
     (32, 64, 3, 2, 1, 40, 56),
     (64, 128, 3, 2, 1, 21, 29),

@@ -1,0 +1,383 @@
+"""Observe ONE layer of a network through the public API, to ~1e-6: everything behind the layer under test is made transparent by the
+choice of its weights ("Per-kernel parity through an identity tail").
+
+For the layer under test L (item `index_of_L` of the arch string `<prefix>,L,c9s1-3`):
+
+  * the norm directly behind L gets gamma = 1 and beta = B -- an nn.InstanceNormalization ("stats" variant: the convolution together with
+    the statistics its kernel's epilogue writes) or an evaluate-mode nn.SpatialBatchNormalization with mean 0 and var 1 - eps ("raw"
+    variant: a fixed shift, so the bias is observed too).  B makes every pre-ReLU value of the float64 reference >= 1: the ReLU is the identity;
+  * the last c9s1-3 layer (the observer) has zero bias and zero taps except the centre one, which is +-2^-k on a disjoint group of at most
+    GROUP_MAX of L's channels per output channel, signs alternating inside a group.  2^-k keeps |tanh argument| <= 0.5 in the float64 reference;
+    y = atanh(out / 150) * 2^k recovers the signed group sums.  Three groups per checkpoint: ceil(C / (3 * GROUP_MAX)) checkpoints cover all channels;
+  * a residual block (L = R<n>) ends in InstanceNorm + join with no ReLU: the observer sees skip + IN(branch) as it is, gamma / beta random;
+  * the last layer itself (index_of_L = the last item) is observed directly: its weights are scaled by a power of two so that the
+    reference's tanh argument stays below 0.5, and atanh(out / 150) is compared.
+
+The reference is a float64 model of the layer list (torch on the CPU), run on extract_layers() of the very checkpoint the GPU loads.  Nothing
+in here calls the library under test."""
+import math
+import os
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from fav_amd import t7
+
+TOL_RAW = 2e-4        # single convolution: 2e-4 * output scale     (tests/test_gpu_parity.py, header)
+TOL_STATS = 5e-4      # convolution + InstanceNorm: 5e-4 * output scale
+TANH_MUL = 150.0
+GROUP_MAX = 8         # (at most 16 would do: with 8 a pixel moved by 1e-2 sigma is twice the tolerance instead of barely above it)
+GROUPS_PER_PASS = 3   # the observer is the network's last layer: three output channels
+
+
+# ------------------------------------------------------------------------------------------------ float64 model
+def instnorm64(x, gamma, beta, eps):
+    mean = x.mean(dim=(1, 2), keepdim=True)
+    var = ((x - mean) ** 2).mean(dim=(1, 2), keepdim=True)           # biased
+    return (x - mean) / torch.sqrt(var + eps) * gamma[:, None, None] + beta[:, None, None]
+
+
+def _t64(a):
+    return torch.from_numpy(np.ascontiguousarray(a, np.float64))
+
+
+def forward64(layers, x, trace=None):
+    """the layer list of t7.extract_layers in float64; x: torch [C][H][W] float64.  trace: (type, tensor) per top-level layer"""
+    for L in layers:
+        t = L["type"]
+        if t == "pad":
+            x = F.pad(x[None], (L["l"], L["r"], L["t"], L["b"]), mode="replicate" if L.get("mode") == "replicate" else "reflect")[0]
+        elif t == "conv":
+            x = F.conv2d(x[None], _t64(L["w"]), None if L["b"] is None else _t64(L["b"]), stride=L["stride"], padding=L["pad"])[0]
+        elif t == "fullconv":
+            x = F.conv_transpose2d(x[None], _t64(L["w"]), None if L["b"] is None else _t64(L["b"]), stride=L["stride"], padding=L["pad"],
+                                   output_padding=L["adj"])[0]
+        elif t == "bn":
+            s = _t64(L["gamma"]) / torch.sqrt(_t64(L["var"]) + L["eps"])
+            x = (x - _t64(L["mean"])[:, None, None]) * s[:, None, None] + _t64(L["beta"])[:, None, None]
+        elif t == "in":
+            x = instnorm64(x, _t64(L["gamma"]), _t64(L["beta"]), L["eps"])
+        elif t == "relu":
+            x = torch.clamp(x, min=0)
+        elif t == "res":
+            y = forward64(L["block"], x)
+            s = L["shave"]
+            x = y + (x[:, s:x.shape[1] - s, s:x.shape[2] - s] if s else x)
+        elif t == "up":
+            x = x.repeat_interleave(L["s"], dim=1).repeat_interleave(L["s"], dim=2)
+        elif t == "tanh":
+            x = torch.tanh(x)
+        elif t == "mul":
+            x = x * L["k"]
+        elif t == "identity":
+            pass
+        else:
+            raise ValueError(t)
+        if trace is not None: trace.append((t, x))
+    return x
+
+
+def _last_conv(layers):
+    return max(i for i, L in enumerate(layers) if L["type"] == "conv")
+
+
+def observed_index(types):
+    """index (in a top-level list of layer types) of the tensor the observer reads: what comes out in front of the last convolution,
+    a padding layer of the observer's own not counted"""
+    j = max(i for i, t in enumerate(types) if t == "conv") - 1
+    if types[j] == "pad": j -= 1
+    return j
+
+
+def reference_parts(layers, x):
+    """float64: (the observed tensor [C][H][W], the pre-ReLU tensor of the norm behind L or None, the tanh argument [3][H][W])"""
+    tr = []
+    forward64(layers, _t64(x), tr)
+    types = [t for t, _ in tr]
+    j = observed_index(types)
+    pre = tr[j - 1][1] if types[j] == "relu" else None
+    return tr[j][1].numpy(), (None if pre is None else pre.numpy()), tr[_last_conv(layers)][1].numpy()
+
+
+# ------------------------------------------------------------------------------------------------ the observer
+def make_table(channels, k):
+    """disjoint groups of at most GROUP_MAX consecutive channels, alternating signs inside a group, GROUPS_PER_PASS groups per pass"""
+    passes_n = -(-channels // (GROUP_MAX * GROUPS_PER_PASS))
+    assert channels % 2 == 0
+    # whole PAIRS of channels per group: an even group size, so that the B offsets cancel and do not widen max |ref|
+    groups = [g.reshape(-1) for g in np.array_split(np.arange(channels).reshape(-1, 2), passes_n * GROUPS_PER_PASS)]
+    assert all(0 < len(g) <= GROUP_MAX for g in groups)
+    passes = []
+    for p in range(passes_n):
+        passes.append([(g, np.where(np.arange(len(g)) % 2 == 0, 1.0, -1.0)) for g in groups[p * GROUPS_PER_PASS:(p + 1) * GROUPS_PER_PASS]])
+    return {"k": int(k), "passes": passes, "channels": channels}
+
+
+def sums_of(y, table):
+    """signed group sums of a [C][H][W] tensor, float64: [groups][H][W]"""
+    if table["passes"] is None: return np.asarray(y, np.float64)
+    y = np.asarray(y, np.float64)
+    return np.stack([np.tensordot(s, y[g], axes=(0, 0)) for p in table["passes"] for g, s in p])
+
+
+def observer_weights(table, p):
+    w = np.zeros((GROUPS_PER_PASS, table["channels"], 9, 9), np.float32)
+    for j, (g, s) in enumerate(table["passes"][p]):
+        w[j, g, 4, 4] = (s * 2.0 ** -table["k"]).astype(np.float32)
+    return w
+
+
+def observe(out3_list, table):
+    """the network outputs of all passes ([3][H][W], the reference's 150 * tanh space) -> what the observer saw, float64"""
+    v = np.concatenate([np.arctanh(np.asarray(o, np.float64) / TANH_MUL) for o in out3_list])
+    return v * 2.0 ** table["k"]
+
+
+def reference_sums(layers, x, table):
+    """float64 model of the checkpoint's own layers: the signed sums the observer should see (direct mode: the last layer's output)"""
+    y, _, arg = reference_parts(layers, x)
+    if table["passes"] is None: return arg
+    return sums_of(y, table)
+
+
+def assert_close(got, ref, tol, what=""):
+    """max |got - ref| <= tol * max(1, max |ref|) over EVERY observed element; returns the normalised error"""
+    got = np.asarray(got, np.float64); ref = np.asarray(ref, np.float64)
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    assert np.isfinite(got).all(), "%s: non-finite observed values" % what
+    err = float(np.abs(got - ref).max() / max(1.0, np.abs(ref).max()))
+    assert err <= tol, "%s: max normalised error %.3e > %.1e (max |ref| %.3f)" % (what, err, tol, np.abs(ref).max())
+    return err
+
+
+# ------------------------------------------------------------------------------------------------ geometry
+def _item_out(v, h, down_shave):
+    c0 = v[0]
+    if c0 == "c": f, s = int(v[1]), int(v[3]); return (h + 2 * ((f - 1) // 2) - f) // s + 1
+    if c0 == "d": return (h + 2 - 3) // 2 + 1
+    if c0 == "U": return h * int(v[1:])
+    if c0 == "u": return 2 * h
+    if c0 == "f": f, s = int(v[1]), int(v[3]); return (h - 1) * s - 2 * ((f - 1) // 2) + f + s - 1
+    if c0 in "RC": return h - 4 if down_shave else h
+    raise ValueError(v)
+
+
+def front_pad(arch, padding_type="reflect-start", insert_pad=True):
+    """the lazily inserted leading reflection padding, as t7.build_model sums it"""
+    lost, down = 0, 1
+    for v in arch.split(","):
+        if v[0] == "c": down *= int(v[3])
+        elif v[0] == "d": down *= 2
+        elif v[0] == "U": down = max(down // int(v[1:]), 1)
+        elif v[0] == "u": down //= 2
+        elif v[0] == "f": down = max(down // int(v[3]), 1)
+        elif v[0] in "RC": lost += 2 * down
+    return lost if insert_pad and lost and padding_type == "reflect-start" else 0
+
+
+def input_size(arch, index_of_L, want, padding_type="reflect-start", **_):
+    """the smallest input extent for which item index_of_L of the arch string puts out `want` pixels (one axis)"""
+    items = arch.split(",")
+    p = front_pad(arch, padding_type)
+    for h in range(max(1, p + 1), 400):
+        o = h + 2 * p
+        for v in items[:index_of_L + 1]:
+            o = _item_out(v, o, padding_type in ("none", "reflect-start"))
+            if o < 1: break
+        if o == want: return h
+    raise ValueError("no input size gives %d behind item %d of %s" % (want, index_of_L, arch))
+
+
+def conv_index(arch, index_of_L):
+    """index of L's first convolution in the network's convolution order (what fav_net's profile is indexed by)"""
+    return sum(2 if v[0] in "RC" else (0 if v[0] == "U" else 1) for v in arch.split(",")[:index_of_L])
+
+
+# ------------------------------------------------------------------------------------------------ checkpoints
+class Probe:
+    pass
+
+
+def _write(path, model, arch, kw):
+    t7.write_checkpoint(path, {"opt": {"arch": arch, "padding_type": kw.get("padding_type", "reflect-start"),
+                                       "use_instance_norm": 1, "tanh_constant": TANH_MUL},
+                               "train_loss_history": {}, "val_loss_history": {}, "iter": 0, "model": model})
+    return t7.extract_layers(t7.load(path)["model"])
+
+
+def probe_checkpoints(arch, index_of_L, variant, seed, hw, out_dir, **build_kw):
+    """Checkpoints (one per pass) that observe item index_of_L of `arch` on a seeded random input of hw = (H, W), and the observer's
+    group / sign table.  variant: "stats" (InstanceNorm everywhere) or "raw" (evaluate-mode BatchNorm everywhere).
+    Returns a Probe: paths, table, x [cin][H][W] float32, layers (extract_layers of the first path), B, direct."""
+    assert variant in ("stats", "raw")
+    items = arch.split(",")
+    direct = index_of_L == len(items) - 1
+    assert direct or items[index_of_L + 1:] == ["c9s1-3"], "the observer is one c9s1-3 item directly behind L"
+    kw = dict(build_kw, use_instance_norm=(variant == "stats"))
+    model = t7.build_model(arch, seed, **kw)
+    mods = model.fields["modules"]
+    cin = kw.get("in_channels", 7)
+    # N(0, 60) like the network tests; N(0, 1) where nothing normalises (BatchNorm with random running statistics): activations of order 1,
+    # so that a bias of +-0.1 is well above 2e-4 of the observed scale
+    x = (np.random.default_rng(seed + 1000).standard_normal((cin, hw[0], hw[1])) * (60 if variant == "stats" else 1)).astype(np.float32)
+    obs_i = max(i for i, m in enumerate(mods) if m.cls == "nn.SpatialConvolution")
+    obs = mods[obs_i]
+    tag = "%s_%d_%s_%d_%dx%d" % (arch.replace(",", "_"), index_of_L, variant, seed, hw[0], hw[1])
+    base = os.path.join(str(out_dir), tag)
+    pr = Probe()
+    pr.x, pr.direct, pr.B, pr.arch, pr.variant = x, direct, 0.0, arch, variant
+
+    if direct:
+        layers = _write(base + "_tmp.t7", model, arch, kw)
+        arg = reference_parts(layers, x)[2]
+        m = max(0, math.ceil(math.log2(float(np.abs(arg).max()) / 0.5)))           # scaling by 2^-m is exact: weights stay fp32 numbers
+        obs.fields["weight"] = (obs.fields["weight"] * np.float32(2.0 ** -m)).astype(np.float32)
+        obs.fields["bias"] = (obs.fields["bias"] * np.float32(2.0 ** -m)).astype(np.float32)
+        pr.table = {"k": 0, "passes": None, "channels": 3}
+        pr.paths = [base + ".t7"]
+        pr.layers = _write(pr.paths[0], model, arch, kw)
+        os.remove(base + "_tmp.t7")
+        return pr
+
+    # the norm directly behind L: [norm, ReLU, (the observer's own padding layer), observer]; nothing to set behind a residual block
+    j = obs_i - 1
+    if mods[j].cls in ("nn.SpatialReflectionPadding", "nn.SpatialReplicationPadding"): j -= 1
+    norm = None
+    if mods[j].cls == "nn.ReLU":
+        norm = mods[j - 1]
+        assert norm.cls == ("nn.InstanceNormalization" if variant == "stats" else "nn.SpatialBatchNormalization"), norm.cls
+    else:
+        assert mods[j].cls == "nn.Sequential", mods[j].cls
+    C = int(obs.fields["nInputPlane"])
+
+    def set_norm(B):
+        if norm is None: return
+        norm.fields["weight"] = np.ones((C,), np.float32)
+        norm.fields["bias"] = np.full((C,), B, np.float32)
+        if variant == "raw":
+            norm.fields["running_mean"] = np.zeros((C,), np.float32)
+            norm.fields["running_var"] = np.full((C,), 1.0 - float(norm.fields["eps"]), np.float32)
+
+    obs.fields["bias"] = np.zeros((3,), np.float32)
+    obs.fields["weight"] = np.zeros((3, C, 9, 9), np.float32)
+    set_norm(0.0)
+    layers = _write(base + "_tmp.t7", model, arch, kw)
+    y0, pre0, _ = reference_parts(layers, x)
+    os.remove(base + "_tmp.t7")
+    if norm is not None:
+        pr.B = float(math.ceil(1.5 - float(pre0.min())))        # min pre-ReLU value >= 1.5 in the reference: the ReLU is the identity on the GPU too
+        set_norm(pr.B)
+    # k from the reference at this B (the offsets cancel in a group of even size and count once in an odd one)
+    s0 = sums_of(y0 if norm is None else pre0 + pr.B, make_table(C, 0))
+    k = max(0, math.ceil(math.log2(float(np.abs(s0).max()) * 1.05 / 0.5)))
+    pr.table = make_table(C, k)
+    pr.paths = []
+    for p in range(len(pr.table["passes"])):
+        obs.fields["weight"] = observer_weights(pr.table, p)
+        pr.paths.append("%s_p%d.t7" % (base, p))
+        ls = _write(pr.paths[-1], model, arch, kw)
+        if p == 0: pr.layers = ls
+    return pr
+
+
+# ------------------------------------------------------------------------------------------------ the cases of tests/test_gpu_layer_parity.py
+def _case(name, arch, index_of_L, out, ids, poison=False, ids_raw=None, **kw):
+    return {"name": name, "arch": arch, "L": index_of_L, "out": out, "ids": ids, "ids_raw": ids_raw or ids, "poison": poison, "kw": kw}
+
+
+# name, arch, item under test, ITS output size, the profile ids its convolutions must report (fav_internal.h, enum ConvKernel).  Sizes per
+# kernel, from its *_tiles() function: less than one tile both ways | exactly one tile | whole tiles plus one row and one column
+CASES = [
+    # CK_FIRST2D, 16 x 32 tiles: 7 and 3 input channels; 32, 64, 96 filters (96 runs as 128 with zero filters)
+    _case("first2d_7_32_small", "c9s1-32,c9s1-3", 0, (9, 20), [16], poison=True),
+    _case("first2d_7_32_tile", "c9s1-32,c9s1-3", 0, (16, 32), [16]),
+    _case("first2d_7_32_ragged", "c9s1-32,c9s1-3", 0, (33, 65), [16]),
+    _case("first2d_3_64", "c9s1-64,c9s1-3", 0, (17, 33), [16], in_channels=3),
+    _case("first2d_7_96", "c9s1-96,c9s1-3", 0, (17, 33), [16]),
+    # CK_S2W, 4 x 32 tiles (64 filters) | 3 x 32 (128-filter groups)
+    _case("s2w_32_64_small", "c9s1-32,d64,c9s1-3", 1, (3, 20), [764], poison=True),
+    _case("s2w_32_64_tile", "c9s1-32,d64,c9s1-3", 1, (4, 32), [764]),
+    _case("s2w_32_64_ragged", "c9s1-32,d64,c9s1-3", 1, (9, 65), [764]),
+    _case("s2w_64_128", "c9s1-64,d128,c9s1-3", 1, (7, 33), [828]),
+    _case("s2w_128_256", "c9s1-128,d256,c9s1-3", 1, (4, 33), [956]),
+    # CK_WINO4, 16 x 16 units.  R<n>: both convolutions of a block -- the first one's InstanceNorm is consumed as accumulators by the
+    # second, the second one's by the join; c3s1-128 behind a padding layer: 16 / 48 (runs as 64) / 64 input channels, with a pending
+    # norm, and without one behind a join
+    _case("wino4_R128_small", "c9s1-128,R128,c9s1-3", 1, (9, 11), [728, 728], poison=True),
+    _case("wino4_R128_tile", "c9s1-128,R128,c9s1-3", 1, (16, 16), [728, 728]),
+    _case("wino4_R128_ragged", "c9s1-128,R128,c9s1-3", 1, (33, 33), [728, 728]),
+    _case("wino4_R256", "c9s1-256,R256,c9s1-3", 1, (17, 17), [856, 856]),
+    _case("wino4_cin16", "c9s1-16,c3s1-128,c9s1-3", 1, (17, 17), [728], padding_type="reflect"),
+    _case("wino4_cin48", "c9s1-48,c3s1-128,c9s1-3", 1, (17, 17), [728], padding_type="reflect"),
+    _case("wino4_cin64", "c9s1-64,c3s1-128,c9s1-3", 1, (17, 17), [728], padding_type="replicate"),
+    _case("wino4_no_pending_norm", "c9s1-128,R128,c3s1-128,c9s1-3", 2, (17, 17), [728], padding_type="reflect"),
+    # CK_UP2 behind a join (R64, U2), tiles of 4 x 32 physical = 8 x 64 output pixels
+    _case("up2_64_small", "c9s1-64,R64,U2,c3s1-64,c9s1-3", 3, (6, 40), [564], poison=True),
+    _case("up2_64_tile", "c9s1-64,R64,U2,c3s1-64,c9s1-3", 3, (8, 64), [564]),
+    _case("up2_64_ragged", "c9s1-64,R64,U2,c3s1-64,c9s1-3", 3, (18, 130), [564]),
+    _case("up2_128", "c9s1-64,R64,U2,c3s1-128,c9s1-3", 3, (10, 66), [628]),
+    _case("up2_256", "c9s1-64,R64,U2,c3s1-256,c9s1-3", 3, (10, 66), [756]),
+    # CK_HALO3, 8 x 32 tiles and 16 x 16 ones on a ragged right edge of at most 16 columns.  The three pad_* cases put a padding layer in
+    # front of L (padding_type reflect / replicate): the library runs it as the element kernel pad_nhwc.  Element kernels have no profile
+    # id, so the public API cannot show that pad_nhwc (and not some folded form) ran: the cases assert the convolution's id only and
+    # check the padded VALUES -- the float64 model pads by reflection / replication, a zero-padded or unpadded input would not match
+    _case("halo3_32_64_small", "c9s1-32,c3s1-64,c9s1-3", 1, (5, 20), [364], poison=True),
+    _case("halo3_32_64_tile", "c9s1-32,c3s1-64,c9s1-3", 1, (8, 32), [364]),
+    _case("halo3_32_64_ragged", "c9s1-32,c3s1-64,c9s1-3", 1, (17, 65), [364]),
+    _case("halo3_32_64_wide_edge", "c9s1-32,c3s1-64,c9s1-3", 1, (9, 52), [364]),
+    _case("halo3_32_128", "c9s1-32,c3s1-128,c9s1-3", 1, (9, 33), [428]),
+    _case("halo3_two_stages_U2", "c9s1-32,U2,c3s1-64,c9s1-3", 2, (18, 66), [364]),
+    _case("halo3_R64", "c9s1-64,R64,c9s1-3", 1, (9, 33), [364, 364]),
+    _case("pad_reflect", "c9s1-32,c3s1-64,c9s1-3", 1, (9, 33), [364], padding_type="reflect"),
+    _case("pad_replicate", "c9s1-32,c3s1-64,c9s1-3", 1, (9, 33), [364], padding_type="replicate"),
+    _case("pad_reflect_U2", "c9s1-32,U2,c3s1-64,c9s1-3", 2, (18, 66), [364], padding_type="reflect"),
+    # CK_FOLD: the last layer itself, 16-row x 128-column tiles; 128 / 256 input channels behind U2 only
+    _case("fold_32_small", "c9s1-32,c9s1-3", 1, (9, 20), [1], poison=True),
+    _case("fold_32_tile", "c9s1-32,c9s1-3", 1, (16, 128), [1]),
+    _case("fold_32_ragged", "c9s1-32,c9s1-3", 1, (17, 129), [1]),
+    _case("fold_64", "c9s1-64,c9s1-3", 1, (17, 40), [1]),
+    _case("fold_32_U2", "c9s1-32,U2,c9s1-3", 2, (34, 66), [1]),
+    _case("fold_128_U2", "c9s1-128,U2,c9s1-3", 2, (34, 66), [1]),
+    _case("fold_256_U2", "c9s1-256,U2,c9s1-3", 2, (18, 34), [1]),
+    # CK_TCONV (8 x 32 input-pixel tiles per phase): its operator test has no statistics variant
+    _case("tconv_64_32", "c9s1-32,d64,u32,c9s1-3", 2, (18, 66), [832], poison=True),
+    # the launched join of three blocks in a row (the pending form: DIAG_CASES)
+    _case("join_launched", "c9s1-128,R128,R128,R128,c9s1-3", 3, (17, 17), [728, 728]),
+]
+
+# the kernels behind the diagnostic switches: one child process per set of switches (read once per process).  The same three sizes per
+# kernel, and the smallest case of each once more in a second child behind NaN-poisoned LDS and memory
+def _sizes(name, arch, index_of_L, ids, small, tile, ragged, **kw):
+    return [_case(name + "_small", arch, index_of_L, small, ids, poison=True, **kw), _case(name + "_tile", arch, index_of_L, tile, ids, **kw),
+            _case(name + "_ragged", arch, index_of_L, ragged, ids, **kw)]
+
+
+DIAG_CASES = [
+    ({"FAV_FIRST_1D": "1", "FAV_NO_S2W": "1"},
+     _sizes("first1d", "c9s1-32,c9s1-3", 0, [6], (5, 40), (8, 64), (9, 65))                      # conv_first_tiles: 8 x 64
+     + _sizes("s2halo", "c9s1-32,d64,c9s1-3", 1, [264], (3, 20), (4, 32), (5, 33))               # conv3s2_tiles: 4 x 32
+     # conv_mblocks: 128 consecutive output pixels per block whatever the row length: 100 | 128 | 231 pixels
+     + _sizes("generic_128", "c9s1-64,d128,c9s1-3", 1, [128], (5, 20), (4, 32), (7, 33))),
+    ({"FAV_NO_S2W": "1", "FAV_NO_S2": "1", "FAV_NO_FIRST": "1", "FAV_NO_C8": "1"},
+     _sizes("generic_64", "c9s1-32,d64,c9s1-3", 1, [64], (5, 20), (4, 32), (5, 33))
+     + _sizes("generic_32", "c9s1-32,c9s1-3", 0, [32], (5, 20), (8, 16), (9, 33))),
+    ({"FAV_NO_FIRST": "1", "FAV_WINO_F2": "1"},
+     _sizes("c8d", "c9s1-32,c9s1-3", 0, [7], (5, 20), (8, 32), (9, 33))                          # conv_c8_tiles: 8 x 32
+     + _sizes("wino_f2", "c9s1-128,R128,c9s1-3", 1, [528, 528], (5, 11), (8, 16), (17, 17))),    # conv3_wino_tiles: 8 x 16 units
+    ({"FAV_NO_C8D": "1", "FAV_W4_GRID": "7", "FAV_LAZY_JOIN": "1"},
+     _sizes("c8", "c9s1-32,c9s1-3", 0, [8], (5, 20), (8, 32), (9, 33))
+     + [_case("wino4_stream_k", "c9s1-128,R128,c9s1-3", 1, (33, 33), [728, 728], poison=True),   # 9 units dealt to 7 shares: cut units
+        # (a join stays pending between blocks of conv - InstanceNorm - ReLU - conv - InstanceNorm only: launched in the raw variant)
+        _case("join_pending", "c9s1-128,R128,R128,R128,c9s1-3", 3, (17, 17), [729, 728], ids_raw=[728, 728])]),
+]
+
+def probe_for(case, variant, out_dir):
+    import zlib
+    kw = case["kw"]
+    hw = tuple(input_size(case["arch"], case["L"], o, **kw) for o in case["out"])
+    pr = probe_checkpoints(case["arch"], case["L"], variant, zlib.crc32(case["name"].encode()) % 100000, hw, out_dir, **kw)
+    pr.tol = TOL_RAW if (variant == "raw" or pr.direct) else TOL_STATS
+    pr.conv0 = conv_index(case["arch"], case["L"])
+    pr.ids = case["ids"] if variant == "stats" else case["ids_raw"]
+    return pr
