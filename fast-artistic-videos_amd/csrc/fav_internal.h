@@ -119,8 +119,17 @@ inline size_t stat_acc_words(int C) { return (size_t)STAT_COPIES * C * 4; }     
 // A unit whose statistics are not finite (a diverged clip, a damaged checkpoint: NaN / Inf activations) cannot be written as fixed point
 // (the double -> integer conversion would be undefined): its producer adds STAT_NONFINITE to the HIGH words instead, and a consumer that
 // finds a high word beyond STAT_NONFINITE / 2 in magnitude forms NaN scale / shift -- what in_finalize_kernel gives for the same input.
-// (legitimate high words stay below 2^45 for any activation range the fp32 network can produce; 300 units x 2^53 still fits 63 bits)
+// What the two words carry: a high word counts 2^-8 (value * 2^40 = hi * 2^32 + lo), and a channel's high words, summed over all its
+// units, must stay below STAT_NONFINITE / 2 = 2^52 in magnitude.  A producer therefore takes a unit's term v (n mean, or M2 + n mean^2 of
+// at most 16 x 16 pixels) as finite only while |hi| x (units per channel) < STAT_UNIT_HI_SUM = 2^51 -- the floor of a negative term adds at
+// most one per unit, far less than the other 2^51 -- and poisons the channel beyond that (NaN, not a wrong value).  In activations:
+//   a frame of U units carries a unit mean square below 2^43 / (256 U): RMS < 2^13.5 = 11 900 at 320 x 180 (1280 x 720 frames, U = 240),
+//   < 2^12 = 4 100 at 960 x 540 (3840 x 2160, U = 2 040), < 2^10.5 = 1 448 at the 2^22 pixels (U = 2^14) launch_conv3_wino4 stops at.
+// The partials form (in_finalize_kernel, fp64) has no such limit.  The poison itself: k non-finite units add k x 2^53, which leaves 64
+// bits from k = 2^10 on; the wrapped sum is still beyond 2^52 in magnitude unless k is a multiple of 2 048, so frames of fewer than
+// 2 048 units (up to 3840 x 2160) cannot lose it.
 constexpr long long STAT_NONFINITE = 1ll << 53;
+constexpr double STAT_UNIT_HI_SUM = 2251799813685248.0;      // 2^51
 __host__ __device__ inline bool stat_acc_poisoned(long long hi_sum, long long hi_squares)
 {
     return hi_sum >= STAT_NONFINITE / 2 || hi_sum <= -(STAT_NONFINITE / 2) || hi_squares >= STAT_NONFINITE / 2 || hi_squares <= -(STAT_NONFINITE / 2);

@@ -592,7 +592,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 const double v = (g & 2) ? (double)m2 + nd * mud * mud : nd * mud;
                 const double tt = v * 1099511627776.0;
                 const double hi = floor(tt * (1.0 / 4294967296.0));
-                const bool fin = fabs(tt) < 9.0e18;                          // (false for NaN / Inf too: STAT_NONFINITE, fav_internal.h)
+                // a unit's share of what the high words can carry (STAT_UNIT_HI_SUM, fav_internal.h): |hi| < 2^51 / units per channel,
+                // so that the sum over all of them stays below the poison threshold.  False for NaN / Inf too: STAT_NONFINITE
+                const bool fin = fabs(hi) * (double)upix < STAT_UNIT_HI_SUM;
                 const long long word = !fin ? ((g & 1) ? STAT_NONFINITE : 0ll) : (g & 1) ? (long long)hi : (long long)(tt - hi * 4294967296.0);
                 long long* const dst = p.stat_acc + ((size_t)(blockIdx.x & (STAT_COPIES - 1)) * (WIDE ? p.COUT : 128) + cb) * 4 + g;
                 __hip_atomic_fetch_add(dst, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

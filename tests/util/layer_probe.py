@@ -42,8 +42,9 @@ def _t64(a):
     return torch.from_numpy(np.ascontiguousarray(a, np.float64))
 
 
-def forward64(layers, x, trace=None):
-    """the layer list of t7.extract_layers in float64; x: torch [C][H][W] float64.  trace: (type, tensor) per top-level layer"""
+def forward64(layers, x, trace=None, convs=None):
+    """the layer list of t7.extract_layers in float64; x: torch [C][H][W] float64.  trace: (type, tensor) per top-level layer;
+    convs: the raw output of every convolution, residual branches included, in the network's convolution order"""
     for L in layers:
         t = L["type"]
         if t == "pad":
@@ -61,7 +62,7 @@ def forward64(layers, x, trace=None):
         elif t == "relu":
             x = torch.clamp(x, min=0)
         elif t == "res":
-            y = forward64(L["block"], x)
+            y = forward64(L["block"], x, convs=convs)
             s = L["shave"]
             x = y + (x[:, s:x.shape[1] - s, s:x.shape[2] - s] if s else x)
         elif t == "up":
@@ -74,6 +75,7 @@ def forward64(layers, x, trace=None):
             pass
         else:
             raise ValueError(t)
+        if convs is not None and t in ("conv", "fullconv"): convs.append(x)
         if trace is not None: trace.append((t, x))
     return x
 
@@ -194,6 +196,119 @@ def conv_index(arch, index_of_L):
     return sum(2 if v[0] in "RC" else (0 if v[0] == "U" else 1) for v in arch.split(",")[:index_of_L])
 
 
+# ------------------------------------------------------------------------------------------------ channel regimes
+# IN(conv) does not change (up to eps) under a per-output-channel affine change of the convolution, so a probe's output channels can be
+# put where InstanceNorm statistics go wrong without touching what the observer needs (tests/test_gpu_stats_edges.py).  Channel c of
+# L gets regime REGIMES[c % 6]: every observer group of 8 consecutive channels holds all six, "plain" as the control.
+#   plain    as drawn: |mean| <~ sigma, sigma of order 1-10
+#   offset+- bias +- 2^j, 2^j ~ 2^OFFSET_LOG2 x sigma: a one-pass fp32 variance is off by percent, a miscounted tile moves the mean by many sigma
+#   big      filters and bias x 2^m, channel RMS in [2^10, 2^11): a full 16 x 16 unit's sum of squares is beyond 2^28
+#   small    x 2^-m, sigma in [2^-9, 2^-8): the variance is comparable to eps = 1e-5
+#   flat     filters zero, bias 0.5 / 0 by turns: the variance is exactly zero and the reference output exactly beta.  (|bias| <= 1: what
+#            is observed is the fp32 rounding of the mean / sqrt(eps))
+REGIMES = ("plain", "offset+", "big", "offset-", "small", "flat")
+OFFSET_LOG2 = 9       # offset / sigma = 2^9 (tests/test_cpu_stats_edges.py: the fp32 oracle stays within a quarter of the bound at this ratio)
+
+
+def regime_of(c, names=REGIMES):
+    return names[c % len(names)]
+
+
+def _conv_modules(m, out=None):
+    """every convolution module below m, in extract_layers' order (a residual branch in front of what follows the block)"""
+    out = [] if out is None else out
+    for q in m.fields.get("modules", []):
+        if q.cls in ("nn.SpatialConvolution", "nn.SpatialFullConvolution"): out.append(q)
+        elif q.cls in ("nn.Sequential", "nn.ConcatTable"): _conv_modules(q, out)
+    return out
+
+
+def _stats(z):
+    z = np.asarray(z, np.float64).reshape(z.shape[0], -1)
+    return z.std(axis=1), np.sqrt((z * z).mean(axis=1))
+
+
+def _conv_regimes(mod, z):
+    """put the output channels of one convolution module into their regimes; z: its float64 output [C][H][W] as the weights stand"""
+    w, b = mod.fields["weight"], mod.fields["bias"]
+    axis = 1 if mod.cls == "nn.SpatialFullConvolution" else 0              # [cin][cout][k][k] there
+    sd, rms = _stats(z)
+    flats = 0
+    for c in range(z.shape[0]):
+        r = regime_of(c)
+        sl = tuple(c if a == axis else slice(None) for a in range(4))
+        if r in ("offset+", "offset-"):
+            b[c] = np.float32(b[c]) + np.float32((1.0 if r == "offset+" else -1.0) * 2.0 ** (round(math.log2(sd[c])) + OFFSET_LOG2))
+        elif r in ("big", "small"):
+            m = 10 - math.floor(math.log2(rms[c])) if r == "big" else -9 - math.floor(math.log2(sd[c]))
+            w[sl] = w[sl] * np.float32(2.0 ** m); b[c] = b[c] * np.float32(2.0 ** m)       # exact: powers of two
+        elif r == "flat":
+            w[sl] = 0; b[c] = 0.5 if flats % 2 == 0 else 0.0; flats += 1
+
+
+# L = U<n> carries its own InstanceNorm + ReLU and has no weights: the regimes of the tensor whose statistics are taken come from the
+# norm(s) in front, with powers of two as gamma.  What each construction can reach:
+#   behind `c..., U<n>` (stats_kernel on a pending InstanceNorm + ReLU): the prefix norm gets gamma = 2^m, beta >= gamma x (1 - min of
+#     the normalised channel), so that the ReLU stays the identity -- the mean is therefore at least ~4 sigma everywhere.  plain (gamma 1,
+#     beta B0 = that minimum), offset+ (beta 2^9), big (gamma 2^m with RMS in [2^10, 2^11)), small (gamma 2^-9), flat (gamma 0, beta 0.5 / 0).
+#     offset- is out of reach: a negative mean would not pass the ReLU.
+#   behind `R<n>, U<n>` (res_add_stats_kernel: z = skip + IN(branch)): the branch's last norm -- plain (as drawn), offset+ / offset- (gamma 1,
+#     beta +- 2^j ~ 2^9 sigma_z), big (gamma 2^10, beta 2^9).  small and flat need the skip term small / constant as well: the prefix norm of
+#     these channels gets gamma 2^-9 / 0 too (small: gamma 2^-9 on both; flat: gamma 0 on both, beta 0.5 / 0 on the branch's norm).
+U_STATS_REGIMES = ("plain", "offset+", "big", "small", "flat")
+
+
+def _norm_regimes(model, arch, index_of_L, x, kw, tmp):
+    mods = model.fields["modules"]
+    up_i = [i for i, m in enumerate(mods) if m.cls == "nn.SpatialUpSamplingNearest"][-1]
+    join = mods[up_i - 1].cls == "nn.Sequential"
+    prefix = mods[up_i - 3 if join else up_i - 2]
+    assert prefix.cls == "nn.InstanceNormalization", prefix.cls
+    C = int(prefix.fields["nOutput"])
+    g0, b0 = np.ones((C,), np.float32), np.zeros((C,), np.float32)
+    prefix.fields["weight"], prefix.fields["bias"] = g0, b0
+
+    def trace():
+        tr = []
+        forward64(_write(tmp, model, arch, kw), _t64(x), tr)
+        os.remove(tmp)
+        u = max(i for i, (t, _) in enumerate(tr) if t == "up")
+        return tr, u
+
+    tr, u = trace()
+    nhat = tr[u - (3 if join else 2)][1].numpy()                   # the prefix norm's output at gamma 1, beta 0
+    assert tr[u - (3 if join else 2)][0] == "in"
+    B0 = np.ceil(1.0 - nhat.reshape(C, -1).min(axis=1))             # gamma x (nhat + B0) >= gamma: the ReLU is the identity
+    if not join:
+        flats = 0
+        for c in range(C):
+            r = regime_of(c, U_STATS_REGIMES)
+            if r == "plain": b0[c] = B0[c]
+            elif r == "offset+": b0[c] = 2.0 ** OFFSET_LOG2
+            elif r == "big":
+                g0[c] = 2.0 ** (10 - math.floor(math.log2(math.sqrt(1.0 + B0[c] ** 2)))); b0[c] = g0[c] * B0[c]
+            elif r == "small": g0[c] = 2.0 ** -9; b0[c] = g0[c] * B0[c]
+            else: g0[c] = 0.0; b0[c] = 0.5 if flats % 2 == 0 else 0.0; flats += 1
+        return [regime_of(c, U_STATS_REGIMES) for c in range(C)]
+    last = mods[up_i - 1].fields["modules"][0].fields["modules"][0].fields["modules"][-1]      # Sequential(ConcatTable(branch, skip), CAddTable)
+    assert last.cls == "nn.InstanceNormalization", last.cls
+    g1, b1 = last.fields["weight"], last.fields["bias"]
+    b0[:] = B0
+    flats = 0
+    for c in range(C):
+        r = regime_of(c)
+        if r in ("offset+", "offset-"): g1[c] = 1.0
+        elif r == "big": g1[c] = 2.0 ** 10; b1[c] = 2.0 ** 9
+        elif r == "small": g1[c] = 2.0 ** -9; g0[c] = 2.0 ** -9; b0[c] = g0[c] * B0[c]
+        elif r == "flat": g1[c] = 0.0; g0[c] = 0.0; b0[c] = 0.0; b1[c] = 0.5 if flats % 2 == 0 else 0.0; flats += 1
+    tr, u = trace()
+    sd, _ = _stats(tr[u - 1][1].numpy())                            # the joined tensor, the offsets still missing
+    for c in range(C):
+        r = regime_of(c)
+        if r in ("offset+", "offset-"): b1[c] = (1.0 if r == "offset+" else -1.0) * 2.0 ** (round(math.log2(sd[c])) + OFFSET_LOG2)
+    return [regime_of(c) for c in range(C)]
+
+
 # ------------------------------------------------------------------------------------------------ checkpoints
 class Probe:
     pass
@@ -206,9 +321,12 @@ def _write(path, model, arch, kw):
     return t7.extract_layers(t7.load(path)["model"])
 
 
-def probe_checkpoints(arch, index_of_L, variant, seed, hw, out_dir, **build_kw):
+def probe_checkpoints(arch, index_of_L, variant, seed, hw, out_dir, regimes=False, **build_kw):
     """Checkpoints (one per pass) that observe item index_of_L of `arch` on a seeded random input of hw = (H, W), and the observer's
     group / sign table.  variant: "stats" (InstanceNorm everywhere) or "raw" (evaluate-mode BatchNorm everywhere).
+    regimes ("stats" only: raw has no statistics): the output channels of L -- of both convolutions of an R<n> item -- by turns in the
+    regimes of REGIMES above; sigma and RMS of a channel are those of the float64 reference as the weights stand when its convolution
+    is changed (the block's second convolution: behind the changed first).  B and k come from the changed checkpoint, as always.
     Returns a Probe: paths, table, x [cin][H][W] float32, layers (extract_layers of the first path), B, direct."""
     assert variant in ("stats", "raw")
     items = arch.split(",")
@@ -223,7 +341,7 @@ def probe_checkpoints(arch, index_of_L, variant, seed, hw, out_dir, **build_kw):
     x = (np.random.default_rng(seed + 1000).standard_normal((cin, hw[0], hw[1])) * (60 if variant == "stats" else 1)).astype(np.float32)
     obs_i = max(i for i, m in enumerate(mods) if m.cls == "nn.SpatialConvolution")
     obs = mods[obs_i]
-    tag = "%s_%d_%s_%d_%dx%d" % (arch.replace(",", "_"), index_of_L, variant, seed, hw[0], hw[1])
+    tag = "%s_%d_%s%s_%d_%dx%d" % (arch.replace(",", "_"), index_of_L, variant, "_regimes" if regimes else "", seed, hw[0], hw[1])
     base = os.path.join(str(out_dir), tag)
     pr = Probe()
     pr.x, pr.direct, pr.B, pr.arch, pr.variant = x, direct, 0.0, arch, variant
@@ -262,6 +380,19 @@ def probe_checkpoints(arch, index_of_L, variant, seed, hw, out_dir, **build_kw):
     obs.fields["bias"] = np.zeros((3,), np.float32)
     obs.fields["weight"] = np.zeros((3, C, 9, 9), np.float32)
     set_norm(0.0)
+    pr.regimes = None
+    if regimes:
+        assert variant == "stats", "regimes: the statistics variant only"
+        if items[index_of_L][0] == "U":
+            pr.regimes = _norm_regimes(model, arch, index_of_L, x, kw, base + "_tmp.t7")
+        else:
+            c0 = conv_index(arch, index_of_L)
+            for i in range(2 if items[index_of_L][0] in "RC" else 1):
+                convs = []
+                forward64(_write(base + "_tmp.t7", model, arch, kw), _t64(x), convs=convs)
+                os.remove(base + "_tmp.t7")
+                _conv_regimes(_conv_modules(model)[c0 + i], convs[c0 + i].numpy())
+            pr.regimes = [regime_of(c) for c in range(C)]
     layers = _write(base + "_tmp.t7", model, arch, kw)
     y0, pre0, _ = reference_parts(layers, x)
     os.remove(base + "_tmp.t7")
@@ -372,12 +503,35 @@ DIAG_CASES = [
         _case("join_pending", "c9s1-128,R128,R128,R128,c9s1-3", 3, (17, 17), [729, 728], ids_raw=[728, 728])]),
 ]
 
-def probe_for(case, variant, out_dir):
+def probe_for(case, variant, out_dir, regimes=False):
     import zlib
     kw = case["kw"]
     hw = tuple(input_size(case["arch"], case["L"], o, **kw) for o in case["out"])
-    pr = probe_checkpoints(case["arch"], case["L"], variant, zlib.crc32(case["name"].encode()) % 100000, hw, out_dir, **kw)
+    pr = probe_checkpoints(case["arch"], case["L"], variant, zlib.crc32(case["name"].encode()) % 100000, hw, out_dir, regimes=regimes, **kw)
     pr.tol = TOL_RAW if (variant == "raw" or pr.direct) else TOL_STATS
     pr.conv0 = conv_index(case["arch"], case["L"])
     pr.ids = case["ids"] if variant == "stats" else case["ids_raw"]
     return pr
+
+
+# ------------------------------------------------------------------------------------------------ the cases of tests/test_gpu_stats_edges.py
+# every kernel family's statistics under the channel regimes: its ragged size of the tables above, and its one-tile size where a full
+# tile is what matters (a full F(4x4) unit is where the accumulator words are largest)
+def _named(name, poison=False):
+    c = next(c for c in CASES + [c for _, cs in DIAG_CASES for c in cs] if c["name"] == name)
+    return dict(c, poison=poison)
+
+
+EDGE_CASES = [_named("wino4_R128_tile"), _named("wino4_R128_ragged", poison=True), _named("wino4_R256"), _named("first2d_7_32_ragged"),
+              _named("s2w_32_64_ragged"), _named("s2w_64_128"), _named("up2_64_ragged"), _named("halo3_32_64_ragged", poison=True),
+              _named("halo3_32_64_wide_edge"), _named("tconv_64_32"), _named("join_launched")]
+EDGE_DIAG_CASES = [(env, [_named(c["name"]) for c in cs if not c["name"].endswith("_small") and (not c["name"].endswith("_tile") or c["name"] == "wino_f2_tile")])
+                   for env, cs in DIAG_CASES]
+# the F(4x4) accumulator cases once more in the partials form (in_finalize_kernel)
+EDGE_PARTIALS_ENV = {"FAV_NO_ACC_STATS": "1"}
+EDGE_PARTIALS_CASES = [_named(n) for n in ("wino4_R128_tile", "wino4_R128_ragged", "wino4_R256", "join_launched")]
+# the element kernels that take statistics, L = U2 with its own InstanceNorm + ReLU (no convolution id to assert).  32 / 64 / 128 channels:
+# stats_kernel<0|8|16>, res_add_stats_kernel<0|8|16>.  Physical sizes: 9 x 33 = 297 pixels (two full blocks of 128 and one of 41); the join
+# 3 rows of 140 (two segments per row, 128 + 12)
+ELEMENT_CASES = [_case("stats_u2_%d" % C, "c9s1-%d,U2,c9s1-3" % C, 1, (18, 66), []) for C in (32, 64, 128)] + \
+                [_case("join_u2_%d" % C, "c9s1-%d,R%d,U2,c9s1-3" % (C, C), 2, (6, 280), []) for C in (32, 64, 128)]
