@@ -307,13 +307,22 @@ int launch_scale_prep(const uint8_t* frame_hwc, int H, int W, int Hs, int Ws, in
 int launch_scale_planar(const float* src, float* dst, int C, int Hs, int Ws, int Hd, int Wd, hipStream_t st);
 // dense optical flow (kernels_flow.hip; tests/util/flow_model.py restates every stage).  Flows are .flo payloads [H][W][2]; `coef` is
 // [H][W][4] (a, b, c, r), 16-byte aligned; launch_flow_sweeps runs `iters` Jacobi sweeps, up to K per launch, between *cur and *other
-// and leaves the result in *cur
+// and leaves the result in *cur.  Every launch works on `items` equal-sized planes at once (grid z): item j of an argument is p[j] of its
+// FlowPtrs, a table that goes into the kernel arguments by value (2 x FAV_FLOW_MAX_PAIRS flows or images at most)
 constexpr int FLOW_MAX_SWEEPS_PER_LAUNCH = 16;
-int launch_flow_grey(const uint8_t* rgb_hwc, float* grey, int W, int H, hipStream_t st);
-int launch_flow_down(const float* src, int W, int H, float* dst, hipStream_t st);                      // dst: ceil(W/2) x ceil(H/2)
-int launch_flow_up(const float* coarse, int Wc, int Hc, float* fine, int W, int H, hipStream_t st);
-int launch_flow_coef(const float* A, const float* B, const float* flow0, float alpha, float* coef, int W, int H, hipStream_t st);
-int launch_flow_sweeps(float** cur, float** other, const float* coef, int iters, int K, int W, int H, hipStream_t st);
+constexpr int FLOW_MAX_ITEMS = 2 * FAV_FLOW_MAX_PAIRS;
+struct FlowPtrs {
+    void* p[FLOW_MAX_ITEMS];
+    FlowPtrs() : p{} {}
+    explicit FlowPtrs(const void* one) : p{} { p[0] = const_cast<void*>(one); }
+    FlowPtrs(void* base, size_t stride_bytes, int items) : p{} { for (int j = 0; j < items; ++j) p[j] = static_cast<char*>(base) + j * stride_bytes; }
+};
+int launch_flow_grey(const FlowPtrs& rgb_hwc, const FlowPtrs& grey, int items, int W, int H, hipStream_t st);
+int launch_flow_down(const FlowPtrs& src, int W, int H, const FlowPtrs& dst, int items, hipStream_t st);   // dst: ceil(W/2) x ceil(H/2)
+int launch_flow_up(const FlowPtrs& coarse, int Wc, int Hc, const FlowPtrs& fine, int items, int W, int H, hipStream_t st);
+int launch_flow_coef(const FlowPtrs& A, const FlowPtrs& B, const FlowPtrs& flow0, float alpha, const FlowPtrs& coef, int items, int W, int H,
+                     hipStream_t st);
+int launch_flow_sweeps(FlowPtrs* cur, FlowPtrs* other, const FlowPtrs& coef, int items, int iters, int K, int W, int H, hipStream_t st);
 // Huffman codes of the PNG encoder (png_tables.cpp): PNG_NTABLES model codes with their dynamic-block headers + the fixed code
 constexpr int PNG_NSYM = 277;            // literals 0..255, end of block 256, length symbols 257..276 (runs of 3..66)
 constexpr int PNG_NTABLES = 12;

@@ -13,17 +13,20 @@ constexpr int MAX_LEVELS = 6, MIN_SIDE = 16;
 constexpr int DEFAULT_WARPS = 3, DEFAULT_ITERS = 30, DEFAULT_SWEEPS_PER_LAUNCH = 6;
 constexpr float DEFAULT_ALPHA = 15.f;
 
+// The workspace of a call on `images` images and `flows` flows (fav_flow_rgb8: 2 and 1; fav_flow_pairs_rgb8: 2 n and 2 n).  The planes
+// of one kind at one level lie one behind the other, `stride` bytes apart (a multiple of 256).
 struct FlowPlan {
-    int levels = 0, warps = 0, iters = 0, K = 0;
+    int levels = 0, warps = 0, iters = 0, K = 0, images = 0, flows = 0;
     float alpha = 0.f;
     int w[MAX_LEVELS], h[MAX_LEVELS];
-    size_t pyr_a[MAX_LEVELS], pyr_b[MAX_LEVELS];      // byte offsets into the workspace
-    size_t flow0[MAX_LEVELS], flow1[MAX_LEVELS];      // the two flow buffers of a level (level 0: flow1 only, the other one is flow_out)
-    size_t coef = 0, bytes = 0;
+    size_t pyr[MAX_LEVELS], pyr_stride[MAX_LEVELS];                          // byte offsets into the workspace: `images` grey planes
+    size_t flow0[MAX_LEVELS], flow1[MAX_LEVELS], flow_stride[MAX_LEVELS];    // the two flow buffers of a level, `flows` planes each (level 0:
+                                                                             // flow1 only, the other ones are the caller's)
+    size_t coef = 0, coef_stride = 0, bytes = 0;
 };
 
 // FAV_OK or FAV_EINVAL (message set)
-int make_plan(int W, int H, const fav_flow_opts* o, FlowPlan& p)
+int make_plan(int W, int H, const fav_flow_opts* o, int images, int flows, FlowPlan& p)
 {
     static const fav_flow_opts none = {0, 0, 0, 0.f, 0};
     if (!o) o = &none;
@@ -37,6 +40,7 @@ int make_plan(int W, int H, const fav_flow_opts* o, FlowPlan& p)
     p.iters = o->iters ? o->iters : DEFAULT_ITERS;
     p.alpha = o->alpha != 0.f ? o->alpha : DEFAULT_ALPHA;
     p.K = o->sweeps_per_launch ? o->sweeps_per_launch : DEFAULT_SWEEPS_PER_LAUNCH;
+    p.images = images; p.flows = flows;
     p.w[0] = W; p.h[0] = H; p.levels = 1;
     // a level is added while its smaller side is still >= 16, at most 6; an explicit count is taken as given
     while (o->levels ? p.levels < o->levels
@@ -45,63 +49,119 @@ int make_plan(int W, int H, const fav_flow_opts* o, FlowPlan& p)
         ++p.levels;
     }
     size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 255) / 256 * 256; return at; };
+    auto round256 = [](size_t bytes) { return (bytes + 255) / 256 * 256; };
+    auto take = [&](size_t stride, int count) { const size_t at = off; off += stride * count; return at; };
     for (int l = 0; l < p.levels; ++l) {
         const size_t n = (size_t)p.w[l] * p.h[l];
-        p.pyr_a[l] = take(n * 4); p.pyr_b[l] = take(n * 4);
-        p.flow0[l] = l ? take(n * 8) : 0; p.flow1[l] = take(n * 8);
+        p.pyr_stride[l] = round256(n * 4); p.flow_stride[l] = round256(n * 8);
+        p.pyr[l] = take(p.pyr_stride[l], images);
+        p.flow0[l] = l ? take(p.flow_stride[l], flows) : 0; p.flow1[l] = take(p.flow_stride[l], flows);
     }
-    p.coef = take((size_t)W * H * 16);
+    p.coef_stride = round256((size_t)W * H * 16);
+    p.coef = take(p.coef_stride, flows);
     p.bytes = off;
     return FAV_OK;
 }
+
+// The launches of a call.  img: the plan's images; flow j is the one with A = image a_of[j], B = image b_of[j] and ends in out.p[j].
+int run_plan(const FlowPlan& p, const FlowPtrs& img, const int* a_of, const int* b_of, const FlowPtrs& out, char* ws, hipStream_t st)
+{
+    int rc;
+    // grey + pyramids: every image once
+    FlowPtrs finer(ws + p.pyr[0], p.pyr_stride[0], p.images);
+    rc = launch_flow_grey(img, finer, p.images, p.w[0], p.h[0], st); if (rc) return rc;
+    for (int l = 1; l < p.levels; ++l) {
+        const FlowPtrs level(ws + p.pyr[l], p.pyr_stride[l], p.images);
+        rc = launch_flow_down(finer, p.w[l - 1], p.h[l - 1], level, p.images, st); if (rc) return rc;
+        finer = level;
+    }
+    // coarse to fine.  Every warp ends ceil(iters / K) buffer swaps later: level 0 starts in the buffers that leave the results in `out`
+    const int swaps = p.warps * ((p.iters + p.K - 1) / p.K);
+    const FlowPtrs coef(ws + p.coef, p.coef_stride, p.flows);
+    FlowPtrs coarser;
+    for (int l = p.levels - 1; l >= 0; --l) {
+        FlowPtrs cur = l ? FlowPtrs(ws + p.flow0[l], p.flow_stride[l], p.flows) : out;
+        FlowPtrs other(ws + p.flow1[l], p.flow_stride[l], p.flows);
+        if (l == 0 && (swaps & 1)) std::swap(cur, other);
+        const bool cur_in_workspace = l != 0 || (swaps & 1);      // then its planes are one range from cur.p[0], flow_stride apart
+        const int w = p.w[l], h = p.h[l];
+        FlowPtrs A, B;
+        for (int j = 0; j < p.flows; ++j) {
+            A.p[j] = ws + p.pyr[l] + a_of[j] * p.pyr_stride[l];
+            B.p[j] = ws + p.pyr[l] + b_of[j] * p.pyr_stride[l];
+        }
+        if (l == p.levels - 1) {                   // the coarsest level starts from zero (in the workspace: padding included)
+            if (cur_in_workspace) FAV_HIP(hipMemsetAsync(cur.p[0], 0, p.flow_stride[l] * p.flows, st));
+            else for (int j = 0; j < p.flows; ++j) FAV_HIP(hipMemsetAsync(cur.p[j], 0, (size_t)w * h * 8, st));
+        } else { rc = launch_flow_up(coarser, p.w[l + 1], p.h[l + 1], cur, p.flows, w, h, st); if (rc) return rc; }
+        for (int k = 0; k < p.warps; ++k) {
+            rc = launch_flow_coef(A, B, cur, p.alpha, coef, p.flows, w, h, st); if (rc) return rc;
+            rc = launch_flow_sweeps(&cur, &other, coef, p.flows, p.iters, p.K, w, h, st); if (rc) return rc;
+        }
+        coarser = cur;
+    }
+    return FAV_OK;
+}
+
+bool aligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
 
 }  // namespace
 
 extern "C" size_t fav_flow_workspace_bytes(int W, int H, const fav_flow_opts* opts_host)
 {
     FlowPlan p;
-    return make_plan(W, H, opts_host, p) ? 0 : p.bytes;
+    return make_plan(W, H, opts_host, 2, 1, p) ? 0 : p.bytes;
 }
 
 extern "C" int fav_flow_rgb8(const uint8_t* a_rgb_hwc, const uint8_t* b_rgb_hwc, int W, int H, const fav_flow_opts* opts_host, float* flow_out,
                              void* workspace, size_t workspace_bytes, fav_hipstream_t stream)
 {
     FlowPlan p;
-    int rc = make_plan(W, H, opts_host, p); if (rc) return rc;
+    int rc = make_plan(W, H, opts_host, 2, 1, p); if (rc) return rc;
     FAV_REQUIRE(a_rgb_hwc && b_rgb_hwc && flow_out && workspace, "fav_flow_rgb8: null pointer");
     FAV_REQUIRE(workspace_bytes >= p.bytes, "fav_flow_rgb8: the workspace holds %zu bytes, fav_flow_workspace_bytes asks for %zu", workspace_bytes, p.bytes);
-    FAV_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0 && reinterpret_cast<uintptr_t>(flow_out) % 8 == 0, "fav_flow_rgb8: the workspace must be 16-byte aligned, flow_out 8-byte aligned");
+    FAV_REQUIRE(aligned(workspace, 16) && aligned(flow_out, 8), "fav_flow_rgb8: the workspace must be 16-byte aligned, flow_out 8-byte aligned");
     rc = ensure_device(); if (rc) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    auto f = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    float* coef = f(p.coef);
+    FlowPtrs img; img.p[0] = const_cast<uint8_t*>(a_rgb_hwc); img.p[1] = const_cast<uint8_t*>(b_rgb_hwc);
+    const int a_of = 0, b_of = 1;
+    return run_plan(p, img, &a_of, &b_of, FlowPtrs(flow_out), static_cast<char*>(workspace), static_cast<hipStream_t>(stream));
+}
 
-    // grey + pyramids
-    const uint8_t* img[2] = {a_rgb_hwc, b_rgb_hwc};
-    for (int k = 0; k < 2; ++k) {
-        const size_t* pyr = k ? p.pyr_b : p.pyr_a;
-        rc = launch_flow_grey(img[k], f(pyr[0]), W, H, st); if (rc) return rc;
-        for (int l = 1; l < p.levels; ++l) { rc = launch_flow_down(f(pyr[l - 1]), p.w[l - 1], p.h[l - 1], f(pyr[l]), st); if (rc) return rc; }
+extern "C" size_t fav_flow_pairs_workspace_bytes(int W, int H, int n_pairs, const fav_flow_opts* opts_host)
+{
+    FlowPlan p;
+    if (n_pairs < 1 || n_pairs > FAV_FLOW_MAX_PAIRS) { set_error("fav_flow_pairs: n_pairs must be 1 .. %d, not %d", FAV_FLOW_MAX_PAIRS, n_pairs); return 0; }
+    return make_plan(W, H, opts_host, 2 * n_pairs, 2 * n_pairs, p) ? 0 : p.bytes;
+}
+
+extern "C" int fav_flow_pairs_rgb8(const uint8_t* const* prev_rgb_hwc, const uint8_t* const* cur_rgb_hwc, int n_pairs, int W, int H,
+                                   const fav_flow_opts* opts_host, float* const* backward_flo, float* const* forward_flo, void* workspace,
+                                   size_t workspace_bytes, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(n_pairs >= 1 && n_pairs <= FAV_FLOW_MAX_PAIRS, "fav_flow_pairs_rgb8: n_pairs must be 1 .. %d, not %d", FAV_FLOW_MAX_PAIRS, n_pairs);
+    const int n = n_pairs;
+    FlowPlan p;
+    int rc = make_plan(W, H, opts_host, 2 * n, 2 * n, p); if (rc) return rc;
+    FAV_REQUIRE(prev_rgb_hwc && cur_rgb_hwc && backward_flo && forward_flo && workspace, "fav_flow_pairs_rgb8: null pointer");
+    // images: prev 0 .. n-1, cur 0 .. n-1;  flows: backward 0 .. n-1 (A = cur k, B = prev k), forward 0 .. n-1 (A = prev k, B = cur k)
+    FlowPtrs img, out;
+    int a_of[FLOW_MAX_ITEMS], b_of[FLOW_MAX_ITEMS];
+    for (int k = 0; k < n; ++k) {
+        FAV_REQUIRE(prev_rgb_hwc[k] && cur_rgb_hwc[k] && backward_flo[k] && forward_flo[k], "fav_flow_pairs_rgb8: null pointer in slot %d", k);
+        FAV_REQUIRE(aligned(backward_flo[k], 8) && aligned(forward_flo[k], 8), "fav_flow_pairs_rgb8: the flows of slot %d must be 8-byte aligned", k);
+        img.p[k] = const_cast<uint8_t*>(prev_rgb_hwc[k]); img.p[n + k] = const_cast<uint8_t*>(cur_rgb_hwc[k]);
+        out.p[k] = backward_flo[k]; out.p[n + k] = forward_flo[k];
+        a_of[k] = n + k; b_of[k] = k;
+        a_of[n + k] = k; b_of[n + k] = n + k;
     }
-    // coarse to fine.  Every warp ends ceil(iters / K) buffer swaps later: level 0 starts in the buffer that leaves the result in flow_out
-    const int swaps = p.warps * ((p.iters + p.K - 1) / p.K);
-    const float* coarser = nullptr;
-    for (int l = p.levels - 1; l >= 0; --l) {
-        float* cur = l ? f(p.flow0[l]) : flow_out;
-        float* other = f(p.flow1[l]);
-        if (l == 0 && (swaps & 1)) std::swap(cur, other);
-        const int w = p.w[l], h = p.h[l];
-        if (!coarser) FAV_HIP(hipMemsetAsync(cur, 0, (size_t)w * h * 8, st));
-        else { rc = launch_flow_up(coarser, p.w[l + 1], p.h[l + 1], cur, w, h, st); if (rc) return rc; }
-        for (int k = 0; k < p.warps; ++k) {
-            rc = launch_flow_coef(f(p.pyr_a[l]), f(p.pyr_b[l]), cur, p.alpha, coef, w, h, st); if (rc) return rc;
-            rc = launch_flow_sweeps(&cur, &other, coef, p.iters, p.K, w, h, st); if (rc) return rc;
-        }
-        coarser = cur;
-    }
-    return FAV_OK;
+    for (int i = 0; i < 2 * n; ++i)
+        for (int j = 0; j < i; ++j)
+            FAV_REQUIRE(out.p[i] != out.p[j], "fav_flow_pairs_rgb8: two outputs are one buffer (%s_flo[%d] and %s_flo[%d])",
+                        j < n ? "backward" : "forward", j % n, i < n ? "backward" : "forward", i % n);
+    FAV_REQUIRE(workspace_bytes >= p.bytes, "fav_flow_pairs_rgb8: the workspace holds %zu bytes, fav_flow_pairs_workspace_bytes asks for %zu", workspace_bytes, p.bytes);
+    FAV_REQUIRE(aligned(workspace, 16), "fav_flow_pairs_rgb8: the workspace must be 16-byte aligned");
+    rc = ensure_device(); if (rc) return rc;
+    return run_plan(p, img, a_of, b_of, out, static_cast<char*>(workspace), static_cast<hipStream_t>(stream));
 }
 
 // ---- the stages on their own (tests: each is held to tests/util/flow_model.py)
@@ -109,14 +169,14 @@ extern "C" int fav_flow_grey_f32(const uint8_t* rgb_hwc, float* grey, int W, int
 {
     FAV_REQUIRE(rgb_hwc && grey && W > 0 && H > 0, "fav_flow_grey_f32: bad argument");
     int rc = ensure_device(); if (rc) return rc;
-    return launch_flow_grey(rgb_hwc, grey, W, H, static_cast<hipStream_t>(stream));
+    return launch_flow_grey(FlowPtrs(rgb_hwc), FlowPtrs(grey), 1, W, H, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int fav_flow_down_f32(const float* src, float* dst, int W, int H, fav_hipstream_t stream)
 {
     FAV_REQUIRE(src && dst && W > 0 && H > 0, "fav_flow_down_f32: bad argument");
     int rc = ensure_device(); if (rc) return rc;
-    return launch_flow_down(src, W, H, dst, static_cast<hipStream_t>(stream));
+    return launch_flow_down(FlowPtrs(src), W, H, FlowPtrs(dst), 1, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int fav_flow_up_f32(const float* coarse_flow, int Wc, int Hc, float* fine_flow, int W, int H, fav_hipstream_t stream)
@@ -124,7 +184,7 @@ extern "C" int fav_flow_up_f32(const float* coarse_flow, int Wc, int Hc, float* 
     FAV_REQUIRE(coarse_flow && fine_flow && Wc > 0 && Hc > 0 && W > 0 && H > 0, "fav_flow_up_f32: bad argument");
     FAV_REQUIRE(reinterpret_cast<uintptr_t>(coarse_flow) % 8 == 0 && reinterpret_cast<uintptr_t>(fine_flow) % 8 == 0, "fav_flow_up_f32: flows must be 8-byte aligned");
     int rc = ensure_device(); if (rc) return rc;
-    return launch_flow_up(coarse_flow, Wc, Hc, fine_flow, W, H, static_cast<hipStream_t>(stream));
+    return launch_flow_up(FlowPtrs(coarse_flow), Wc, Hc, FlowPtrs(fine_flow), 1, W, H, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int fav_flow_coefficients_f32(const float* a_grey, const float* b_grey, const float* flow0, float alpha, float* coef, int W, int H,
@@ -133,7 +193,7 @@ extern "C" int fav_flow_coefficients_f32(const float* a_grey, const float* b_gre
     FAV_REQUIRE(a_grey && b_grey && flow0 && coef && W > 0 && H > 0 && std::isfinite(alpha) && alpha > 0.f, "fav_flow_coefficients_f32: bad argument");
     FAV_REQUIRE(reinterpret_cast<uintptr_t>(flow0) % 8 == 0 && reinterpret_cast<uintptr_t>(coef) % 16 == 0, "fav_flow_coefficients_f32: flow0 must be 8-byte aligned, coef 16-byte aligned");
     int rc = ensure_device(); if (rc) return rc;
-    return launch_flow_coef(a_grey, b_grey, flow0, alpha, coef, W, H, static_cast<hipStream_t>(stream));
+    return launch_flow_coef(FlowPtrs(a_grey), FlowPtrs(b_grey), FlowPtrs(flow0), alpha, FlowPtrs(coef), 1, W, H, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int fav_flow_sweeps_f32(const float* flow0, const float* coef, int iters, int sweeps_per_launch, float* flow_out, float* scratch,
@@ -148,11 +208,9 @@ extern "C" int fav_flow_sweeps_f32(const float* flow0, const float* coef, int it
     const int K = sweeps_per_launch ? sweeps_per_launch : DEFAULT_SWEEPS_PER_LAUNCH;
     // flow0 is read only: the first launch goes from it into the buffer from which the remaining launches end in flow_out
     const int first = std::min(K, iters), rest_launches = (iters - first + K - 1) / K;
-    float* src = const_cast<float*>(flow0);
-    float* cur = (rest_launches & 1) ? scratch : flow_out;
-    float* other = (rest_launches & 1) ? flow_out : scratch;
-    float* first_dst = cur;
-    rc = launch_flow_sweeps(&src, &first_dst, coef, first, K, W, H, st); if (rc) return rc;
-    if (iters > first) { rc = launch_flow_sweeps(&cur, &other, coef, iters - first, K, W, H, st); if (rc) return rc; }
+    FlowPtrs src(flow0), cur((rest_launches & 1) ? scratch : flow_out), other((rest_launches & 1) ? flow_out : scratch), first_dst = cur;
+    const FlowPtrs cf(coef);
+    rc = launch_flow_sweeps(&src, &first_dst, cf, 1, first, K, W, H, st); if (rc) return rc;
+    if (iters > first) { rc = launch_flow_sweeps(&cur, &other, cf, 1, iters - first, K, W, H, st); if (rc) return rc; }
     return FAV_OK;
 }

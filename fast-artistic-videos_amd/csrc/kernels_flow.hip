@@ -13,6 +13,11 @@
 // 32 bytes per pixel; flow_sweep_kernel runs up to K sweeps per launch on a tile that lives in LDS (temporal blocking).  Jacobi reads
 // the previous sweep only, so the result does not depend on K or on the tiling.
 // Compiled with -ffp-contract=off: every operation rounds like the CPU restatement.
+//
+// Every kernel is batched: blockIdx.z is the ITEM (an image for grey / down, a flow for up / coefficients / sweeps), all items of a launch
+// have one size, and an item's planes are found through FlowPtrs tables that travel BY VALUE in the kernel arguments (<= 16 pointers each,
+// read with scalar loads; no table in device memory, so a call needs no copy and may run on two streams at once).  The per-pixel
+// arithmetic knows nothing of the batch: an item's bits are those of a launch of its own.
 #include "fav_internal.h"
 
 namespace fav {
@@ -35,8 +40,10 @@ __device__ __forceinline__ float bilinear(const float* __restrict__ img, int w, 
     return top + fy * (bot - top);
 }
 
-__global__ __launch_bounds__(256) void flow_grey_kernel(const uint8_t* __restrict__ rgb, float* __restrict__ g, size_t n)
+__global__ __launch_bounds__(256) void flow_grey_kernel(FlowPtrs rgbs, FlowPtrs greys, size_t n)
 {
+    const uint8_t* __restrict__ rgb = static_cast<const uint8_t*>(rgbs.p[blockIdx.z]);
+    float* __restrict__ g = static_cast<float*>(greys.p[blockIdx.z]);
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float r = (float)rgb[i * 3], gr = (float)rgb[i * 3 + 1], b = (float)rgb[i * 3 + 2];
@@ -44,8 +51,10 @@ __global__ __launch_bounds__(256) void flow_grey_kernel(const uint8_t* __restric
 }
 
 // one lane per destination sample: the four blurred samples under it, each from its 3 x 3 neighbourhood (a 4 x 4 gather the L1 serves)
-__global__ __launch_bounds__(256) void flow_down_kernel(const float* __restrict__ src, int w, int h, float* __restrict__ dst, int wd, int hd)
+__global__ __launch_bounds__(256) void flow_down_kernel(FlowPtrs srcs, int w, int h, FlowPtrs dsts, int wd, int hd)
 {
+    const float* __restrict__ src = static_cast<const float*>(srcs.p[blockIdx.z]);
+    float* __restrict__ dst = static_cast<float*>(dsts.p[blockIdx.z]);
     const int ox = blockIdx.x * 64 + (threadIdx.x & 63), oy = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (ox >= wd || oy >= hd) return;
     auto blur_x = [&](int y, int x) {      // y, x inside the image
@@ -57,9 +66,10 @@ __global__ __launch_bounds__(256) void flow_down_kernel(const float* __restrict_
     dst[(size_t)oy * wd + ox] = ((blur(y0, x0) + blur(y0, x1)) + (blur(y1, x0) + blur(y1, x1))) * 0.25f;
 }
 
-__global__ __launch_bounds__(256) void flow_up_kernel(const float2* __restrict__ coarse, int wc, int hc, float2* __restrict__ fine, int w, int h,
-                                                      float sx, float sy)
+__global__ __launch_bounds__(256) void flow_up_kernel(FlowPtrs coarses, int wc, int hc, FlowPtrs fines, int w, int h, float sx, float sy)
 {
+    const float2* __restrict__ coarse = static_cast<const float2*>(coarses.p[blockIdx.z]);
+    float2* __restrict__ fine = static_cast<float2*>(fines.p[blockIdx.z]);
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= w || y >= h) return;
     float px = ((float)x + 0.5f) * 0.5f - 0.5f, py = ((float)y + 0.5f) * 0.5f - 0.5f;
@@ -78,9 +88,12 @@ __global__ __launch_bounds__(256) void flow_up_kernel(const float2* __restrict__
 
 // warp + derivatives + coefficients in one launch: a lane forms Bw at its pixel and at its four (replicated) neighbours -- each with that
 // pixel's own flow -- instead of a second pass over a stored Bw
-__global__ __launch_bounds__(256) void flow_coef_kernel(const float* __restrict__ A, const float* __restrict__ B, const float2* __restrict__ flow0,
-                                                        float alpha2, float4* __restrict__ coef, int w, int h)
+__global__ __launch_bounds__(256) void flow_coef_kernel(FlowPtrs As, FlowPtrs Bs, FlowPtrs flow0s, float alpha2, FlowPtrs coefs, int w, int h)
 {
+    const float* __restrict__ A = static_cast<const float*>(As.p[blockIdx.z]);
+    const float* __restrict__ B = static_cast<const float*>(Bs.p[blockIdx.z]);
+    const float2* __restrict__ flow0 = static_cast<const float2*>(flow0s.p[blockIdx.z]);
+    float4* __restrict__ coef = static_cast<float4*>(coefs.p[blockIdx.z]);
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= w || y >= h) return;
     auto bw = [&](int yy, int xx) {
@@ -111,10 +124,12 @@ __global__ __launch_bounds__(256) void flow_coef_kernel(const float* __restrict_
 constexpr int SW_R = 64;           // region side
 constexpr int SW_ROWS = 16;        // rows per lane (256 lanes: 64 columns x 4)
 
-__global__ __launch_bounds__(256) void flow_sweep_kernel(const float2* __restrict__ fin, const float4* __restrict__ coef, float2* __restrict__ fout,
-                                                         int W, int H, int K, int n)
+__global__ __launch_bounds__(256) void flow_sweep_kernel(FlowPtrs fins, FlowPtrs coefs, FlowPtrs fouts, int W, int H, int K, int n)
 {
     __shared__ float2 s[SW_R][SW_R];
+    const float2* __restrict__ fin = static_cast<const float2*>(fins.p[blockIdx.z]);
+    const float4* __restrict__ coef = static_cast<const float4*>(coefs.p[blockIdx.z]);
+    float2* __restrict__ fout = static_cast<float2*>(fouts.p[blockIdx.z]);
     const int lx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const int TI = SW_R - 2 * K;
     const int x0 = (int)blockIdx.x * TI - K, y0 = (int)blockIdx.y * TI - K;
@@ -158,57 +173,57 @@ __global__ __launch_bounds__(256) void flow_sweep_kernel(const float2* __restric
     }
 }
 
-inline dim3 grid_64x4(int w, int h) { return dim3((w + 63) / 64, (h + 3) / 4); }
+inline dim3 grid_64x4(int w, int h, int items) { return dim3((w + 63) / 64, (h + 3) / 4, items); }
 inline bool size_ok(int w, int h) { return w > 0 && h > 0 && (long long)w * h <= (1ll << 28) && (h + 3) / 4 <= 65535; }
+inline bool items_ok(int items) { return items >= 1 && items <= FLOW_MAX_ITEMS; }
 
 }  // namespace
 
-int launch_flow_grey(const uint8_t* rgb_hwc, float* grey, int W, int H, hipStream_t st)
+int launch_flow_grey(const FlowPtrs& rgb_hwc, const FlowPtrs& grey, int items, int W, int H, hipStream_t st)
 {
-    FAV_REQUIRE(size_ok(W, H), "flow grey: bad size %dx%d", W, H);
+    FAV_REQUIRE(size_ok(W, H) && items_ok(items), "flow grey: bad size %dx%d x %d", W, H, items);
     const size_t n = (size_t)W * H;
-    hipLaunchKernelGGL(flow_grey_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rgb_hwc, grey, n);
+    hipLaunchKernelGGL(flow_grey_kernel, dim3((unsigned)((n + 255) / 256), 1, items), dim3(256), 0, st, rgb_hwc, grey, n);
     FAV_LAUNCH_CHECK("flow_grey_kernel");
     return FAV_OK;
 }
 
-int launch_flow_down(const float* src, int W, int H, float* dst, hipStream_t st)
+int launch_flow_down(const FlowPtrs& src, int W, int H, const FlowPtrs& dst, int items, hipStream_t st)
 {
-    FAV_REQUIRE(size_ok(W, H), "flow down: bad size %dx%d", W, H);
+    FAV_REQUIRE(size_ok(W, H) && items_ok(items), "flow down: bad size %dx%d x %d", W, H, items);
     const int wd = (W + 1) / 2, hd = (H + 1) / 2;
-    hipLaunchKernelGGL(flow_down_kernel, grid_64x4(wd, hd), dim3(256), 0, st, src, W, H, dst, wd, hd);
+    hipLaunchKernelGGL(flow_down_kernel, grid_64x4(wd, hd, items), dim3(256), 0, st, src, W, H, dst, wd, hd);
     FAV_LAUNCH_CHECK("flow_down_kernel");
     return FAV_OK;
 }
 
-int launch_flow_up(const float* coarse, int Wc, int Hc, float* fine, int W, int H, hipStream_t st)
+int launch_flow_up(const FlowPtrs& coarse, int Wc, int Hc, const FlowPtrs& fine, int items, int W, int H, hipStream_t st)
 {
-    FAV_REQUIRE(size_ok(W, H) && size_ok(Wc, Hc), "flow up: bad size %dx%d -> %dx%d", Wc, Hc, W, H);
-    hipLaunchKernelGGL(flow_up_kernel, grid_64x4(W, H), dim3(256), 0, st, reinterpret_cast<const float2*>(coarse), Wc, Hc,
-                       reinterpret_cast<float2*>(fine), W, H, (float)W / (float)Wc, (float)H / (float)Hc);
+    FAV_REQUIRE(size_ok(W, H) && size_ok(Wc, Hc) && items_ok(items), "flow up: bad size %dx%d -> %dx%d x %d", Wc, Hc, W, H, items);
+    hipLaunchKernelGGL(flow_up_kernel, grid_64x4(W, H, items), dim3(256), 0, st, coarse, Wc, Hc, fine, W, H, (float)W / (float)Wc, (float)H / (float)Hc);
     FAV_LAUNCH_CHECK("flow_up_kernel");
     return FAV_OK;
 }
 
-int launch_flow_coef(const float* A, const float* B, const float* flow0, float alpha, float* coef, int W, int H, hipStream_t st)
+int launch_flow_coef(const FlowPtrs& A, const FlowPtrs& B, const FlowPtrs& flow0, float alpha, const FlowPtrs& coef, int items, int W, int H,
+                     hipStream_t st)
 {
-    FAV_REQUIRE(size_ok(W, H), "flow coefficients: bad size %dx%d", W, H);
-    hipLaunchKernelGGL(flow_coef_kernel, grid_64x4(W, H), dim3(256), 0, st, A, B, reinterpret_cast<const float2*>(flow0), alpha * alpha,
-                       reinterpret_cast<float4*>(coef), W, H);
+    FAV_REQUIRE(size_ok(W, H) && items_ok(items), "flow coefficients: bad size %dx%d x %d", W, H, items);
+    hipLaunchKernelGGL(flow_coef_kernel, grid_64x4(W, H, items), dim3(256), 0, st, A, B, flow0, alpha * alpha, coef, W, H);
     FAV_LAUNCH_CHECK("flow_coef_kernel");
     return FAV_OK;
 }
 
-// `iters` sweeps from *cur, ceil(iters / K) launches between *cur and *other; on return *cur holds the result
-int launch_flow_sweeps(float** cur, float** other, const float* coef, int iters, int K, int W, int H, hipStream_t st)
+// `iters` sweeps from *cur, ceil(iters / K) launches between *cur and *other (every item at once); on return *cur holds the results
+int launch_flow_sweeps(FlowPtrs* cur, FlowPtrs* other, const FlowPtrs& coef, int items, int iters, int K, int W, int H, hipStream_t st)
 {
-    FAV_REQUIRE(size_ok(W, H) && iters >= 1 && K >= 1 && K <= FLOW_MAX_SWEEPS_PER_LAUNCH, "flow sweeps: bad argument (%dx%d, %d sweeps, %d per launch)", W, H, iters, K);
+    FAV_REQUIRE(size_ok(W, H) && items_ok(items) && iters >= 1 && K >= 1 && K <= FLOW_MAX_SWEEPS_PER_LAUNCH,
+                "flow sweeps: bad argument (%dx%d x %d, %d sweeps, %d per launch)", W, H, items, iters, K);
     const int ti = SW_R - 2 * K;
-    const dim3 grid((W + ti - 1) / ti, (H + ti - 1) / ti);
+    const dim3 grid((W + ti - 1) / ti, (H + ti - 1) / ti, items);
     FAV_REQUIRE(grid.y <= 65535, "flow sweeps: %d rows are too many", H);
     for (int done = 0; done < iters; done += K) {
-        hipLaunchKernelGGL(flow_sweep_kernel, grid, dim3(256), 0, st, reinterpret_cast<const float2*>(*cur), reinterpret_cast<const float4*>(coef),
-                           reinterpret_cast<float2*>(*other), W, H, K, std::min(K, iters - done));
+        hipLaunchKernelGGL(flow_sweep_kernel, grid, dim3(256), 0, st, *cur, coef, *other, W, H, K, std::min(K, iters - done));
         FAV_LAUNCH_CHECK("flow_sweep_kernel");
         std::swap(*cur, *other);
     }

@@ -345,7 +345,9 @@ extern "C" int fav_stream_next_frame_flow(fav_stream* s, const uint8_t* frame_rg
 }
 
 // -estimate_flow: both flows from the two frames on the caller's queue, then the frame as above (never prefetched: the flows do not exist
-// before this call)
+// before this call).  A workspace of fav_flow_pairs_workspace_bytes(W, H, 1) bytes gets the batch of one: each frame's pyramid built once,
+// both flows in every launch, the same bits.  The smaller fav_flow_workspace_bytes that callers have always passed holds one flow at a
+// time: two single calls
 extern "C" int fav_stream_next_frame_estimate(fav_stream* s, const uint8_t* frame_rgb_hwc, const uint8_t* prev_frame_rgb_hwc,
                                               const fav_flow_opts* flow_opts_host, int use_structure, float* backward_flo, float* forward_flo,
                                               void* workspace, size_t workspace_bytes, float* out_rgb_f32, uint8_t* out_rgb8_hwc,
@@ -353,10 +355,18 @@ extern "C" int fav_stream_next_frame_estimate(fav_stream* s, const uint8_t* fram
 {
     FAV_REQUIRE(s && frame_rgb_hwc && prev_frame_rgb_hwc && backward_flo && forward_flo, "fav_stream_next_frame_estimate: null argument");
     FAV_HIP(hipSetDevice(net_device(s->net)));
-    int rc = fav_flow_rgb8(frame_rgb_hwc, prev_frame_rgb_hwc, s->W, s->H, flow_opts_host, backward_flo, workspace, workspace_bytes, stream);
-    if (rc) return rc;
-    rc = fav_flow_rgb8(prev_frame_rgb_hwc, frame_rgb_hwc, s->W, s->H, flow_opts_host, forward_flo, workspace, workspace_bytes, stream);
-    if (rc) return rc;
+    const size_t pair_bytes = fav_flow_pairs_workspace_bytes(s->W, s->H, 1, flow_opts_host);      // (0: a bad option; the single call reports it)
+    int rc;
+    if (pair_bytes && workspace_bytes >= pair_bytes) {
+        rc = fav_flow_pairs_rgb8(&prev_frame_rgb_hwc, &frame_rgb_hwc, 1, s->W, s->H, flow_opts_host, &backward_flo, &forward_flo, workspace,
+                                 workspace_bytes, stream);
+        if (rc) return rc;
+    } else {
+        rc = fav_flow_rgb8(frame_rgb_hwc, prev_frame_rgb_hwc, s->W, s->H, flow_opts_host, backward_flo, workspace, workspace_bytes, stream);
+        if (rc) return rc;
+        rc = fav_flow_rgb8(prev_frame_rgb_hwc, frame_rgb_hwc, s->W, s->H, flow_opts_host, forward_flo, workspace, workspace_bytes, stream);
+        if (rc) return rc;
+    }
     return fav_stream_next_frame_flow(s, frame_rgb_hwc, backward_flo, forward_flo, use_structure, out_rgb_f32, out_rgb8_hwc, stream);
 }
 

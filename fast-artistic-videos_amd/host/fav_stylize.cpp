@@ -606,7 +606,7 @@ void run_stream(const Opt& o, fav_net* net, fav_net* net_img, int nwriters, Stre
                 hipStreamSynchronize(st); hipFree(d_state);
             }
             if (estimate) {
-                flow_ws_bytes = fav_flow_workspace_bytes(W, H, &flow_opts);
+                flow_ws_bytes = fav_flow_pairs_workspace_bytes(W, H, 1, &flow_opts);      // room for both flows at once: the batch of one
                 if (!flow_ws_bytes) die(std::string("-estimate_flow: ") + fav_last_error());
                 if (hipMalloc(&d_flow_ws, flow_ws_bytes) != hipSuccess) die("hipMalloc failed");
                 if (!cur.single) {                       // -continue_with: the frame before the first one is read as well, into the set "before" dset

@@ -59,6 +59,8 @@ def lib() -> C.CDLL:
     L.fav_png_crc32_combine_host.restype = C.c_uint32; L.fav_png_crc32_combine_host.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
     L.fav_flow_workspace_bytes.restype = C.c_size_t
     L.fav_flow_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_void_p]
+    L.fav_flow_pairs_workspace_bytes.restype = C.c_size_t
+    L.fav_flow_pairs_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
     _lib = L
     return L
 
@@ -80,6 +82,7 @@ EXPORTS = [
     "fav_vr_face_flow", "fav_vr_prefetch_mask", "fav_vr_last_mask",
     "fav_flow_workspace_bytes", "fav_flow_rgb8", "fav_flow_grey_f32", "fav_flow_down_f32", "fav_flow_up_f32", "fav_flow_coefficients_f32",
     "fav_flow_sweeps_f32", "fav_stream_next_frame_estimate",
+    "fav_flow_pairs_workspace_bytes", "fav_flow_pairs_rgb8",
 ]
 
 
@@ -226,6 +229,40 @@ def flow_rgb8(a, b, **opts):
     out = torch.empty((h, w, 2), dtype=torch.float32, device=a.device)
     _check(lib().fav_flow_rgb8(_p(a), _p(b), w, h, C.byref(o), _p(out), _p(ws), C.c_size_t(nb), _stream()))
     return out
+
+
+FLOW_MAX_PAIRS = 8
+
+
+def flow_pairs_workspace_bytes(w: int, h: int, n_pairs: int, **opts) -> int:
+    """fav_flow_pairs_workspace_bytes (host only); raises on a bad size, pair count or option"""
+    o = _flow_opts(opts)
+    n = lib().fav_flow_pairs_workspace_bytes(w, h, n_pairs, C.cast(C.pointer(o), C.c_void_p))
+    if n == 0:
+        _check(-1)
+    return n
+
+
+def flow_pairs(prev_list, cur_list, opts=None):
+    """fav_flow_pairs_rgb8: both flows of every (prev[k], cur[k]) in one batched call -> (backward_list, forward_list), .flo payloads
+    [H][W][2]: backward[k] is flow_rgb8(cur[k], prev[k]), forward[k] is flow_rgb8(prev[k], cur[k]), bit for bit.
+    opts: a dict of levels, warps, iters, alpha, sweeps_per_launch (0 / absent = default)."""
+    torch = _torch()
+    opts = dict(opts or {})
+    n = len(prev_list)
+    imgs = list(prev_list) + list(cur_list)
+    if n != len(cur_list) or n == 0 or not all(t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 3 and t.shape[2] == 3 and
+                                               t.shape == imgs[0].shape for t in imgs):
+        raise FavError("flow_pairs: prev_list and cur_list must be equally long lists of contiguous uint8 CUDA tensors [H][W][3] of one size")
+    h, w = imgs[0].shape[0], imgs[0].shape[1]
+    o = _flow_opts(opts)
+    nb = flow_pairs_workspace_bytes(w, h, n, **opts)
+    ws = torch.empty(nb, dtype=torch.uint8, device=imgs[0].device)
+    bw = [torch.empty((h, w, 2), dtype=torch.float32, device=imgs[0].device) for _ in range(n)]
+    fw = [torch.empty((h, w, 2), dtype=torch.float32, device=imgs[0].device) for _ in range(n)]
+    arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
+    _check(lib().fav_flow_pairs_rgb8(arr(prev_list), arr(cur_list), n, w, h, C.byref(o), arr(bw), arr(fw), _p(ws), C.c_size_t(nb), _stream()))
+    return bw, fw
 
 
 def flow_grey(rgb_hwc):
@@ -436,13 +473,14 @@ class Stream:
                                                 1 if use_structure else 0, _p(f), _p(u), _stream()))
         return f, u
 
-    def next_frame_estimate(self, frame_u8_hwc, prev_frame_u8_hwc, use_structure=False, want_f32=True, want_u8=False, **flow_opts):
+    def next_frame_estimate(self, frame_u8_hwc, prev_frame_u8_hwc, use_structure=False, want_f32=True, want_u8=False, batched=False, **flow_opts):
         """fav_stream_next_frame_estimate (the -estimate_flow path): both flows from the two frames, then next_frame_flow.
+        batched: pass the workspace of the batch of one (flow_pairs_workspace_bytes), as bin/fav_stylize does -- the same bits.
         Returns (f32, u8, backward_flo, forward_flo)."""
         torch = _torch()
         f, u = self._outs(frame_u8_hwc.device, want_f32, want_u8)
         o = _flow_opts(flow_opts)
-        nb = flow_workspace_bytes(self.W, self.H, **flow_opts)
+        nb = flow_pairs_workspace_bytes(self.W, self.H, 1, **flow_opts) if batched else flow_workspace_bytes(self.W, self.H, **flow_opts)
         ws = torch.empty(nb, dtype=torch.uint8, device=frame_u8_hwc.device)
         bw = torch.empty((self.H, self.W, 2), dtype=torch.float32, device=frame_u8_hwc.device)
         fw = torch.empty_like(bw)

@@ -115,6 +115,18 @@ typedef struct fav_flow_opts { int levels; int warps; int iters; float alpha; in
 size_t fav_flow_workspace_bytes(int W, int H, const fav_flow_opts* opts_host);
 int fav_flow_rgb8(const uint8_t* a_rgb_hwc, const uint8_t* b_rgb_hwc, int W, int H, const fav_flow_opts* opts_host,
                   float* flow_out, void* workspace, size_t workspace_bytes, fav_hipstream_t stream);
+/* Both flows of n_pairs (1..FAV_FLOW_MAX_PAIRS) frame pairs of one size in ONE sequence of launches (every launch works on all 2 n_pairs
+ * flows; the grey pyramid of each of the 2 n_pairs images is built once and serves both directions): what the six cube faces of a
+ * 360-degree frame need.  The four arrays are HOST arrays of n_pairs device pointers; an image may appear in more than one slot.
+ *   backward_flo[k]: the flow with A = cur[k], B = prev[k];  forward_flo[k]: the flow with A = prev[k], B = cur[k]
+ * (the two flows of fav_stream_next_frame_estimate), each bit-identical to what fav_flow_rgb8 writes for the same (A, B, options), for
+ * every n_pairs.  Workspace and contract as fav_flow_rgb8 with fav_flow_pairs_workspace_bytes; the 2 n_pairs outputs are 8-byte aligned
+ * and distinct.  The call may run on several streams at once (with a workspace each). */
+#define FAV_FLOW_MAX_PAIRS 8
+size_t fav_flow_pairs_workspace_bytes(int W, int H, int n_pairs, const fav_flow_opts* opts_host);
+int fav_flow_pairs_rgb8(const uint8_t* const* prev_rgb_hwc, const uint8_t* const* cur_rgb_hwc, int n_pairs, int W, int H,
+                        const fav_flow_opts* opts_host, float* const* backward_flo, float* const* forward_flo,
+                        void* workspace, size_t workspace_bytes, fav_hipstream_t stream);
 /* the estimator's stages on their own (operator-level entries, as fav_scale_bicubic_f32 is one): the grey image [H][W]; one pyramid step
  * to ceil(W/2) x ceil(H/2); the x2 flow upsampling between two level sizes; the coefficients (a, b, c, r) of one warp around flow0,
  * [H][W][4], 16-byte aligned; `iters` Jacobi sweeps from flow0 into flow_out (scratch: a second flow buffer [H][W][2]; flow0 is not
@@ -272,7 +284,9 @@ int fav_stream_next_frame_flow(fav_stream* s, const uint8_t* frame_rgb_hwc, cons
                                float* out_rgb_f32, uint8_t* out_rgb8_hwc, fav_hipstream_t stream);
 /* next frame from the frames alone (fav_stylize -estimate_flow 1): the backward flow (A = this frame, B = the previous one) and the
  * forward flow (A = the previous frame, B = this one) are estimated with fav_flow_rgb8 into the caller's buffers backward_flo /
- * forward_flo ([H][W][2] each) on `stream`, then the frame runs as fav_stream_next_frame_flow with them.  workspace: as fav_flow_rgb8. */
+ * forward_flo ([H][W][2] each) on `stream`, then the frame runs as fav_stream_next_frame_flow with them.  workspace: as fav_flow_rgb8
+ * (two single estimates, one after the other), or -- better -- fav_flow_pairs_workspace_bytes(W, H, 1, opts) bytes: both flows are then
+ * estimated together as the batch of one (fav_flow_pairs_rgb8: each frame's pyramid once, half the launches; the same bits). */
 int fav_stream_next_frame_estimate(fav_stream* s, const uint8_t* frame_rgb_hwc, const uint8_t* prev_frame_rgb_hwc,
                                    const fav_flow_opts* flow_opts_host, int use_structure, float* backward_flo, float* forward_flo,
                                    void* workspace, size_t workspace_bytes, float* out_rgb_f32, uint8_t* out_rgb8_hwc,
