@@ -93,6 +93,7 @@ struct Layer {
     float mul = 1.f;
     int shave = 0;
     std::vector<Layer> block;       // residual branch
+    int dev_index = -1;             // executed copy only: this layer's entry in fav_net::convs (conv) | ins (instance / batch norm), set by upload_layers
 };
 
 int t7_parse_model(const char* path, std::vector<Layer>& out);          // .t7 -> layer list
@@ -173,81 +174,80 @@ struct ConvLaunch {
     // bytes: 256 boundaries x 2 parts x 16 x 16 pixels x 128 channels) and their arrival counters (256 ints, zero between launches);
     // null => whole units only
     float* ks_ws = nullptr; int* ks_cnt = nullptr;
+    const float* wpk = nullptr;     // the selected kernel's own packing of the weights (the kernels that do not read wgt / wgt16)
+    int cin_real = 0; int* counts = nullptr;      // input channels that carry data (first layer: 7 | 3 of its 8) | per-partial pixel counts, where the kernel writes them
 };
+// What a kernel's eligibility depends on: fav_net builds one per layer and asks every predicate below with it.  stages / ups = the pending
+// normalisations and x`2^ups` upsampling of the input -- as it then is (select_conv), or as the kernel is built for (packing); a launcher checks its own descriptor
+struct ConvShape { int cin_pitch = 0, cin_real = 0, cout = 0, coutp = 0, k = 0, stride = 1, pad = 0, adj = 0, transposed = 0, stages = 0, ups = 0; };
+inline ConvShape conv_shape(const ConvLaunch& c, int transposed = 0, int adj = 0) { return {c.CIN, c.cin_real, c.COUT, c.COUTp, c.KH, c.stride, c.pad, adj, transposed, c.pre.stages, c.ups}; }
 inline size_t conv3_wino4_ksplit_bytes() { return (size_t)256 * 2 * 256 * 128 * sizeof(float); }
 // kernels_conv.hip: the generic implicit-GEMM kernel (data-parallel or stream-K)
 size_t conv_streamk_workspace_bytes();
 int conv_streamk_grid();
 constexpr int CONV_BM = 128;
-inline int conv_mblocks(int OH, int OW) { return (OH * OW + CONV_BM - 1) / CONV_BM; }
+inline int conv_tiles(const ConvLaunch& p) { return (p.OH * p.OW + CONV_BM - 1) / CONV_BM; }
 int launch_conv(const ConvLaunch& p, hipStream_t st);
 // first layer (8-channel input pitch, 9x9), kernels_c8.hip: LDS-resident halo + weights, persistent blocks; partial statistics are
 // per 16x16 tile with explicit counts
-bool conv_c8_eligible(int cin_pitch, int coutp, int k, int stride, int stages, int ups);
-int conv_c8_tiles(int OH, int OW);
-int launch_conv_c8(const ConvLaunch& p, int* counts, hipStream_t st);
+bool conv_c8_eligible(const ConvShape& s);
+int conv_c8_tiles(const ConvLaunch& p);
+int launch_conv_c8(const ConvLaunch& p, hipStream_t st);
 // the same layer with dense K for 7 (video model) or 3 (image model) real input channels: taps paired so that no zero channel is
 // multiplied; wc8d = conv_c8d_pack() of the [cout][cin][9][9] weights
-bool conv_c8d_eligible(int cin_pitch, int cin_real, int coutp, int k, int stride, int stages, int ups);
+bool conv_c8d_eligible(const ConvShape& s);
 void conv_c8d_pack(const float* w, int cin, int cout, std::vector<float>& out);
-int launch_conv_c8d(const ConvLaunch& p, int cin_real, const float* wc8d, int* counts, hipStream_t st);
+int launch_conv_c8d(const ConvLaunch& p, hipStream_t st);
 // 3x3 stride-1 layers, kernels_halo.hip: halo-resident implicit GEMM (stream-K, needs the ConvLaunch sk_* fields); partials per 8x32 tile
-bool conv3_halo_eligible(int cin_pitch, int coutp, int k, int stride);
-int conv3_halo_tiles(int OH, int OW, bool edge_b);      // edge_b: fp32 kernel (16 x 16 tiles on a narrow ragged right edge)
-int launch_conv3_halo(const ConvLaunch& p, int* counts, hipStream_t st);
+bool conv3_halo_eligible(const ConvShape& s);
+int conv3_halo_tiles(const ConvLaunch& p);      // (no wgt16, i.e. the fp32 kernel: 16 x 16 tiles on a narrow ragged right edge)
+int launch_conv3_halo(const ConvLaunch& p, hipStream_t st);
 // 3x3 stride-2 layers, kernels_halo_s2.hip: halo-resident implicit GEMM with even / odd column planes (stream-K); partials per 4x32 tile
-bool conv3s2_eligible(int cin_pitch, int coutp, int k, int stride, int stages, int ups);
-int conv3s2_tiles(int OH, int OW);
-int launch_conv3s2(const ConvLaunch& p, int* counts, hipStream_t st);
+bool conv3s2_eligible(const ConvShape& s);
+int conv3s2_tiles(const ConvLaunch& p);
+int launch_conv3s2(const ConvLaunch& p, hipStream_t st);
 // last layer with few output channels: kx taps folded into N (kernels_fold.hip); wfold = [KH][32][CIN]
-bool conv_fold_eligible(int cin_pitch, int cout, int k, int stride);
+bool conv_fold_eligible(const ConvShape& s);
 bool conv_fold_launchable(int cin_pitch, int k, int pad, int ups, int IH, int IW);      // 128 / 256 input channels: on a x2-upsampled input only
-int launch_conv_fold(const ConvLaunch& p, const float* wfold, hipStream_t st);
+int launch_conv_fold(const ConvLaunch& p, hipStream_t st);
 // the same first layer with 1-D minimal filtering F(2,3) along x (kernels_first.hip); wpk = conv_first_pack() (first_pack.h);
 // eligibility as conv_c8d_eligible; partials per 8x64 tile with explicit counts
-int conv_first_tiles(int OH, int OW);
-int launch_conv_first(const ConvLaunch& p, int cin_real, const float* wpk, int* counts, hipStream_t st);
+int conv_first_tiles(const ConvLaunch& p);
+int launch_conv_first(const ConvLaunch& p, hipStream_t st);
 // ... and with 2-D minimal filtering F(2x2,3x3) over its nine 3x3 blocks (conv_first2d_kernel); wpk = conv_first2d_pack() (first2d_pack.h);
 // partials per 16x32-pixel tile
-bool conv_first2d_eligible(int cin_pitch, int cin_real, int coutp, int k, int stride, int stages, int ups);      // any number of 32-filter groups
-int conv_first2d_tiles(int OH, int OW);
-int launch_conv_first2d(const ConvLaunch& p, int cin_real, const float* wpk, int* counts, hipStream_t st);
+bool conv_first2d_eligible(const ConvShape& s);      // any number of 32-filter groups
+int conv_first2d_tiles(const ConvLaunch& p);
+int launch_conv_first2d(const ConvLaunch& p, hipStream_t st);
 // 3x3 stride-1 UNPADDED 128-channel layers (the residual blocks): Winograd F(2x2,3x3), kernels_wino.hip; wpk = conv_wino_pack()
 // of the [cout][cin][3][3] weights (wino_pack.h); partials per 8x16-pixel unit with explicit counts
-bool conv3_wino_eligible(int cin_pitch, int cout, int coutp, int k, int stride, int pad, int stages, int ups);
-int conv3_wino_tiles(int OH, int OW);
-int launch_conv3_wino(const ConvLaunch& p, const float* wpk, int* counts, hipStream_t st);
+bool conv3_wino_eligible(const ConvShape& s);
+int conv3_wino_tiles(const ConvLaunch& p);
+int launch_conv3_wino(const ConvLaunch& p, hipStream_t st);
 // the same layers as Winograd F(4x4,3x3), kernels_wino4.hip (round 4); wpk = conv_wino4_pack() (wino4_pack.h); partials per 16x16-pixel unit
-bool conv3_wino4_eligible(int cin_pitch, int cout, int coutp, int k, int stride, int pad, int stages, int ups);
-int conv3_wino4_tiles(int OH, int OW);
-int launch_conv3_wino4(const ConvLaunch& p, const float* wpk, int* counts, hipStream_t st);
+bool conv3_wino4_eligible(const ConvShape& s);
+int conv3_wino4_tiles(const ConvLaunch& p);
+int launch_conv3_wino4(const ConvLaunch& p, hipStream_t st);
 // 3x3 stride-1 pad-1 64-channel layer on a x2 nearest-upsampled materialised input (U2 + c3s1-64): four 2x2 convolutions on the
 // physical pixels with merged weights, kernels_up2.hip; wpk = conv_up2_pack() (up2_pack.h); partials per 8x32 physical-pixel tile
-bool conv3_up2_eligible(int cin_pitch, int cout, int coutp, int k, int stride, int pad, int stages, int ups);
-int conv3_up2_tiles(int OH, int OW);
-int launch_conv3_up2(const ConvLaunch& p, const float* wpk, int* counts, hipStream_t st);
+bool conv3_up2_eligible(const ConvShape& s);
+int conv3_up2_tiles(const ConvLaunch& p);
+int launch_conv3_up2(const ConvLaunch& p, hipStream_t st);
 // the 3x3 stride-2 layers (d64 / d128) with fragment-order weights read global -> registers, halo chunks of 16 channels double-buffered
 // in LDS, whole tiles per block (kernels_s2.hip); wpk = conv_s2w_pack() (s2_pack.h); partials per TR x 32 output-pixel tile (TR = 4 for
 // 64 output channels, 2 for 128)
-bool conv3s2w_eligible(int cin_pitch, int cout, int coutp, int k, int stride, int pad, int stages, int ups);
-int conv3s2w_tiles(int OH, int OW, int coutp);
-int launch_conv3s2w(const ConvLaunch& p, const float* wpk, int* counts, hipStream_t st);
+bool conv3s2w_eligible(const ConvShape& s);
+int conv3s2w_tiles(const ConvLaunch& p);
+int launch_conv3s2w(const ConvLaunch& p, hipStream_t st);
 // nn.SpatialFullConvolution with stride 2..4 (`u<n>`, `f<k>s<s>-<n>`) by output phase on the physical input (kernels_tconv.hip); p = the
 // PHYSICAL input with the module's own k / stride / pad; wpk = conv_tconv_pack() of the [cin][cout][k][k] weights (tconv_pack.h); partials
 // per (8 x 32 input-pixel tile, phase) with explicit counts
-bool conv_tconv_eligible(int cin_pitch, int coutp, int k, int stride, int pad, int adj, int ups);
-int conv_tconv_tiles(int OH, int OW, int stride);
-int launch_conv_tconv(const ConvLaunch& p, const float* wpk, int* counts, hipStream_t st);
+bool conv_tconv_eligible(const ConvShape& s);
+int conv_tconv_tiles(const ConvLaunch& p);
+int launch_conv_tconv(const ConvLaunch& p, hipStream_t st);
 // One enumerator per launch wrapper above.  fav_net picks one per layer (net.cpp: select_conv) and reports it through
-// fav_net_profile_read_host as a kernel id -- a contract: bench.py, scripts/wide_bench.py and the GPU tests read the ids
-// (N = the padded output channel count COUTp):
-//   CK_GENERIC  launch_conv          32 | 64 | 128 (its N tile)     CK_S2W     launch_conv3s2w     700 + N
-//   CK_FOLD     launch_conv_fold     1                              CK_UP2     launch_conv3_up2    500 + N
-//   CK_C8       launch_conv_c8       8                              CK_WINO    launch_conv3_wino   400 + N  (+ 1: a pending residual join as its input)
-//   CK_C8D      launch_conv_c8d      7                              CK_WINO4   launch_conv3_wino4  600 + N  (+ 1: likewise)
-//   CK_FIRST1D  launch_conv_first    6                              CK_HALO3   launch_conv3_halo   300 + N
-//   CK_FIRST2D  launch_conv_first2d  16                             CK_S2HALO  launch_conv3s2      200 + N
-//                                                                   CK_TCONV   launch_conv_tconv   800 + N
+// fav_net_profile_read_host as a kernel id -- a contract: bench.py, scripts/wide_bench.py and the GPU tests read the ids.  Everything else
+// fav_net knows about a kernel -- its profile id among it -- is that kernel's row of CONV_KERNEL_TABLE (net_model.cpp)
 enum ConvKernel { CK_GENERIC, CK_FOLD, CK_C8, CK_C8D, CK_FIRST1D, CK_FIRST2D, CK_S2W, CK_UP2, CK_WINO, CK_WINO4, CK_HALO3, CK_S2HALO, CK_TCONV };
 constexpr int CONV_KERNELS = CK_TCONV + 1;      // (the last enumerator)
 // kernels_elem.hip.  Per-channel finalize of (mean, M2) partials -> scale/shift:  scale = gamma/sqrt(var+eps)

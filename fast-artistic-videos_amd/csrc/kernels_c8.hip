@@ -148,19 +148,19 @@ __global__ __launch_bounds__(512, 2) void conv_c8_kernel(const C8Args p)
 
 }  // namespace
 
-bool conv_c8_eligible(int cin_pitch, int coutp, int k, int stride, int stages, int ups)
+bool conv_c8_eligible(const ConvShape& s)
 {
-    return cin_pitch == 8 && coutp == 32 && k == 9 && stride == 1 && stages == 0 && ups == 0;
+    return !s.transposed && s.cin_pitch == 8 && s.coutp == 32 && s.k == 9 && s.stride == 1 && s.stages == 0 && s.ups == 0;
 }
-int conv_c8_tiles(int OH, int OW) { return ((OH + C8_TH - 1) / C8_TH) * ((OW + C8_TW - 1) / C8_TW); }
+int conv_c8_tiles(const ConvLaunch& c) { return ((c.OH + C8_TH - 1) / C8_TH) * ((c.OW + C8_TW - 1) / C8_TW); }
 
-int launch_conv_c8(const ConvLaunch& c, int* counts, hipStream_t st)
+int launch_conv_c8(const ConvLaunch& c, hipStream_t st)
 {
-    FAV_REQUIRE(conv_c8_eligible(c.CIN, c.COUTp, c.KH, c.stride, c.pre.stages, c.ups) && c.KH == c.KW && !c.final_mode,
+    FAV_REQUIRE(conv_c8_eligible(conv_shape(c)) && c.KH == c.KW && !c.final_mode,
                 "first-layer conv: not eligible");
     FAV_REQUIRE(c.Kpad >= 81 * 8 && (long long)c.IH * c.IWp * 8 < (1ll << 31), "first-layer conv: bad shape");
     C8Args a;
-    a.in = c.in; a.wgt = c.wgt; a.bias = c.bias; a.out = c.out; a.partials = reinterpret_cast<float2*>(c.partials); a.counts = counts;
+    a.in = c.in; a.wgt = c.wgt; a.bias = c.bias; a.out = c.out; a.partials = reinterpret_cast<float2*>(c.partials); a.counts = c.counts;
     a.IH = c.IH; a.IW = c.IW; a.IWp = c.IWp; a.COUT = c.COUT; a.pad = c.pad; a.OH = c.OH; a.OW = c.OW; a.Kpad = c.Kpad;
     a.tiles_x = (c.OW + C8_TW - 1) / C8_TW; a.tiles_y = (c.OH + C8_TH - 1) / C8_TH;
     constexpr int HPc = (C8_TH + 8) * (C8_TW + 8), WSc = 81 * 8 + 4;
@@ -327,10 +327,7 @@ __global__ __launch_bounds__(512, 2) void conv_c8d_kernel(const C8Args p)
 
 }  // namespace
 
-bool conv_c8d_eligible(int cin_pitch, int cin_real, int coutp, int k, int stride, int stages, int ups)
-{
-    return conv_c8_eligible(cin_pitch, coutp, k, stride, stages, ups) && (cin_real == 7 || cin_real == 3);
-}
+bool conv_c8d_eligible(const ConvShape& s) { return conv_c8_eligible(s) && (s.cin_real == 7 || s.cin_real == 3); }
 
 // weights [cout][cin][9][9] -> [pair j][half][32]: the pairing of conv_c8d_kernel
 void conv_c8d_pack(const float* w, int cin, int cout, std::vector<float>& out)
@@ -361,16 +358,16 @@ static int launch_c8d_t(const C8Args& a, int reserve_cus, hipStream_t st)
     return FAV_OK;
 }
 
-int launch_conv_c8d(const ConvLaunch& c, int cin_real, const float* wc8d, int* counts, hipStream_t st)
+int launch_conv_c8d(const ConvLaunch& c, hipStream_t st)
 {
-    FAV_REQUIRE(conv_c8d_eligible(c.CIN, cin_real, c.COUTp, c.KH, c.stride, c.pre.stages, c.ups) && c.KH == c.KW && !c.final_mode && wc8d,
+    FAV_REQUIRE(conv_c8d_eligible(conv_shape(c)) && c.KH == c.KW && !c.final_mode && c.wpk,
                 "first-layer conv (dense K): not eligible");
     FAV_REQUIRE((long long)c.IH * c.IWp * 8 < (1ll << 31), "first-layer conv: bad shape");
     C8Args a;
-    a.in = c.in; a.wgt = wc8d; a.bias = c.bias; a.out = c.out; a.partials = reinterpret_cast<float2*>(c.partials); a.counts = counts;
+    a.in = c.in; a.wgt = c.wpk; a.bias = c.bias; a.out = c.out; a.partials = reinterpret_cast<float2*>(c.partials); a.counts = c.counts;
     a.IH = c.IH; a.IW = c.IW; a.IWp = c.IWp; a.COUT = c.COUT; a.pad = c.pad; a.OH = c.OH; a.OW = c.OW; a.Kpad = c.Kpad;
     a.tiles_x = (c.OW + C8_TW - 1) / C8_TW; a.tiles_y = (c.OH + C8_TH - 1) / C8_TH;
-    return cin_real == 7 ? launch_c8d_t<7>(a, c.reserve_cus, st) : launch_c8d_t<3>(a, c.reserve_cus, st);
+    return c.cin_real == 7 ? launch_c8d_t<7>(a, c.reserve_cus, st) : launch_c8d_t<3>(a, c.reserve_cus, st);
 }
 
 }  // namespace fav

@@ -555,41 +555,41 @@ int launch_first2d_t(const FirstArgs& a, int reserve_cus, hipStream_t st)
 
 }  // namespace
 
-int conv_first_tiles(int OH, int OW) { return ((OH + F_TH - 1) / F_TH) * ((OW + F_TW - 1) / F_TW); }
+int conv_first_tiles(const ConvLaunch& c) { return ((c.OH + F_TH - 1) / F_TH) * ((c.OW + F_TW - 1) / F_TW); }
 
 // eligibility = conv_c8d_eligible (8-channel input pitch, 7 or 3 real channels, 9x9, stride 1, <= 32 output channels, no pending transform)
-int launch_conv_first(const ConvLaunch& c, int cin_real, const float* wpk, int* counts, hipStream_t st)
+int launch_conv_first(const ConvLaunch& c, hipStream_t st)
 {
-    FAV_REQUIRE(c.CIN == 8 && (cin_real == 7 || cin_real == 3) && c.COUTp == 32 && c.KH == 9 && c.KW == 9 && c.stride == 1 && c.pre.stages == 0 &&
-                c.ups == 0 && !c.final_mode && wpk, "first-layer conv (F(2,3) along x): not eligible");
+    FAV_REQUIRE(conv_c8d_eligible(conv_shape(c)) && c.KW == 9 && !c.final_mode && c.wpk, "first-layer conv (F(2,3) along x): not eligible");
     FAV_REQUIRE((long long)c.IH * c.IWp * 8 < (1ll << 31), "first-layer conv: bad shape");
     FirstArgs a;
-    a.in = c.in; a.wpk = wpk; a.bias = c.bias; a.out = c.out; a.partials = reinterpret_cast<float2*>(c.partials); a.counts = counts;
+    a.in = c.in; a.wpk = c.wpk; a.bias = c.bias; a.out = c.out; a.partials = reinterpret_cast<float2*>(c.partials); a.counts = c.counts;
     a.IH = c.IH; a.IW = c.IW; a.IWp = c.IWp; a.COUT = c.COUT; a.pad = c.pad; a.OH = c.OH; a.OW = c.OW;
     a.tiles_x = (c.OW + F_TW - 1) / F_TW; a.tiles_y = (c.OH + F_TH - 1) / F_TH;
-    return cin_real == 7 ? launch_first_t<7>(a, c.reserve_cus, st) : launch_first_t<3>(a, c.reserve_cus, st);
+    return c.cin_real == 7 ? launch_first_t<7>(a, c.reserve_cus, st) : launch_first_t<3>(a, c.reserve_cus, st);
 }
 
 // the 2-D form takes any number of 32-filter groups (c9s1-32: one; c9s1-64, the "more filters" checkpoints of README.md:141: two)
-bool conv_first2d_eligible(int cin_pitch, int cin_real, int coutp, int k, int stride, int stages, int ups)
+bool conv_first2d_eligible(const ConvShape& s)
 {
-    return cin_pitch == 8 && (cin_real == 7 || cin_real == 3) && k == 9 && stride == 1 && stages == 0 && ups == 0 && coutp % 32 == 0 && coutp >= 32 && coutp <= 256;
+    return !s.transposed && s.cin_pitch == 8 && (s.cin_real == 7 || s.cin_real == 3) && s.k == 9 && s.stride == 1 && s.stages == 0 && s.ups == 0 &&
+           s.coutp % 32 == 0 && s.coutp >= 32 && s.coutp <= 256;
 }
-int conv_first2d_tiles(int OH, int OW) { return ((OH + G_TH - 1) / G_TH) * ((OW + G_TW - 1) / G_TW); }
+int conv_first2d_tiles(const ConvLaunch& c) { return ((c.OH + G_TH - 1) / G_TH) * ((c.OW + G_TW - 1) / G_TW); }
 
 // same eligibility as launch_conv_first; wpk = conv_first2d_pack() (first2d_pack.h)
-int launch_conv_first2d(const ConvLaunch& c, int cin_real, const float* wpk, int* counts, hipStream_t st)
+int launch_conv_first2d(const ConvLaunch& c, hipStream_t st)
 {
-    FAV_REQUIRE(conv_first2d_eligible(c.CIN, cin_real, c.COUTp, c.KH, c.stride, c.pre.stages, c.ups) && c.KW == 9 && !c.final_mode && wpk,
+    FAV_REQUIRE(conv_first2d_eligible(conv_shape(c)) && c.KW == 9 && !c.final_mode && c.wpk,
                 "first-layer conv (F(2x2,3x3) over the nine 3x3 blocks): not eligible");
     FAV_REQUIRE((long long)c.IH * c.IWp * 32 < (1ll << 31) - 512, "first-layer conv: input too large for 32-bit byte offsets");
     FirstArgs a;
-    a.in = c.in; a.wpk = wpk; a.bias = c.bias; a.out = c.out; a.partials = reinterpret_cast<float2*>(c.partials); a.counts = counts;
+    a.in = c.in; a.wpk = c.wpk; a.bias = c.bias; a.out = c.out; a.partials = reinterpret_cast<float2*>(c.partials); a.counts = c.counts;
     a.IH = c.IH; a.IW = c.IW; a.IWp = c.IWp; a.COUT = c.COUT; a.pad = c.pad; a.OH = c.OH; a.OW = c.OW;
     a.tiles_x = (c.OW + G_TW - 1) / G_TW; a.tiles_y = (c.OH + G_TH - 1) / G_TH;
     a.COUTP = c.COUTp; a.groups = c.COUTp / 32; a.dbg = nullptr;
-    if (a.groups > 1) return cin_real == 7 ? launch_first2d_t<7, true>(a, c.reserve_cus, st) : launch_first2d_t<3, true>(a, c.reserve_cus, st);
-    return cin_real == 7 ? launch_first2d_t<7>(a, c.reserve_cus, st) : launch_first2d_t<3>(a, c.reserve_cus, st);
+    if (a.groups > 1) return c.cin_real == 7 ? launch_first2d_t<7, true>(a, c.reserve_cus, st) : launch_first2d_t<3, true>(a, c.reserve_cus, st);
+    return c.cin_real == 7 ? launch_first2d_t<7>(a, c.reserve_cus, st) : launch_first2d_t<3>(a, c.reserve_cus, st);
 }
 
 }  // namespace fav

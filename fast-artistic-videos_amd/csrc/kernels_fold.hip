@@ -443,9 +443,10 @@ int launch_fold_t(FoldArgs a, int reserve_cus, hipStream_t st)
 
 }  // namespace
 
-bool conv_fold_eligible(int cin_pitch, int cout, int k, int stride)
+bool conv_fold_eligible(const ConvShape& s)
 {
-    return stride == 1 && cout * k <= 32 && k <= 9 && (cin_pitch == 16 || cin_pitch == 32 || cin_pitch == 64 || cin_pitch == 128 || cin_pitch == 256);
+    return !s.transposed && s.stride == 1 && s.cout * s.k <= 32 && s.k <= 9 &&
+           (s.cin_pitch == 16 || s.cin_pitch == 32 || s.cin_pitch == 64 || s.cin_pitch == 128 || s.cin_pitch == 256);
 }
 // 128 / 256 input channels (checkpoints with more filters, README.md:141): only the form for a x2-upsampled input exists (U2 + c9s1-3,
 // every architecture string of the reference ends that way); anything else with that many channels takes the generic kernel
@@ -456,12 +457,12 @@ bool conv_fold_launchable(int cin_pitch, int k, int pad, int ups, int IH, int IW
     return ups == 1 && !no_up2 && (pad & 1) == 0 && (k & 1) == 1 && (IH & 1) == 0 && (IW & 1) == 0 && k + 1 <= 10;
 }
 
-int launch_conv_fold(const ConvLaunch& c, const float* wfold, hipStream_t st)
+int launch_conv_fold(const ConvLaunch& c, hipStream_t st)
 {
-    FAV_REQUIRE(conv_fold_eligible(c.CIN, c.COUT, c.KW, c.stride) && c.KH == c.KW && c.final_mode, "row-folded conv: not eligible");
+    FAV_REQUIRE(conv_fold_eligible(conv_shape(c)) && c.KH == c.KW && c.final_mode && c.wpk, "row-folded conv: not eligible");
     FoldArgs a;
     a.dbg = nullptr;
-    a.in = c.in; a.wfold = wfold; a.bias = c.bias;
+    a.in = c.in; a.wfold = c.wpk; a.bias = c.bias;
     a.scale1 = c.pre.scale1; a.shift1 = c.pre.shift1; a.scale2 = c.pre.scale2; a.shift2 = c.pre.shift2;
     a.stages = c.pre.stages; a.relu1 = c.pre.relu1; a.relu2 = c.pre.relu2;
     a.out_planar = c.out_planar; a.out_raw = c.out_raw_nchw;

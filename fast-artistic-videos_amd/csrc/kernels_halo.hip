@@ -650,9 +650,9 @@ __global__ __launch_bounds__(512, 2) void conv3_halo_bf16_kernel(const H3Args p)
 
 }  // namespace
 
-bool conv3_halo_eligible(int cin_pitch, int coutp, int k, int stride)
+bool conv3_halo_eligible(const ConvShape& s)
 {
-    return k == 3 && stride == 1 && cin_pitch % 32 == 0 && cin_pitch >= 32 && cin_pitch <= 256 && (coutp == 128 || coutp == 64);
+    return !s.transposed && s.k == 3 && s.stride == 1 && s.cin_pitch % 32 == 0 && s.cin_pitch >= 32 && s.cin_pitch <= 256 && (s.coutp == 128 || s.coutp == 64);
 }
 // Tile count.  edge_b (fp32 kernel): when the ragged right edge is at most 16 columns wide it is covered by ceil(OH / 16) tiles of
 // 16 x 16 instead of ceil(OH / 8) tiles of 8 x 32 -- the residual layers' widths (338 ... 320) leave 2 ... 18 columns there, i.e.
@@ -664,7 +664,7 @@ static void h3_tiling(int OH, int OW, bool edge_b, int* tx, int* ty, int* nb)
     if (edge_b && r > 0 && r <= 16 && OW > H3_TW) { *tx = OW / H3_TW; *nb = (OH + 15) / 16; }
     else { *tx = (OW + H3_TW - 1) / H3_TW; *nb = 0; }
 }
-int conv3_halo_tiles(int OH, int OW, bool edge_b) { int tx, ty, nb; h3_tiling(OH, OW, edge_b, &tx, &ty, &nb); return tx * ty + nb; }
+int conv3_halo_tiles(const ConvLaunch& c) { int tx, ty, nb; h3_tiling(c.OH, c.OW, c.wgt16 == nullptr, &tx, &ty, &nb); return tx * ty + nb; }      // (as launch_conv3_halo)
 
 // FAV_H3_DBG=n: print the in-kernel timeline (prologue / K loop / stream-K fix-up / epilogue, shader clock) of the n-th launch
 static void h3_debug_report(const long long* h, int grid)
@@ -727,16 +727,16 @@ static int launch_h3_t(const H3Args& a0, int cin, int reserve_cus, bool no_sk, h
     return FAV_OK;
 }
 
-int launch_conv3_halo(const ConvLaunch& c, int* counts, hipStream_t st)
+int launch_conv3_halo(const ConvLaunch& c, hipStream_t st)
 {
-    FAV_REQUIRE(conv3_halo_eligible(c.CIN, c.COUTp, c.KH, c.stride) && c.KH == c.KW && !c.final_mode && !c.stuff && c.sk_ws && c.sk_flags,
+    FAV_REQUIRE(conv3_halo_eligible(conv_shape(c)) && c.KH == c.KW && !c.final_mode && !c.stuff && c.sk_ws && c.sk_flags,
                 "halo conv: not eligible");
     FAV_REQUIRE((long long)((c.IH >> c.ups) + 1) * c.IWp * c.CIN < (1ll << 31), "halo conv: tensor too large for 32-bit offsets");
     H3Args a;
     a.in = c.in; a.wgt = c.wgt; a.bias = c.bias;
     a.scale1 = c.pre.scale1; a.shift1 = c.pre.shift1; a.scale2 = c.pre.scale2; a.shift2 = c.pre.shift2;
     a.stages = c.pre.stages; a.relu1 = c.pre.relu1; a.relu2 = c.pre.relu2;
-    a.out = c.out; a.partials = reinterpret_cast<float2*>(c.partials); a.counts = counts;
+    a.out = c.out; a.partials = reinterpret_cast<float2*>(c.partials); a.counts = c.counts;
     a.sk_ws = c.sk_ws; a.sk_flags = c.sk_flags; a.sk_epoch = c.sk_epoch; a.sk_err = c.sk_err;
     a.IH = c.IH; a.IW = c.IW; a.IWp = c.IWp; a.ups = c.ups; a.CIN = c.CIN; a.COUT = c.COUT; a.COUTp = c.COUTp; a.pad = c.pad;
     a.OH = c.OH; a.OW = c.OW; a.Kpad = c.Kpad;

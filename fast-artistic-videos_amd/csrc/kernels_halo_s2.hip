@@ -323,13 +323,13 @@ __global__ __launch_bounds__(512, 2) void conv3s2_halo_kernel(const S2Args p)
 
 }  // namespace
 
-bool conv3s2_eligible(int cin_pitch, int coutp, int k, int stride, int stages, int ups)
+bool conv3s2_eligible(const ConvShape& s)
 {
     // 64 output channels only: the 128-wide instance (d128) measured 126 us against 115 us of the generic kernel (register
     // pressure: accumulators + the parked halo), the 64-wide one 122 us against 148 us (d64)
-    return k == 3 && stride == 2 && ups == 0 && stages <= 1 && cin_pitch % 32 == 0 && cin_pitch >= 32 && cin_pitch <= 256 && coutp == 64;
+    return !s.transposed && s.k == 3 && s.stride == 2 && s.ups == 0 && s.stages <= 1 && s.cin_pitch % 32 == 0 && s.cin_pitch >= 32 && s.cin_pitch <= 256 && s.coutp == 64;
 }
-int conv3s2_tiles(int OH, int OW) { return ((OH + S2_TH - 1) / S2_TH) * ((OW + S2_TW - 1) / S2_TW); }
+int conv3s2_tiles(const ConvLaunch& c) { return ((c.OH + S2_TH - 1) / S2_TH) * ((c.OW + S2_TW - 1) / S2_TW); }
 
 template <int BN>
 static int launch_s2_t(const S2Args& a, int cin, int reserve_cus, bool no_sk, hipStream_t st)
@@ -355,14 +355,14 @@ static int launch_s2_t(const S2Args& a, int cin, int reserve_cus, bool no_sk, hi
     return FAV_OK;
 }
 
-int launch_conv3s2(const ConvLaunch& c, int* counts, hipStream_t st)
+int launch_conv3s2(const ConvLaunch& c, hipStream_t st)
 {
-    FAV_REQUIRE(conv3s2_eligible(c.CIN, c.COUTp, c.KH, c.stride, c.pre.stages, c.ups) && c.KH == c.KW && !c.final_mode && !c.stuff && c.sk_ws && c.sk_flags,
+    FAV_REQUIRE(conv3s2_eligible(conv_shape(c)) && c.KH == c.KW && !c.final_mode && !c.stuff && c.sk_ws && c.sk_flags,
                 "stride-2 halo conv: not eligible");
     FAV_REQUIRE((long long)(c.IH + 1) * c.IWp * c.CIN < (1ll << 31), "stride-2 halo conv: tensor too large for 32-bit offsets");
     S2Args a;
     a.in = c.in; a.wgt = c.wgt; a.bias = c.bias; a.scale1 = c.pre.scale1; a.shift1 = c.pre.shift1; a.stages = c.pre.stages; a.relu1 = c.pre.relu1;
-    a.out = c.out; a.partials = reinterpret_cast<float2*>(c.partials); a.counts = counts;
+    a.out = c.out; a.partials = reinterpret_cast<float2*>(c.partials); a.counts = c.counts;
     a.sk_ws = c.sk_ws; a.sk_flags = c.sk_flags; a.sk_epoch = c.sk_epoch; a.sk_err = c.sk_err;
     a.IH = c.IH; a.IW = c.IW; a.IWp = c.IWp; a.CIN = c.CIN; a.COUT = c.COUT; a.COUTp = c.COUTp; a.pad = c.pad;
     a.OH = c.OH; a.OW = c.OW; a.Kpad = c.Kpad;

@@ -333,24 +333,25 @@ int launch_s2w_t(const S2wArgs& a, int reserve_cus, hipStream_t st)
 
 }  // namespace
 
-bool conv3s2w_eligible(int cin_pitch, int cout, int coutp, int k, int stride, int pad, int stages, int ups)
+bool conv3s2w_eligible(const ConvShape& s)      // (cin_real == cin_pitch: the packing has no zero channels)
 {
-    return k == 3 && stride == 2 && pad <= 1 && ups == 0 && stages <= 1 && cin_pitch % 16 == 0 && cin_pitch >= 32 && cin_pitch <= 512 &&
-           cout == coutp && (coutp == 64 || (coutp % 128 == 0 && coutp <= 1024));      // 64, or any number of 128-filter groups
+    return !s.transposed && s.k == 3 && s.stride == 2 && s.pad <= 1 && s.ups == 0 && s.stages <= 1 && s.cin_real == s.cin_pitch &&
+           s.cin_pitch % 16 == 0 && s.cin_pitch >= 32 && s.cin_pitch <= 512 &&
+           s.cout == s.coutp && (s.coutp == 64 || (s.coutp % 128 == 0 && s.coutp <= 1024));      // 64, or any number of 128-filter groups
 }
 // tile rows: d64 4 (8 waves); d128 3 (12 waves: 737 tiles = 3 rounds on 256 CUs at 1280x720; with 2 rows 1100 tiles = 5 rounds where 4.3 would do)
 // (measured and not kept: d64 with 6 rows on 12 waves -- 104 us against 98.8 us with 4 rows on 8: profiles/r02y_s2w_rows_ab.log)
 static int s2w_rows(int coutp) { static const int r128 = diag_env("FAV_S2W_ROWS128") ? atoi(diag_env("FAV_S2W_ROWS128")) : 3; return coutp == 64 ? 4 : (r128 == 2 && coutp == 128 ? 2 : 3); }      // (tuning: read once)
-int conv3s2w_tiles(int OH, int OW, int coutp) { const int tr = s2w_rows(coutp); return ((OH + tr - 1) / tr) * ((OW + 31) / 32); }
+int conv3s2w_tiles(const ConvLaunch& c) { const int tr = s2w_rows(c.COUTp); return ((c.OH + tr - 1) / tr) * ((c.OW + 31) / 32); }
 
-int launch_conv3s2w(const ConvLaunch& c, const float* wpk, int* counts, hipStream_t st)
+int launch_conv3s2w(const ConvLaunch& c, hipStream_t st)
 {
-    FAV_REQUIRE(conv3s2w_eligible(c.CIN, c.COUT, c.COUTp, c.KH, c.stride, c.pad, c.pre.stages, c.ups) && c.KH == c.KW && !c.final_mode && !c.stuff && wpk,
+    FAV_REQUIRE(conv3s2w_eligible(conv_shape(c)) && c.KH == c.KW && !c.final_mode && !c.stuff && c.wpk,
                 "stride-2 conv: not eligible");
     FAV_REQUIRE((long long)(c.IH + 1) * c.IWp * c.CIN < (1ll << 29), "stride-2 conv: tensor too large for 32-bit byte offsets");
     S2wArgs a;
-    a.in = c.in; a.wpk = wpk; a.bias = c.bias; a.scale1 = c.pre.scale1; a.shift1 = c.pre.shift1; a.stages = c.pre.stages; a.relu1 = c.pre.relu1;
-    a.out = c.out; a.partials = reinterpret_cast<float2*>(c.partials); a.counts = counts;
+    a.in = c.in; a.wpk = c.wpk; a.bias = c.bias; a.scale1 = c.pre.scale1; a.shift1 = c.pre.shift1; a.stages = c.pre.stages; a.relu1 = c.pre.relu1;
+    a.out = c.out; a.partials = reinterpret_cast<float2*>(c.partials); a.counts = c.counts;
     a.IH = c.IH; a.IW = c.IW; a.IWp = c.IWp; a.CIN = c.CIN; a.OH = c.OH; a.OW = c.OW; a.pad = c.pad;
     const int tr = s2w_rows(c.COUTp);
     a.tiles_x = (c.OW + 31) / 32; a.tiles_y = (c.OH + tr - 1) / tr;

@@ -169,32 +169,32 @@ __global__ __launch_bounds__(256, 2) void conv_tconv_kernel(const TconvArgs a)
 
 }  // namespace
 
-bool conv_tconv_eligible(int cin_pitch, int coutp, int k, int stride, int pad, int adj, int ups)
+bool conv_tconv_eligible(const ConvShape& s)
 {
-    return cin_pitch % 8 == 0 && cin_pitch >= 8 && coutp % 32 == 0 && coutp >= 32 && k >= 1 && k <= TCONV_MAX_K && stride >= 2 && stride <= TCONV_MAX_S &&
-           pad >= 0 && pad <= k - 1 && adj >= 0 && adj < stride && ups == 0;
+    return s.transposed && s.cin_pitch % 8 == 0 && s.cin_pitch >= 8 && s.coutp % 32 == 0 && s.coutp >= 32 && s.k >= 1 && s.k <= TCONV_MAX_K &&
+           s.stride >= 2 && s.stride <= TCONV_MAX_S && s.pad >= 0 && s.pad <= s.k - 1 && s.adj >= 0 && s.adj < s.stride && s.ups == 0;
 }
-int conv_tconv_tiles(int OH, int OW, int stride)
+int conv_tconv_tiles(const ConvLaunch& c)
 {
-    const int UH = (OH + stride - 1) / stride, UW = (OW + stride - 1) / stride;
-    return ((UH + TCONV_TILE_H - 1) / TCONV_TILE_H) * ((UW + TCONV_TILE_W - 1) / TCONV_TILE_W) * stride * stride;
+    const int UH = (c.OH + c.stride - 1) / c.stride, UW = (c.OW + c.stride - 1) / c.stride;
+    return ((UH + TCONV_TILE_H - 1) / TCONV_TILE_H) * ((UW + TCONV_TILE_W - 1) / TCONV_TILE_W) * c.stride * c.stride;
 }
 
 // c: the PHYSICAL input (IH x IW, ups 0), KH = k, stride / pad as the module has them, OH x OW = (in - 1) s - 2 p + k + adj
-int launch_conv_tconv(const ConvLaunch& c, const float* wpk, int* counts, hipStream_t st)
+int launch_conv_tconv(const ConvLaunch& c, hipStream_t st)
 {
     const int k = c.KH, s = c.stride, p = c.pad;
-    FAV_REQUIRE(c.KH == c.KW && wpk && !c.final_mode && !c.stuff && c.OWp == 0 && c.pre.acc1 == nullptr && c.pre.stages <= 2 && c.join_skip == nullptr,
+    FAV_REQUIRE(c.KH == c.KW && c.wpk && !c.final_mode && !c.stuff && c.OWp == 0 && c.pre.acc1 == nullptr && c.pre.stages <= 2 && c.join_skip == nullptr,
                 "transposed conv: not eligible");
     const int adj = c.OH - ((c.IH - 1) * s - 2 * p + k);
-    FAV_REQUIRE(conv_tconv_eligible(c.CIN, c.COUTp, k, s, p, adj, c.ups) && c.COUT <= c.COUTp && c.IH > 0 && c.IW > 0 &&
+    FAV_REQUIRE(conv_tconv_eligible(conv_shape(c, 1, adj)) && c.COUT <= c.COUTp && c.IH > 0 && c.IW > 0 &&
                 c.OW == (c.IW - 1) * s - 2 * p + k + adj && c.OH > 0 && c.OW > 0 && c.IWp >= c.IW, "transposed conv: bad geometry");
-    FAV_REQUIRE(c.partials == nullptr || counts != nullptr, "transposed conv: statistics without counts");
+    FAV_REQUIRE(c.partials == nullptr || c.counts != nullptr, "transposed conv: statistics without counts");
     TconvArgs a;
-    a.in = c.in; a.wpk = wpk; a.bias = c.bias;
+    a.in = c.in; a.wpk = c.wpk; a.bias = c.bias;
     a.scale1 = c.pre.scale1; a.shift1 = c.pre.shift1; a.scale2 = c.pre.scale2; a.shift2 = c.pre.shift2;
     a.stages = c.pre.stages; a.relu1 = c.pre.relu1; a.relu2 = c.pre.relu2;
-    a.out = c.out; a.partials = reinterpret_cast<float2*>(c.partials); a.counts = counts;
+    a.out = c.out; a.partials = reinterpret_cast<float2*>(c.partials); a.counts = c.counts;
     a.IH = c.IH; a.IW = c.IW; a.IWp = c.IWp; a.CIN = c.CIN; a.COUT = c.COUT; a.COUTp = c.COUTp; a.OH = c.OH; a.OW = c.OW;
     a.k = k; a.s = s; a.p = p; a.lo = tconv_lo(k, s, p);
     const int span = tconv_hi(k, s, p) - a.lo;

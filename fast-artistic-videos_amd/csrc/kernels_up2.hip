@@ -451,21 +451,22 @@ __global__ __launch_bounds__(768) void conv3_up2w_kernel(const Up2Args p)
 }  // namespace
 
 static bool up2_winograd() { static const bool w = diag_env("FAV_UP2_PHASES") == nullptr; return w; }      // (tuning: read once)
-bool conv3_up2_eligible(int cin_pitch, int cout, int coutp, int k, int stride, int pad, int stages, int ups)
+bool conv3_up2_eligible(const ConvShape& s)      // (cin_real == cin_pitch: the packing has no zero channels)
 {
-    return k == 3 && stride == 1 && pad == 1 && ups == 1 && stages == 1 && cin_pitch % 32 == 0 && cin_pitch >= 32 && cin_pitch <= 256 &&
-           cout == coutp && (cout == 64 || (up2_winograd() && cout % 64 == 0 && cout <= 512));      // the nine-position kernel: any number of 64-filter groups
+    return !s.transposed && s.k == 3 && s.stride == 1 && s.pad == 1 && s.ups == 1 && s.stages == 1 && s.cin_real == s.cin_pitch &&
+           s.cin_pitch % 32 == 0 && s.cin_pitch >= 32 && s.cin_pitch <= 256 &&
+           s.cout == s.coutp && (s.cout == 64 || (up2_winograd() && s.cout % 64 == 0 && s.cout <= 512));      // the nine-position kernel: any number of 64-filter groups
 }
-int conv3_up2_tiles(int OH, int OW) { return ((OH / 2 + (up2_winograd() ? 3 : 7)) / (up2_winograd() ? 4 : 8)) * ((OW / 2 + 31) / 32); }
+int conv3_up2_tiles(const ConvLaunch& c) { return ((c.OH / 2 + (up2_winograd() ? 3 : 7)) / (up2_winograd() ? 4 : 8)) * ((c.OW / 2 + 31) / 32); }
 
-int launch_conv3_up2(const ConvLaunch& c, const float* wpk, int* counts, hipStream_t st)
+int launch_conv3_up2(const ConvLaunch& c, hipStream_t st)
 {
-    FAV_REQUIRE(conv3_up2_eligible(c.CIN, c.COUT, c.COUTp, c.KH, c.stride, c.pad, c.pre.stages, c.ups) && c.KH == c.KW && !c.final_mode && !c.stuff && wpk,
+    FAV_REQUIRE(conv3_up2_eligible(conv_shape(c)) && c.KH == c.KW && !c.final_mode && !c.stuff && c.wpk,
                 "upsampled 3x3 conv: not eligible");
     FAV_REQUIRE((c.IH & 1) == 0 && (c.IW & 1) == 0 && c.OH == c.IH && c.OW == c.IW, "upsampled 3x3 conv: bad geometry");
     FAV_REQUIRE((long long)(c.IH / 2 + 1) * c.IWp * c.CIN < (1ll << 29), "upsampled 3x3 conv: tensor too large for 32-bit byte offsets");
     Up2Args a;
-    a.in = c.in; a.wpk = wpk; a.bias = c.bias; a.scale1 = c.pre.scale1; a.shift1 = c.pre.shift1; a.relu1 = c.pre.relu1; a.out = c.out; a.partials = reinterpret_cast<float2*>(c.partials); a.counts = counts;
+    a.in = c.in; a.wpk = c.wpk; a.bias = c.bias; a.scale1 = c.pre.scale1; a.shift1 = c.pre.shift1; a.relu1 = c.pre.relu1; a.out = c.out; a.partials = reinterpret_cast<float2*>(c.partials); a.counts = c.counts;
     a.PH = c.IH / 2; a.PW = c.IW / 2; a.IWp = c.IWp; a.CIN = c.CIN;
     const bool wg = up2_winograd();
     a.tiles_x = (a.PW + 31) / 32; a.tiles_y = wg ? (a.PH + 3) / 4 : (a.PH + 7) / 8;
@@ -479,7 +480,7 @@ int launch_conv3_up2(const ConvLaunch& c, const float* wpk, int* counts, hipStre
     const int grid = std::min(tiles, persistent_slots(cus, c.reserve_cus));
     // (every U2 of the reference's builder is followed by a normalisation: stages == 1)
     if (wg && a.groups > 1) { hipLaunchKernelGGL(conv3_up2w_kernel<true>, dim3(grid), dim3(768), lds, st, a); }      // (wpk: the groups' nine-position blocks only)
-    else if (wg) { a.wpk = wpk + conv_up2_packed_floats(c.CIN); hipLaunchKernelGGL(conv3_up2w_kernel<false>, dim3(grid), dim3(768), lds, st, a); }
+    else if (wg) { a.wpk = c.wpk + conv_up2_packed_floats(c.CIN); hipLaunchKernelGGL(conv3_up2w_kernel<false>, dim3(grid), dim3(768), lds, st, a); }
     else hipLaunchKernelGGL(conv3_up2_kernel<true>, dim3(grid), dim3(512), lds, st, a);
     FAV_LAUNCH_CHECK("conv3_up2_kernel");
     return FAV_OK;

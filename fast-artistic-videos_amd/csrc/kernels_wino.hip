@@ -467,22 +467,22 @@ int launch_wino_t(const WinoArgs& a0, int reserve_cus, hipStream_t st)
 
 }  // namespace
 
-bool conv3_wino_eligible(int cin_pitch, int cout, int coutp, int k, int stride, int pad, int stages, int ups)
+bool conv3_wino_eligible(const ConvShape& s)      // (cin_real == cin_pitch: the packing has no zero channels)
 {
-    return k == 3 && stride == 1 && pad == 0 && ups == 0 && stages <= 1 && cin_pitch % 32 == 0 && cin_pitch >= 32 && cin_pitch <= 256 &&
-           cout == 128 && coutp == 128;
+    return !s.transposed && s.k == 3 && s.stride == 1 && s.pad == 0 && s.ups == 0 && s.stages <= 1 && s.cin_real == s.cin_pitch &&
+           s.cin_pitch % 32 == 0 && s.cin_pitch >= 32 && s.cin_pitch <= 256 && s.cout == 128 && s.coutp == 128;
 }
-int conv3_wino_tiles(int OH, int OW) { return ((OH + 7) / 8) * ((OW + 15) / 16); }
+int conv3_wino_tiles(const ConvLaunch& c) { return ((c.OH + 7) / 8) * ((c.OW + 15) / 16); }
 
-int launch_conv3_wino(const ConvLaunch& c, const float* wpk, int* counts, hipStream_t st)
+int launch_conv3_wino(const ConvLaunch& c, hipStream_t st)
 {
-    FAV_REQUIRE(conv3_wino_eligible(c.CIN, c.COUT, c.COUTp, c.KH, c.stride, c.pad, c.pre.stages, c.ups) && c.KH == c.KW && !c.final_mode && !c.stuff && wpk,
+    FAV_REQUIRE(conv3_wino_eligible(conv_shape(c)) && c.KH == c.KW && !c.final_mode && !c.stuff && c.wpk,
                 "winograd conv: not eligible");
     FAV_REQUIRE((long long)(c.IH + 1) * c.IWp * c.CIN < (1ll << 29), "winograd conv: tensor too large for 32-bit byte offsets");
     FAV_REQUIRE(c.OH == c.IH - 2 && c.OW == c.IW - 2, "winograd conv: bad geometry");
     WinoArgs a;
-    a.in = c.in; a.wpk = wpk; a.bias = c.bias; a.scale1 = c.pre.scale1; a.shift1 = c.pre.shift1; a.relu1 = c.pre.relu1;
-    a.out = c.out; a.partials = reinterpret_cast<float2*>(c.partials); a.counts = counts;
+    a.in = c.in; a.wpk = c.wpk; a.bias = c.bias; a.scale1 = c.pre.scale1; a.shift1 = c.pre.shift1; a.relu1 = c.pre.relu1;
+    a.out = c.out; a.partials = reinterpret_cast<float2*>(c.partials); a.counts = c.counts;
     a.IH = c.IH; a.IW = c.IW; a.IWp = c.IWp; a.CIN = c.CIN; a.OH = c.OH; a.OW = c.OW;
     a.units_x = (c.OW + 15) / 16; a.units_y = (c.OH + 7) / 8;
     a.dbg = nullptr;

@@ -34,20 +34,16 @@
 #include <type_traits>
 #include <vector>
 
-#include "fav_internal.h"
+#include "conv_device.h"
+#include "launch_common.h"
 #include "wino4_pack.h"
 
 namespace fav {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef int v4i __attribute__((ext_vector_type(4)));
-
 namespace {
 
-constexpr int MAX_DEVICES = 64;
 constexpr int W4_MEET_MAX = 256;             // meeting places of ks_ws / ks_cnt (conv3_wino4_ksplit_bytes): one per share boundary of a stream-K launch
 constexpr int W4_SHARES = 252;               // shares of a stream-K launch: a constant, so that the cuts (and with them the output's bits) do not depend on the device
-inline int cur_dev() { int d = 0; (void)hipGetDevice(&d); return (d >= 0 && d < MAX_DEVICES) ? d : 0; }
 
 // LDS layouts, in 16-byte SLOTS (4 words).  A ds_read_b128 is served in four NON-contiguous groups of 16 lanes -- {0-3, 12-15, 20-27},
 // {4-11, 16-19, 28-31} and the same + 32 -- over 16 slots (64 banks); a ds_write_b128 in eight contiguous groups of 8 lanes over 8
@@ -92,20 +88,11 @@ struct Wino4Args {
     int COUT, groups;
 };
 
-// 16-byte write-through store (sc1), as in kernels_conv.hip: the partial outputs of a K-split unit are published with these +
-// `s_waitcnt vmcnt(0)` + a relaxed agent-scope counter instead of plain stores + a release fence (which would write back the whole
-// XCD L2's dirty lines, i.e. the output tiles of the round before)
-__device__ __forceinline__ void w4_store16_wt(void* ptr, v4f v)
-{
-    asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(ptr), "v"(v) : "memory");
-}
-
 // B^T d and A^T m (wino4_pack.h) with every multiply-add WRITTEN as one: the three instantiations of the kernel (plain input, pending
 // normalisation, pending join) must round alike -- a network computes the same bits whether a residual join is launched or left pending
 // (test_pending_residual_joins_give_the_bits_of_the_launched_ones) -- and the compiler's own choice of contractions differs with context
 // (round 6: the same operations on PAIRS of values -- v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32, each component rounded exactly like
 //  the single-value instruction; four-wide vectors are legalised to single-value instructions, two-wide ones to the packed forms)
-typedef float v2f __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ v2f w4_fma(float a, v2f b, v2f c) { return __builtin_elementwise_fma(v2f{a, a}, b, c); }
 __device__ __forceinline__ void w4_bt2(const v2f d[6], v2f v[6])
 {
@@ -503,7 +490,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 for (int a = 0; a < 4; ++a)
 #pragma unroll
                     for (int b = 0; b < 4; ++b)
-                        w4_store16_wt(mine + (a * 4 + b) * 2048, v4f{y[a][b][0], y[a][b][1], y[a][b][2], y[a][b][3]});
+                        store16_wt(mine + (a * 4 + b) * 2048, v4f{y[a][b][0], y[a][b][1], y[a][b][2], y[a][b][3]});
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
                 if (t == 0) *flag = __hip_atomic_fetch_add(p.ks_cnt + meet, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -660,18 +647,18 @@ int launch_wino4_t(const Wino4Args& a0, int reserve_cus, hipStream_t st)
     const bool pair = MODE != 2;
 #endif
     const size_t lds = (size_t)(W4_SMEM + ((MODE == 2 || pair) ? W4_RBUF : 0) + 2 * a0.CIN + 4) * sizeof(float);
+    static PerDevice cache;
     const int dv = cur_dev();
-    static int cus[MAX_DEVICES] = {};
-    if (!cus[dv]) {
-        FAV_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        int occ = 0; int prop_cus = 0;
-        FAV_HIP(hipDeviceGetAttribute(&prop_cus, hipDeviceAttributeMultiprocessorCount, dv));
-        FAV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(kern), 512, lds));
+    int cus = cache.get(dv);
+    if (!cus) {
+        FAV_HIP(first_launch_setup(dv, &cus, kern));
+        int occ = 0;
+        FAV_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 512, lds));
         if (occ < 1) { set_error("winograd F(4x4) conv: kernel does not fit on a CU"); return FAV_EHIP; }
-        cus[dv] = prop_cus;          // one block per CU
+        cache.set(dv, cus);          // one block per CU
     }
     const int units = a0.units_x * a0.units_y * (WIDE ? a0.groups : 1);
-    int grid = std::min(units, std::max(1, cus[dv] - reserve_cus));
+    int grid = std::min(units, persistent_slots(cus, reserve_cus));
     Wino4Args a = a0; a.dbg = nullptr;
     // A CU holds one unit at a time, so a launch takes ceil(units / grid) rounds of one unit time -- and three of the ten layers at
     // 1280x720 have 273-286 units for 256 CUs (a unit is 256 pixels, the layers 64.8-66.9 k): two rounds for 1.07-1.12 rounds of work.
@@ -709,23 +696,23 @@ int launch_wino4_t(const Wino4Args& a0, int reserve_cus, hipStream_t st)
 }  // namespace
 
 // any number of 128-filter groups (the canonical network has one; checkpoints with more filters -- README.md:141 -- two or more)
-bool conv3_wino4_eligible(int cin_pitch, int cout, int coutp, int k, int stride, int pad, int stages, int ups)
+bool conv3_wino4_eligible(const ConvShape& s)      // (cin_real == cin_pitch: the packing has no zero channels)
 {
-    return k == 3 && stride == 1 && pad == 0 && ups == 0 && stages <= 1 && cin_pitch % 16 == 0 && cin_pitch >= 16 && cin_pitch <= 512 &&
-           cout == coutp && cout % 128 == 0 && cout >= 128 && cout <= 1024;
+    return !s.transposed && s.k == 3 && s.stride == 1 && s.pad == 0 && s.ups == 0 && s.stages <= 1 && s.cin_real == s.cin_pitch &&
+           s.cin_pitch % 16 == 0 && s.cin_pitch >= 16 && s.cin_pitch <= 512 && s.cout == s.coutp && s.cout % 128 == 0 && s.cout >= 128 && s.cout <= 1024;
 }
-int conv3_wino4_tiles(int OH, int OW) { return ((OH + 15) / 16) * ((OW + 15) / 16); }
+int conv3_wino4_tiles(const ConvLaunch& c) { return ((c.OH + 15) / 16) * ((c.OW + 15) / 16); }
 
-int launch_conv3_wino4(const ConvLaunch& c, const float* wpk, int* counts, hipStream_t st)
+int launch_conv3_wino4(const ConvLaunch& c, hipStream_t st)
 {
-    FAV_REQUIRE(conv3_wino4_eligible(c.CIN, c.COUT, c.COUTp, c.KH, c.stride, c.pad, c.pre.stages, c.ups) && c.KH == c.KW && !c.final_mode && !c.stuff && wpk,
+    FAV_REQUIRE(conv3_wino4_eligible(conv_shape(c)) && c.KH == c.KW && !c.final_mode && !c.stuff && c.wpk,
                 "winograd F(4x4) conv: not eligible");
     FAV_REQUIRE((long long)(c.IH + 1) * c.IWp * c.CIN < (1ll << 29), "winograd F(4x4) conv: tensor too large for 32-bit byte offsets");
     FAV_REQUIRE(c.OH == c.IH - 2 && c.OW == c.IW - 2, "winograd F(4x4) conv: bad geometry");
     FAV_REQUIRE((long long)(c.OH + 1) * (c.OWp > 0 ? c.OWp : c.OW) * c.COUT < (1ll << 29), "winograd F(4x4) conv: output too large for 32-bit byte offsets");
     Wino4Args a;
-    a.in = c.in; a.wpk = wpk; a.bias = c.bias; a.scale1 = c.pre.scale1; a.shift1 = c.pre.shift1; a.relu1 = c.pre.relu1;
-    a.out = c.out; a.partials = reinterpret_cast<float2*>(c.partials); a.counts = counts;
+    a.in = c.in; a.wpk = c.wpk; a.bias = c.bias; a.scale1 = c.pre.scale1; a.shift1 = c.pre.shift1; a.relu1 = c.pre.relu1;
+    a.out = c.out; a.partials = reinterpret_cast<float2*>(c.partials); a.counts = c.counts;
     a.IH = c.IH; a.IW = c.IW; a.IWp = c.IWp; a.CIN = c.CIN; a.OH = c.OH; a.OW = c.OW;
     a.units_x = (c.OW + 15) / 16; a.units_y = (c.OH + 15) / 16;
     a.dbg = nullptr;

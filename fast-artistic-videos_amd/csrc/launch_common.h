@@ -1,7 +1,5 @@
 // Host side of a kernel launch, shared by the kernels_*.hip units: the current device, and the "first launch of this kernel
 // instantiation on this device" step that every persistent launcher opens with.
-// (kernels_wino4.hip keeps its private cur_dev, w4_store16_wt and prologue for now: profiles/pmc_traffic.json records that file's hash as
-// the source its HBM traffic was measured on, so the file changes only together with the next traffic measurement.)
 #pragma once
 #include <algorithm>
 #include <atomic>
