@@ -372,6 +372,9 @@ int launch_vr_strip(const float* face, int FH, int FW, int cy, int cx, int CH, i
                     int x0, hipStream_t st);
 int launch_vr_prep(const uint8_t* frame_hwc, const float* prior, const float* cert, int fill_random, unsigned seed, unsigned index,
                    int H, int W, int pad, float* in8, hipStream_t st);
+// one equirectangular frame -> the six expanded cube faces (kernels_equi.hip); faces_u8 / faces_f32_or_null: HOST arrays of 6 device pointers
+int launch_equi_to_faces(const uint8_t* equi_rgb_hwc, int ew, int eh, int hplus, int wplus, int overlap_w, int overlap_h, int supersample,
+                         uint8_t* const* faces_u8, float* const* faces_f32_or_null, hipStream_t st);
 int launch_vr_flo_to_lua(const float* flo_uv, float* lua_dydx, size_t n, hipStream_t st);
 
 }  // namespace fav

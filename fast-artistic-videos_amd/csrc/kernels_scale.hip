@@ -19,6 +19,7 @@
 // tiles in LDS would save load instructions, not traffic: at 3840x2160 -> 1920x1080 the pair is a small fraction of the network it brackets,
 // DESIGN.md section 4.)
 // Compiled with -ffp-contract=off so that every operation rounds like the CPU restatement (tests/util/bicubic_model.py).
+#include "cubic.h"
 #include "fav_internal.h"
 
 namespace fav {
@@ -55,10 +56,7 @@ __device__ __forceinline__ float resample(const AxisTap& t, int src_len, Sample 
     const float p1 = s(t.i), p2 = s(t.i + 1);
     const float p0 = t.i > 0 ? s(t.i - 1) : 2.f * p1 - p2;
     const float p3 = t.i + 2 < src_len ? s(t.i + 2) : 2.f * p2 - p1;
-    const float a1 = p2 - p0;
-    const float a2 = 2.f * p0 - 5.f * p1 + 4.f * p2 - p3;
-    const float a3 = 3.f * (p1 - p2) + p3 - p0;
-    return p1 + 0.5f * t.x * (a1 + t.x * (a2 + t.x * a3));
+    return catmull_rom(p0, p1, p2, p3, t.x);
 }
 
 // scale_prep: the first frame's network input at the scaled size in one launch -- image.load's byte / 255, the resampling H x W ->

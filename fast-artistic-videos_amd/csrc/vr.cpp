@@ -212,6 +212,22 @@ extern "C" int fav_vr_map_host(int kind, int hplus, int wplus, int overlap, int 
     return FAV_OK;
 }
 
+extern "C" int fav_vr_equi_to_faces_rgb8(const uint8_t* equi_rgb_hwc, int equi_w, int equi_h, int hplus, int wplus, int overlap_w,
+                                         int overlap_h, int supersample, uint8_t* const* faces_rgb_hwc, float* const* faces_f32_or_null,
+                                         fav_hipstream_t stream)
+{
+    FAV_REQUIRE(equi_rgb_hwc && faces_rgb_hwc, "fav_vr_equi_to_faces_rgb8: null pointer");
+    FAV_REQUIRE(equi_w >= 4 && equi_h >= 2 && equi_w <= (1 << 20) && equi_h <= (1 << 20), "fav_vr_equi_to_faces_rgb8: bad equirectangular size %dx%d", equi_w, equi_h);
+    FAV_REQUIRE(hplus > 0 && wplus > 0 && hplus <= 65535 * 4 && wplus <= (1 << 20), "fav_vr_equi_to_faces_rgb8: bad face size %dx%d", wplus, hplus);
+    FAV_REQUIRE(overlap_w >= 0 && overlap_w < wplus && overlap_h >= 0 && overlap_h < hplus, "fav_vr_equi_to_faces_rgb8: overlap %d, %d does not fit a %dx%d face",
+                overlap_w, overlap_h, wplus, hplus);
+    FAV_REQUIRE(supersample >= 1 && supersample <= 4, "fav_vr_equi_to_faces_rgb8: supersample must be 1 .. 4, not %d", supersample);
+    for (int k = 0; k < 6; ++k) FAV_REQUIRE(faces_rgb_hwc[k], "fav_vr_equi_to_faces_rgb8: null face %d", k);
+    int rc = ensure_device(); if (rc) return rc;
+    return launch_equi_to_faces(equi_rgb_hwc, equi_w, equi_h, hplus, wplus, overlap_w, overlap_h, supersample, faces_rgb_hwc, faces_f32_or_null,
+                                static_cast<hipStream_t>(stream));
+}
+
 extern "C" int fav_vr_create(fav_net* video_net, fav_net* image_net_or_null, int hplus, int wplus, const fav_vr_opts* opts,
                              fav_vr** out)
 {

@@ -10,6 +10,12 @@
 // -occlusions_pattern is then not required, and if both are given the forward flow wins.  -structure <0|1> (default 1, as
 // makeOptFlow_deepflow.sh:59 calls the checker) selects the checker's 4-argument mode on the face's frame.  At the first face of a
 // frame the masks of the faces whose files are complete already are started ahead of the faces (fav_vr_prefetch_mask).
+// -input_equi_pattern <pat> (additive; one integer: the frame) selects a second mode by its input: the video's equirectangular frames
+// INSTEAD of face, flow and certainty files (naming any of -input_pattern, -flow_pattern, -forward_flow_pattern, -occlusions_pattern next
+// to it is an error).  Every frame is turned into six faces of -cube_edge_length <n> (768) pixels with -overlap_pixel_w / _h of margin
+// (fav_vr_equi_to_faces_rgb8, -supersample <1..4>, default 2; the reference script's pair is 768 / 128), both flows of all six faces are
+// estimated in one batched call (fav_flow_pairs_rgb8; -flow_alpha, -flow_warps, -flow_iters as in fav_stylize, 0 = default) and the faces
+// run as with -forward_flow_pattern.  One GPU.  (-estimate_flow is NOT a flag here: the flows follow from there being no face files.)
 // Additive flags: -precision <fp32|bf16>, -warp_border <stn|cpu>, -poll_timeout <sec>, -poll_settle <sec> (host/fav_poll.h), -png_level <0..9>, -seed <n> (uniform-random fill), -timing <0|1>,
 // and -- several 360-degree videos on several GPUs (BASELINE config 5; the faces of one frame depend on each other through the
 // border priors, so the unit of sharding is the video) -- -streams <a,b,...> / -gpus <n> / -force_dist / -dry_run exactly as in
@@ -253,12 +259,146 @@ int run_video(std::map<std::string, std::string>& v, std::map<std::string, bool>
     return frames_done;
 }
 
+// -input_equi_pattern: the same video from its equirectangular frames alone.  Per frame one PPM goes to the device, one launch makes the
+// six faces (fav_vr_equi_to_faces_rgb8), one batched call estimates the twelve flows between the previous faces and these
+// (fav_flow_pairs_rgb8), the six masks start on the library's side stream and the faces run through fav_vr_face_flow as in the file
+// mode with -forward_flow_pattern; no face, flow or certainty file exists.  Everything is enqueued on one stream.  (run_video above is
+// the reference's file contract and stays as it is; the frame's way out of the device is restated here.)
+int run_video_equi(std::map<std::string, std::string>& v, std::map<std::string, bool>& b, fav_net* vid, fav_net* img, double* seconds_out)
+{
+    auto I = [&](const char* k) { return atoi(v[k].c_str()); };
+    const bool timing = I("timing") != 0, gpu_png = v["png_encoder"] == "gpu", inconsistent = b["create_inconsistent"];
+    static const int proc_order[6] = {6, 1, 2, 5, 3, 4};                                                           // :103
+    const int W = I("cube_edge_length"), H = W, use_structure = I("structure"), start = I("start_frame"), count = I("num_frames");
+    const fav_flow_opts fo{0, I("flow_warps"), I("flow_iters"), (float)atof(v["flow_alpha"].c_str()), 0};
+    hipStream_t st; hipc(hipStreamCreate(&st), "hipStreamCreate");
+    fav_vr* vr = nullptr;
+    fav_vr_opts o{};
+    o.overlap_w = I("overlap_pixel_w"); o.overlap_h = I("overlap_pixel_h"); o.occlusions_min_filter = I("occlusions_min_filter");
+    o.median_filter = I("median_filter"); o.fill_random = v["fill_occlusions"] == "uniform-random"; o.seed = (unsigned)I("seed");
+    o.create_inconsistent = inconsistent; o.create_inconsistent_border = b["create_inconsistent_border"];
+    o.out_equi_w = b["out_equi"] ? I("out_equi_w") : 0; o.out_equi_h = b["out_equi"] ? I("out_equi_h") : 0;
+    o.border_mode = v["warp_border"] == "cpu" ? FAV_BORDER_CPU : FAV_BORDER_STN;
+    check(fav_vr_create(vid, img, H, W, &o, &vr), "fav_vr_create");
+    int ew = 0, eh = 0, cw = 0, ch = 0;
+    check(fav_vr_output_sizes(vr, &ew, &eh, &cw, &ch, nullptr, nullptr), "fav_vr_output_sizes");
+    if (b["out_cubemap"] && !cw) die("-out_cubemap needs square cropped faces");
+    if (gpu_png && (ew > 9000 || (b["out_cubemap"] && cw > 9000))) die("-png_encoder gpu encodes rows of up to 9000 pixels; pass -png_encoder host for these output sizes");
+    // two sets of six faces (previous, current), the twelve flows, the estimator's workspace, the source frame
+    const size_t face_bytes = (size_t)W * H * 3, flow_bytes = (size_t)W * H * 8;
+    uint8_t* d_faces[2][6] = {}; float* d_bw[6] = {}; float* d_fw[6] = {};
+    for (int k = 0; k < 6; ++k) {
+        hipc(hipMalloc(reinterpret_cast<void**>(&d_faces[0][k]), face_bytes), "hipMalloc");
+        hipc(hipMalloc(reinterpret_cast<void**>(&d_faces[1][k]), face_bytes), "hipMalloc");
+        if (!inconsistent) { hipc(hipMalloc(reinterpret_cast<void**>(&d_bw[k]), flow_bytes), "hipMalloc"); hipc(hipMalloc(reinterpret_cast<void**>(&d_fw[k]), flow_bytes), "hipMalloc"); }
+    }
+    void* d_flow_ws = nullptr; size_t flow_ws_bytes = 0;
+    if (!inconsistent) {
+        flow_ws_bytes = fav_flow_pairs_workspace_bytes(W, H, 6, &fo);
+        if (!flow_ws_bytes) die(std::string("-input_equi_pattern: ") + fav_last_error());
+        hipc(hipMalloc(&d_flow_ws, flow_ws_bytes), "hipMalloc");
+    }
+    uint8_t *d_src = nullptr, *d_equi = nullptr, *d_cube = nullptr; int sw = 0, sh = 0;
+    std::vector<uint8_t> h_equi, h_cube;
+    uint8_t *d_png_e = nullptr, *d_png_c = nullptr; uint32_t* d_png_n = nullptr; void* d_png_ws = nullptr; size_t png_ws_bytes = 0, cap_e = 0, cap_c = 0;
+    if (ew) { hipc(hipMalloc(reinterpret_cast<void**>(&d_equi), (size_t)ew * eh * 3), "hipMalloc"); h_equi.resize((size_t)ew * eh * 3); }
+    if (b["out_cubemap"]) { hipc(hipMalloc(reinterpret_cast<void**>(&d_cube), (size_t)cw * ch * 3), "hipMalloc"); h_cube.resize((size_t)cw * ch * 3); }
+    if (gpu_png) {
+        if (ew) { cap_e = fav_png_capacity(ew, eh); hipc(hipMalloc(reinterpret_cast<void**>(&d_png_e), cap_e), "hipMalloc"); h_equi.resize(cap_e); png_ws_bytes = std::max(png_ws_bytes, fav_png_workspace_bytes(ew, eh)); }
+        if (b["out_cubemap"]) { cap_c = fav_png_capacity(cw, ch); hipc(hipMalloc(reinterpret_cast<void**>(&d_png_c), cap_c), "hipMalloc"); h_cube.resize(cap_c); png_ws_bytes = std::max(png_ws_bytes, fav_png_workspace_bytes(cw, ch)); }
+        hipc(hipMalloc(reinterpret_cast<void**>(&d_png_n), 16), "hipMalloc");
+        hipc(hipMemset(d_png_n, 0, 16), "hipMemset");
+        if (png_ws_bytes) hipc(hipMalloc(&d_png_ws, png_ws_bytes), "hipMalloc");
+    }
+    std::future<void> writer;
+    const auto t_all = std::chrono::steady_clock::now();
+    int frames_done = 0;
+    for (int n = 0; n < count; ++n) {
+        const int file_idx = start + n, cur = n & 1, prev = cur ^ 1;
+        const std::string path = fmt1(v["input_equi_pattern"], file_idx);
+        if (!file_exists(path)) break;
+        uint8_t* rgb = nullptr; int w = 0, h = 0, c = 0;
+        check(fav_read_pnm_host(path.c_str(), &rgb, &w, &h, &c), "reading the equirectangular frame");
+        if (c != 3) die(path + ": not a P6 image");
+        if (!d_src) { sw = w; sh = h; hipc(hipMalloc(reinterpret_cast<void**>(&d_src), (size_t)w * h * 3), "hipMalloc"); }
+        else if (w != sw || h != sh) die(path + ": frame size changed");
+        hipc(hipMemcpyAsync(d_src, rgb, (size_t)sw * sh * 3, hipMemcpyHostToDevice, st), "H2D frame");
+        check(fav_vr_equi_to_faces_rgb8(d_src, sw, sh, H, W, o.overlap_w, o.overlap_h, I("supersample"), d_faces[cur], nullptr, st), "fav_vr_equi_to_faces_rgb8");
+        const bool temporal = n > 0 && !inconsistent;
+        const int i0 = n * 6 + 1;                                              // the frame's first face, 1-based and frame-major
+        if (temporal) {
+            check(fav_flow_pairs_rgb8(d_faces[prev], d_faces[cur], 6, W, H, &fo, d_bw, d_fw, d_flow_ws, flow_ws_bytes, st), "fav_flow_pairs_rgb8");
+            for (int k = 0; k < 6; ++k) check(fav_vr_prefetch_mask(vr, i0 + k, d_faces[cur][k], d_bw[k], d_fw[k], use_structure, st), "fav_vr_prefetch_mask");
+        }
+        hipc(hipStreamSynchronize(st), "sync");                                // the copy has left the host buffer
+        fav_free_host(rgb);
+        for (int k = 0; k < 6; ++k) {
+            const auto t0 = std::chrono::steady_clock::now();
+            check(fav_vr_face_flow(vr, i0 + k, d_faces[cur][k], temporal ? d_bw[k] : nullptr, temporal ? d_fw[k] : nullptr, use_structure, nullptr, st), "fav_vr_face_flow");
+            hipc(hipStreamSynchronize(st), "sync");
+            check(fav_net_check(vid), "stylising a face");                       // before any output derived from the face is written
+            if (img) check(fav_net_check(img), "stylising a face (image model)");
+            if (timing) printf("Elapsed time for stylizing face %d of frame %d: %.4f\n", proc_order[k], file_idx, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+        }
+        if (writer.valid()) writer.get();
+        check(fav_vr_finish_frame(vr, d_equi, d_cube, st), "fav_vr_finish_frame");
+        uint32_t png_n[2] = {0, 0};
+        if (gpu_png) {
+            if (d_equi) check(fav_png_encode_rgb8(d_equi, ew, eh, d_png_e, cap_e, d_png_n, d_png_ws, png_ws_bytes, st), "fav_png_encode_rgb8");
+            if (d_cube) check(fav_png_encode_rgb8(d_cube, cw, ch, d_png_c, cap_c, d_png_n + 1, d_png_ws, png_ws_bytes, st), "fav_png_encode_rgb8");
+            hipc(hipMemcpyAsync(png_n, d_png_n, 8, hipMemcpyDeviceToHost, st), "D2H");
+            hipc(hipStreamSynchronize(st), "sync");
+            if (png_n[0] > cap_e || png_n[1] > cap_c) die("fav_png_encode_rgb8 returned an impossible size");
+            if (d_equi) hipc(hipMemcpyAsync(h_equi.data(), d_png_e, png_n[0], hipMemcpyDeviceToHost, st), "D2H");
+            if (d_cube) hipc(hipMemcpyAsync(h_cube.data(), d_png_c, png_n[1], hipMemcpyDeviceToHost, st), "D2H");
+        } else {
+            if (d_equi) hipc(hipMemcpyAsync(h_equi.data(), d_equi, h_equi.size(), hipMemcpyDeviceToHost, st), "D2H");
+            if (d_cube) hipc(hipMemcpyAsync(h_cube.data(), d_cube, h_cube.size(), hipMemcpyDeviceToHost, st), "D2H");
+        }
+        hipc(hipStreamSynchronize(st), "sync");
+        check(fav_net_check(vid), "finishing a frame");
+        const int out_idx = n + 1;                                              // :517 (not offset by -start_frame)
+        const std::string prefix = v["output_prefix"]; const int lvl = I("png_level");
+        std::vector<uint8_t> e = h_equi, cb = h_cube;
+        if (gpu_png) { e.resize(d_equi ? png_n[0] : 0); cb.resize(d_cube ? png_n[1] : 0); }
+        writer = std::async(std::launch::async, [=]() {
+            auto put = [&](const char* kind, const std::vector<uint8_t>& bytes, int pw, int ph) {
+                if (bytes.empty()) return;
+                char name[4096];
+                snprintf(name, sizeof name, "%s-%05d_%s.png", prefix.c_str(), out_idx, kind); mkdirs_for(name);
+                if (gpu_png) {                                                   // the bytes ARE the file
+                    FILE* f = fopen(name, "wb");
+                    if (!f || fwrite(bytes.data(), 1, bytes.size(), f) != bytes.size() || fclose(f)) die(std::string("writing ") + name + " failed");
+                } else if (fav_write_png_rgb8_host(name, bytes.data(), pw, ph, lvl)) die(std::string("writing ") + name + ": " + fav_last_error());
+            };
+            put("equi", e, ew, eh); put("cubemap", cb, cw, ch);
+        });
+        ++frames_done;
+    }
+    if (writer.valid()) writer.get();
+    if (timing && frames_done) {
+        const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_all).count();
+        printf("%d frames (x6 faces) in %.3f s: %.2f frames/s\n", frames_done, s, frames_done / s);
+    }
+    fav_vr_destroy(vr);
+    check(fav_net_check(vid), "stylising the video");
+    if (img) check(fav_net_check(img), "stylising the video (image model)");
+    for (int k = 0; k < 6; ++k) { (void)hipFree(d_faces[0][k]); (void)hipFree(d_faces[1][k]); (void)hipFree(d_bw[k]); (void)hipFree(d_fw[k]); }
+    (void)hipFree(d_flow_ws); (void)hipFree(d_src); (void)hipFree(d_equi); (void)hipFree(d_cube);
+    (void)hipFree(d_png_e); (void)hipFree(d_png_c); (void)hipFree(d_png_n); (void)hipFree(d_png_ws);
+    (void)fav_net_forget_stream(vid, st);
+    hipStreamDestroy(st);
+    *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_all).count();
+    return frames_done;
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
 {
     std::map<std::string, std::string> v = {
-        {"input_pattern", ""}, {"flow_pattern", ""}, {"occlusions_pattern", ""}, {"forward_flow_pattern", ""}, {"structure", "1"}, {"model_img", ""}, {"model_vid", ""},
+        {"input_pattern", ""}, {"input_equi_pattern", ""}, {"cube_edge_length", "768"}, {"supersample", "2"}, {"flow_alpha", "0"}, {"flow_warps", "0"}, {"flow_iters", "0"},
+        {"flow_pattern", ""}, {"occlusions_pattern", ""}, {"forward_flow_pattern", ""}, {"structure", "1"}, {"model_img", ""}, {"model_vid", ""},
         {"start_frame", "1"}, {"continue_with", "1"}, {"num_frames", "9999"}, {"occlusions_min_filter", "7"},
         {"fill_occlusions", "vgg-mean"}, {"overlap_pixel_w", "20"}, {"overlap_pixel_h", "20"}, {"output_prefix", "out"},
         {"out_equi_w", "768"}, {"out_equi_h", "768"}, {"median_filter", "3"}, {"gpu", "-1"}, {"backend", "cuda"}, {"use_cudnn", "1"},
@@ -281,9 +421,21 @@ int main(int argc, char** argv)
         v[k] = argv[++a];
     }
     auto I = [&](const char* k) { return atoi(v[k].c_str()); };
-    if (v["input_pattern"].empty()) die("Must give -input_pattern");                                               // :564-566
+    // -input_equi_pattern: the faces are made from the equirectangular frames and both flows of every face are estimated from them, so
+    // no face, flow or certainty file exists and none may be named
+    const bool from_equi = !v["input_equi_pattern"].empty();
+    if (from_equi) {
+        for (const char* k : {"input_pattern", "flow_pattern", "forward_flow_pattern", "occlusions_pattern"})
+            if (!v[k].empty()) die(std::string("-input_equi_pattern makes the faces and their flows from the equirectangular frames: it cannot be combined with -") + k);
+        if (I("supersample") < 1 || I("supersample") > 4) die("-supersample must be 1 .. 4, not '" + v["supersample"] + "'");
+        if (I("cube_edge_length") < 16 || I("cube_edge_length") > 16384) die("-cube_edge_length must be 16 .. 16384, not '" + v["cube_edge_length"] + "'");
+        const fav_flow_opts fo{0, I("flow_warps"), I("flow_iters"), (float)atof(v["flow_alpha"].c_str()), 0};
+        if (fav_flow_workspace_bytes(16, 16, &fo) == 0) die(std::string("-flow_alpha / -flow_iters / -flow_warps: ") + fav_last_error());
+        if (std::max(1, I("gpus")) > 1 || I("force_dist")) die("-input_equi_pattern runs on one GPU: it cannot be combined with -gpus > 1 or -force_dist");
+    }
+    if (!from_equi && v["input_pattern"].empty()) die("Must give -input_pattern");                                  // :564-566
     // (-forward_flow_pattern: the certainty is computed from the two flows, -occlusions_pattern is not needed -- and not read if given)
-    if (!b["create_inconsistent"] && (v["flow_pattern"].empty() || (v["occlusions_pattern"].empty() && v["forward_flow_pattern"].empty())))
+    if (!from_equi && !b["create_inconsistent"] && (v["flow_pattern"].empty() || (v["occlusions_pattern"].empty() && v["forward_flow_pattern"].empty())))
         die("Must give -flow_pattern and -occlusions_pattern");                                                     // :567-569
     if (v["structure"] != "0" && v["structure"] != "1") die("-structure must be 0 or 1");
     if (!v["forward_flow_pattern"].empty() && !v["occlusions_pattern"].empty() && atoi(v["worker_rank"].c_str()) < 0)
@@ -303,7 +455,7 @@ int main(int argc, char** argv)
     if (!named) streams.push_back("");
     int world = std::max(1, I("gpus"));
     const int rank = I("worker_rank");
-    static const char* const path_opts[] = {"input_pattern", "flow_pattern", "occlusions_pattern", "forward_flow_pattern", "output_prefix"};
+    static const char* const path_opts[] = {"input_pattern", "input_equi_pattern", "flow_pattern", "occlusions_pattern", "forward_flow_pattern", "output_prefix"};
     if (named && streams.size() > 1 && v["output_prefix"].find("%S") == std::string::npos)
         die("-streams: -output_prefix must contain %S (the videos would overwrite each other's frames)");
     if (rank < 0 && (world > 1 || I("force_dist"))) {                                   // launcher: one worker process per GPU
@@ -353,7 +505,7 @@ int main(int argc, char** argv)
         std::map<std::string, std::string> vs = v;
         if (named) for (const char* po : path_opts) vs[po] = favl::subst_stream(v[po], name);
         double sec = 0;
-        frames += run_video(vs, b, vid, img, &sec);
+        frames += from_equi ? run_video_equi(vs, b, vid, img, &sec) : run_video(vs, b, vid, img, &sec);
         seconds += sec;
     }
     if (dist && timing) favl::write_worker_result(v["rccl_id_file"], rank, frames, seconds);

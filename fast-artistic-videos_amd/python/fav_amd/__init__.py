@@ -83,6 +83,7 @@ EXPORTS = [
     "fav_flow_workspace_bytes", "fav_flow_rgb8", "fav_flow_grey_f32", "fav_flow_down_f32", "fav_flow_up_f32", "fav_flow_coefficients_f32",
     "fav_flow_sweeps_f32", "fav_stream_next_frame_estimate",
     "fav_flow_pairs_workspace_bytes", "fav_flow_pairs_rgb8",
+    "fav_vr_equi_to_faces_rgb8",
 ]
 
 
@@ -614,6 +615,23 @@ def vr_map_host(kind: int, hplus: int, wplus: int, overlap: int, median: int = 3
     out = np.empty(shape, np.float32)
     _check(lib().fav_vr_map_host(kind, hplus, wplus, overlap, median, out_w, out_h, out.ctypes.data_as(C.c_void_p)))
     return out
+
+
+def vr_equi_to_faces(equi_u8_hwc, edge: int, overlap_w: int, overlap_h: Optional[int] = None, supersample: int = 2, want_f32: bool = False):
+    """fav_vr_equi_to_faces_rgb8: one equirectangular frame (u8 [H][W][3]) -> the six expanded cube faces in processing order, a list of
+    u8 [edge][edge][3] tensors; with want_f32 also the list of the unrounded fp32 planes [edge][edge][3] (0..255 units)."""
+    torch = _torch()
+    if not (equi_u8_hwc.is_cuda and equi_u8_hwc.dtype == torch.uint8 and equi_u8_hwc.is_contiguous() and equi_u8_hwc.dim() == 3 and
+            equi_u8_hwc.shape[2] == 3):
+        raise FavError("vr_equi_to_faces: the frame must be a contiguous uint8 CUDA tensor [H][W][3]")
+    overlap_h = overlap_w if overlap_h is None else overlap_h
+    eh, ew = equi_u8_hwc.shape[0], equi_u8_hwc.shape[1]
+    faces = [torch.empty((edge, edge, 3), dtype=torch.uint8, device=equi_u8_hwc.device) for _ in range(6)]
+    planes = [torch.empty((edge, edge, 3), dtype=torch.float32, device=equi_u8_hwc.device) for _ in range(6)] if want_f32 else None
+    arr = lambda ts: (C.c_void_p * 6)(*[t.data_ptr() for t in ts])
+    _check(lib().fav_vr_equi_to_faces_rgb8(_p(equi_u8_hwc), ew, eh, edge, edge, overlap_w, overlap_h, supersample, arr(faces),
+                                           arr(planes) if want_f32 else None, _stream()))
+    return (faces, planes) if want_f32 else faces
 
 
 class VR:

@@ -380,6 +380,19 @@ int fav_vr_get_f32(const fav_vr* v, int which, int k, float* out_dev, fav_hipstr
 /* the static maps, computed on the host (no device needed): kind 0..3 = perspective map left/right/top/bottom
  * ([2][hplus][wplus], `overlap` = the crop along that axis), 4 = cube->equirectangular map ([2][out_h][out_w]) */
 int fav_vr_map_host(int kind, int hplus, int wplus, int overlap, int median_filter, int out_w, int out_h, float* out_host);
+/* The transform stage: one equirectangular frame (u8 [equi_h][equi_w][3]) -> the six expanded cube faces (u8 [hplus][wplus][3] each) the
+ * calls above take.  Stands in for transformVRVideo.sh's `ffmpeg -vf transform360=...:cube_edge_length=768:expand_coef=1.2` (a filter
+ * that stock ffmpeg does not have).  The geometry is the inverse of the map of kind 4 above (median_filter 0) on the strip of
+ * fast_artistic_video_vr.lua:543 -- faces[k] is processing position k = strip segment k, segments 4 and 5 rotated by 180 degrees -- on the
+ * inner (hplus - overlap_h) x (wplus - overlap_w) of a face, continued over the overlap margin by the same pinhole projection: a face
+ * spans tan = +-wplus / (wplus - overlap_w) (768 / 128: +-1.2).  Pixel index i of the frame is phi = 2 pi i / equi_w, row j is
+ * theta = pi (1 - j / equi_h).  An output pixel is the mean of supersample^2 (1..4) Catmull-Rom bicubic samples on the regular grid of
+ * sub-pixel centres, columns wrapping modulo equi_w, rows clamped; fp32; the u8 result is clamp(floor(v + 0.5), 0, 255) and the optional
+ * fp32 planes ([hplus][wplus][3], 0..255 units) hold v.  This is NOT transform360's Lanczos-4 + low-pass filter; its quality against it
+ * is unmeasured.  faces_rgb_hwc / faces_f32_or_null: HOST arrays of six device pointers (the second, or any entry of it, may be NULL).
+ * One launch; allocates nothing, does not synchronise. */
+int fav_vr_equi_to_faces_rgb8(const uint8_t* equi_rgb_hwc, int equi_w, int equi_h, int hplus, int wplus, int overlap_w, int overlap_h,
+                              int supersample, uint8_t* const* faces_rgb_hwc, float* const* faces_f32_or_null, fav_hipstream_t stream);
 
 /* ---- host-side formats (A1, A9) ----------------------------------------------------------------
  * .flo: flowFileLoader.lua:14-34 / consistencyChecker.cpp:16-36 (tag read, not validated);
