@@ -1,6 +1,6 @@
 // flow.cpp -- the coarse-to-fine optical-flow estimator behind fav_flow_rgb8 (kernels in kernels_flow.hip; the algorithm is stated in
-// DESIGN.md, "fav_flow", and restated in numpy by tests/util/flow_model.py): option defaults, the layout of the caller's workspace and
-// the sequence of launches.  Nothing here allocates or synchronises.
+// DESIGN.md, "fav_flow", and restated in numpy by tests/util/flow_model.py and, for smooth_eps > 0, tests/util/flow_robust_model.py):
+// option defaults, the layout of the caller's workspace and the sequence of launches.  Nothing here allocates or synchronises.
 #include <cmath>
 
 #include "fav_internal.h"
@@ -11,24 +11,25 @@ namespace {
 
 constexpr int MAX_LEVELS = 6, MIN_SIDE = 16;
 constexpr int DEFAULT_WARPS = 3, DEFAULT_ITERS = 30, DEFAULT_SWEEPS_PER_LAUNCH = 6;
-constexpr float DEFAULT_ALPHA = 15.f;
+constexpr float DEFAULT_ALPHA = 15.f, DEFAULT_ALPHA_ROBUST = 5.f;      // (robust: with smooth_eps > 0)
+constexpr float MIN_EPS = 1e-6f, MAX_EPS = 1e6f;                      // eps^2 and 1 / eps stay normal fp32 numbers
 
 // The workspace of a call on `images` images and `flows` flows (fav_flow_rgb8: 2 and 1; fav_flow_pairs_rgb8: 2 n and 2 n).  The planes
 // of one kind at one level lie one behind the other, `stride` bytes apart (a multiple of 256).
 struct FlowPlan {
     int levels = 0, warps = 0, iters = 0, K = 0, images = 0, flows = 0;
-    float alpha = 0.f;
+    float alpha = 0.f, eps = 0.f;                                            // eps > 0: edge-preserving smoothness
     int w[MAX_LEVELS], h[MAX_LEVELS];
     size_t pyr[MAX_LEVELS], pyr_stride[MAX_LEVELS];                          // byte offsets into the workspace: `images` grey planes
     size_t flow0[MAX_LEVELS], flow1[MAX_LEVELS], flow_stride[MAX_LEVELS];    // the two flow buffers of a level, `flows` planes each (level 0:
                                                                              // flow1 only, the other ones are the caller's)
-    size_t coef = 0, coef_stride = 0, bytes = 0;
+    size_t coef = 0, coef_stride = 0, wgt = 0, bytes = 0;                    // wgt: the edge weights (eps > 0 only), coef_stride apart
 };
 
 // FAV_OK or FAV_EINVAL (message set)
 int make_plan(int W, int H, const fav_flow_opts* o, int images, int flows, FlowPlan& p)
 {
-    static const fav_flow_opts none = {0, 0, 0, 0.f, 0};
+    static const fav_flow_opts none = {0, 0, 0, 0.f, 0, 0.f};
     if (!o) o = &none;
     FAV_REQUIRE(W >= MIN_SIDE && H >= MIN_SIDE && (long long)W * H <= (1ll << 28), "fav_flow: frames must be at least %dx%d (and at most 2^28 pixels), not %dx%d", MIN_SIDE, MIN_SIDE, W, H);
     FAV_REQUIRE(o->levels >= 0 && o->levels <= MAX_LEVELS, "fav_flow: levels must be 0 (default) .. %d, not %d", MAX_LEVELS, o->levels);
@@ -36,9 +37,12 @@ int make_plan(int W, int H, const fav_flow_opts* o, int images, int flows, FlowP
     FAV_REQUIRE(o->iters >= 0 && o->iters <= 1000, "fav_flow: iters must be 0 (default) .. 1000, not %d", o->iters);
     FAV_REQUIRE(std::isfinite(o->alpha) && o->alpha >= 0.f && o->alpha <= 1e6f, "fav_flow: alpha must be 0 (default) or a positive number up to 1e6, not %g", (double)o->alpha);
     FAV_REQUIRE(o->sweeps_per_launch >= 0 && o->sweeps_per_launch <= FLOW_MAX_SWEEPS_PER_LAUNCH, "fav_flow: sweeps_per_launch must be 0 (default) .. %d, not %d", FLOW_MAX_SWEEPS_PER_LAUNCH, o->sweeps_per_launch);
+    FAV_REQUIRE(o->smooth_eps == 0.f || (std::isfinite(o->smooth_eps) && o->smooth_eps >= MIN_EPS && o->smooth_eps <= MAX_EPS),
+                "fav_flow: smooth_eps must be 0 (off) or a number in 1e-6 .. 1e6, not %g", (double)o->smooth_eps);
+    p.eps = o->smooth_eps;
     p.warps = o->warps ? o->warps : DEFAULT_WARPS;
     p.iters = o->iters ? o->iters : DEFAULT_ITERS;
-    p.alpha = o->alpha != 0.f ? o->alpha : DEFAULT_ALPHA;
+    p.alpha = o->alpha != 0.f ? o->alpha : (p.eps > 0.f ? DEFAULT_ALPHA_ROBUST : DEFAULT_ALPHA);
     p.K = o->sweeps_per_launch ? o->sweeps_per_launch : DEFAULT_SWEEPS_PER_LAUNCH;
     p.images = images; p.flows = flows;
     p.w[0] = W; p.h[0] = H; p.levels = 1;
@@ -59,6 +63,7 @@ int make_plan(int W, int H, const fav_flow_opts* o, int images, int flows, FlowP
     }
     p.coef_stride = round256((size_t)W * H * 16);
     p.coef = take(p.coef_stride, flows);
+    if (p.eps > 0.f) p.wgt = take(p.coef_stride, flows);
     p.bytes = off;
     return FAV_OK;
 }
@@ -78,6 +83,8 @@ int run_plan(const FlowPlan& p, const FlowPtrs& img, const int* a_of, const int*
     // coarse to fine.  Every warp ends ceil(iters / K) buffer swaps later: level 0 starts in the buffers that leave the results in `out`
     const int swaps = p.warps * ((p.iters + p.K - 1) / p.K);
     const FlowPtrs coef(ws + p.coef, p.coef_stride, p.flows);
+    const FlowPtrs wgt_planes(ws + p.wgt, p.coef_stride, p.flows);
+    const FlowPtrs* wgt = p.eps > 0.f ? &wgt_planes : nullptr;
     FlowPtrs coarser;
     for (int l = p.levels - 1; l >= 0; --l) {
         FlowPtrs cur = l ? FlowPtrs(ws + p.flow0[l], p.flow_stride[l], p.flows) : out;
@@ -95,8 +102,8 @@ int run_plan(const FlowPlan& p, const FlowPtrs& img, const int* a_of, const int*
             else for (int j = 0; j < p.flows; ++j) FAV_HIP(hipMemsetAsync(cur.p[j], 0, (size_t)w * h * 8, st));
         } else { rc = launch_flow_up(coarser, p.w[l + 1], p.h[l + 1], cur, p.flows, w, h, st); if (rc) return rc; }
         for (int k = 0; k < p.warps; ++k) {
-            rc = launch_flow_coef(A, B, cur, p.alpha, coef, p.flows, w, h, st); if (rc) return rc;
-            rc = launch_flow_sweeps(&cur, &other, coef, p.flows, p.iters, p.K, w, h, st); if (rc) return rc;
+            rc = launch_flow_coef(A, B, cur, p.alpha, p.eps, coef, wgt, p.flows, w, h, st); if (rc) return rc;
+            rc = launch_flow_sweeps(&cur, &other, coef, wgt, p.flows, p.iters, p.K, w, h, st); if (rc) return rc;
         }
         coarser = cur;
     }
@@ -193,24 +200,55 @@ extern "C" int fav_flow_coefficients_f32(const float* a_grey, const float* b_gre
     FAV_REQUIRE(a_grey && b_grey && flow0 && coef && W > 0 && H > 0 && std::isfinite(alpha) && alpha > 0.f, "fav_flow_coefficients_f32: bad argument");
     FAV_REQUIRE(reinterpret_cast<uintptr_t>(flow0) % 8 == 0 && reinterpret_cast<uintptr_t>(coef) % 16 == 0, "fav_flow_coefficients_f32: flow0 must be 8-byte aligned, coef 16-byte aligned");
     int rc = ensure_device(); if (rc) return rc;
-    return launch_flow_coef(FlowPtrs(a_grey), FlowPtrs(b_grey), FlowPtrs(flow0), alpha, FlowPtrs(coef), 1, W, H, static_cast<hipStream_t>(stream));
+    return launch_flow_coef(FlowPtrs(a_grey), FlowPtrs(b_grey), FlowPtrs(flow0), alpha, 0.f, FlowPtrs(coef), nullptr, 1, W, H, static_cast<hipStream_t>(stream));
 }
 
-extern "C" int fav_flow_sweeps_f32(const float* flow0, const float* coef, int iters, int sweeps_per_launch, float* flow_out, float* scratch,
-                                   int W, int H, fav_hipstream_t stream)
+extern "C" int fav_flow_coefficients_robust_f32(const float* a_grey, const float* b_grey, const float* flow0, float alpha, float smooth_eps, float* coef,
+                                                float* weights, int W, int H, fav_hipstream_t stream)
 {
-    FAV_REQUIRE(flow0 && coef && flow_out && scratch && W > 0 && H > 0, "fav_flow_sweeps_f32: bad argument");
-    FAV_REQUIRE(iters >= 1 && sweeps_per_launch >= 0 && sweeps_per_launch <= FLOW_MAX_SWEEPS_PER_LAUNCH, "fav_flow_sweeps_f32: iters must be >= 1, sweeps_per_launch 0 (default) .. %d", FLOW_MAX_SWEEPS_PER_LAUNCH);
+    FAV_REQUIRE(a_grey && b_grey && flow0 && coef && weights && W > 0 && H > 0 && std::isfinite(alpha) && alpha > 0.f, "fav_flow_coefficients_robust_f32: bad argument");
+    FAV_REQUIRE(std::isfinite(smooth_eps) && smooth_eps >= MIN_EPS && smooth_eps <= MAX_EPS, "fav_flow_coefficients_robust_f32: smooth_eps must be a number in 1e-6 .. 1e6, not %g", (double)smooth_eps);
+    FAV_REQUIRE(reinterpret_cast<uintptr_t>(flow0) % 8 == 0 && reinterpret_cast<uintptr_t>(coef) % 16 == 0 && reinterpret_cast<uintptr_t>(weights) % 16 == 0 && coef != weights,
+                "fav_flow_coefficients_robust_f32: flow0 must be 8-byte aligned, coef and weights 16-byte aligned and distinct");
+    int rc = ensure_device(); if (rc) return rc;
+    const FlowPtrs wgt(weights);
+    return launch_flow_coef(FlowPtrs(a_grey), FlowPtrs(b_grey), FlowPtrs(flow0), alpha, smooth_eps, FlowPtrs(coef), &wgt, 1, W, H, static_cast<hipStream_t>(stream));
+}
+
+namespace {
+
+// the two sweep entries: `weights` == nullptr is the plain mean
+int sweeps_entry(const char* who, const float* flow0, const float* coef, const float* weights, int iters, int sweeps_per_launch, float* flow_out,
+                 float* scratch, int W, int H, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(flow0 && coef && flow_out && scratch && W > 0 && H > 0, "%s: bad argument", who);
+    FAV_REQUIRE(iters >= 1 && sweeps_per_launch >= 0 && sweeps_per_launch <= FLOW_MAX_SWEEPS_PER_LAUNCH, "%s: iters must be >= 1, sweeps_per_launch 0 (default) .. %d", who, FLOW_MAX_SWEEPS_PER_LAUNCH);
     FAV_REQUIRE(reinterpret_cast<uintptr_t>(flow0) % 8 == 0 && reinterpret_cast<uintptr_t>(flow_out) % 8 == 0 && reinterpret_cast<uintptr_t>(scratch) % 8 == 0 &&
-                reinterpret_cast<uintptr_t>(coef) % 16 == 0, "fav_flow_sweeps_f32: flows must be 8-byte aligned, coef 16-byte aligned");
+                reinterpret_cast<uintptr_t>(coef) % 16 == 0 && reinterpret_cast<uintptr_t>(weights) % 16 == 0, "%s: flows must be 8-byte aligned, coef%s 16-byte aligned", who, weights ? " and weights" : "");
     int rc = ensure_device(); if (rc) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int K = sweeps_per_launch ? sweeps_per_launch : DEFAULT_SWEEPS_PER_LAUNCH;
     // flow0 is read only: the first launch goes from it into the buffer from which the remaining launches end in flow_out
     const int first = std::min(K, iters), rest_launches = (iters - first + K - 1) / K;
     FlowPtrs src(flow0), cur((rest_launches & 1) ? scratch : flow_out), other((rest_launches & 1) ? flow_out : scratch), first_dst = cur;
-    const FlowPtrs cf(coef);
-    rc = launch_flow_sweeps(&src, &first_dst, cf, 1, first, K, W, H, st); if (rc) return rc;
-    if (iters > first) { rc = launch_flow_sweeps(&cur, &other, cf, 1, iters - first, K, W, H, st); if (rc) return rc; }
+    const FlowPtrs cf(coef), wgt_plane(weights);
+    const FlowPtrs* wgt = weights ? &wgt_plane : nullptr;
+    rc = launch_flow_sweeps(&src, &first_dst, cf, wgt, 1, first, K, W, H, st); if (rc) return rc;
+    if (iters > first) { rc = launch_flow_sweeps(&cur, &other, cf, wgt, 1, iters - first, K, W, H, st); if (rc) return rc; }
     return FAV_OK;
+}
+
+}  // namespace
+
+extern "C" int fav_flow_sweeps_f32(const float* flow0, const float* coef, int iters, int sweeps_per_launch, float* flow_out, float* scratch,
+                                   int W, int H, fav_hipstream_t stream)
+{
+    return sweeps_entry("fav_flow_sweeps_f32", flow0, coef, nullptr, iters, sweeps_per_launch, flow_out, scratch, W, H, stream);
+}
+
+extern "C" int fav_flow_sweeps_robust_f32(const float* flow0, const float* coef, const float* weights, int iters, int sweeps_per_launch, float* flow_out,
+                                          float* scratch, int W, int H, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(weights, "fav_flow_sweeps_robust_f32: bad argument");
+    return sweeps_entry("fav_flow_sweeps_robust_f32", flow0, coef, weights, iters, sweeps_per_launch, flow_out, scratch, W, H, stream);
 }

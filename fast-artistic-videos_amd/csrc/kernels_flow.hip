@@ -8,6 +8,12 @@
 //   coefficients  Bw = B(p + w0) bilinear with clamped coordinates; a = Ix, b = Iy central differences of Bw * 0.5 (borders replicated);
 //                 c = (Bw - A) - a u0 - b v0;  r = 1 / (alpha^2 + a^2 + b^2)  -> float4 (a, b, c, r) per pixel
 //   sweep         u_bar, v_bar = 4-neighbour means (borders replicated); t = (a u_bar + b v_bar + c) r;  u = u_bar - a t, v = v_bar - b t
+// Edge-preserving smoothness (smooth_eps > 0; restated by tests/util/flow_robust_model.py), per warp from its starting flow w0, fixed for
+// all its sweeps:
+//   diffusivity   g = 1 / sqrt(((u_x^2 + v_x^2) + (u_y^2 + v_y^2)) + eps^2), central differences * 0.5 of w0, borders replicated
+//   edge weights  w_q = 0.5 (g_p + g_q), q = left, right, up, down (index clamped to the image);  S = (w_l + w_r) + (w_u + w_d)
+//                 r = 1 / (((alpha^2 S) 0.25 + a^2) + b^2);  stored: n_q = w_q / S -> float4 (n_l, n_r, n_u, n_d) per pixel
+//   sweep         u_bar = (n_l u_l + n_r u_r) + (n_u u_u + n_d u_d), v_bar likewise; the rest as above
 //
 // The sweeps are the hot path: iters x warps x levels x 2 directions of them per frame.  One sweep per launch is a pass over HBM of
 // 32 bytes per pixel; flow_sweep_kernel runs up to K sweeps per launch on a tile that lives in LDS (temporal blocking).  Jacobi reads
@@ -87,8 +93,19 @@ __global__ __launch_bounds__(256) void flow_up_kernel(FlowPtrs coarses, int wc, 
 }
 
 // warp + derivatives + coefficients in one launch: a lane forms Bw at its pixel and at its four (replicated) neighbours -- each with that
-// pixel's own flow -- instead of a second pass over a stored Bw
-__global__ __launch_bounds__(256) void flow_coef_kernel(FlowPtrs As, FlowPtrs Bs, FlowPtrs flow0s, float alpha2, FlowPtrs coefs, int w, int h)
+// pixel's own flow -- instead of a second pass over a stored Bw.
+// ROBUST: the lane also forms the diffusivity g at its pixel and at its four (clamped) neighbours, each from the four neighbours of THAT
+// pixel: a 13-point stencil of flow0 that the L1 serves, once per warp.  eps2 = eps^2 (formed on the host in fp32).  The option's arguments
+// come last and are an empty struct in the plain instantiation: it reads its arguments where it always has, and a launch carries no
+// table it does not use (the estimator is launch-bound).
+template <bool ROBUST> struct CoefRobustArgs {};
+template <> struct CoefRobustArgs<true> { float eps2; FlowPtrs wgts; };
+template <bool ROBUST> struct SweepRobustArgs {};
+template <> struct SweepRobustArgs<true> { FlowPtrs wgts; };
+
+template <bool ROBUST>
+__global__ __launch_bounds__(256) void flow_coef_kernel(FlowPtrs As, FlowPtrs Bs, FlowPtrs flow0s, float alpha2, FlowPtrs coefs, int w, int h,
+                                                        CoefRobustArgs<ROBUST> ra)
 {
     const float* __restrict__ A = static_cast<const float*>(As.p[blockIdx.z]);
     const float* __restrict__ B = static_cast<const float*>(Bs.p[blockIdx.z]);
@@ -106,8 +123,24 @@ __global__ __launch_bounds__(256) void flow_coef_kernel(FlowPtrs As, FlowPtrs Bs
     const float b = (bw(min(y + 1, h - 1), x) - bw(max(y - 1, 0), x)) * 0.5f;
     const float it = bc - A[(size_t)y * w + x];
     const float c = (it - a * f0.x) - b * f0.y;
-    const float r = 1.f / ((alpha2 + a * a) + b * b);      // one correctly rounded division (-fhip-fp32-correctly-rounded-divide-sqrt)
-    coef[(size_t)y * w + x] = make_float4(a, b, c, r);
+    if constexpr (!ROBUST) {
+        const float r = 1.f / ((alpha2 + a * a) + b * b);      // one correctly rounded division (-fhip-fp32-correctly-rounded-divide-sqrt)
+        coef[(size_t)y * w + x] = make_float4(a, b, c, r);
+    } else {
+        auto g_at = [&](int yy, int xx) {      // yy, xx inside the image
+            const float2 l = flow0[(size_t)yy * w + max(xx - 1, 0)], r = flow0[(size_t)yy * w + min(xx + 1, w - 1)];
+            const float2 u = flow0[(size_t)max(yy - 1, 0) * w + xx], d = flow0[(size_t)min(yy + 1, h - 1) * w + xx];
+            const float ux = (r.x - l.x) * 0.5f, vx = (r.y - l.y) * 0.5f, uy = (d.x - u.x) * 0.5f, vy = (d.y - u.y) * 0.5f;
+            return 1.f / sqrtf(((ux * ux + vx * vx) + (uy * uy + vy * vy)) + ra.eps2);      // sqrt and division correctly rounded, each
+        };
+        const float gp = g_at(y, x);
+        const float wl = 0.5f * (gp + g_at(y, max(x - 1, 0))), wr = 0.5f * (gp + g_at(y, min(x + 1, w - 1)));
+        const float wu = 0.5f * (gp + g_at(max(y - 1, 0), x)), wd = 0.5f * (gp + g_at(min(y + 1, h - 1), x));
+        const float S = (wl + wr) + (wu + wd);
+        const float r = 1.f / ((((alpha2 * S) * 0.25f) + a * a) + b * b);
+        coef[(size_t)y * w + x] = make_float4(a, b, c, r);
+        static_cast<float4*>(ra.wgts.p[blockIdx.z])[(size_t)y * w + x] = make_float4(wl / S, wr / S, wu / S, wd / S);
+    }
 }
 
 // ---- the sweeps, temporally blocked.
@@ -121,11 +154,24 @@ __global__ __launch_bounds__(256) void flow_coef_kernel(FlowPtrs As, FlowPtrs Bs
 // LDS traffic: a wave reads rows of 64 float2 -- 32 lanes x 8 B = one 256-B bank row per half wave, conflict-free for the centre, left /
 // right (shifted by one lane) and up / down (another row) taps alike.  Two barriers per sweep (all new values are formed in registers
 // before any is stored), one buffer: 32 KB per block leave four 256-thread blocks per CU next to ~110 VGPRs per lane.
+// ROBUST: the weighted mean of the edge-preserving smoothness.  The four normalised weights of a cell travel next to its coefficients, in
+// registers too: eight values per cell.  With 16 rows per lane that is 128 VGPRs of coefficients and the compiler's report shows 256
+// VGPRs + 46 AGPRs, one wave per SIMD; so this instantiation runs 512 lanes per block and 8 rows per lane (ty + 8 j) -- the same region,
+// the same LDS layout and barriers, half the cells per lane (the figures are in DESIGN.md).
 constexpr int SW_R = 64;           // region side
-constexpr int SW_ROWS = 16;        // rows per lane (256 lanes: 64 columns x 4)
 
-__global__ __launch_bounds__(256) void flow_sweep_kernel(FlowPtrs fins, FlowPtrs coefs, FlowPtrs fouts, int W, int H, int K, int n)
+template <bool ROBUST>
+struct SweepShape {
+    static constexpr int ROWS = ROBUST ? 8 : 16;       // rows per lane
+    static constexpr int TY = SW_R / ROWS;             // lanes per column: 64 columns x TY lanes
+    static constexpr int THREADS = SW_R * TY;          // 256 | 512
+};
+
+template <bool ROBUST>
+__global__ __launch_bounds__(SweepShape<ROBUST>::THREADS) void flow_sweep_kernel(FlowPtrs fins, FlowPtrs coefs, FlowPtrs fouts, int W, int H, int K, int n,
+                                                                                  SweepRobustArgs<ROBUST> ra)
 {
+    constexpr int SW_ROWS = SweepShape<ROBUST>::ROWS, TY = SweepShape<ROBUST>::TY;
     __shared__ float2 s[SW_R][SW_R];
     const float2* __restrict__ fin = static_cast<const float2*>(fins.p[blockIdx.z]);
     const float4* __restrict__ coef = static_cast<const float4*>(coefs.p[blockIdx.z]);
@@ -138,37 +184,45 @@ __global__ __launch_bounds__(256) void flow_sweep_kernel(FlowPtrs fins, FlowPtrs
     const int lxl = (gx > 0 && lx > 0) ? lx - 1 : lx;
     const int lxr = (gx < W - 1 && lx < SW_R - 1) ? lx + 1 : lx;
     float4 cf[SW_ROWS];
+    float4 wt[ROBUST ? SW_ROWS : 1];
     float2 nv[SW_ROWS];
 #pragma unroll
     for (int j = 0; j < SW_ROWS; ++j) {
-        const int ly = ty + 4 * j;
+        const int ly = ty + TY * j;
         const int cy = min(max(y0 + ly, 0), H - 1);
         const size_t idx = (size_t)cy * W + cx;
         cf[j] = coef[idx];
+        if constexpr (ROBUST) wt[j] = static_cast<const float4*>(ra.wgts.p[blockIdx.z])[idx];
         s[ly][lx] = fin[idx];
     }
     __syncthreads();
     for (int sweep = 0; sweep < n; ++sweep) {
 #pragma unroll
         for (int j = 0; j < SW_ROWS; ++j) {
-            const int ly = ty + 4 * j, gy = y0 + ly;
+            const int ly = ty + TY * j, gy = y0 + ly;
             const int lyu = (gy > 0 && ly > 0) ? ly - 1 : ly;
             const int lyd = (gy < H - 1 && ly < SW_R - 1) ? ly + 1 : ly;
             const float2 L = s[ly][lxl], R = s[ly][lxr], U = s[lyu][lx], D = s[lyd][lx];
-            const float ub = ((L.x + R.x) + (U.x + D.x)) * 0.25f;
-            const float vb = ((L.y + R.y) + (U.y + D.y)) * 0.25f;
+            float ub, vb;
+            if constexpr (ROBUST) {
+                ub = (wt[j].x * L.x + wt[j].y * R.x) + (wt[j].z * U.x + wt[j].w * D.x);
+                vb = (wt[j].x * L.y + wt[j].y * R.y) + (wt[j].z * U.y + wt[j].w * D.y);
+            } else {
+                ub = ((L.x + R.x) + (U.x + D.x)) * 0.25f;
+                vb = ((L.y + R.y) + (U.y + D.y)) * 0.25f;
+            }
             const float t = ((cf[j].x * ub + cf[j].y * vb) + cf[j].z) * cf[j].w;
             nv[j] = make_float2(ub - cf[j].x * t, vb - cf[j].y * t);
         }
         __syncthreads();
 #pragma unroll
-        for (int j = 0; j < SW_ROWS; ++j) s[ty + 4 * j][lx] = nv[j];
+        for (int j = 0; j < SW_ROWS; ++j) s[ty + TY * j][lx] = nv[j];
         __syncthreads();
     }
     if (lx < K || lx >= SW_R - K || gx >= W) return;      // (gx >= 0 here: lx >= K)
 #pragma unroll
     for (int j = 0; j < SW_ROWS; ++j) {
-        const int ly = ty + 4 * j, gy = y0 + ly;
+        const int ly = ty + TY * j, gy = y0 + ly;
         if (ly >= K && ly < SW_R - K && gy < H) fout[(size_t)gy * W + gx] = s[ly][lx];
     }
 }
@@ -205,17 +259,20 @@ int launch_flow_up(const FlowPtrs& coarse, int Wc, int Hc, const FlowPtrs& fine,
     return FAV_OK;
 }
 
-int launch_flow_coef(const FlowPtrs& A, const FlowPtrs& B, const FlowPtrs& flow0, float alpha, const FlowPtrs& coef, int items, int W, int H,
-                     hipStream_t st)
+// wgt == nullptr: the quadratic smoothness term (eps is not read); otherwise the edge weights of eps > 0 are written next to the coefficients
+int launch_flow_coef(const FlowPtrs& A, const FlowPtrs& B, const FlowPtrs& flow0, float alpha, float eps, const FlowPtrs& coef, const FlowPtrs* wgt,
+                     int items, int W, int H, hipStream_t st)
 {
     FAV_REQUIRE(size_ok(W, H) && items_ok(items), "flow coefficients: bad size %dx%d x %d", W, H, items);
-    hipLaunchKernelGGL(flow_coef_kernel, grid_64x4(W, H, items), dim3(256), 0, st, A, B, flow0, alpha * alpha, coef, W, H);
+    if (wgt) hipLaunchKernelGGL(flow_coef_kernel<true>, grid_64x4(W, H, items), dim3(256), 0, st, A, B, flow0, alpha * alpha, coef, W, H, CoefRobustArgs<true>{eps * eps, *wgt});
+    else hipLaunchKernelGGL(flow_coef_kernel<false>, grid_64x4(W, H, items), dim3(256), 0, st, A, B, flow0, alpha * alpha, coef, W, H, CoefRobustArgs<false>{});
     FAV_LAUNCH_CHECK("flow_coef_kernel");
     return FAV_OK;
 }
 
-// `iters` sweeps from *cur, ceil(iters / K) launches between *cur and *other (every item at once); on return *cur holds the results
-int launch_flow_sweeps(FlowPtrs* cur, FlowPtrs* other, const FlowPtrs& coef, int items, int iters, int K, int W, int H, hipStream_t st)
+// `iters` sweeps from *cur, ceil(iters / K) launches between *cur and *other (every item at once); on return *cur holds the results.
+// wgt: the normalised edge weights of the edge-preserving smoothness, or nullptr for the plain 4-neighbour mean
+int launch_flow_sweeps(FlowPtrs* cur, FlowPtrs* other, const FlowPtrs& coef, const FlowPtrs* wgt, int items, int iters, int K, int W, int H, hipStream_t st)
 {
     FAV_REQUIRE(size_ok(W, H) && items_ok(items) && iters >= 1 && K >= 1 && K <= FLOW_MAX_SWEEPS_PER_LAUNCH,
                 "flow sweeps: bad argument (%dx%d x %d, %d sweeps, %d per launch)", W, H, items, iters, K);
@@ -223,7 +280,8 @@ int launch_flow_sweeps(FlowPtrs* cur, FlowPtrs* other, const FlowPtrs& coef, int
     const dim3 grid((W + ti - 1) / ti, (H + ti - 1) / ti, items);
     FAV_REQUIRE(grid.y <= 65535, "flow sweeps: %d rows are too many", H);
     for (int done = 0; done < iters; done += K) {
-        hipLaunchKernelGGL(flow_sweep_kernel, grid, dim3(256), 0, st, *cur, coef, *other, W, H, K, std::min(K, iters - done));
+        if (wgt) hipLaunchKernelGGL(flow_sweep_kernel<true>, grid, dim3(SweepShape<true>::THREADS), 0, st, *cur, coef, *other, W, H, K, std::min(K, iters - done), SweepRobustArgs<true>{*wgt});
+        else hipLaunchKernelGGL(flow_sweep_kernel<false>, grid, dim3(SweepShape<false>::THREADS), 0, st, *cur, coef, *other, W, H, K, std::min(K, iters - done), SweepRobustArgs<false>{});
         FAV_LAUNCH_CHECK("flow_sweep_kernel");
         std::swap(*cur, *other);
     }

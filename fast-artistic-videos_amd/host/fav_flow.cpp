@@ -5,6 +5,7 @@
 //   fav_flow [options] <img1.ppm> <img2.ppm> <out.flo> [downscale]      the 4th argument is accepted and ignored
 //   fav_flow [options] -batch <list.txt>                                one "img1 img2 out.flo" per line: start-up is paid once
 //   options: -alpha <x>  -iters <n>  -warps <n>  -levels <n>  (0 = default, each)   -gpu <n>
+//            -eps <x>    edge-preserving smoothness (fav_flow_opts.smooth_eps; 0 = off, the default; 0.3 is the measured choice)
 //
 // The .flo is written under a temporary name and renamed into place, so a polling consumer never reads a partial file.
 #include <hip/hip_runtime.h>
@@ -26,7 +27,7 @@ namespace {
 
 [[noreturn]] void usage(const std::string& why)
 {
-    fprintf(stderr, "%s\nusage: fav_flow [-alpha x] [-iters n] [-warps n] [-levels n] [-gpu n] <img1.ppm> <img2.ppm> <out.flo> [downscale]\n"
+    fprintf(stderr, "%s\nusage: fav_flow [-alpha x] [-eps x] [-iters n] [-warps n] [-levels n] [-gpu n] <img1.ppm> <img2.ppm> <out.flo> [downscale]\n"
                     "       fav_flow [options] -batch <list.txt>      (one \"img1 img2 out.flo\" per line)\n", why.c_str());
     exit(2);
 }
@@ -58,7 +59,7 @@ bool parse_int(const char* s, int* out)
 
 int main(int argc, char** argv)
 {
-    fav_flow_opts fo = {0, 0, 0, 0.f, 0};
+    fav_flow_opts fo = {0, 0, 0, 0.f, 0, 0.f};
     int gpu = 0;
     std::string batch;
     std::vector<std::string> pos;
@@ -70,6 +71,7 @@ int main(int argc, char** argv)
             bool ok = true;
             if (k == "-batch") batch = v;
             else if (k == "-alpha") { char* end = nullptr; fo.alpha = strtof(v, &end); ok = end != v && *end == '\0'; }
+            else if (k == "-eps") { char* end = nullptr; fo.smooth_eps = strtof(v, &end); ok = end != v && *end == '\0'; }
             else if (k == "-iters") ok = parse_int(v, &fo.iters);
             else if (k == "-warps") ok = parse_int(v, &fo.warps);
             else if (k == "-levels") ok = parse_int(v, &fo.levels);

@@ -83,6 +83,7 @@ EXPORTS = [
     "fav_flow_workspace_bytes", "fav_flow_rgb8", "fav_flow_grey_f32", "fav_flow_down_f32", "fav_flow_up_f32", "fav_flow_coefficients_f32",
     "fav_flow_sweeps_f32", "fav_stream_next_frame_estimate",
     "fav_flow_pairs_workspace_bytes", "fav_flow_pairs_rgb8",
+    "fav_flow_coefficients_robust_f32", "fav_flow_sweeps_robust_f32",
     "fav_vr_equi_to_faces_rgb8",
 ]
 
@@ -196,7 +197,8 @@ def scale_bicubic(x, hd: int, wd: int):
 
 # ------------------------------------------------------------------------------------------------ optical flow
 class _FlowOpts(C.Structure):
-    _fields_ = [("levels", C.c_int), ("warps", C.c_int), ("iters", C.c_int), ("alpha", C.c_float), ("sweeps_per_launch", C.c_int)]
+    _fields_ = [("levels", C.c_int), ("warps", C.c_int), ("iters", C.c_int), ("alpha", C.c_float), ("sweeps_per_launch", C.c_int),
+                ("smooth_eps", C.c_float)]
 
 
 def _flow_opts(opts) -> "_FlowOpts":
@@ -204,7 +206,7 @@ def _flow_opts(opts) -> "_FlowOpts":
     if unknown:
         raise FavError(f"unknown flow option(s) {sorted(unknown)}")
     return _FlowOpts(int(opts.get("levels", 0)), int(opts.get("warps", 0)), int(opts.get("iters", 0)), float(opts.get("alpha", 0.0)),
-                     int(opts.get("sweeps_per_launch", 0)))
+                     int(opts.get("sweeps_per_launch", 0)), float(opts.get("smooth_eps", 0.0)))
 
 
 def flow_workspace_bytes(w: int, h: int, **opts) -> int:
@@ -218,7 +220,7 @@ def flow_workspace_bytes(w: int, h: int, **opts) -> int:
 
 def flow_rgb8(a, b, **opts):
     """fav_flow_rgb8: the flow w "from a to b", b(p + w(p)) ~ a(p), of two u8 [H][W][3] frames -> .flo payload [H][W][2] (u, v).
-    opts: levels, warps, iters, alpha, sweeps_per_launch (0 / absent = default)."""
+    opts: levels, warps, iters, alpha, sweeps_per_launch (0 / absent = default); smooth_eps > 0 turns the edge-preserving smoothness on."""
     torch = _torch()
     if not (a.is_cuda and b.is_cuda and a.dtype == torch.uint8 and b.dtype == torch.uint8 and a.is_contiguous() and b.is_contiguous() and
             a.dim() == 3 and a.shape[2] == 3 and a.shape == b.shape):
@@ -247,7 +249,7 @@ def flow_pairs_workspace_bytes(w: int, h: int, n_pairs: int, **opts) -> int:
 def flow_pairs(prev_list, cur_list, opts=None):
     """fav_flow_pairs_rgb8: both flows of every (prev[k], cur[k]) in one batched call -> (backward_list, forward_list), .flo payloads
     [H][W][2]: backward[k] is flow_rgb8(cur[k], prev[k]), forward[k] is flow_rgb8(prev[k], cur[k]), bit for bit.
-    opts: a dict of levels, warps, iters, alpha, sweeps_per_launch (0 / absent = default)."""
+    opts: a dict of levels, warps, iters, alpha, sweeps_per_launch, smooth_eps (0 / absent = default)."""
     torch = _torch()
     opts = dict(opts or {})
     n = len(prev_list)
@@ -302,6 +304,25 @@ def flow_sweeps(flow0, coef, iters: int, sweeps_per_launch: int = 0):
     h, w, _ = flow0.shape
     out, scratch = torch.empty_like(flow0), torch.empty_like(flow0)
     _check(lib().fav_flow_sweeps_f32(_p(flow0), _p(coef), iters, sweeps_per_launch, _p(out), _p(scratch), w, h, _stream()))
+    return out
+
+
+def flow_coefficients_robust(a_grey, b_grey, flow0, alpha: float = 5.0, smooth_eps: float = 0.3):
+    """one warp of the edge-preserving smoothness -> (coef [H][W][4] = (a, b, c, r), weights [H][W][4] = (n_l, n_r, n_u, n_d))"""
+    torch = _torch(); _chk_f32(a_grey, "a_grey"); _chk_f32(b_grey, "b_grey"); _chk_f32(flow0, "flow0")
+    h, w = a_grey.shape
+    coef = torch.empty((h, w, 4), dtype=torch.float32, device=a_grey.device)
+    weights = torch.empty((h, w, 4), dtype=torch.float32, device=a_grey.device)
+    _check(lib().fav_flow_coefficients_robust_f32(_p(a_grey), _p(b_grey), _p(flow0), C.c_float(alpha), C.c_float(smooth_eps), _p(coef), _p(weights),
+                                                  w, h, _stream()))
+    return coef, weights
+
+
+def flow_sweeps_robust(flow0, coef, weights, iters: int, sweeps_per_launch: int = 0):
+    torch = _torch(); _chk_f32(flow0, "flow0"); _chk_f32(coef, "coef"); _chk_f32(weights, "weights")
+    h, w, _ = flow0.shape
+    out, scratch = torch.empty_like(flow0), torch.empty_like(flow0)
+    _check(lib().fav_flow_sweeps_robust_f32(_p(flow0), _p(coef), _p(weights), iters, sweeps_per_launch, _p(out), _p(scratch), w, h, _stream()))
     return out
 
 

@@ -110,8 +110,17 @@ int fav_scale_bicubic_f32(const float* src, float* dst, int C, int Hs, int Ws, i
  * runs on a tile in LDS, 1..16: the result is bit-identical for every value); opts_host may be NULL.
  * workspace: fav_flow_workspace_bytes(W, H, opts) bytes of device memory, 16-byte aligned, owned by the caller, private to the call until
  * the stream has passed it (0 with a message: bad size or options).  The call allocates nothing and does not synchronise.
- * W, H >= 16; anything else, or an option out of range, is FAV_EINVAL. */
-typedef struct fav_flow_opts { int levels; int warps; int iters; float alpha; int sweeps_per_launch; } fav_flow_opts;
+ * W, H >= 16; anything else, or an option out of range, is FAV_EINVAL.
+ * smooth_eps = eps > 0 makes the smoothness term EDGE-PRESERVING ("Edge-preserving smoothness"; restated by
+ * tests/util/flow_robust_model.py): every warp weights the four neighbours of a pixel with the lagged diffusivity
+ * g = 1 / sqrt(|grad u0|^2 + |grad v0|^2 + eps^2) of its starting flow, so the flow is no longer smeared across motion boundaries; with
+ * g = 1 it is the quadratic term, and alpha keeps its meaning.  alpha 0 then means 5; 0.3 is the measured choice for eps.  0 = off: the
+ * estimator, its launches and its workspace are what they were.  Negative, non-finite, or outside 1e-6 .. 1e6: FAV_EINVAL.  The workspace
+ * grows by one weight image of 16 bytes per pixel and flow.  fav_flow_rgb8, fav_flow_pairs_rgb8 and fav_stream_next_frame_estimate honour
+ * the field.
+ * THE STRUCT GREW by this trailing field (24 bytes, was 20): a caller compiled against the earlier header passes a shorter struct and must
+ * be rebuilt; every in-tree user (bin/, python/fav_amd) is. */
+typedef struct fav_flow_opts { int levels; int warps; int iters; float alpha; int sweeps_per_launch; float smooth_eps; } fav_flow_opts;
 size_t fav_flow_workspace_bytes(int W, int H, const fav_flow_opts* opts_host);
 int fav_flow_rgb8(const uint8_t* a_rgb_hwc, const uint8_t* b_rgb_hwc, int W, int H, const fav_flow_opts* opts_host,
                   float* flow_out, void* workspace, size_t workspace_bytes, fav_hipstream_t stream);
@@ -130,7 +139,9 @@ int fav_flow_pairs_rgb8(const uint8_t* const* prev_rgb_hwc, const uint8_t* const
 /* the estimator's stages on their own (operator-level entries, as fav_scale_bicubic_f32 is one): the grey image [H][W]; one pyramid step
  * to ceil(W/2) x ceil(H/2); the x2 flow upsampling between two level sizes; the coefficients (a, b, c, r) of one warp around flow0,
  * [H][W][4], 16-byte aligned; `iters` Jacobi sweeps from flow0 into flow_out (scratch: a second flow buffer [H][W][2]; flow0 is not
- * written and must be neither of the two). */
+ * written and must be neither of the two).
+ * The _robust_ pair is one warp of the edge-preserving smoothness (smooth_eps > 0): the coefficients (r with the weights' sum in it) plus
+ * the four normalised edge weights (n_left, n_right, n_up, n_down), [H][W][4], 16-byte aligned, and the sweeps that use them. */
 int fav_flow_grey_f32(const uint8_t* rgb_hwc, float* grey, int W, int H, fav_hipstream_t stream);
 int fav_flow_down_f32(const float* src, float* dst, int W, int H, fav_hipstream_t stream);
 int fav_flow_up_f32(const float* coarse_flow, int Wc, int Hc, float* fine_flow, int W, int H, fav_hipstream_t stream);
@@ -138,6 +149,10 @@ int fav_flow_coefficients_f32(const float* a_grey, const float* b_grey, const fl
                               fav_hipstream_t stream);
 int fav_flow_sweeps_f32(const float* flow0, const float* coef, int iters, int sweeps_per_launch, float* flow_out, float* scratch,
                         int W, int H, fav_hipstream_t stream);
+int fav_flow_coefficients_robust_f32(const float* a_grey, const float* b_grey, const float* flow0, float alpha, float smooth_eps, float* coef,
+                                     float* weights, int W, int H, fav_hipstream_t stream);
+int fav_flow_sweeps_robust_f32(const float* flow0, const float* coef, const float* weights, int iters, int sweeps_per_launch, float* flow_out,
+                               float* scratch, int W, int H, fav_hipstream_t stream);
 
 /* ---- A6/A7: VGG preprocessing + 7-channel input assembly --------------------------------------
  * Replaces run_next_image's input construction (fast_artistic_video_core.lua:161-171) and the first

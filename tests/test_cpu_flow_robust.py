@@ -1,0 +1,204 @@
+"""Host side of the estimator's edge-preserving smoothness (fav_flow_opts.smooth_eps; no GPU needed): the premise that it lowers the error
+on a scene with two motions, the numpy model's normalisation, the workspace sizes, the argument checks, the flags of the three executables
+and the resource report of the new sweep instantiation."""
+import ctypes as C
+import json
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "util"))
+import flow_model as M  # noqa: E402
+import flow_robust_model as R  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "fast-artistic-videos_amd")
+BIN = os.path.join(PKG, "bin")
+FLOW, STYLIZE, STYLIZE_VR = (os.path.join(BIN, n) for n in ("fav_flow", "fav_stylize", "fav_stylize_vr"))
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+
+def _run(args):
+    return subprocess.run(args, capture_output=True, text=True, timeout=60)
+
+
+# ------------------------------------------------------------------------------------------------ 1. the premise
+@pytest.mark.parametrize("h,w,seed", R.SCENES)
+def test_robust_smoothness_lowers_the_error_on_two_motions(h, w, seed):
+    """A rectangle moving by (-3, +1.5) px over a background moving by (+2, 0) px (flow_robust_model.two_motion_scene); mean endpoint
+    error of the fp64 models over the non-occluded pixels, 12 px of frame border excluded, default warps (3) and iters (30).
+    Measured, quadratic (alpha 15) -> robust (alpha 5, eps 0.3): 96x128 seed 1: 0.997 -> 0.628 (0.63); seed 2: 1.144 -> 0.727 (0.64);
+    150x203 seed 1: 0.656 -> 0.417 (0.64); seed 2: 0.628 -> 0.444 (0.71).  Required: robust <= 0.8 x quadratic."""
+    A, B, truth, valid = R.two_motion_scene(h, w, seed)
+    assert A.shape == (h, w, 3) and A.dtype == np.uint8 and 0 < (~valid).mean() < 0.05
+    quad = R.scene_epe(M.flow(A, B, dtype=np.float64), truth, valid)
+    robust = R.scene_epe(R.flow(A, B, dtype=np.float64), truth, valid)
+    print(f"{h}x{w} seed {seed}: quadratic {quad:.3f} px, robust {robust:.3f} px, ratio {robust / quad:.2f}")
+    assert robust <= 0.8 * quad
+
+
+def test_robust_smoothness_does_not_hurt_a_constant_shift():
+    """flow_model.shifted_pair(1), one motion in the whole frame: measured 0.0656 px (quadratic) -> 0.0504 px (robust)"""
+    A, B, w = M.shifted_pair(1)
+    quad = M.interior_epe(M.flow(A, B, dtype=np.float64), w)
+    robust = M.interior_epe(R.flow(A, B, dtype=np.float64), w)
+    print(f"constant shift: quadratic {quad:.4f} px, robust {robust:.4f} px")
+    assert robust <= quad
+
+
+# ------------------------------------------------------------------------------------------------ 2. the model's normalisation
+def test_model_with_constant_diffusivity_is_the_quadratic_estimator():
+    """g == 1: w_q = 1, S = 4, n_q = 1/4, r = 1 / (alpha^2 + a^2 + b^2).  A weight of exactly 1/4 on each neighbour distributes over the
+    sum without a rounding, so the fp64 flows agree to rounding (measured: bit for bit); a constant g = 4 is alpha doubled."""
+    A, B = M.warped_pair(64, 64, 11)
+    want = M.flow(A, B, dtype=np.float64)
+    got = R.flow(A, B, alpha=M.ALPHA, dtype=np.float64, g=lambda h, w: np.ones((h, w)))
+    assert np.abs(got - want).max() <= 1e-12 * max(1.0, np.abs(want).max())
+    got4 = R.flow(A, B, alpha=M.ALPHA, dtype=np.float64, g=lambda h, w: np.full((h, w), 4.0))
+    assert np.abs(got4 - M.flow(A, B, alpha=2 * M.ALPHA, dtype=np.float64)).max() <= 1e-12 * max(1.0, np.abs(want).max())
+    f0 = np.random.default_rng(3).standard_normal((19, 27, 2))
+    _, n = R.coefficients(M.grey(A[:19, :27], np.float64), M.grey(B[:19, :27], np.float64), f0, dtype=np.float64)
+    assert np.abs(n.sum(-1) - 1).max() < 1e-15 and (n > 0).all()          # the stored weights are a convex combination
+    g = R.diffusivity(f0, 0.3, np.float64)
+    assert g.max() <= 1 / 0.3 and np.allclose(R.diffusivity(np.zeros((8, 9, 2)), 0.3, np.float64), 1 / 0.3)
+
+
+def test_model_sweeps_compose():
+    rng = np.random.default_rng(5)
+    f0 = rng.standard_normal((19, 27, 2)).astype(np.float32)
+    from fav_amd import synth
+    A, B = M.grey(synth.smooth_frame(19, 27, 1)), M.grey(synth.smooth_frame(19, 27, 2))
+    coef, n = R.coefficients(A, B, f0)
+    step = f0
+    for _ in range(7):
+        step = R.sweeps(step, coef, n, 1)
+    assert np.array_equal(R.sweeps(f0, coef, n, 7), step)
+
+
+# ------------------------------------------------------------------------------------------------ 3. workspace, argument checks, symbols
+def _r256(n):
+    return (n + 255) // 256 * 256
+
+
+def test_workspace_grows_by_the_weight_image_only_when_asked(favlib):
+    for (h, w) in M.SIZES + [(720, 1280)]:
+        lv = M.level_sizes(h, w)
+        # the formulas of tests/test_cpu_flow.py and tests/test_cpu_flow_pairs.py: what the sizes were before the field existed
+        single = sum(2 * _r256(lh * lw * 4) + (2 if l else 1) * _r256(lh * lw * 8) for l, (lh, lw) in enumerate(lv)) + _r256(h * w * 16)
+        assert favlib.flow_workspace_bytes(w, h) == favlib.flow_workspace_bytes(w, h, smooth_eps=0.0) == single
+        assert favlib.flow_workspace_bytes(w, h, smooth_eps=0.3) == single + _r256(h * w * 16)
+        for n in (1, 2, 6):
+            pairs = sum(2 * n * _r256(lh * lw * 4) + 2 * n * (2 if l else 1) * _r256(lh * lw * 8) for l, (lh, lw) in enumerate(lv)) + 2 * n * _r256(h * w * 16)
+            assert favlib.flow_pairs_workspace_bytes(w, h, n) == favlib.flow_pairs_workspace_bytes(w, h, n, smooth_eps=0.0) == pairs
+            assert favlib.flow_pairs_workspace_bytes(w, h, n, smooth_eps=0.3) == pairs + 2 * n * _r256(h * w * 16)
+
+
+def test_bad_eps_is_refused_before_the_device(favlib):
+    L = favlib.lib()
+    assert C.sizeof(favlib._FlowOpts) == 24
+    hdr = open(os.path.join(ROOT, "include", "fav.h")).read()
+    assert "int sweeps_per_launch; float smooth_eps; } fav_flow_opts;" in hdr
+    for bad in (-0.3, -1e-9, float("nan"), float("inf"), float("-inf"), 1e-30, 1e7):
+        o = favlib._flow_opts({"smooth_eps": bad})
+        assert L.fav_flow_workspace_bytes(64, 64, C.cast(C.pointer(o), C.c_void_p)) == 0 and b"smooth_eps must be" in L.fav_last_error(), bad
+        assert L.fav_flow_pairs_workspace_bytes(64, 64, 2, C.cast(C.pointer(o), C.c_void_p)) == 0 and b"smooth_eps must be" in L.fav_last_error(), bad
+        assert L.fav_flow_rgb8(C.c_void_p(256), C.c_void_p(256), 64, 64, C.byref(o), C.c_void_p(256), C.c_void_p(256), C.c_size_t(1 << 30), None) == -1
+        assert b"smooth_eps must be" in L.fav_last_error()
+        with pytest.raises(favlib.FavError, match="smooth_eps must be"):
+            favlib.flow_workspace_bytes(64, 64, smooth_eps=bad)
+        assert L.fav_flow_coefficients_robust_f32(C.c_void_p(256), C.c_void_p(256), C.c_void_p(256), C.c_float(5.0), C.c_float(bad), C.c_void_p(256),
+                                                  C.c_void_p(512), 64, 64, None) == -1 and b"smooth_eps must be" in L.fav_last_error()
+    o = favlib._flow_opts({"smooth_eps": 0.3, "alpha": -1.0})
+    assert L.fav_flow_workspace_bytes(64, 64, C.cast(C.pointer(o), C.c_void_p)) == 0 and b"alpha must be" in L.fav_last_error()
+    with pytest.raises(favlib.FavError, match="unknown flow option"):
+        favlib.flow_workspace_bytes(64, 64, smooth_epsilon=0.3)
+    # the stage entries' own checks
+    assert L.fav_flow_coefficients_robust_f32(None, None, None, C.c_float(5.0), C.c_float(0.3), None, None, 64, 64, None) == -1 and b"bad argument" in L.fav_last_error()
+    assert L.fav_flow_coefficients_robust_f32(C.c_void_p(256), C.c_void_p(256), C.c_void_p(256), C.c_float(5.0), C.c_float(0.3), C.c_void_p(256),
+                                              C.c_void_p(264), 64, 64, None) == -1 and b"16-byte aligned" in L.fav_last_error()
+    assert L.fav_flow_sweeps_robust_f32(C.c_void_p(256), C.c_void_p(256), None, 3, 0, C.c_void_p(256), C.c_void_p(256), 64, 64, None) == -1
+    assert b"fav_flow_sweeps_robust_f32: bad argument" in L.fav_last_error()
+    assert L.fav_flow_sweeps_robust_f32(C.c_void_p(256), C.c_void_p(256), C.c_void_p(256), 3, 17, C.c_void_p(256), C.c_void_p(256), 64, 64, None) == -1
+    assert b"sweeps_per_launch 0 (default) .. 16" in L.fav_last_error()
+    import torch
+    if not torch.cuda.is_available():      # valid arguments, no device: FAV_ENODEVICE before anything is dereferenced
+        o = favlib._flow_opts({"smooth_eps": 0.3})
+        nb = favlib.flow_workspace_bytes(64, 64, smooth_eps=0.3)
+        assert L.fav_flow_rgb8(C.c_void_p(256), C.c_void_p(256), 64, 64, C.byref(o), C.c_void_p(256), C.c_void_p(256), C.c_size_t(nb), None) == -6
+        assert L.fav_flow_rgb8(C.c_void_p(256), C.c_void_p(256), 64, 64, C.byref(o), C.c_void_p(256), C.c_void_p(256), C.c_size_t(nb - 1), None) == -1
+        assert L.fav_flow_sweeps_robust_f32(C.c_void_p(256), C.c_void_p(256), C.c_void_p(256), 3, 0, C.c_void_p(256), C.c_void_p(256), 64, 64, None) == -6
+
+
+def test_robust_stage_entries_are_exported_and_bound(favlib):
+    out = subprocess.run(["nm", "-D", "--defined-only", favlib.LIB_PATH], capture_output=True, text=True).stdout
+    defined = {l.split()[-1] for l in out.splitlines() if l.strip()}
+    hdr = open(os.path.join(ROOT, "include", "fav.h")).read()
+    for name in ("fav_flow_coefficients_robust_f32", "fav_flow_sweeps_robust_f32"):
+        assert name in defined and name in favlib.EXPORTS and name + "(" in hdr, name
+    assert callable(favlib.flow_coefficients_robust) and callable(favlib.flow_sweeps_robust)
+
+
+# ------------------------------------------------------------------------------------------------ 4. the flags
+def test_fav_flow_eps_flag(favlib, tmp_path):
+    r = _run([FLOW])
+    assert r.returncode == 2 and "[-eps x]" in r.stderr
+    r = _run([FLOW, "-eps", "soft", "a.ppm", "b.ppm", "c.flo"])
+    assert r.returncode == 2 and "bad value for -eps" in r.stderr
+    r = _run([FLOW, "-eps", "-0.3", "a.ppm", "b.ppm", "c.flo"])          # the library's range check, before any file or device
+    assert r.returncode == 1 and "smooth_eps must be" in r.stderr
+    r = _run([FLOW, "-eps", "0.3", str(tmp_path / "a.ppm"), str(tmp_path / "b.ppm"), str(tmp_path / "c.flo")])      # accepted
+    assert r.returncode == 1 and "usage" not in r.stderr and ("no HIP device" in r.stderr or "Could not open" in r.stderr)
+
+
+def test_fav_stylize_flow_eps_flag(favlib):
+    base = [STYLIZE, "-input_pattern", "v/f_%05d.ppm", "-model_vid", "m.t7", "-output_prefix", "o/out", "-estimate_flow", "1"]
+    r = _run(base + ["-flow_eps", "0.3", "-flow_alpha", "4", "-dry_run", "1"])
+    assert r.returncode == 0, r.stderr
+    assert json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])["streams"][0]["flow_pattern"] == ""
+    r = _run(base + ["-dry_run", "1"])                                        # the default is 0: nothing to ask for
+    assert r.returncode == 0, r.stderr
+    for bad in ("-0.3", "nan", "1e9"):
+        r = _run(base + ["-flow_eps", bad, "-dry_run", "1"])
+        assert r.returncode != 0 and "-flow_eps" in r.stderr and "smooth_eps must be" in r.stderr, (bad, r.stderr)
+
+
+def test_fav_stylize_vr_flow_eps_flag(favlib):
+    base = [STYLIZE_VR, "-input_equi_pattern", "v/e_%05d.ppm", "-model_vid", "m.t7", "-output_prefix", "o/out"]
+    ok = _run(base + ["-dry_run", "1"])
+    r = _run(base + ["-flow_eps", "0.3", "-dry_run", "1"])
+    assert r.returncode == ok.returncode and "unknown option" not in r.stderr and "smooth_eps" not in r.stderr, r.stderr
+    r = _run(base + ["-flow_eps", "-1", "-dry_run", "1"])
+    assert r.returncode != 0 and "-flow_eps" in r.stderr and "smooth_eps must be" in r.stderr, r.stderr
+
+
+# ------------------------------------------------------------------------------------------------ 5. the resource gate
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+def test_robust_sweep_instantiation_does_not_spill(tmp_path):
+    """the compiler's kernel-resource-usage remarks for kernels_flow.hip with the Makefile's flags (as tests/test_cpu_kernel_budget.py
+    reads them): the instantiation that carries eight values per cell keeps them in registers -- scratch 0 -- at two waves per SIMD or
+    better and with the 32 KB LDS tile of the plain one, whose own figures (176 VGPRs, occupancy 2: DESIGN.md) do not move."""
+    p = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fhip-fp32-correctly-rounded-divide-sqrt", "-ffp-contract=off",
+                        "--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage", "-I", os.path.join(ROOT, "include"),
+                        os.path.join(PKG, "csrc", "kernels_flow.hip"), "-o", str(tmp_path / "flow.o")], capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-2000:]
+    usage, cur = {}, None
+    for line in p.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            cur = usage.setdefault(m.group(1), {})
+        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
+        if m and cur is not None:
+            cur[m.group(1).split(" ")[0]] = int(m.group(2))
+    robust = [u for k, u in usage.items() if "flow_sweep_kernelILb1E" in k]
+    plain = [u for k, u in usage.items() if "flow_sweep_kernelILb0E" in k]
+    assert len(robust) == 1 and len(plain) == 1, sorted(usage)
+    print("robust", robust[0], "plain", plain[0])
+    assert robust[0]["ScratchSize"] == 0 and robust[0]["AGPRs"] == 0 and robust[0]["VGPRs"] <= 256 and robust[0]["Occupancy"] >= 2 and robust[0]["LDS"] == 32768, robust
+    assert plain[0]["ScratchSize"] == 0 and plain[0]["VGPRs"] <= 176 and plain[0]["Occupancy"] == 2 and plain[0]["LDS"] == 32768, plain
+    for k, u in usage.items():
+        if "flow_coef_kernel" in k:
+            assert u["ScratchSize"] == 0, (k, u)
