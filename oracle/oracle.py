@@ -282,11 +282,12 @@ def bf16_round(a: np.ndarray) -> np.ndarray:
 
 
 def _bf16_conv(L: dict) -> bool:
-    """the convolutions the fast mode touches: 3x3, stride 1, 32..256 input channels in multiples of 32, <= 128 outputs
-    padded to 64 or 128 (= conv3_halo_eligible in the product)"""
+    """the convolutions the fast mode touches: 3x3, stride 1, 32..256 input channels, 64 or 128 outputs (= conv3_halo_eligible in the
+    product) -- both counts as the product executes them, padded to the next power of two with zero filters (pad_channel_counts: 48
+    filters run as 64, 96 as 128)"""
     cout, cin, kh, kw = L["w"].shape
-    cp = (cout + 31) // 32 * 32
-    return kh == 3 and kw == 3 and L["stride"] == 1 and cin % 32 == 0 and 32 <= cin <= 256 and cp in (64, 128)
+    cp, ci = 1 << max(cout - 1, 0).bit_length(), 1 << max(cin - 1, 0).bit_length()
+    return kh == 3 and kw == 3 and L["stride"] == 1 and 32 <= ci <= 256 and cp in (64, 128)
 
 
 def net_forward(layers: List[dict], x: np.ndarray, trace: Optional[list] = None, bf16_ops: bool = False) -> np.ndarray:

@@ -42,11 +42,13 @@ def _t64(a):
     return torch.from_numpy(np.ascontiguousarray(a, np.float64))
 
 
-def forward64(layers, x, trace=None, convs=None):
+def forward64(layers, x, trace=None, convs=None, conv_ins=None):
     """the layer list of t7.extract_layers in float64; x: torch [C][H][W] float64.  trace: (type, tensor) per top-level layer;
-    convs: the raw output of every convolution, residual branches included, in the network's convolution order"""
+    convs: the raw output of every convolution, residual branches included, in the network's convolution order; conv_ins: what each of
+    them reads (before its own zero padding), in the same order"""
     for L in layers:
         t = L["type"]
+        if conv_ins is not None and t in ("conv", "fullconv"): conv_ins.append(x)
         if t == "pad":
             x = F.pad(x[None], (L["l"], L["r"], L["t"], L["b"]), mode="replicate" if L.get("mode") == "replicate" else "reflect")[0]
         elif t == "conv":
@@ -62,7 +64,7 @@ def forward64(layers, x, trace=None, convs=None):
         elif t == "relu":
             x = torch.clamp(x, min=0)
         elif t == "res":
-            y = forward64(L["block"], x, convs=convs)
+            y = forward64(L["block"], x, convs=convs, conv_ins=conv_ins)
             s = L["shave"]
             x = y + (x[:, s:x.shape[1] - s, s:x.shape[2] - s] if s else x)
         elif t == "up":
@@ -309,6 +311,148 @@ def _norm_regimes(model, arch, index_of_L, x, kw, tmp):
     return [regime_of(c) for c in range(C)]
 
 
+# ------------------------------------------------------------------------------------------------ bf16-exact probes
+# fav_net_set_precision(1) runs the 3x3 stride-1 layers on conv3_halo_bf16_kernel: activations (after the pending norm / ReLU stages) and
+# weights rounded to bf16, fp32 accumulation.  A probe whose rounding is the IDENTITY holds that kernel to the float64 convolution at the
+# ordinary per-kernel tolerances -- a bf16 x bf16 product is exact in fp32, what remains is the accumulation:
+#   * input: seeded integers in [-8, 8];
+#   * every convolution in front of L's last one (the first layer; a block's first convolution): two taps of +-1 per filter and an
+#     integer bias in [-2, 2] -- its float64 output is an integer or a dyadic of few bits, and fp32 arithmetic on it is exact;
+#   * every norm in front of L: evaluate-mode BatchNorm (a pending stage, net.cpp `case L_BN`) with mean 0, var 1 - eps, per channel
+#     gamma from BF16_SCALES (rotating, so that channels c and c + 32 differ) and an integer beta that centres the channel -- chosen so
+#     that relu(gamma z + beta) is bf16-representable everywhere (asserted: probe_checkpoints, is_bf16).  The library's fp32 scale is
+#     gamma / sqrt(fl32(1 - eps) + eps) = gamma (1 - 1.5e-8), which rounds to gamma itself; the reference runs these norms with the
+#     intended numbers (var 1, eps 0).  What the kernel rounds on the GPU then differs from a bf16 number by a few fp32 ulps at most
+#     (the scale to within an ulp, a producer kernel's own rounding): 2^-22 relative, against half a bf16 ulp = 2^-9 -- the kernel's own
+#     round-to-nearest absorbs it, no rounding can flip (a value that is exactly 0 in the reference may come out ~1e-5 instead of 0:
+#     that is an absolute error of 1e-5 x a weight, far below the bound);
+#   * the norm behind L: BatchNorm ("raw") or InstanceNorm with gamma 1, beta B ("stats": the bf16 kernel's partials / counts epilogue
+#     through in_finalize) -- swapped into the model tree, so the stats variant is a mixed checkpoint;
+#   * the weights of L's last convolution: as drawn, NOT bf16 numbers.  The reference convolves with bf16_round(w) -- the host's
+#     round-to-nearest-even copy (net_model.cpp, wgt16) is under test, and the probe fails if the fp32 kernel ran instead.
+BF16_SCALES = (0.5, -1.0, 2.0, 1.5, -0.5, 1.0, -2.0)
+
+
+def is_bf16(a):
+    """every value of a float64 array is a bf16 number"""
+    import oracle
+    a = np.asarray(a, np.float64)
+    f = a.astype(np.float32)
+    return bool(np.all(f.astype(np.float64) == a) and np.all(oracle.bf16_round(f) == f))
+
+
+def conv_layers(layers, out=None):
+    """the convolution layers of an extract_layers list in the network's convolution order (forward64's `convs`)"""
+    out = [] if out is None else out
+    for L in layers:
+        if L["type"] in ("conv", "fullconv"): out.append(L)
+        elif L["type"] == "res": conv_layers(L["block"], out)
+    return out
+
+
+def front_norms(layers, conv0, n_convs):
+    """the BatchNorm layers whose output a convolution under test reads (through ReLU / upsampling / padding): every top-level one in
+    front of L, and the one between the two convolutions of a block"""
+    first = conv_layers(layers)[conv0]
+    out = []
+    for L in layers:
+        if L is first: return out
+        if L["type"] == "bn": out.append(L)
+        if L["type"] == "res" and any(q is first for q in L["block"]):
+            assert n_convs == 2
+            return out + [q for q in L["block"][:-1] if q["type"] == "bn"]
+    raise ValueError("convolution %d not found" % conv0)
+
+
+def bf16_reference_layers(layers, conv0, n_convs):
+    """what the float64 reference of a bf16 probe runs: the checkpoint's layers with the weights of L's convolutions rounded to bf16
+    (nearest even) and the norms in front of them with the intended scale (var 1, eps 0 instead of var fl32(1 - eps), eps)"""
+    import copy
+    import oracle
+    ls = copy.deepcopy(layers)
+    for L in conv_layers(ls)[conv0:conv0 + n_convs]: L["w"] = oracle.bf16_round(L["w"])
+    for L in front_norms(ls, conv0, n_convs):
+        assert np.all(L["mean"] == 0) and np.all(L["var"] == np.float32(1.0 - L["eps"]))
+        L["var"] = np.ones_like(L["var"]); L["eps"] = 0.0
+    return ls
+
+
+def bf16_conv_inputs(layers, x):
+    """float64: what every convolution reads, in the network's convolution order"""
+    ins = []
+    forward64(layers, _t64(x), conv_ins=ins)
+    return [a.numpy() for a in ins]
+
+
+def _sparse_conv(mod, rng):
+    w = np.zeros_like(mod.fields["weight"])
+    cout, cin, k, _ = w.shape
+    for o in range(cout):
+        for pos in rng.choice(cin * k * k, size=2, replace=False):
+            w[o].reshape(-1)[pos] = rng.choice((-1.0, 1.0))
+    mod.fields["weight"] = w
+    mod.fields["bias"] = rng.integers(-2, 3, size=cout).astype(np.float32)
+
+
+def _fit_norm(bn, z):
+    """gamma / beta of an evaluate-mode BatchNorm in front of L; z: float64 [C][H][W], what it reads"""
+    C = z.shape[0]
+    assert bn.cls == "nn.SpatialBatchNormalization" and bn.fields["weight"].shape == (C,)
+    g, b = np.zeros((C,), np.float32), np.zeros((C,), np.float32)
+    for c in range(C):
+        for t in range(len(BF16_SCALES)):
+            s = BF16_SCALES[(c + t) % len(BF16_SCALES)]
+            sh = float(c % 5 - 1 - round(s * float(np.median(z[c]))))
+            v = np.maximum(z[c] * s + sh, 0.0)
+            if is_bf16(v) and v.max() > 0: break
+        else:
+            raise AssertionError("no scale keeps channel %d bf16-representable" % c)
+        g[c], b[c] = s, sh
+    bn.fields["weight"], bn.fields["bias"] = g, b
+    bn.fields["running_mean"] = np.zeros((C,), np.float32)
+    bn.fields["running_var"] = np.full((C,), 1.0 - float(bn.fields["eps"]), np.float32)
+
+
+def _bf16_front(model, arch, index_of_L, variant, seed, x_shape, kw, tmp):
+    """make everything in front of L's last convolution bf16-exact (see above) and put the norm `variant` asks for behind L; returns the input"""
+    rng = np.random.default_rng(seed + 2000)
+    x = rng.integers(-8, 9, size=x_shape).astype(np.float32)
+    mods = model.fields["modules"]
+    c0 = conv_index(arch, index_of_L)
+    block = arch.split(",")[index_of_L][0] in "RC"
+    cm = _conv_modules(model)
+    assert cm[c0].fields["kW"] == 3 and cm[c0].fields["dW"] == 1, "bf16 probes are for the 3x3 stride-1 layers"
+    for m in cm[:c0 + (1 if block else 0)]: _sparse_conv(m, rng)
+    iL = next(i for i, m in enumerate(mods) if m is cm[c0] or (m.cls == "nn.Sequential" and any(q is cm[c0] for q in _conv_modules(m))))
+    inner = mods[iL].fields["modules"][0].fields["modules"][0].fields["modules"] if block else None      # Sequential(ConcatTable(branch, skip), CAddTable)
+    # the norm behind L
+    holder, at = (inner, len(inner) - 1) if block else (mods, iL + 1)
+    assert holder[at].cls == "nn.SpatialBatchNormalization", holder[at].cls
+    C = int(cm[c0].fields["nOutputPlane"])
+    if variant == "stats": holder[at] = t7._inorm(rng, C)
+    if block:
+        # behind a join the observer sees skip + norm(branch), the skip of order 10: the branch is made to dominate max |ref| -- its
+        # InstanceNorm with gamma 32, beta 0 (sigma 32), its BatchNorm the identity (the raw convolution, sigma of order 30, bias included)
+        f = holder[at].fields
+        f["weight"] = np.full((C,), 32.0 if variant == "stats" else 1.0, np.float32); f["bias"] = np.zeros((C,), np.float32)
+        if variant == "raw": f["running_mean"] = np.zeros((C,), np.float32); f["running_var"] = np.full((C,), 1.0 - float(f["eps"]), np.float32)
+    # the norms in front, in the network's order: each is fitted to the float64 tensor it reads with the earlier ones in place
+    fits = [(mods[i], ("top", i)) for i in range(iL) if mods[i].cls == "nn.SpatialBatchNormalization"]
+    if block: fits += [(m, ("conv", c0)) for m in inner[:-1] if m.cls == "nn.SpatialBatchNormalization"]
+    assert fits
+    done = 0
+    for bn, (kind, i) in fits:
+        tr, convs = [], []
+        layers = _write(tmp, model, arch, kw)
+        os.remove(tmp)
+        for L in (front_norms(layers, c0, 2 if block else 1)[:done]): L["var"] = np.ones_like(L["var"]); L["eps"] = 0.0      # (as the reference runs them)
+        done += 1
+        forward64(layers, _t64(x), tr, convs)
+        if kind == "top": assert tr[i][0] == "bn", tr[i][0]
+        _fit_norm(bn, (tr[i - 1][1] if kind == "top" else convs[i]).numpy())
+    return x
+
+
 # ------------------------------------------------------------------------------------------------ checkpoints
 class Probe:
     pass
@@ -321,9 +465,11 @@ def _write(path, model, arch, kw):
     return t7.extract_layers(t7.load(path)["model"])
 
 
-def probe_checkpoints(arch, index_of_L, variant, seed, hw, out_dir, regimes=False, **build_kw):
+def probe_checkpoints(arch, index_of_L, variant, seed, hw, out_dir, regimes=False, bf16=False, **build_kw):
     """Checkpoints (one per pass) that observe item index_of_L of `arch` on a seeded random input of hw = (H, W), and the observer's
     group / sign table.  variant: "stats" (InstanceNorm everywhere) or "raw" (evaluate-mode BatchNorm everywhere).
+    bf16: the probe for the bf16-operand fast mode ("bf16-exact probes" below) -- BatchNorm everywhere but behind L, where `variant`
+    decides; the Probe then carries ref_layers, the layer list the float64 reference runs.
     regimes ("stats" only: raw has no statistics): the output channels of L -- of both convolutions of an R<n> item -- by turns in the
     regimes of REGIMES above; sigma and RMS of a channel are those of the float64 reference as the weights stand when its convolution
     is changed (the block's second convolution: behind the changed first).  B and k come from the changed checkpoint, as always.
@@ -332,7 +478,7 @@ def probe_checkpoints(arch, index_of_L, variant, seed, hw, out_dir, regimes=Fals
     items = arch.split(",")
     direct = index_of_L == len(items) - 1
     assert direct or items[index_of_L + 1:] == ["c9s1-3"], "the observer is one c9s1-3 item directly behind L"
-    kw = dict(build_kw, use_instance_norm=(variant == "stats"))
+    kw = dict(build_kw, use_instance_norm=(variant == "stats" and not bf16))
     model = t7.build_model(arch, seed, **kw)
     mods = model.fields["modules"]
     cin = kw.get("in_channels", 7)
@@ -341,8 +487,14 @@ def probe_checkpoints(arch, index_of_L, variant, seed, hw, out_dir, regimes=Fals
     x = (np.random.default_rng(seed + 1000).standard_normal((cin, hw[0], hw[1])) * (60 if variant == "stats" else 1)).astype(np.float32)
     obs_i = max(i for i, m in enumerate(mods) if m.cls == "nn.SpatialConvolution")
     obs = mods[obs_i]
-    tag = "%s_%d_%s%s_%d_%dx%d" % (arch.replace(",", "_"), index_of_L, variant, "_regimes" if regimes else "", seed, hw[0], hw[1])
+    tag = "%s_%d_%s%s_%d_%dx%d" % (arch.replace(",", "_"), index_of_L, variant, "_regimes" if regimes else ("_bf16" if bf16 else ""), seed, hw[0], hw[1])
     base = os.path.join(str(out_dir), tag)
+    n_convs = 2 if items[index_of_L][0] in "RC" else 1
+    # what the float64 reference runs: the checkpoint's own layers, or (bf16) those with L's weights rounded and the norms in front exact
+    ref_of = (lambda ls: bf16_reference_layers(ls, conv_index(arch, index_of_L), n_convs)) if bf16 else (lambda ls: ls)
+    if bf16:
+        assert not regimes and not direct, "bf16 probes: a 3x3 layer behind an observer, no regimes"
+        x = _bf16_front(model, arch, index_of_L, variant, seed, x.shape, kw, base + "_tmp.t7")
     pr = Probe()
     pr.x, pr.direct, pr.B, pr.arch, pr.variant = x, direct, 0.0, arch, variant
 
@@ -394,7 +546,7 @@ def probe_checkpoints(arch, index_of_L, variant, seed, hw, out_dir, regimes=Fals
                 _conv_regimes(_conv_modules(model)[c0 + i], convs[c0 + i].numpy())
             pr.regimes = [regime_of(c) for c in range(C)]
     layers = _write(base + "_tmp.t7", model, arch, kw)
-    y0, pre0, _ = reference_parts(layers, x)
+    y0, pre0, _ = reference_parts(ref_of(layers), x)
     os.remove(base + "_tmp.t7")
     if norm is not None:
         pr.B = float(math.ceil(1.5 - float(pre0.min())))        # min pre-ReLU value >= 1.5 in the reference: the ReLU is the identity on the GPU too
@@ -409,6 +561,11 @@ def probe_checkpoints(arch, index_of_L, variant, seed, hw, out_dir, regimes=Fals
         pr.paths.append("%s_p%d.t7" % (base, p))
         ls = _write(pr.paths[-1], model, arch, kw)
         if p == 0: pr.layers = ls
+    if bf16:
+        pr.ref_layers = ref_of(pr.layers)
+        c0 = conv_index(arch, index_of_L)
+        for a in bf16_conv_inputs(pr.ref_layers, x)[c0:c0 + n_convs]:      # a badly built probe fails here, before a GPU sees it
+            assert is_bf16(a), "bf16 probe %s: a tensor in front of L is not bf16-representable in the reference" % tag
     return pr
 
 
@@ -507,7 +664,8 @@ def probe_for(case, variant, out_dir, regimes=False):
     import zlib
     kw = case["kw"]
     hw = tuple(input_size(case["arch"], case["L"], o, **kw) for o in case["out"])
-    pr = probe_checkpoints(case["arch"], case["L"], variant, zlib.crc32(case["name"].encode()) % 100000, hw, out_dir, regimes=regimes, **kw)
+    pr = probe_checkpoints(case["arch"], case["L"], variant, zlib.crc32(case["name"].encode()) % 100000, hw, out_dir, regimes=regimes,
+                           bf16=case.get("bf16", False), **kw)
     pr.tol = TOL_RAW if (variant == "raw" or pr.direct) else TOL_STATS
     pr.conv0 = conv_index(case["arch"], case["L"])
     pr.ids = case["ids"] if variant == "stats" else case["ids_raw"]
@@ -535,3 +693,49 @@ EDGE_PARTIALS_CASES = [_named(n) for n in ("wino4_R128_tile", "wino4_R128_ragged
 # 3 rows of 140 (two segments per row, 128 + 12)
 ELEMENT_CASES = [_case("stats_u2_%d" % C, "c9s1-%d,U2,c9s1-3" % C, 1, (18, 66), []) for C in (32, 64, 128)] + \
                 [_case("join_u2_%d" % C, "c9s1-%d,R%d,U2,c9s1-3" % (C, C), 2, (6, 280), []) for C in (32, 64, 128)]
+
+
+# ------------------------------------------------------------------------------------------------ the cases of tests/test_gpu_bf16_parity.py
+# conv3_halo_bf16_kernel<BN, S2> (precision 1; ids as CK_HALO3: 364 for 64 filters, 428 for 128).  8 x 32 tiles only; sizes are L's output
+def _bcase(name, arch, index_of_L, out, ids, poison=False, **kw):
+    return dict(_case(name, arch, index_of_L, out, ids, poison=poison, **kw), bf16=True)
+
+
+def bf16_units(case):
+    """stream-K work units of L's (last) convolution: tiles of 8 x 32 times cin / 32 x 3 tap rows (launch_h3_t; an R<n> item is unpadded
+    and keeps its channel count, so both of its convolutions have this many)"""
+    items = case["arch"].split(",")
+    v = items[case["L"] - 1]
+    prev = items[case["L"] - 2] if v[0] == "U" else v
+    cin = int(prev[5:]) if prev[0] == "c" else int(prev[1:])
+    return -(-case["out"][0] // 8) * -(-case["out"][1] // 32) * (cin // 32) * 3
+
+
+BF16_CASES = [
+    # <64, false>: zero padding 1 (the mask path); under a tile | one tile | ragged | a 20-column right edge, which the fp32 kernel cuts
+    # into 16 x 16 tiles and this one must not
+    _bcase("bf16_64_small", "c9s1-32,c3s1-64,c9s1-3", 1, (5, 20), [364], poison=True),
+    _bcase("bf16_64_tile", "c9s1-32,c3s1-64,c9s1-3", 1, (8, 32), [364]),
+    _bcase("bf16_64_ragged", "c9s1-32,c3s1-64,c9s1-3", 1, (17, 65), [364]),
+    _bcase("bf16_64_no_edge_tiles", "c9s1-32,c3s1-64,c9s1-3", 1, (9, 52), [364]),
+    # <128, false>; R128: unpadded, both convolutions on the kernel, the second one behind a sparse first
+    _bcase("bf16_128", "c9s1-32,c3s1-128,c9s1-3", 1, (9, 33), [428]),
+    _bcase("bf16_R128_small", "c9s1-128,R128,c9s1-3", 1, (9, 11), [428, 428]),
+    _bcase("bf16_R128_ragged", "c9s1-128,R128,c9s1-3", 1, (17, 33), [428, 428]),
+    # <64, true>, <128, true>: two pending stages and ups = 1
+    _bcase("bf16_64_U2", "c9s1-32,U2,c3s1-64,c9s1-3", 2, (18, 66), [364]),
+    _bcase("bf16_128_U2", "c9s1-64,U2,c3s1-128,c9s1-3", 2, (18, 66), [428]),
+    # behind the element kernel pad_nhwc
+    _bcase("bf16_pad_reflect", "c9s1-32,c3s1-64,c9s1-3", 1, (9, 33), [364], padding_type="reflect"),
+    _bcase("bf16_pad_replicate", "c9s1-32,c3s1-64,c9s1-3", 1, (9, 33), [364], padding_type="replicate"),
+    # filter counts that run padded: the n < COUT store guard, zero channels in the statistics
+    _bcase("bf16_48_as_64", "c9s1-32,c3s1-48,c9s1-3", 1, (9, 33), [364]),
+    _bcase("bf16_96_as_128", "c9s1-32,c3s1-96,c9s1-3", 1, (9, 33), [428]),
+]
+# stream-K with cut tiles: 288 units = 12 tiles x 24 | 24 tiles x 12 -- at least 257 and no multiple of 256, so the grid is one block per
+# CU on any MI355X and every tile's units are spread over several blocks, unit ranges starting mid-slice (tests/test_cpu_bf16_probe.py
+# re-derives the counts)
+BF16_SK_CASES = [
+    _bcase("bf16_sk_256_128", "c9s1-256,c3s1-128,c9s1-3", 1, (17, 97), [428], poison=True),
+    _bcase("bf16_sk_R128", "c9s1-128,R128,c9s1-3", 1, (41, 97), [428, 428], poison=True),
+]
