@@ -1,5 +1,6 @@
 // flow.cpp -- the coarse-to-fine optical-flow estimator behind fav_flow_rgb8 (kernels in kernels_flow.hip; the algorithm is stated in
-// DESIGN.md, "fav_flow", and restated in numpy by tests/util/flow_model.py and, for smooth_eps > 0, tests/util/flow_robust_model.py):
+// DESIGN.md, "fav_flow", and restated in numpy by tests/util/flow_model.py, for smooth_eps > 0 by tests/util/flow_robust_model.py and for the
+// gradient-constancy data term by tests/util/flow_grad_model.py):
 // option defaults, the layout of the caller's workspace and the sequence of launches.  Nothing here allocates or synchronises.
 #include <cmath>
 
@@ -12,6 +13,7 @@ namespace {
 constexpr int MAX_LEVELS = 6, MIN_SIDE = 16;
 constexpr int DEFAULT_WARPS = 3, DEFAULT_ITERS = 30, DEFAULT_SWEEPS_PER_LAUNCH = 6;
 constexpr float DEFAULT_ALPHA = 15.f, DEFAULT_ALPHA_ROBUST = 5.f;      // (robust: with smooth_eps > 0)
+constexpr float DEFAULT_ALPHA_GRAD = 8.f, DEFAULT_ALPHA_GRAD_ROBUST = 8.f;      // with the gradient-constancy data term (measured)
 constexpr float MIN_EPS = 1e-6f, MAX_EPS = 1e6f;                      // eps^2 and 1 / eps stay normal fp32 numbers
 
 // The workspace of a call on `images` images and `flows` flows (fav_flow_rgb8: 2 and 1; fav_flow_pairs_rgb8: 2 n and 2 n).  The planes
@@ -19,18 +21,23 @@ constexpr float MIN_EPS = 1e-6f, MAX_EPS = 1e6f;                      // eps^2 a
 struct FlowPlan {
     int levels = 0, warps = 0, iters = 0, K = 0, images = 0, flows = 0;
     float alpha = 0.f, eps = 0.f;                                            // eps > 0: edge-preserving smoothness
+    bool grad = false;                                                       // the gradient-constancy data term: coef is five planes
     int w[MAX_LEVELS], h[MAX_LEVELS];
     size_t pyr[MAX_LEVELS], pyr_stride[MAX_LEVELS];                          // byte offsets into the workspace: `images` grey planes
     size_t flow0[MAX_LEVELS], flow1[MAX_LEVELS], flow_stride[MAX_LEVELS];    // the two flow buffers of a level, `flows` planes each (level 0:
                                                                              // flow1 only, the other ones are the caller's)
-    size_t coef = 0, coef_stride = 0, wgt = 0, bytes = 0;                    // wgt: the edge weights (eps > 0 only), coef_stride apart
+    size_t coef = 0, coef_stride = 0, wgt = 0, wgt_stride = 0, bytes = 0;    // wgt: the edge weights (eps > 0 only)
 };
 
 // FAV_OK or FAV_EINVAL (message set)
-int make_plan(int W, int H, const fav_flow_opts* o, int images, int flows, FlowPlan& p)
+int make_plan(int W, int H, const fav_flow_opts_ex* ex, int images, int flows, FlowPlan& p)
 {
-    static const fav_flow_opts none = {0, 0, 0, 0.f, 0, 0.f};
-    if (!o) o = &none;
+    static const fav_flow_opts_ex none = {{0, 0, 0, 0.f, 0, 0.f}, FAV_FLOW_DATA_BRIGHTNESS};
+    if (!ex) ex = &none;
+    const fav_flow_opts* o = &ex->base;
+    FAV_REQUIRE(ex->data_term == FAV_FLOW_DATA_BRIGHTNESS || ex->data_term == FAV_FLOW_DATA_GRADIENT,
+                "fav_flow: data_term must be 0 (brightness constancy) or 1 (gradient constancy), not %d", ex->data_term);
+    p.grad = ex->data_term == FAV_FLOW_DATA_GRADIENT;
     FAV_REQUIRE(W >= MIN_SIDE && H >= MIN_SIDE && (long long)W * H <= (1ll << 28), "fav_flow: frames must be at least %dx%d (and at most 2^28 pixels), not %dx%d", MIN_SIDE, MIN_SIDE, W, H);
     FAV_REQUIRE(o->levels >= 0 && o->levels <= MAX_LEVELS, "fav_flow: levels must be 0 (default) .. %d, not %d", MAX_LEVELS, o->levels);
     FAV_REQUIRE(o->warps >= 0 && o->warps <= 32, "fav_flow: warps must be 0 (default) .. 32, not %d", o->warps);
@@ -42,7 +49,8 @@ int make_plan(int W, int H, const fav_flow_opts* o, int images, int flows, FlowP
     p.eps = o->smooth_eps;
     p.warps = o->warps ? o->warps : DEFAULT_WARPS;
     p.iters = o->iters ? o->iters : DEFAULT_ITERS;
-    p.alpha = o->alpha != 0.f ? o->alpha : (p.eps > 0.f ? DEFAULT_ALPHA_ROBUST : DEFAULT_ALPHA);
+    p.alpha = o->alpha != 0.f ? o->alpha
+            : p.grad ? (p.eps > 0.f ? DEFAULT_ALPHA_GRAD_ROBUST : DEFAULT_ALPHA_GRAD) : (p.eps > 0.f ? DEFAULT_ALPHA_ROBUST : DEFAULT_ALPHA);
     p.K = o->sweeps_per_launch ? o->sweeps_per_launch : DEFAULT_SWEEPS_PER_LAUNCH;
     p.images = images; p.flows = flows;
     p.w[0] = W; p.h[0] = H; p.levels = 1;
@@ -61,9 +69,10 @@ int make_plan(int W, int H, const fav_flow_opts* o, int images, int flows, FlowP
         p.pyr[l] = take(p.pyr_stride[l], images);
         p.flow0[l] = l ? take(p.flow_stride[l], flows) : 0; p.flow1[l] = take(p.flow_stride[l], flows);
     }
-    p.coef_stride = round256((size_t)W * H * 16);
+    p.coef_stride = round256((size_t)W * H * (p.grad ? 20 : 16));
     p.coef = take(p.coef_stride, flows);
-    if (p.eps > 0.f) p.wgt = take(p.coef_stride, flows);
+    p.wgt_stride = round256((size_t)W * H * 16);
+    if (p.eps > 0.f) p.wgt = take(p.wgt_stride, flows);
     p.bytes = off;
     return FAV_OK;
 }
@@ -83,7 +92,7 @@ int run_plan(const FlowPlan& p, const FlowPtrs& img, const int* a_of, const int*
     // coarse to fine.  Every warp ends ceil(iters / K) buffer swaps later: level 0 starts in the buffers that leave the results in `out`
     const int swaps = p.warps * ((p.iters + p.K - 1) / p.K);
     const FlowPtrs coef(ws + p.coef, p.coef_stride, p.flows);
-    const FlowPtrs wgt_planes(ws + p.wgt, p.coef_stride, p.flows);
+    const FlowPtrs wgt_planes(ws + p.wgt, p.wgt_stride, p.flows);
     const FlowPtrs* wgt = p.eps > 0.f ? &wgt_planes : nullptr;
     FlowPtrs coarser;
     for (int l = p.levels - 1; l >= 0; --l) {
@@ -102,8 +111,8 @@ int run_plan(const FlowPlan& p, const FlowPtrs& img, const int* a_of, const int*
             else for (int j = 0; j < p.flows; ++j) FAV_HIP(hipMemsetAsync(cur.p[j], 0, (size_t)w * h * 8, st));
         } else { rc = launch_flow_up(coarser, p.w[l + 1], p.h[l + 1], cur, p.flows, w, h, st); if (rc) return rc; }
         for (int k = 0; k < p.warps; ++k) {
-            rc = launch_flow_coef(A, B, cur, p.alpha, p.eps, coef, wgt, p.flows, w, h, st); if (rc) return rc;
-            rc = launch_flow_sweeps(&cur, &other, coef, wgt, p.flows, p.iters, p.K, w, h, st); if (rc) return rc;
+            rc = launch_flow_coef(A, B, cur, p.alpha, p.eps, coef, wgt, p.flows, w, h, st, p.grad); if (rc) return rc;
+            rc = launch_flow_sweeps(&cur, &other, coef, wgt, p.flows, p.iters, p.K, w, h, st, p.grad); if (rc) return rc;
         }
         coarser = cur;
     }
@@ -112,16 +121,37 @@ int run_plan(const FlowPlan& p, const FlowPtrs& img, const int* a_of, const int*
 
 bool aligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
 
+// the options of an entry from before data_term existed: its fav_flow_opts (or none) with the brightness term
+fav_flow_opts_ex brightness(const fav_flow_opts* o)
+{
+    fav_flow_opts_ex ex = {{0, 0, 0, 0.f, 0, 0.f}, FAV_FLOW_DATA_BRIGHTNESS};
+    if (o) ex.base = *o;
+    return ex;
+}
+
 }  // namespace
 
-extern "C" size_t fav_flow_workspace_bytes(int W, int H, const fav_flow_opts* opts_host)
+extern "C" size_t fav_flow_workspace_bytes_ex(int W, int H, const fav_flow_opts_ex* opts_host)
 {
     FlowPlan p;
     return make_plan(W, H, opts_host, 2, 1, p) ? 0 : p.bytes;
 }
 
+extern "C" size_t fav_flow_workspace_bytes(int W, int H, const fav_flow_opts* opts_host)
+{
+    const fav_flow_opts_ex ex = brightness(opts_host);
+    return fav_flow_workspace_bytes_ex(W, H, &ex);
+}
+
 extern "C" int fav_flow_rgb8(const uint8_t* a_rgb_hwc, const uint8_t* b_rgb_hwc, int W, int H, const fav_flow_opts* opts_host, float* flow_out,
                              void* workspace, size_t workspace_bytes, fav_hipstream_t stream)
+{
+    const fav_flow_opts_ex ex = brightness(opts_host);
+    return fav_flow_rgb8_ex(a_rgb_hwc, b_rgb_hwc, W, H, &ex, flow_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int fav_flow_rgb8_ex(const uint8_t* a_rgb_hwc, const uint8_t* b_rgb_hwc, int W, int H, const fav_flow_opts_ex* opts_host, float* flow_out,
+                                void* workspace, size_t workspace_bytes, fav_hipstream_t stream)
 {
     FlowPlan p;
     int rc = make_plan(W, H, opts_host, 2, 1, p); if (rc) return rc;
@@ -136,14 +166,28 @@ extern "C" int fav_flow_rgb8(const uint8_t* a_rgb_hwc, const uint8_t* b_rgb_hwc,
 
 extern "C" size_t fav_flow_pairs_workspace_bytes(int W, int H, int n_pairs, const fav_flow_opts* opts_host)
 {
-    FlowPlan p;
-    if (n_pairs < 1 || n_pairs > FAV_FLOW_MAX_PAIRS) { set_error("fav_flow_pairs: n_pairs must be 1 .. %d, not %d", FAV_FLOW_MAX_PAIRS, n_pairs); return 0; }
-    return make_plan(W, H, opts_host, 2 * n_pairs, 2 * n_pairs, p) ? 0 : p.bytes;
+    const fav_flow_opts_ex ex = brightness(opts_host);
+    return fav_flow_pairs_workspace_bytes_ex(W, H, n_pairs, &ex);
 }
 
 extern "C" int fav_flow_pairs_rgb8(const uint8_t* const* prev_rgb_hwc, const uint8_t* const* cur_rgb_hwc, int n_pairs, int W, int H,
                                    const fav_flow_opts* opts_host, float* const* backward_flo, float* const* forward_flo, void* workspace,
                                    size_t workspace_bytes, fav_hipstream_t stream)
+{
+    const fav_flow_opts_ex ex = brightness(opts_host);
+    return fav_flow_pairs_rgb8_ex(prev_rgb_hwc, cur_rgb_hwc, n_pairs, W, H, &ex, backward_flo, forward_flo, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t fav_flow_pairs_workspace_bytes_ex(int W, int H, int n_pairs, const fav_flow_opts_ex* opts_host)
+{
+    FlowPlan p;
+    if (n_pairs < 1 || n_pairs > FAV_FLOW_MAX_PAIRS) { set_error("fav_flow_pairs: n_pairs must be 1 .. %d, not %d", FAV_FLOW_MAX_PAIRS, n_pairs); return 0; }
+    return make_plan(W, H, opts_host, 2 * n_pairs, 2 * n_pairs, p) ? 0 : p.bytes;
+}
+
+extern "C" int fav_flow_pairs_rgb8_ex(const uint8_t* const* prev_rgb_hwc, const uint8_t* const* cur_rgb_hwc, int n_pairs, int W, int H,
+                                      const fav_flow_opts_ex* opts_host, float* const* backward_flo, float* const* forward_flo, void* workspace,
+                                      size_t workspace_bytes, fav_hipstream_t stream)
 {
     FAV_REQUIRE(n_pairs >= 1 && n_pairs <= FAV_FLOW_MAX_PAIRS, "fav_flow_pairs_rgb8: n_pairs must be 1 .. %d, not %d", FAV_FLOW_MAX_PAIRS, n_pairs);
     const int n = n_pairs;
@@ -215,16 +259,31 @@ extern "C" int fav_flow_coefficients_robust_f32(const float* a_grey, const float
     return launch_flow_coef(FlowPtrs(a_grey), FlowPtrs(b_grey), FlowPtrs(flow0), alpha, smooth_eps, FlowPtrs(coef), &wgt, 1, W, H, static_cast<hipStream_t>(stream));
 }
 
+// the gradient-constancy term: coef is five planes [5][H][W]; weights == nullptr: the quadratic smoothness term (smooth_eps is not read)
+extern "C" int fav_flow_coefficients_grad_f32(const float* a_grey, const float* b_grey, const float* flow0, float alpha, float smooth_eps, float* coef,
+                                              float* weights, int W, int H, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(a_grey && b_grey && flow0 && coef && W > 0 && H > 0 && std::isfinite(alpha) && alpha > 0.f, "fav_flow_coefficients_grad_f32: bad argument");
+    FAV_REQUIRE(!weights || (std::isfinite(smooth_eps) && smooth_eps >= MIN_EPS && smooth_eps <= MAX_EPS), "fav_flow_coefficients_grad_f32: smooth_eps must be a number in 1e-6 .. 1e6, not %g", (double)smooth_eps);
+    FAV_REQUIRE(reinterpret_cast<uintptr_t>(flow0) % 8 == 0 && reinterpret_cast<uintptr_t>(coef) % 4 == 0 && reinterpret_cast<uintptr_t>(weights) % 16 == 0 && coef != weights,
+                "fav_flow_coefficients_grad_f32: flow0 must be 8-byte aligned, coef 4-byte aligned, weights 16-byte aligned and distinct from coef");
+    int rc = ensure_device(); if (rc) return rc;
+    const FlowPtrs wgt(weights);
+    return launch_flow_coef(FlowPtrs(a_grey), FlowPtrs(b_grey), FlowPtrs(flow0), alpha, weights ? smooth_eps : 0.f, FlowPtrs(coef), weights ? &wgt : nullptr, 1, W, H,
+                            static_cast<hipStream_t>(stream), true);
+}
+
 namespace {
 
-// the two sweep entries: `weights` == nullptr is the plain mean
+// the sweep entries: `weights` == nullptr is the plain mean; grad: the tensor form (coef: five planes, 4-byte aligned)
 int sweeps_entry(const char* who, const float* flow0, const float* coef, const float* weights, int iters, int sweeps_per_launch, float* flow_out,
-                 float* scratch, int W, int H, fav_hipstream_t stream)
+                 float* scratch, int W, int H, fav_hipstream_t stream, bool grad = false)
 {
     FAV_REQUIRE(flow0 && coef && flow_out && scratch && W > 0 && H > 0, "%s: bad argument", who);
     FAV_REQUIRE(iters >= 1 && sweeps_per_launch >= 0 && sweeps_per_launch <= FLOW_MAX_SWEEPS_PER_LAUNCH, "%s: iters must be >= 1, sweeps_per_launch 0 (default) .. %d", who, FLOW_MAX_SWEEPS_PER_LAUNCH);
     FAV_REQUIRE(reinterpret_cast<uintptr_t>(flow0) % 8 == 0 && reinterpret_cast<uintptr_t>(flow_out) % 8 == 0 && reinterpret_cast<uintptr_t>(scratch) % 8 == 0 &&
-                reinterpret_cast<uintptr_t>(coef) % 16 == 0 && reinterpret_cast<uintptr_t>(weights) % 16 == 0, "%s: flows must be 8-byte aligned, coef%s 16-byte aligned", who, weights ? " and weights" : "");
+                reinterpret_cast<uintptr_t>(coef) % (grad ? 4 : 16) == 0 && reinterpret_cast<uintptr_t>(weights) % 16 == 0, "%s: flows must be 8-byte aligned, coef%s 16-byte aligned", who,
+                grad ? " 4-byte aligned, weights" : weights ? " and weights" : "");
     int rc = ensure_device(); if (rc) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int K = sweeps_per_launch ? sweeps_per_launch : DEFAULT_SWEEPS_PER_LAUNCH;
@@ -233,8 +292,8 @@ int sweeps_entry(const char* who, const float* flow0, const float* coef, const f
     FlowPtrs src(flow0), cur((rest_launches & 1) ? scratch : flow_out), other((rest_launches & 1) ? flow_out : scratch), first_dst = cur;
     const FlowPtrs cf(coef), wgt_plane(weights);
     const FlowPtrs* wgt = weights ? &wgt_plane : nullptr;
-    rc = launch_flow_sweeps(&src, &first_dst, cf, wgt, 1, first, K, W, H, st); if (rc) return rc;
-    if (iters > first) { rc = launch_flow_sweeps(&cur, &other, cf, wgt, 1, iters - first, K, W, H, st); if (rc) return rc; }
+    rc = launch_flow_sweeps(&src, &first_dst, cf, wgt, 1, first, K, W, H, st, grad); if (rc) return rc;
+    if (iters > first) { rc = launch_flow_sweeps(&cur, &other, cf, wgt, 1, iters - first, K, W, H, st, grad); if (rc) return rc; }
     return FAV_OK;
 }
 
@@ -251,4 +310,10 @@ extern "C" int fav_flow_sweeps_robust_f32(const float* flow0, const float* coef,
 {
     FAV_REQUIRE(weights, "fav_flow_sweeps_robust_f32: bad argument");
     return sweeps_entry("fav_flow_sweeps_robust_f32", flow0, coef, weights, iters, sweeps_per_launch, flow_out, scratch, W, H, stream);
+}
+
+extern "C" int fav_flow_sweeps_grad_f32(const float* flow0, const float* coef, const float* weights, int iters, int sweeps_per_launch, float* flow_out,
+                                        float* scratch, int W, int H, fav_hipstream_t stream)
+{
+    return sweeps_entry("fav_flow_sweeps_grad_f32", flow0, coef, weights, iters, sweeps_per_launch, flow_out, scratch, W, H, stream, true);
 }

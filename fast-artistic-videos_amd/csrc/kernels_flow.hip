@@ -143,6 +143,83 @@ __global__ __launch_bounds__(256) void flow_coef_kernel(FlowPtrs As, FlowPtrs Bs
     }
 }
 
+// ---- gradient-constancy data term (fav_flow_opts_ex.data_term = FAV_FLOW_DATA_GRADIENT; restated by tests/util/flow_grad_model.py).
+// The data term is taken on (Bx, By) = grad Bw against (Ax, Ay) = grad A instead of Bw against A: two channels k = x, y with
+//   a_k = dx(B_k), b_k = dy(B_k), c_k = ((B_k - A_k) - a_k u0) - b_k v0          (dx, dy: central differences * 0.5, borders replicated at
+//                                                                                each application)
+//   J11 = a_x^2 + a_y^2, J12 = a_x b_x + a_y b_y, J22 = b_x^2 + b_y^2, h1 = a_x c_x + a_y c_y, h2 = b_x c_x + b_y c_y
+//   w = alpha^2 | (alpha^2 S) 0.25;  d11 = w + J11, d22 = w + J22, det = d11 d22 - J12^2
+//   stored, FIVE PLANES [5][H][W]:  q11 = w d22 / det, q12 = -(w J12 / det), q22 = w d11 / det, e1 = -((d22 h1 - J12 h2) / det),
+//                                   e2 = -((d11 h2 - J12 h1) / det)
+//   sweep   u = (q11 u_bar + q12 v_bar) + e1, v = (q12 u_bar + q22 v_bar) + e2
+// A lane forms Bw on the 13-point diamond of radius 2 around its pixel -- each sample with that pixel's own flow, the L1 serves them --
+// and reads A on its cross.  A second difference at the image border nests two clamps: clamp(clamp(x + 1) - 1) is x inside the image and
+// x - 1 on its last column, so the sample it needs is one of the 13 either way and is chosen by value.
+// The five values are planes, not a record: a wave's loads and stores are 256 contiguous bytes each, and 20 bytes per pixel need no padding.
+__device__ __forceinline__ float4 edge_weights(const float2* __restrict__ flow0, int w, int h, int x, int y, float eps2, float& S)
+{
+    auto g_at = [&](int yy, int xx) {      // yy, xx inside the image
+        const float2 l = flow0[(size_t)yy * w + max(xx - 1, 0)], r = flow0[(size_t)yy * w + min(xx + 1, w - 1)];
+        const float2 u = flow0[(size_t)max(yy - 1, 0) * w + xx], d = flow0[(size_t)min(yy + 1, h - 1) * w + xx];
+        const float ux = (r.x - l.x) * 0.5f, vx = (r.y - l.y) * 0.5f, uy = (d.x - u.x) * 0.5f, vy = (d.y - u.y) * 0.5f;
+        return 1.f / sqrtf(((ux * ux + vx * vx) + (uy * uy + vy * vy)) + eps2);
+    };
+    const float gp = g_at(y, x);
+    const float wl = 0.5f * (gp + g_at(y, max(x - 1, 0))), wr = 0.5f * (gp + g_at(y, min(x + 1, w - 1)));
+    const float wu = 0.5f * (gp + g_at(max(y - 1, 0), x)), wd = 0.5f * (gp + g_at(min(y + 1, h - 1), x));
+    S = (wl + wr) + (wu + wd);
+    return make_float4(wl, wr, wu, wd);
+}
+
+template <bool ROBUST>
+__global__ __launch_bounds__(256) void flow_coef_grad_kernel(FlowPtrs As, FlowPtrs Bs, FlowPtrs flow0s, float alpha2, FlowPtrs coefs, int w, int h,
+                                                             CoefRobustArgs<ROBUST> ra)
+{
+    const float* __restrict__ A = static_cast<const float*>(As.p[blockIdx.z]);
+    const float* __restrict__ B = static_cast<const float*>(Bs.p[blockIdx.z]);
+    const float2* __restrict__ flow0 = static_cast<const float2*>(flow0s.p[blockIdx.z]);
+    float* __restrict__ coef = static_cast<float*>(coefs.p[blockIdx.z]);
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= w || y >= h) return;
+    auto bw = [&](int yy, int xx) {        // yy, xx inside the image
+        const float2 f = flow0[(size_t)yy * w + xx];
+        return bilinear(B, w, h, (float)xx + f.x, (float)yy + f.y);
+    };
+    const int xm = max(x - 1, 0), xp = min(x + 1, w - 1), ym = max(y - 1, 0), yp = min(y + 1, h - 1);
+    const float c0 = bw(y, x);
+    const float l1 = bw(y, xm), r1 = bw(y, xp), u1 = bw(ym, x), d1 = bw(yp, x);
+    const float l2 = bw(y, max(xm - 1, 0)), r2 = bw(y, min(xp + 1, w - 1)), u2 = bw(max(ym - 1, 0), x), d2 = bw(min(yp + 1, h - 1), x);
+    const float ul = bw(ym, xm), ur = bw(ym, xp), dl = bw(yp, xm), dr = bw(yp, xp);
+    // Bw at clamp(xm + 1), clamp(xp - 1), clamp(ym + 1), clamp(yp - 1): the centre, or on the image's edge the neighbour on the other side
+    const float xm_p = x > 0 ? c0 : r1, xp_m = x < w - 1 ? c0 : l1, ym_p = y > 0 ? c0 : d1, yp_m = y < h - 1 ? c0 : u1;
+    const float Bx = (r1 - l1) * 0.5f, By = (d1 - u1) * 0.5f;
+    const float Bx_r = (r2 - xp_m) * 0.5f, Bx_l = (xm_p - l2) * 0.5f, Bx_u = (ur - ul) * 0.5f, Bx_d = (dr - dl) * 0.5f;      // Bx at the four neighbours
+    const float By_d = (d2 - yp_m) * 0.5f, By_u = (ym_p - u2) * 0.5f, By_l = (dl - ul) * 0.5f, By_r = (dr - ur) * 0.5f;      // By likewise
+    const float ax = (Bx_r - Bx_l) * 0.5f, bx = (Bx_d - Bx_u) * 0.5f;
+    const float ay = (By_r - By_l) * 0.5f, by = (By_d - By_u) * 0.5f;
+    const float Ax = (A[(size_t)y * w + xp] - A[(size_t)y * w + xm]) * 0.5f, Ay = (A[(size_t)yp * w + x] - A[(size_t)ym * w + x]) * 0.5f;
+    const float2 f0 = flow0[(size_t)y * w + x];
+    const float cx = ((Bx - Ax) - ax * f0.x) - bx * f0.y;
+    const float cy = ((By - Ay) - ay * f0.x) - by * f0.y;
+    const float J11 = ax * ax + ay * ay, J12 = ax * bx + ay * by, J22 = bx * bx + by * by;
+    const float h1 = ax * cx + ay * cy, h2 = bx * cx + by * cy;
+    float wgt = alpha2;
+    if constexpr (ROBUST) {
+        float S;
+        const float4 wq = edge_weights(flow0, w, h, x, y, ra.eps2, S);
+        wgt = (alpha2 * S) * 0.25f;
+        static_cast<float4*>(ra.wgts.p[blockIdx.z])[(size_t)y * w + x] = make_float4(wq.x / S, wq.y / S, wq.z / S, wq.w / S);
+    }
+    const float d11 = wgt + J11, d22 = wgt + J22;
+    const float det = d11 * d22 - J12 * J12;
+    const size_t n = (size_t)w * h, i = (size_t)y * w + x;
+    coef[i] = (wgt * d22) / det;                          // five correctly rounded divisions (-fhip-fp32-correctly-rounded-divide-sqrt)
+    coef[n + i] = -((wgt * J12) / det);
+    coef[2 * n + i] = (wgt * d11) / det;
+    coef[3 * n + i] = -((d22 * h1 - J12 * h2) / det);
+    coef[4 * n + i] = -((d11 * h2 - J12 * h1) / det);
+}
+
 // ---- the sweeps, temporally blocked.
 // A block owns a REGION of 64 x 64 cells: an interior of (64 - 2K)^2 cells and a halo of K cells around it.  It loads the region's (u, v)
 // into LDS (float2, 32 KB) and its coefficients into registers (a lane keeps one column position and 16 rows, ty + 4 j: 64 VGPRs), runs
@@ -227,6 +304,70 @@ __global__ __launch_bounds__(SweepShape<ROBUST>::THREADS) void flow_sweep_kernel
     }
 }
 
+// The tensor form of the gradient-constancy term: the same region, LDS layout, clamping and barriers; a cell carries five values (q11, q12,
+// q22, e1, e2) instead of four, from the five planes of flow_coef_grad_kernel, and WEIGHTED adds the four n_q: nine values per cell.  Both
+// instantiations take the robust variant's shape -- 512 lanes, 8 rows per lane: 40 | 72 VGPRs of coefficients (the figures are in DESIGN.md).
+constexpr int SWG_ROWS = 8, SWG_TY = SW_R / SWG_ROWS, SWG_THREADS = SW_R * SWG_TY;
+
+template <bool WEIGHTED>
+__global__ __launch_bounds__(SWG_THREADS) void flow_sweep_grad_kernel(FlowPtrs fins, FlowPtrs coefs, FlowPtrs fouts, int W, int H, int K, int n,
+                                                                      SweepRobustArgs<WEIGHTED> ra)
+{
+    __shared__ float2 s[SW_R][SW_R];
+    const float2* __restrict__ fin = static_cast<const float2*>(fins.p[blockIdx.z]);
+    const float* __restrict__ coef = static_cast<const float*>(coefs.p[blockIdx.z]);
+    float2* __restrict__ fout = static_cast<float2*>(fouts.p[blockIdx.z]);
+    const size_t plane = (size_t)W * H;
+    const int lx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int TI = SW_R - 2 * K;
+    const int x0 = (int)blockIdx.x * TI - K, y0 = (int)blockIdx.y * TI - K;
+    const int gx = x0 + lx;
+    const int cx = min(max(gx, 0), W - 1);
+    const int lxl = (gx > 0 && lx > 0) ? lx - 1 : lx;
+    const int lxr = (gx < W - 1 && lx < SW_R - 1) ? lx + 1 : lx;
+    float q11[SWG_ROWS], q12[SWG_ROWS], q22[SWG_ROWS], e1[SWG_ROWS], e2[SWG_ROWS];
+    float4 wt[WEIGHTED ? SWG_ROWS : 1];
+    float2 nv[SWG_ROWS];
+#pragma unroll
+    for (int j = 0; j < SWG_ROWS; ++j) {
+        const int ly = ty + SWG_TY * j;
+        const int cy = min(max(y0 + ly, 0), H - 1);
+        const size_t idx = (size_t)cy * W + cx;
+        q11[j] = coef[idx]; q12[j] = coef[plane + idx]; q22[j] = coef[2 * plane + idx]; e1[j] = coef[3 * plane + idx]; e2[j] = coef[4 * plane + idx];
+        if constexpr (WEIGHTED) wt[j] = static_cast<const float4*>(ra.wgts.p[blockIdx.z])[idx];
+        s[ly][lx] = fin[idx];
+    }
+    __syncthreads();
+    for (int sweep = 0; sweep < n; ++sweep) {
+#pragma unroll
+        for (int j = 0; j < SWG_ROWS; ++j) {
+            const int ly = ty + SWG_TY * j, gy = y0 + ly;
+            const int lyu = (gy > 0 && ly > 0) ? ly - 1 : ly;
+            const int lyd = (gy < H - 1 && ly < SW_R - 1) ? ly + 1 : ly;
+            const float2 L = s[ly][lxl], R = s[ly][lxr], U = s[lyu][lx], D = s[lyd][lx];
+            float ub, vb;
+            if constexpr (WEIGHTED) {
+                ub = (wt[j].x * L.x + wt[j].y * R.x) + (wt[j].z * U.x + wt[j].w * D.x);
+                vb = (wt[j].x * L.y + wt[j].y * R.y) + (wt[j].z * U.y + wt[j].w * D.y);
+            } else {
+                ub = ((L.x + R.x) + (U.x + D.x)) * 0.25f;
+                vb = ((L.y + R.y) + (U.y + D.y)) * 0.25f;
+            }
+            nv[j] = make_float2((q11[j] * ub + q12[j] * vb) + e1[j], (q12[j] * ub + q22[j] * vb) + e2[j]);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < SWG_ROWS; ++j) s[ty + SWG_TY * j][lx] = nv[j];
+        __syncthreads();
+    }
+    if (lx < K || lx >= SW_R - K || gx >= W) return;      // (gx >= 0 here: lx >= K)
+#pragma unroll
+    for (int j = 0; j < SWG_ROWS; ++j) {
+        const int ly = ty + SWG_TY * j, gy = y0 + ly;
+        if (ly >= K && ly < SW_R - K && gy < H) fout[(size_t)gy * W + gx] = s[ly][lx];
+    }
+}
+
 inline dim3 grid_64x4(int w, int h, int items) { return dim3((w + 63) / 64, (h + 3) / 4, items); }
 inline bool size_ok(int w, int h) { return w > 0 && h > 0 && (long long)w * h <= (1ll << 28) && (h + 3) / 4 <= 65535; }
 inline bool items_ok(int items) { return items >= 1 && items <= FLOW_MAX_ITEMS; }
@@ -261,18 +402,21 @@ int launch_flow_up(const FlowPtrs& coarse, int Wc, int Hc, const FlowPtrs& fine,
 
 // wgt == nullptr: the quadratic smoothness term (eps is not read); otherwise the edge weights of eps > 0 are written next to the coefficients
 int launch_flow_coef(const FlowPtrs& A, const FlowPtrs& B, const FlowPtrs& flow0, float alpha, float eps, const FlowPtrs& coef, const FlowPtrs* wgt,
-                     int items, int W, int H, hipStream_t st)
+                     int items, int W, int H, hipStream_t st, bool grad)
 {
     FAV_REQUIRE(size_ok(W, H) && items_ok(items), "flow coefficients: bad size %dx%d x %d", W, H, items);
-    if (wgt) hipLaunchKernelGGL(flow_coef_kernel<true>, grid_64x4(W, H, items), dim3(256), 0, st, A, B, flow0, alpha * alpha, coef, W, H, CoefRobustArgs<true>{eps * eps, *wgt});
+    if (grad && wgt) hipLaunchKernelGGL(flow_coef_grad_kernel<true>, grid_64x4(W, H, items), dim3(256), 0, st, A, B, flow0, alpha * alpha, coef, W, H, CoefRobustArgs<true>{eps * eps, *wgt});
+    else if (grad) hipLaunchKernelGGL(flow_coef_grad_kernel<false>, grid_64x4(W, H, items), dim3(256), 0, st, A, B, flow0, alpha * alpha, coef, W, H, CoefRobustArgs<false>{});
+    else if (wgt) hipLaunchKernelGGL(flow_coef_kernel<true>, grid_64x4(W, H, items), dim3(256), 0, st, A, B, flow0, alpha * alpha, coef, W, H, CoefRobustArgs<true>{eps * eps, *wgt});
     else hipLaunchKernelGGL(flow_coef_kernel<false>, grid_64x4(W, H, items), dim3(256), 0, st, A, B, flow0, alpha * alpha, coef, W, H, CoefRobustArgs<false>{});
     FAV_LAUNCH_CHECK("flow_coef_kernel");
     return FAV_OK;
 }
 
 // `iters` sweeps from *cur, ceil(iters / K) launches between *cur and *other (every item at once); on return *cur holds the results.
-// wgt: the normalised edge weights of the edge-preserving smoothness, or nullptr for the plain 4-neighbour mean
-int launch_flow_sweeps(FlowPtrs* cur, FlowPtrs* other, const FlowPtrs& coef, const FlowPtrs* wgt, int items, int iters, int K, int W, int H, hipStream_t st)
+// wgt: the normalised edge weights of the edge-preserving smoothness, or nullptr for the plain 4-neighbour mean; grad: the tensor form
+int launch_flow_sweeps(FlowPtrs* cur, FlowPtrs* other, const FlowPtrs& coef, const FlowPtrs* wgt, int items, int iters, int K, int W, int H, hipStream_t st,
+                       bool grad)
 {
     FAV_REQUIRE(size_ok(W, H) && items_ok(items) && iters >= 1 && K >= 1 && K <= FLOW_MAX_SWEEPS_PER_LAUNCH,
                 "flow sweeps: bad argument (%dx%d x %d, %d sweeps, %d per launch)", W, H, items, iters, K);
@@ -280,7 +424,9 @@ int launch_flow_sweeps(FlowPtrs* cur, FlowPtrs* other, const FlowPtrs& coef, con
     const dim3 grid((W + ti - 1) / ti, (H + ti - 1) / ti, items);
     FAV_REQUIRE(grid.y <= 65535, "flow sweeps: %d rows are too many", H);
     for (int done = 0; done < iters; done += K) {
-        if (wgt) hipLaunchKernelGGL(flow_sweep_kernel<true>, grid, dim3(SweepShape<true>::THREADS), 0, st, *cur, coef, *other, W, H, K, std::min(K, iters - done), SweepRobustArgs<true>{*wgt});
+        if (grad && wgt) hipLaunchKernelGGL(flow_sweep_grad_kernel<true>, grid, dim3(SWG_THREADS), 0, st, *cur, coef, *other, W, H, K, std::min(K, iters - done), SweepRobustArgs<true>{*wgt});
+        else if (grad) hipLaunchKernelGGL(flow_sweep_grad_kernel<false>, grid, dim3(SWG_THREADS), 0, st, *cur, coef, *other, W, H, K, std::min(K, iters - done), SweepRobustArgs<false>{});
+        else if (wgt) hipLaunchKernelGGL(flow_sweep_kernel<true>, grid, dim3(SweepShape<true>::THREADS), 0, st, *cur, coef, *other, W, H, K, std::min(K, iters - done), SweepRobustArgs<true>{*wgt});
         else hipLaunchKernelGGL(flow_sweep_kernel<false>, grid, dim3(SweepShape<false>::THREADS), 0, st, *cur, coef, *other, W, H, K, std::min(K, iters - done), SweepRobustArgs<false>{});
         FAV_LAUNCH_CHECK("flow_sweep_kernel");
         std::swap(*cur, *other);

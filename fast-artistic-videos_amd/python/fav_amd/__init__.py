@@ -61,6 +61,10 @@ def lib() -> C.CDLL:
     L.fav_flow_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_void_p]
     L.fav_flow_pairs_workspace_bytes.restype = C.c_size_t
     L.fav_flow_pairs_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.fav_flow_workspace_bytes_ex.restype = C.c_size_t
+    L.fav_flow_workspace_bytes_ex.argtypes = [C.c_int, C.c_int, C.c_void_p]
+    L.fav_flow_pairs_workspace_bytes_ex.restype = C.c_size_t
+    L.fav_flow_pairs_workspace_bytes_ex.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
     _lib = L
     return L
 
@@ -84,6 +88,8 @@ EXPORTS = [
     "fav_flow_sweeps_f32", "fav_stream_next_frame_estimate",
     "fav_flow_pairs_workspace_bytes", "fav_flow_pairs_rgb8",
     "fav_flow_coefficients_robust_f32", "fav_flow_sweeps_robust_f32",
+    "fav_flow_workspace_bytes_ex", "fav_flow_rgb8_ex", "fav_flow_pairs_workspace_bytes_ex", "fav_flow_pairs_rgb8_ex",
+    "fav_stream_next_frame_estimate_ex", "fav_flow_coefficients_grad_f32", "fav_flow_sweeps_grad_f32",
     "fav_vr_equi_to_faces_rgb8",
 ]
 
@@ -201,6 +207,14 @@ class _FlowOpts(C.Structure):
                 ("smooth_eps", C.c_float)]
 
 
+class _FlowOptsEx(C.Structure):
+    _fields_ = [("base", _FlowOpts), ("data_term", C.c_int)]
+
+
+FLOW_DATA_BRIGHTNESS, FLOW_DATA_GRADIENT = 0, 1
+_DATA_KEYS = {"data_term", "gradient_data"}
+
+
 def _flow_opts(opts) -> "_FlowOpts":
     unknown = set(opts) - {f for f, _ in _FlowOpts._fields_}
     if unknown:
@@ -209,10 +223,19 @@ def _flow_opts(opts) -> "_FlowOpts":
                      int(opts.get("sweeps_per_launch", 0)), float(opts.get("smooth_eps", 0.0)))
 
 
+def _flow_opts_ex(opts) -> "_FlowOptsEx":
+    """fav_flow_opts_ex of the flow options: the fields of fav_flow_opts plus data_term= (0 | 1) or gradient_data= (bool), which select
+    the data term; every Python entry goes through the _ex entries of the library"""
+    if _DATA_KEYS <= set(opts) and int(opts["data_term"]) != (FLOW_DATA_GRADIENT if opts["gradient_data"] else FLOW_DATA_BRIGHTNESS):
+        raise FavError("flow options: data_term and gradient_data contradict each other")
+    term = int(opts["data_term"]) if "data_term" in opts else (FLOW_DATA_GRADIENT if opts.get("gradient_data") else FLOW_DATA_BRIGHTNESS)
+    return _FlowOptsEx(_flow_opts({k: v for k, v in opts.items() if k not in _DATA_KEYS}), term)
+
+
 def flow_workspace_bytes(w: int, h: int, **opts) -> int:
-    """fav_flow_workspace_bytes (host only); raises on a bad size or option"""
-    o = _flow_opts(opts)
-    n = lib().fav_flow_workspace_bytes(w, h, C.cast(C.pointer(o), C.c_void_p))
+    """fav_flow_workspace_bytes_ex (host only); raises on a bad size or option"""
+    o = _flow_opts_ex(opts)
+    n = lib().fav_flow_workspace_bytes_ex(w, h, C.cast(C.pointer(o), C.c_void_p))
     if n == 0:
         _check(-1)
     return n
@@ -220,17 +243,18 @@ def flow_workspace_bytes(w: int, h: int, **opts) -> int:
 
 def flow_rgb8(a, b, **opts):
     """fav_flow_rgb8: the flow w "from a to b", b(p + w(p)) ~ a(p), of two u8 [H][W][3] frames -> .flo payload [H][W][2] (u, v).
-    opts: levels, warps, iters, alpha, sweeps_per_launch (0 / absent = default); smooth_eps > 0 turns the edge-preserving smoothness on."""
+    opts: levels, warps, iters, alpha, sweeps_per_launch (0 / absent = default); smooth_eps > 0 turns the edge-preserving smoothness on;
+    data_term=1 / gradient_data=True takes the data term on the image gradients (frames whose lighting changes)."""
     torch = _torch()
     if not (a.is_cuda and b.is_cuda and a.dtype == torch.uint8 and b.dtype == torch.uint8 and a.is_contiguous() and b.is_contiguous() and
             a.dim() == 3 and a.shape[2] == 3 and a.shape == b.shape):
         raise FavError("flow_rgb8: a and b must be contiguous uint8 CUDA tensors [H][W][3] of one size")
     h, w = a.shape[0], a.shape[1]
-    o = _flow_opts(opts)
+    o = _flow_opts_ex(opts)
     nb = flow_workspace_bytes(w, h, **opts)
     ws = torch.empty(nb, dtype=torch.uint8, device=a.device)
     out = torch.empty((h, w, 2), dtype=torch.float32, device=a.device)
-    _check(lib().fav_flow_rgb8(_p(a), _p(b), w, h, C.byref(o), _p(out), _p(ws), C.c_size_t(nb), _stream()))
+    _check(lib().fav_flow_rgb8_ex(_p(a), _p(b), w, h, C.byref(o), _p(out), _p(ws), C.c_size_t(nb), _stream()))
     return out
 
 
@@ -238,9 +262,9 @@ FLOW_MAX_PAIRS = 8
 
 
 def flow_pairs_workspace_bytes(w: int, h: int, n_pairs: int, **opts) -> int:
-    """fav_flow_pairs_workspace_bytes (host only); raises on a bad size, pair count or option"""
-    o = _flow_opts(opts)
-    n = lib().fav_flow_pairs_workspace_bytes(w, h, n_pairs, C.cast(C.pointer(o), C.c_void_p))
+    """fav_flow_pairs_workspace_bytes_ex (host only); raises on a bad size, pair count or option"""
+    o = _flow_opts_ex(opts)
+    n = lib().fav_flow_pairs_workspace_bytes_ex(w, h, n_pairs, C.cast(C.pointer(o), C.c_void_p))
     if n == 0:
         _check(-1)
     return n
@@ -249,7 +273,7 @@ def flow_pairs_workspace_bytes(w: int, h: int, n_pairs: int, **opts) -> int:
 def flow_pairs(prev_list, cur_list, opts=None):
     """fav_flow_pairs_rgb8: both flows of every (prev[k], cur[k]) in one batched call -> (backward_list, forward_list), .flo payloads
     [H][W][2]: backward[k] is flow_rgb8(cur[k], prev[k]), forward[k] is flow_rgb8(prev[k], cur[k]), bit for bit.
-    opts: a dict of levels, warps, iters, alpha, sweeps_per_launch, smooth_eps (0 / absent = default)."""
+    opts: a dict of levels, warps, iters, alpha, sweeps_per_launch, smooth_eps, data_term / gradient_data (0 / absent = default)."""
     torch = _torch()
     opts = dict(opts or {})
     n = len(prev_list)
@@ -258,13 +282,13 @@ def flow_pairs(prev_list, cur_list, opts=None):
                                                t.shape == imgs[0].shape for t in imgs):
         raise FavError("flow_pairs: prev_list and cur_list must be equally long lists of contiguous uint8 CUDA tensors [H][W][3] of one size")
     h, w = imgs[0].shape[0], imgs[0].shape[1]
-    o = _flow_opts(opts)
+    o = _flow_opts_ex(opts)
     nb = flow_pairs_workspace_bytes(w, h, n, **opts)
     ws = torch.empty(nb, dtype=torch.uint8, device=imgs[0].device)
     bw = [torch.empty((h, w, 2), dtype=torch.float32, device=imgs[0].device) for _ in range(n)]
     fw = [torch.empty((h, w, 2), dtype=torch.float32, device=imgs[0].device) for _ in range(n)]
     arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
-    _check(lib().fav_flow_pairs_rgb8(arr(prev_list), arr(cur_list), n, w, h, C.byref(o), arr(bw), arr(fw), _p(ws), C.c_size_t(nb), _stream()))
+    _check(lib().fav_flow_pairs_rgb8_ex(arr(prev_list), arr(cur_list), n, w, h, C.byref(o), arr(bw), arr(fw), _p(ws), C.c_size_t(nb), _stream()))
     return bw, fw
 
 
@@ -323,6 +347,31 @@ def flow_sweeps_robust(flow0, coef, weights, iters: int, sweeps_per_launch: int 
     h, w, _ = flow0.shape
     out, scratch = torch.empty_like(flow0), torch.empty_like(flow0)
     _check(lib().fav_flow_sweeps_robust_f32(_p(flow0), _p(coef), _p(weights), iters, sweeps_per_launch, _p(out), _p(scratch), w, h, _stream()))
+    return out
+
+
+def flow_coefficients_grad(a_grey, b_grey, flow0, alpha: float = 8.0, smooth_eps: float = 0.0):
+    """one warp of the gradient-constancy data term -> coef [5][H][W] = the planes (q11, q12, q22, e1, e2); with smooth_eps > 0 (the
+    edge-preserving smoothness) -> (coef, weights [H][W][4] = (n_l, n_r, n_u, n_d))"""
+    torch = _torch(); _chk_f32(a_grey, "a_grey"); _chk_f32(b_grey, "b_grey"); _chk_f32(flow0, "flow0")
+    h, w = a_grey.shape
+    coef = torch.empty((5, h, w), dtype=torch.float32, device=a_grey.device)
+    weights = torch.empty((h, w, 4), dtype=torch.float32, device=a_grey.device) if smooth_eps else None
+    _check(lib().fav_flow_coefficients_grad_f32(_p(a_grey), _p(b_grey), _p(flow0), C.c_float(alpha), C.c_float(smooth_eps), _p(coef), _p(weights),
+                                                w, h, _stream()))
+    return (coef, weights) if smooth_eps else coef
+
+
+def flow_sweeps_grad(flow0, coef, iters: int, sweeps_per_launch: int = 0, weights=None):
+    """`iters` sweeps of the tensor form; coef [5][H][W]; weights: the [H][W][4] of the weighted mean, None for the plain mean"""
+    torch = _torch(); _chk_f32(flow0, "flow0"); _chk_f32(coef, "coef")
+    if weights is not None:
+        _chk_f32(weights, "weights")
+    h, w, _ = flow0.shape
+    if tuple(coef.shape) != (5, h, w) or (weights is not None and tuple(weights.shape) != (h, w, 4)):
+        raise FavError("flow_sweeps_grad: coef must be [5][H][W] and weights [H][W][4] for a flow [H][W][2]")
+    out, scratch = torch.empty_like(flow0), torch.empty_like(flow0)
+    _check(lib().fav_flow_sweeps_grad_f32(_p(flow0), _p(coef), _p(weights), iters, sweeps_per_launch, _p(out), _p(scratch), w, h, _stream()))
     return out
 
 
@@ -501,13 +550,13 @@ class Stream:
         Returns (f32, u8, backward_flo, forward_flo)."""
         torch = _torch()
         f, u = self._outs(frame_u8_hwc.device, want_f32, want_u8)
-        o = _flow_opts(flow_opts)
+        o = _flow_opts_ex(flow_opts)
         nb = flow_pairs_workspace_bytes(self.W, self.H, 1, **flow_opts) if batched else flow_workspace_bytes(self.W, self.H, **flow_opts)
         ws = torch.empty(nb, dtype=torch.uint8, device=frame_u8_hwc.device)
         bw = torch.empty((self.H, self.W, 2), dtype=torch.float32, device=frame_u8_hwc.device)
         fw = torch.empty_like(bw)
-        _check(lib().fav_stream_next_frame_estimate(self.h, _p(frame_u8_hwc), _p(prev_frame_u8_hwc), C.byref(o), 1 if use_structure else 0,
-                                                    _p(bw), _p(fw), _p(ws), C.c_size_t(nb), _p(f), _p(u), _stream()))
+        _check(lib().fav_stream_next_frame_estimate_ex(self.h, _p(frame_u8_hwc), _p(prev_frame_u8_hwc), C.byref(o), 1 if use_structure else 0,
+                                                       _p(bw), _p(fw), _p(ws), C.c_size_t(nb), _p(f), _p(u), _stream()))
         return f, u, bw, fw
 
     def prefetch_mask(self, frame_u8_hwc, backward_flo, forward_flo, use_structure=False):

@@ -136,6 +136,22 @@ size_t fav_flow_pairs_workspace_bytes(int W, int H, int n_pairs, const fav_flow_
 int fav_flow_pairs_rgb8(const uint8_t* const* prev_rgb_hwc, const uint8_t* const* cur_rgb_hwc, int n_pairs, int W, int H,
                         const fav_flow_opts* opts_host, float* const* backward_flo, float* const* forward_flo,
                         void* workspace, size_t workspace_bytes, fav_hipstream_t stream);
+/* The extended options: fav_flow_opts (which keeps its 24 bytes) plus the DATA TERM.  FAV_FLOW_DATA_BRIGHTNESS (0) compares grey levels, as
+ * ever; FAV_FLOW_DATA_GRADIENT (1) compares the image gradients INSTEAD (gradient constancy, Brox et al. 2004; DESIGN.md, "Gradient-
+ * constancy data term"; restated by tests/util/flow_grad_model.py), so a change of exposure between the two frames -- gain, offset, a slow
+ * ramp -- is not read as motion; in constant light it costs a few hundredths of a pixel.  Any other value is FAV_EINVAL.  alpha 0 then
+ * means 8, with smooth_eps > 0 as well.  The workspace holds 20 instead of 16 bytes of coefficients per pixel and flow.  Every entry
+ * without _ex is its _ex twin with data_term 0: the same bits, launches and workspace. */
+#define FAV_FLOW_DATA_BRIGHTNESS 0
+#define FAV_FLOW_DATA_GRADIENT 1
+typedef struct fav_flow_opts_ex { fav_flow_opts base; int data_term; } fav_flow_opts_ex;
+size_t fav_flow_workspace_bytes_ex(int W, int H, const fav_flow_opts_ex* opts_host);
+int fav_flow_rgb8_ex(const uint8_t* a_rgb_hwc, const uint8_t* b_rgb_hwc, int W, int H, const fav_flow_opts_ex* opts_host,
+                     float* flow_out, void* workspace, size_t workspace_bytes, fav_hipstream_t stream);
+size_t fav_flow_pairs_workspace_bytes_ex(int W, int H, int n_pairs, const fav_flow_opts_ex* opts_host);
+int fav_flow_pairs_rgb8_ex(const uint8_t* const* prev_rgb_hwc, const uint8_t* const* cur_rgb_hwc, int n_pairs, int W, int H,
+                           const fav_flow_opts_ex* opts_host, float* const* backward_flo, float* const* forward_flo,
+                           void* workspace, size_t workspace_bytes, fav_hipstream_t stream);
 /* the estimator's stages on their own (operator-level entries, as fav_scale_bicubic_f32 is one): the grey image [H][W]; one pyramid step
  * to ceil(W/2) x ceil(H/2); the x2 flow upsampling between two level sizes; the coefficients (a, b, c, r) of one warp around flow0,
  * [H][W][4], 16-byte aligned; `iters` Jacobi sweeps from flow0 into flow_out (scratch: a second flow buffer [H][W][2]; flow0 is not
@@ -153,6 +169,14 @@ int fav_flow_coefficients_robust_f32(const float* a_grey, const float* b_grey, c
                                      float* weights, int W, int H, fav_hipstream_t stream);
 int fav_flow_sweeps_robust_f32(const float* flow0, const float* coef, const float* weights, int iters, int sweeps_per_launch, float* flow_out,
                                float* scratch, int W, int H, fav_hipstream_t stream);
+/* The _grad_ pair is one warp of the gradient-constancy data term: coef is FIVE PLANES [5][H][W] (q11, q12, q22, e1, e2), 4-byte aligned --
+ * the per-pixel 2 x 2 system already solved, so that a sweep is u = (q11 u_bar + q12 v_bar) + e1, v = (q12 u_bar + q22 v_bar) + e2.
+ * weights NULL: the quadratic smoothness term and the plain mean (smooth_eps is not read); otherwise the edge-preserving smoothness, with
+ * the weights written by the coefficients and read by the sweeps as in the _robust_ pair. */
+int fav_flow_coefficients_grad_f32(const float* a_grey, const float* b_grey, const float* flow0, float alpha, float smooth_eps, float* coef,
+                                   float* weights, int W, int H, fav_hipstream_t stream);
+int fav_flow_sweeps_grad_f32(const float* flow0, const float* coef, const float* weights, int iters, int sweeps_per_launch, float* flow_out,
+                             float* scratch, int W, int H, fav_hipstream_t stream);
 
 /* ---- A6/A7: VGG preprocessing + 7-channel input assembly --------------------------------------
  * Replaces run_next_image's input construction (fast_artistic_video_core.lua:161-171) and the first
@@ -306,6 +330,11 @@ int fav_stream_next_frame_estimate(fav_stream* s, const uint8_t* frame_rgb_hwc, 
                                    const fav_flow_opts* flow_opts_host, int use_structure, float* backward_flo, float* forward_flo,
                                    void* workspace, size_t workspace_bytes, float* out_rgb_f32, uint8_t* out_rgb8_hwc,
                                    fav_hipstream_t stream);
+/* ... with the extended flow options (fav_flow_opts_ex: the data term); workspace sizes from the _ex queries */
+int fav_stream_next_frame_estimate_ex(fav_stream* s, const uint8_t* frame_rgb_hwc, const uint8_t* prev_frame_rgb_hwc,
+                                      const fav_flow_opts_ex* flow_opts_host, int use_structure, float* backward_flo, float* forward_flo,
+                                      void* workspace, size_t workspace_bytes, float* out_rgb_f32, uint8_t* out_rgb8_hwc,
+                                      fav_hipstream_t stream);
 /* optional look-ahead: start computing the consistency mask of a FUTURE frame on an internal side stream (the mask
  * depends only on that frame and its two flows, not on the recurrent state), so the order-preserving 4-argument
  * structure pass overlaps the network of the current frame.  The inputs must already be complete on `stream`.  The next
