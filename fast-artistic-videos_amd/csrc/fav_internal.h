@@ -320,14 +320,16 @@ struct FlowPtrs {
 int launch_flow_grey(const FlowPtrs& rgb_hwc, const FlowPtrs& grey, int items, int W, int H, hipStream_t st);
 int launch_flow_down(const FlowPtrs& src, int W, int H, const FlowPtrs& dst, int items, hipStream_t st);   // dst: ceil(W/2) x ceil(H/2)
 int launch_flow_up(const FlowPtrs& coarse, int Wc, int Hc, const FlowPtrs& fine, int items, int W, int H, hipStream_t st);
-// `wgt` (both): the edge weights of the edge-preserving smoothness (smooth_eps > 0), [H][W][4] (n_l, n_r, n_u, n_d), 16-byte aligned --
-// written by launch_flow_coef from flow0 and `eps`, read by the sweeps; nullptr: the quadratic term, the kernels of before.
-// `grad` (both): the gradient-constancy data term (tests/util/flow_grad_model.py); `coef` is then five planes [5][H][W] (q11, q12, q22, e1,
-// e2), 4-byte aligned
-int launch_flow_coef(const FlowPtrs& A, const FlowPtrs& B, const FlowPtrs& flow0, float alpha, float eps, const FlowPtrs& coef, const FlowPtrs* wgt,
-                     int items, int W, int H, hipStream_t st, bool grad = false);
-int launch_flow_sweeps(FlowPtrs* cur, FlowPtrs* other, const FlowPtrs& coef, const FlowPtrs* wgt, int items, int iters, int K, int W, int H,
-                       hipStream_t st, bool grad = false);
+// The variant of the coefficient and sweep launches.  wgt: the edge weights of the edge-preserving smoothness (smooth_eps > 0), [H][W][4]
+// (n_l, n_r, n_u, n_d), 16-byte aligned -- written by launch_flow_coef from flow0 and `eps`, read by the sweeps; nullptr: the quadratic
+// term (eps is not read).  grad: the gradient-constancy data term (tests/util/flow_grad_model.py); `coef` is then five planes [5][H][W]
+// (q11, q12, q22, e1, e2), 4-byte aligned
+struct FlowVariant { float alpha; float eps; bool grad; const FlowPtrs* wgt; };
+int launch_flow_coef(const FlowPtrs& A, const FlowPtrs& B, const FlowPtrs& flow0, const FlowPtrs& coef, const FlowVariant& v, int items, int W, int H,
+                     hipStream_t st);
+int launch_flow_sweeps(FlowPtrs* cur, FlowPtrs* other, const FlowPtrs& coef, const FlowVariant& v, int items, int iters, int K, int W, int H, hipStream_t st);
+// the options of an entry from before data_term existed: its fav_flow_opts (or none) with the brightness term
+inline fav_flow_opts_ex flow_opts_brightness(const fav_flow_opts* o) { return {o ? *o : fav_flow_opts{0, 0, 0, 0.f, 0, 0.f}, FAV_FLOW_DATA_BRIGHTNESS}; }
 // Huffman codes of the PNG encoder (png_tables.cpp): PNG_NTABLES model codes with their dynamic-block headers + the fixed code
 constexpr int PNG_NSYM = 277;            // literals 0..255, end of block 256, length symbols 257..276 (runs of 3..66)
 constexpr int PNG_NTABLES = 12;

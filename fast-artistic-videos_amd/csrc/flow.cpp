@@ -20,8 +20,7 @@ constexpr float MIN_EPS = 1e-6f, MAX_EPS = 1e6f;                      // eps^2 a
 // of one kind at one level lie one behind the other, `stride` bytes apart (a multiple of 256).
 struct FlowPlan {
     int levels = 0, warps = 0, iters = 0, K = 0, images = 0, flows = 0;
-    float alpha = 0.f, eps = 0.f;                                            // eps > 0: edge-preserving smoothness
-    bool grad = false;                                                       // the gradient-constancy data term: coef is five planes
+    FlowVariant v = {0.f, 0.f, false, nullptr};                              // eps > 0: edge-preserving smoothness (wgt: set by run_plan)
     int w[MAX_LEVELS], h[MAX_LEVELS];
     size_t pyr[MAX_LEVELS], pyr_stride[MAX_LEVELS];                          // byte offsets into the workspace: `images` grey planes
     size_t flow0[MAX_LEVELS], flow1[MAX_LEVELS], flow_stride[MAX_LEVELS];    // the two flow buffers of a level, `flows` planes each (level 0:
@@ -32,12 +31,12 @@ struct FlowPlan {
 // FAV_OK or FAV_EINVAL (message set)
 int make_plan(int W, int H, const fav_flow_opts_ex* ex, int images, int flows, FlowPlan& p)
 {
-    static const fav_flow_opts_ex none = {{0, 0, 0, 0.f, 0, 0.f}, FAV_FLOW_DATA_BRIGHTNESS};
+    static const fav_flow_opts_ex none = flow_opts_brightness(nullptr);
     if (!ex) ex = &none;
     const fav_flow_opts* o = &ex->base;
     FAV_REQUIRE(ex->data_term == FAV_FLOW_DATA_BRIGHTNESS || ex->data_term == FAV_FLOW_DATA_GRADIENT,
                 "fav_flow: data_term must be 0 (brightness constancy) or 1 (gradient constancy), not %d", ex->data_term);
-    p.grad = ex->data_term == FAV_FLOW_DATA_GRADIENT;
+    p.v.grad = ex->data_term == FAV_FLOW_DATA_GRADIENT;
     FAV_REQUIRE(W >= MIN_SIDE && H >= MIN_SIDE && (long long)W * H <= (1ll << 28), "fav_flow: frames must be at least %dx%d (and at most 2^28 pixels), not %dx%d", MIN_SIDE, MIN_SIDE, W, H);
     FAV_REQUIRE(o->levels >= 0 && o->levels <= MAX_LEVELS, "fav_flow: levels must be 0 (default) .. %d, not %d", MAX_LEVELS, o->levels);
     FAV_REQUIRE(o->warps >= 0 && o->warps <= 32, "fav_flow: warps must be 0 (default) .. 32, not %d", o->warps);
@@ -46,11 +45,11 @@ int make_plan(int W, int H, const fav_flow_opts_ex* ex, int images, int flows, F
     FAV_REQUIRE(o->sweeps_per_launch >= 0 && o->sweeps_per_launch <= FLOW_MAX_SWEEPS_PER_LAUNCH, "fav_flow: sweeps_per_launch must be 0 (default) .. %d, not %d", FLOW_MAX_SWEEPS_PER_LAUNCH, o->sweeps_per_launch);
     FAV_REQUIRE(o->smooth_eps == 0.f || (std::isfinite(o->smooth_eps) && o->smooth_eps >= MIN_EPS && o->smooth_eps <= MAX_EPS),
                 "fav_flow: smooth_eps must be 0 (off) or a number in 1e-6 .. 1e6, not %g", (double)o->smooth_eps);
-    p.eps = o->smooth_eps;
+    p.v.eps = o->smooth_eps;
     p.warps = o->warps ? o->warps : DEFAULT_WARPS;
     p.iters = o->iters ? o->iters : DEFAULT_ITERS;
-    p.alpha = o->alpha != 0.f ? o->alpha
-            : p.grad ? (p.eps > 0.f ? DEFAULT_ALPHA_GRAD_ROBUST : DEFAULT_ALPHA_GRAD) : (p.eps > 0.f ? DEFAULT_ALPHA_ROBUST : DEFAULT_ALPHA);
+    p.v.alpha = o->alpha != 0.f ? o->alpha
+              : p.v.grad ? (p.v.eps > 0.f ? DEFAULT_ALPHA_GRAD_ROBUST : DEFAULT_ALPHA_GRAD) : (p.v.eps > 0.f ? DEFAULT_ALPHA_ROBUST : DEFAULT_ALPHA);
     p.K = o->sweeps_per_launch ? o->sweeps_per_launch : DEFAULT_SWEEPS_PER_LAUNCH;
     p.images = images; p.flows = flows;
     p.w[0] = W; p.h[0] = H; p.levels = 1;
@@ -69,10 +68,10 @@ int make_plan(int W, int H, const fav_flow_opts_ex* ex, int images, int flows, F
         p.pyr[l] = take(p.pyr_stride[l], images);
         p.flow0[l] = l ? take(p.flow_stride[l], flows) : 0; p.flow1[l] = take(p.flow_stride[l], flows);
     }
-    p.coef_stride = round256((size_t)W * H * (p.grad ? 20 : 16));
+    p.coef_stride = round256((size_t)W * H * (p.v.grad ? 20 : 16));
     p.coef = take(p.coef_stride, flows);
     p.wgt_stride = round256((size_t)W * H * 16);
-    if (p.eps > 0.f) p.wgt = take(p.wgt_stride, flows);
+    if (p.v.eps > 0.f) p.wgt = take(p.wgt_stride, flows);
     p.bytes = off;
     return FAV_OK;
 }
@@ -93,7 +92,8 @@ int run_plan(const FlowPlan& p, const FlowPtrs& img, const int* a_of, const int*
     const int swaps = p.warps * ((p.iters + p.K - 1) / p.K);
     const FlowPtrs coef(ws + p.coef, p.coef_stride, p.flows);
     const FlowPtrs wgt_planes(ws + p.wgt, p.wgt_stride, p.flows);
-    const FlowPtrs* wgt = p.eps > 0.f ? &wgt_planes : nullptr;
+    FlowVariant v = p.v;
+    if (v.eps > 0.f) v.wgt = &wgt_planes;
     FlowPtrs coarser;
     for (int l = p.levels - 1; l >= 0; --l) {
         FlowPtrs cur = l ? FlowPtrs(ws + p.flow0[l], p.flow_stride[l], p.flows) : out;
@@ -111,8 +111,8 @@ int run_plan(const FlowPlan& p, const FlowPtrs& img, const int* a_of, const int*
             else for (int j = 0; j < p.flows; ++j) FAV_HIP(hipMemsetAsync(cur.p[j], 0, (size_t)w * h * 8, st));
         } else { rc = launch_flow_up(coarser, p.w[l + 1], p.h[l + 1], cur, p.flows, w, h, st); if (rc) return rc; }
         for (int k = 0; k < p.warps; ++k) {
-            rc = launch_flow_coef(A, B, cur, p.alpha, p.eps, coef, wgt, p.flows, w, h, st, p.grad); if (rc) return rc;
-            rc = launch_flow_sweeps(&cur, &other, coef, wgt, p.flows, p.iters, p.K, w, h, st, p.grad); if (rc) return rc;
+            rc = launch_flow_coef(A, B, cur, coef, v, p.flows, w, h, st); if (rc) return rc;
+            rc = launch_flow_sweeps(&cur, &other, coef, v, p.flows, p.iters, p.K, w, h, st); if (rc) return rc;
         }
         coarser = cur;
     }
@@ -120,14 +120,6 @@ int run_plan(const FlowPlan& p, const FlowPtrs& img, const int* a_of, const int*
 }
 
 bool aligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
-
-// the options of an entry from before data_term existed: its fav_flow_opts (or none) with the brightness term
-fav_flow_opts_ex brightness(const fav_flow_opts* o)
-{
-    fav_flow_opts_ex ex = {{0, 0, 0, 0.f, 0, 0.f}, FAV_FLOW_DATA_BRIGHTNESS};
-    if (o) ex.base = *o;
-    return ex;
-}
 
 }  // namespace
 
@@ -139,14 +131,14 @@ extern "C" size_t fav_flow_workspace_bytes_ex(int W, int H, const fav_flow_opts_
 
 extern "C" size_t fav_flow_workspace_bytes(int W, int H, const fav_flow_opts* opts_host)
 {
-    const fav_flow_opts_ex ex = brightness(opts_host);
+    const fav_flow_opts_ex ex = flow_opts_brightness(opts_host);
     return fav_flow_workspace_bytes_ex(W, H, &ex);
 }
 
 extern "C" int fav_flow_rgb8(const uint8_t* a_rgb_hwc, const uint8_t* b_rgb_hwc, int W, int H, const fav_flow_opts* opts_host, float* flow_out,
                              void* workspace, size_t workspace_bytes, fav_hipstream_t stream)
 {
-    const fav_flow_opts_ex ex = brightness(opts_host);
+    const fav_flow_opts_ex ex = flow_opts_brightness(opts_host);
     return fav_flow_rgb8_ex(a_rgb_hwc, b_rgb_hwc, W, H, &ex, flow_out, workspace, workspace_bytes, stream);
 }
 
@@ -166,7 +158,7 @@ extern "C" int fav_flow_rgb8_ex(const uint8_t* a_rgb_hwc, const uint8_t* b_rgb_h
 
 extern "C" size_t fav_flow_pairs_workspace_bytes(int W, int H, int n_pairs, const fav_flow_opts* opts_host)
 {
-    const fav_flow_opts_ex ex = brightness(opts_host);
+    const fav_flow_opts_ex ex = flow_opts_brightness(opts_host);
     return fav_flow_pairs_workspace_bytes_ex(W, H, n_pairs, &ex);
 }
 
@@ -174,7 +166,7 @@ extern "C" int fav_flow_pairs_rgb8(const uint8_t* const* prev_rgb_hwc, const uin
                                    const fav_flow_opts* opts_host, float* const* backward_flo, float* const* forward_flo, void* workspace,
                                    size_t workspace_bytes, fav_hipstream_t stream)
 {
-    const fav_flow_opts_ex ex = brightness(opts_host);
+    const fav_flow_opts_ex ex = flow_opts_brightness(opts_host);
     return fav_flow_pairs_rgb8_ex(prev_rgb_hwc, cur_rgb_hwc, n_pairs, W, H, &ex, backward_flo, forward_flo, workspace, workspace_bytes, stream);
 }
 
@@ -233,83 +225,81 @@ extern "C" int fav_flow_down_f32(const float* src, float* dst, int W, int H, fav
 extern "C" int fav_flow_up_f32(const float* coarse_flow, int Wc, int Hc, float* fine_flow, int W, int H, fav_hipstream_t stream)
 {
     FAV_REQUIRE(coarse_flow && fine_flow && Wc > 0 && Hc > 0 && W > 0 && H > 0, "fav_flow_up_f32: bad argument");
-    FAV_REQUIRE(reinterpret_cast<uintptr_t>(coarse_flow) % 8 == 0 && reinterpret_cast<uintptr_t>(fine_flow) % 8 == 0, "fav_flow_up_f32: flows must be 8-byte aligned");
+    FAV_REQUIRE(aligned(coarse_flow, 8) && aligned(fine_flow, 8), "fav_flow_up_f32: flows must be 8-byte aligned");
     int rc = ensure_device(); if (rc) return rc;
     return launch_flow_up(FlowPtrs(coarse_flow), Wc, Hc, FlowPtrs(fine_flow), 1, W, H, static_cast<hipStream_t>(stream));
 }
 
-extern "C" int fav_flow_coefficients_f32(const float* a_grey, const float* b_grey, const float* flow0, float alpha, float* coef, int W, int H,
-                                         fav_hipstream_t stream)
-{
-    FAV_REQUIRE(a_grey && b_grey && flow0 && coef && W > 0 && H > 0 && std::isfinite(alpha) && alpha > 0.f, "fav_flow_coefficients_f32: bad argument");
-    FAV_REQUIRE(reinterpret_cast<uintptr_t>(flow0) % 8 == 0 && reinterpret_cast<uintptr_t>(coef) % 16 == 0, "fav_flow_coefficients_f32: flow0 must be 8-byte aligned, coef 16-byte aligned");
-    int rc = ensure_device(); if (rc) return rc;
-    return launch_flow_coef(FlowPtrs(a_grey), FlowPtrs(b_grey), FlowPtrs(flow0), alpha, 0.f, FlowPtrs(coef), nullptr, 1, W, H, static_cast<hipStream_t>(stream));
-}
-
-extern "C" int fav_flow_coefficients_robust_f32(const float* a_grey, const float* b_grey, const float* flow0, float alpha, float smooth_eps, float* coef,
-                                                float* weights, int W, int H, fav_hipstream_t stream)
-{
-    FAV_REQUIRE(a_grey && b_grey && flow0 && coef && weights && W > 0 && H > 0 && std::isfinite(alpha) && alpha > 0.f, "fav_flow_coefficients_robust_f32: bad argument");
-    FAV_REQUIRE(std::isfinite(smooth_eps) && smooth_eps >= MIN_EPS && smooth_eps <= MAX_EPS, "fav_flow_coefficients_robust_f32: smooth_eps must be a number in 1e-6 .. 1e6, not %g", (double)smooth_eps);
-    FAV_REQUIRE(reinterpret_cast<uintptr_t>(flow0) % 8 == 0 && reinterpret_cast<uintptr_t>(coef) % 16 == 0 && reinterpret_cast<uintptr_t>(weights) % 16 == 0 && coef != weights,
-                "fav_flow_coefficients_robust_f32: flow0 must be 8-byte aligned, coef and weights 16-byte aligned and distinct");
-    int rc = ensure_device(); if (rc) return rc;
-    const FlowPtrs wgt(weights);
-    return launch_flow_coef(FlowPtrs(a_grey), FlowPtrs(b_grey), FlowPtrs(flow0), alpha, smooth_eps, FlowPtrs(coef), &wgt, 1, W, H, static_cast<hipStream_t>(stream));
-}
-
-// the gradient-constancy term: coef is five planes [5][H][W]; weights == nullptr: the quadratic smoothness term (smooth_eps is not read)
-extern "C" int fav_flow_coefficients_grad_f32(const float* a_grey, const float* b_grey, const float* flow0, float alpha, float smooth_eps, float* coef,
-                                              float* weights, int W, int H, fav_hipstream_t stream)
-{
-    FAV_REQUIRE(a_grey && b_grey && flow0 && coef && W > 0 && H > 0 && std::isfinite(alpha) && alpha > 0.f, "fav_flow_coefficients_grad_f32: bad argument");
-    FAV_REQUIRE(!weights || (std::isfinite(smooth_eps) && smooth_eps >= MIN_EPS && smooth_eps <= MAX_EPS), "fav_flow_coefficients_grad_f32: smooth_eps must be a number in 1e-6 .. 1e6, not %g", (double)smooth_eps);
-    FAV_REQUIRE(reinterpret_cast<uintptr_t>(flow0) % 8 == 0 && reinterpret_cast<uintptr_t>(coef) % 4 == 0 && reinterpret_cast<uintptr_t>(weights) % 16 == 0 && coef != weights,
-                "fav_flow_coefficients_grad_f32: flow0 must be 8-byte aligned, coef 4-byte aligned, weights 16-byte aligned and distinct from coef");
-    int rc = ensure_device(); if (rc) return rc;
-    const FlowPtrs wgt(weights);
-    return launch_flow_coef(FlowPtrs(a_grey), FlowPtrs(b_grey), FlowPtrs(flow0), alpha, weights ? smooth_eps : 0.f, FlowPtrs(coef), weights ? &wgt : nullptr, 1, W, H,
-                            static_cast<hipStream_t>(stream), true);
-}
-
 namespace {
+
+// the coefficient entries: `weights` == nullptr is the quadratic smoothness term (smooth_eps is not read); grad: the gradient-constancy
+// term (coef: five planes [5][H][W], 4-byte aligned)
+int coef_entry(const char* who, const float* a_grey, const float* b_grey, const float* flow0, float alpha, float smooth_eps, float* coef, float* weights,
+               int W, int H, fav_hipstream_t stream, bool grad)
+{
+    FAV_REQUIRE(a_grey && b_grey && flow0 && coef && W > 0 && H > 0 && std::isfinite(alpha) && alpha > 0.f, "%s: bad argument", who);
+    FAV_REQUIRE(!weights || (std::isfinite(smooth_eps) && smooth_eps >= MIN_EPS && smooth_eps <= MAX_EPS), "%s: smooth_eps must be a number in 1e-6 .. 1e6, not %g", who, (double)smooth_eps);
+    FAV_REQUIRE(aligned(flow0, 8) && aligned(coef, grad ? 4 : 16) && aligned(weights, 16) && coef != weights, "%s: flow0 must be 8-byte aligned, coef %s", who,
+                grad ? "4-byte aligned, weights 16-byte aligned and distinct from coef" : weights ? "and weights 16-byte aligned and distinct" : "16-byte aligned");
+    int rc = ensure_device(); if (rc) return rc;
+    const FlowPtrs wgt(weights);
+    return launch_flow_coef(FlowPtrs(a_grey), FlowPtrs(b_grey), FlowPtrs(flow0), FlowPtrs(coef), {alpha, weights ? smooth_eps : 0.f, grad, weights ? &wgt : nullptr}, 1, W, H,
+                            static_cast<hipStream_t>(stream));
+}
 
 // the sweep entries: `weights` == nullptr is the plain mean; grad: the tensor form (coef: five planes, 4-byte aligned)
 int sweeps_entry(const char* who, const float* flow0, const float* coef, const float* weights, int iters, int sweeps_per_launch, float* flow_out,
-                 float* scratch, int W, int H, fav_hipstream_t stream, bool grad = false)
+                 float* scratch, int W, int H, fav_hipstream_t stream, bool grad)
 {
     FAV_REQUIRE(flow0 && coef && flow_out && scratch && W > 0 && H > 0, "%s: bad argument", who);
     FAV_REQUIRE(iters >= 1 && sweeps_per_launch >= 0 && sweeps_per_launch <= FLOW_MAX_SWEEPS_PER_LAUNCH, "%s: iters must be >= 1, sweeps_per_launch 0 (default) .. %d", who, FLOW_MAX_SWEEPS_PER_LAUNCH);
-    FAV_REQUIRE(reinterpret_cast<uintptr_t>(flow0) % 8 == 0 && reinterpret_cast<uintptr_t>(flow_out) % 8 == 0 && reinterpret_cast<uintptr_t>(scratch) % 8 == 0 &&
-                reinterpret_cast<uintptr_t>(coef) % (grad ? 4 : 16) == 0 && reinterpret_cast<uintptr_t>(weights) % 16 == 0, "%s: flows must be 8-byte aligned, coef%s 16-byte aligned", who,
-                grad ? " 4-byte aligned, weights" : weights ? " and weights" : "");
+    FAV_REQUIRE(aligned(flow0, 8) && aligned(flow_out, 8) && aligned(scratch, 8) && aligned(coef, grad ? 4 : 16) && aligned(weights, 16),
+                "%s: flows must be 8-byte aligned, coef%s 16-byte aligned", who, grad ? " 4-byte aligned, weights" : weights ? " and weights" : "");
     int rc = ensure_device(); if (rc) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int K = sweeps_per_launch ? sweeps_per_launch : DEFAULT_SWEEPS_PER_LAUNCH;
     // flow0 is read only: the first launch goes from it into the buffer from which the remaining launches end in flow_out
     const int first = std::min(K, iters), rest_launches = (iters - first + K - 1) / K;
     FlowPtrs src(flow0), cur((rest_launches & 1) ? scratch : flow_out), other((rest_launches & 1) ? flow_out : scratch), first_dst = cur;
-    const FlowPtrs cf(coef), wgt_plane(weights);
-    const FlowPtrs* wgt = weights ? &wgt_plane : nullptr;
-    rc = launch_flow_sweeps(&src, &first_dst, cf, wgt, 1, first, K, W, H, st, grad); if (rc) return rc;
-    if (iters > first) { rc = launch_flow_sweeps(&cur, &other, cf, wgt, 1, iters - first, K, W, H, st, grad); if (rc) return rc; }
+    const FlowPtrs cf(coef), wgt(weights);
+    const FlowVariant v = {0.f, 0.f, grad, weights ? &wgt : nullptr};      // (the sweeps read neither alpha nor eps)
+    rc = launch_flow_sweeps(&src, &first_dst, cf, v, 1, first, K, W, H, st); if (rc) return rc;
+    if (iters > first) { rc = launch_flow_sweeps(&cur, &other, cf, v, 1, iters - first, K, W, H, st); if (rc) return rc; }
     return FAV_OK;
 }
 
 }  // namespace
 
+extern "C" int fav_flow_coefficients_f32(const float* a_grey, const float* b_grey, const float* flow0, float alpha, float* coef, int W, int H,
+                                         fav_hipstream_t stream)
+{
+    return coef_entry("fav_flow_coefficients_f32", a_grey, b_grey, flow0, alpha, 0.f, coef, nullptr, W, H, stream, false);
+}
+
+extern "C" int fav_flow_coefficients_robust_f32(const float* a_grey, const float* b_grey, const float* flow0, float alpha, float smooth_eps, float* coef,
+                                                float* weights, int W, int H, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(weights, "fav_flow_coefficients_robust_f32: bad argument");
+    return coef_entry("fav_flow_coefficients_robust_f32", a_grey, b_grey, flow0, alpha, smooth_eps, coef, weights, W, H, stream, false);
+}
+
+extern "C" int fav_flow_coefficients_grad_f32(const float* a_grey, const float* b_grey, const float* flow0, float alpha, float smooth_eps, float* coef,
+                                              float* weights, int W, int H, fav_hipstream_t stream)
+{
+    return coef_entry("fav_flow_coefficients_grad_f32", a_grey, b_grey, flow0, alpha, smooth_eps, coef, weights, W, H, stream, true);
+}
+
 extern "C" int fav_flow_sweeps_f32(const float* flow0, const float* coef, int iters, int sweeps_per_launch, float* flow_out, float* scratch,
                                    int W, int H, fav_hipstream_t stream)
 {
-    return sweeps_entry("fav_flow_sweeps_f32", flow0, coef, nullptr, iters, sweeps_per_launch, flow_out, scratch, W, H, stream);
+    return sweeps_entry("fav_flow_sweeps_f32", flow0, coef, nullptr, iters, sweeps_per_launch, flow_out, scratch, W, H, stream, false);
 }
 
 extern "C" int fav_flow_sweeps_robust_f32(const float* flow0, const float* coef, const float* weights, int iters, int sweeps_per_launch, float* flow_out,
                                           float* scratch, int W, int H, fav_hipstream_t stream)
 {
     FAV_REQUIRE(weights, "fav_flow_sweeps_robust_f32: bad argument");
-    return sweeps_entry("fav_flow_sweeps_robust_f32", flow0, coef, weights, iters, sweeps_per_launch, flow_out, scratch, W, H, stream);
+    return sweeps_entry("fav_flow_sweeps_robust_f32", flow0, coef, weights, iters, sweeps_per_launch, flow_out, scratch, W, H, stream, false);
 }
 
 extern "C" int fav_flow_sweeps_grad_f32(const float* flow0, const float* coef, const float* weights, int iters, int sweeps_per_launch, float* flow_out,
@@ -317,3 +307,4 @@ extern "C" int fav_flow_sweeps_grad_f32(const float* flow0, const float* coef, c
 {
     return sweeps_entry("fav_flow_sweeps_grad_f32", flow0, coef, weights, iters, sweeps_per_launch, flow_out, scratch, W, H, stream, true);
 }
+

@@ -24,6 +24,8 @@
 // have one size, and an item's planes are found through FlowPtrs tables that travel BY VALUE in the kernel arguments (<= 16 pointers each,
 // read with scalar loads; no table in device memory, so a call needs no copy and may run on two streams at once).  The per-pixel
 // arithmetic knows nothing of the batch: an item's bits are those of a launch of its own.
+#include <type_traits>
+
 #include "fav_internal.h"
 
 namespace fav {
@@ -103,6 +105,30 @@ template <> struct CoefRobustArgs<true> { float eps2; FlowPtrs wgts; };
 template <bool ROBUST> struct SweepRobustArgs {};
 template <> struct SweepRobustArgs<true> { FlowPtrs wgts; };
 
+// Bw at (xx, yy) inside the image: B at the pixel displaced by its own flow
+__device__ __forceinline__ float warped(const float* __restrict__ B, const float2* __restrict__ flow0, int w, int h, int yy, int xx)
+{
+    const float2 f = flow0[(size_t)yy * w + xx];
+    return bilinear(B, w, h, (float)xx + f.x, (float)yy + f.y);
+}
+
+// the diffusivity and the four edge weights of pixel (x, y): stores the normalised n_q = w_q / S at wgt and returns S
+__device__ __forceinline__ float edge_weights(const float2* __restrict__ flow0, int w, int h, int x, int y, float eps2, float4* wgt)
+{
+    auto g_at = [&](int yy, int xx) {      // yy, xx inside the image
+        const float2 l = flow0[(size_t)yy * w + max(xx - 1, 0)], r = flow0[(size_t)yy * w + min(xx + 1, w - 1)];
+        const float2 u = flow0[(size_t)max(yy - 1, 0) * w + xx], d = flow0[(size_t)min(yy + 1, h - 1) * w + xx];
+        const float ux = (r.x - l.x) * 0.5f, vx = (r.y - l.y) * 0.5f, uy = (d.x - u.x) * 0.5f, vy = (d.y - u.y) * 0.5f;
+        return 1.f / sqrtf(((ux * ux + vx * vx) + (uy * uy + vy * vy)) + eps2);      // sqrt and division correctly rounded, each
+    };
+    const float gp = g_at(y, x);
+    const float wl = 0.5f * (gp + g_at(y, max(x - 1, 0))), wr = 0.5f * (gp + g_at(y, min(x + 1, w - 1)));
+    const float wu = 0.5f * (gp + g_at(max(y - 1, 0), x)), wd = 0.5f * (gp + g_at(min(y + 1, h - 1), x));
+    const float S = (wl + wr) + (wu + wd);
+    *wgt = make_float4(wl / S, wr / S, wu / S, wd / S);
+    return S;
+}
+
 template <bool ROBUST>
 __global__ __launch_bounds__(256) void flow_coef_kernel(FlowPtrs As, FlowPtrs Bs, FlowPtrs flow0s, float alpha2, FlowPtrs coefs, int w, int h,
                                                         CoefRobustArgs<ROBUST> ra)
@@ -113,34 +139,17 @@ __global__ __launch_bounds__(256) void flow_coef_kernel(FlowPtrs As, FlowPtrs Bs
     float4* __restrict__ coef = static_cast<float4*>(coefs.p[blockIdx.z]);
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= w || y >= h) return;
-    auto bw = [&](int yy, int xx) {
-        const float2 f = flow0[(size_t)yy * w + xx];
-        return bilinear(B, w, h, (float)xx + f.x, (float)yy + f.y);
-    };
+    auto bw = [&](int yy, int xx) { return warped(B, flow0, w, h, yy, xx); };
     const float2 f0 = flow0[(size_t)y * w + x];
     const float bc = bilinear(B, w, h, (float)x + f0.x, (float)y + f0.y);
     const float a = (bw(y, min(x + 1, w - 1)) - bw(y, max(x - 1, 0))) * 0.5f;
     const float b = (bw(min(y + 1, h - 1), x) - bw(max(y - 1, 0), x)) * 0.5f;
     const float it = bc - A[(size_t)y * w + x];
     const float c = (it - a * f0.x) - b * f0.y;
-    if constexpr (!ROBUST) {
-        const float r = 1.f / ((alpha2 + a * a) + b * b);      // one correctly rounded division (-fhip-fp32-correctly-rounded-divide-sqrt)
-        coef[(size_t)y * w + x] = make_float4(a, b, c, r);
-    } else {
-        auto g_at = [&](int yy, int xx) {      // yy, xx inside the image
-            const float2 l = flow0[(size_t)yy * w + max(xx - 1, 0)], r = flow0[(size_t)yy * w + min(xx + 1, w - 1)];
-            const float2 u = flow0[(size_t)max(yy - 1, 0) * w + xx], d = flow0[(size_t)min(yy + 1, h - 1) * w + xx];
-            const float ux = (r.x - l.x) * 0.5f, vx = (r.y - l.y) * 0.5f, uy = (d.x - u.x) * 0.5f, vy = (d.y - u.y) * 0.5f;
-            return 1.f / sqrtf(((ux * ux + vx * vx) + (uy * uy + vy * vy)) + ra.eps2);      // sqrt and division correctly rounded, each
-        };
-        const float gp = g_at(y, x);
-        const float wl = 0.5f * (gp + g_at(y, max(x - 1, 0))), wr = 0.5f * (gp + g_at(y, min(x + 1, w - 1)));
-        const float wu = 0.5f * (gp + g_at(max(y - 1, 0), x)), wd = 0.5f * (gp + g_at(min(y + 1, h - 1), x));
-        const float S = (wl + wr) + (wu + wd);
-        const float r = 1.f / ((((alpha2 * S) * 0.25f) + a * a) + b * b);
-        coef[(size_t)y * w + x] = make_float4(a, b, c, r);
-        static_cast<float4*>(ra.wgts.p[blockIdx.z])[(size_t)y * w + x] = make_float4(wl / S, wr / S, wu / S, wd / S);
-    }
+    float wgt = alpha2;
+    if constexpr (ROBUST) wgt = (alpha2 * edge_weights(flow0, w, h, x, y, ra.eps2, static_cast<float4*>(ra.wgts.p[blockIdx.z]) + (size_t)y * w + x)) * 0.25f;
+    const float r = 1.f / ((wgt + a * a) + b * b);      // one correctly rounded division (-fhip-fp32-correctly-rounded-divide-sqrt)
+    coef[(size_t)y * w + x] = make_float4(a, b, c, r);
 }
 
 // ---- gradient-constancy data term (fav_flow_opts_ex.data_term = FAV_FLOW_DATA_GRADIENT; restated by tests/util/flow_grad_model.py).
@@ -156,21 +165,6 @@ __global__ __launch_bounds__(256) void flow_coef_kernel(FlowPtrs As, FlowPtrs Bs
 // and reads A on its cross.  A second difference at the image border nests two clamps: clamp(clamp(x + 1) - 1) is x inside the image and
 // x - 1 on its last column, so the sample it needs is one of the 13 either way and is chosen by value.
 // The five values are planes, not a record: a wave's loads and stores are 256 contiguous bytes each, and 20 bytes per pixel need no padding.
-__device__ __forceinline__ float4 edge_weights(const float2* __restrict__ flow0, int w, int h, int x, int y, float eps2, float& S)
-{
-    auto g_at = [&](int yy, int xx) {      // yy, xx inside the image
-        const float2 l = flow0[(size_t)yy * w + max(xx - 1, 0)], r = flow0[(size_t)yy * w + min(xx + 1, w - 1)];
-        const float2 u = flow0[(size_t)max(yy - 1, 0) * w + xx], d = flow0[(size_t)min(yy + 1, h - 1) * w + xx];
-        const float ux = (r.x - l.x) * 0.5f, vx = (r.y - l.y) * 0.5f, uy = (d.x - u.x) * 0.5f, vy = (d.y - u.y) * 0.5f;
-        return 1.f / sqrtf(((ux * ux + vx * vx) + (uy * uy + vy * vy)) + eps2);
-    };
-    const float gp = g_at(y, x);
-    const float wl = 0.5f * (gp + g_at(y, max(x - 1, 0))), wr = 0.5f * (gp + g_at(y, min(x + 1, w - 1)));
-    const float wu = 0.5f * (gp + g_at(max(y - 1, 0), x)), wd = 0.5f * (gp + g_at(min(y + 1, h - 1), x));
-    S = (wl + wr) + (wu + wd);
-    return make_float4(wl, wr, wu, wd);
-}
-
 template <bool ROBUST>
 __global__ __launch_bounds__(256) void flow_coef_grad_kernel(FlowPtrs As, FlowPtrs Bs, FlowPtrs flow0s, float alpha2, FlowPtrs coefs, int w, int h,
                                                              CoefRobustArgs<ROBUST> ra)
@@ -181,10 +175,7 @@ __global__ __launch_bounds__(256) void flow_coef_grad_kernel(FlowPtrs As, FlowPt
     float* __restrict__ coef = static_cast<float*>(coefs.p[blockIdx.z]);
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= w || y >= h) return;
-    auto bw = [&](int yy, int xx) {        // yy, xx inside the image
-        const float2 f = flow0[(size_t)yy * w + xx];
-        return bilinear(B, w, h, (float)xx + f.x, (float)yy + f.y);
-    };
+    auto bw = [&](int yy, int xx) { return warped(B, flow0, w, h, yy, xx); };
     const int xm = max(x - 1, 0), xp = min(x + 1, w - 1), ym = max(y - 1, 0), yp = min(y + 1, h - 1);
     const float c0 = bw(y, x);
     const float l1 = bw(y, xm), r1 = bw(y, xp), u1 = bw(ym, x), d1 = bw(yp, x);
@@ -204,12 +195,7 @@ __global__ __launch_bounds__(256) void flow_coef_grad_kernel(FlowPtrs As, FlowPt
     const float J11 = ax * ax + ay * ay, J12 = ax * bx + ay * by, J22 = bx * bx + by * by;
     const float h1 = ax * cx + ay * cy, h2 = bx * cx + by * cy;
     float wgt = alpha2;
-    if constexpr (ROBUST) {
-        float S;
-        const float4 wq = edge_weights(flow0, w, h, x, y, ra.eps2, S);
-        wgt = (alpha2 * S) * 0.25f;
-        static_cast<float4*>(ra.wgts.p[blockIdx.z])[(size_t)y * w + x] = make_float4(wq.x / S, wq.y / S, wq.z / S, wq.w / S);
-    }
+    if constexpr (ROBUST) wgt = (alpha2 * edge_weights(flow0, w, h, x, y, ra.eps2, static_cast<float4*>(ra.wgts.p[blockIdx.z]) + (size_t)y * w + x)) * 0.25f;
     const float d11 = wgt + J11, d22 = wgt + J22;
     const float det = d11 * d22 - J12 * J12;
     const size_t n = (size_t)w * h, i = (size_t)y * w + x;
@@ -222,7 +208,7 @@ __global__ __launch_bounds__(256) void flow_coef_grad_kernel(FlowPtrs As, FlowPt
 
 // ---- the sweeps, temporally blocked.
 // A block owns a REGION of 64 x 64 cells: an interior of (64 - 2K)^2 cells and a halo of K cells around it.  It loads the region's (u, v)
-// into LDS (float2, 32 KB) and its coefficients into registers (a lane keeps one column position and 16 rows, ty + 4 j: 64 VGPRs), runs
+// into LDS (float2, 32 KB) and its coefficients into registers (a lane keeps one column position and ROWS rows, ty + TY j), runs
 // n <= K sweeps there and writes the interior.  After sweep s the cells nearer than s to the region's edge are stale; they are never
 // written back, and the interior stays s <= K cells away from them.
 // Image borders: a neighbour index is clamped to the IMAGE first (then to the region), at every sweep, so the edge cell of the image is
@@ -230,92 +216,61 @@ __global__ __launch_bounds__(256) void flow_coef_grad_kernel(FlowPtrs As, FlowPt
 // cell inside it and are never stored.
 // LDS traffic: a wave reads rows of 64 float2 -- 32 lanes x 8 B = one 256-B bank row per half wave, conflict-free for the centre, left /
 // right (shifted by one lane) and up / down (another row) taps alike.  Two barriers per sweep (all new values are formed in registers
-// before any is stored), one buffer: 32 KB per block leave four 256-thread blocks per CU next to ~110 VGPRs per lane.
-// ROBUST: the weighted mean of the edge-preserving smoothness.  The four normalised weights of a cell travel next to its coefficients, in
-// registers too: eight values per cell.  With 16 rows per lane that is 128 VGPRs of coefficients and the compiler's report shows 256
-// VGPRs + 46 AGPRs, one wave per SIMD; so this instantiation runs 512 lanes per block and 8 rows per lane (ty + 8 j) -- the same region,
-// the same LDS layout and barriers, half the cells per lane (the figures are in DESIGN.md).
+// before any is stored), one buffer: 32 KB per block.
+// The data term is the CELL: what a lane keeps per cell next to the flow, how it is loaded, and the update from the neighbour mean.
+// WEIGHTED: the weighted mean of the edge-preserving smoothness; the four normalised weights of a cell travel in registers too.
+// Rows per lane: the brightness cell with the plain mean takes 16 (64 VGPRs of coefficients, 256 lanes per block); with the weights that
+// would be 128 VGPRs of coefficients and one wave per SIMD, so every other instantiation runs 512 lanes per block and 8 rows per lane --
+// the same region, the same LDS layout and barriers, half the cells per lane (the figures are in DESIGN.md).
 constexpr int SW_R = 64;           // region side
 
-template <bool ROBUST>
+// brightness constancy: (a, b, c, r) of flow_coef_kernel;  t = ((a u_bar + b v_bar) + c) r;  u = u_bar - a t, v = v_bar - b t
+struct BrightCell {
+    static constexpr int rows(bool weighted) { return weighted ? 8 : 16; }
+    float4 cf;
+    __device__ __forceinline__ void load(const void* __restrict__ coef, size_t idx, size_t) { cf = static_cast<const float4*>(coef)[idx]; }
+    __device__ __forceinline__ float2 update(float ub, float vb) const
+    {
+        const float t = ((cf.x * ub + cf.y * vb) + cf.z) * cf.w;
+        return make_float2(ub - cf.x * t, vb - cf.y * t);
+    }
+};
+
+// gradient constancy, the tensor form: the five planes of flow_coef_grad_kernel
+struct GradCell {
+    static constexpr int rows(bool) { return 8; }
+    float q11, q12, q22, e1, e2;
+    __device__ __forceinline__ void load(const void* __restrict__ coef, size_t idx, size_t plane)
+    {
+        const float* __restrict__ c = static_cast<const float*>(coef);
+        q11 = c[idx]; q12 = c[plane + idx]; q22 = c[2 * plane + idx]; e1 = c[3 * plane + idx]; e2 = c[4 * plane + idx];
+    }
+    __device__ __forceinline__ float2 update(float ub, float vb) const { return make_float2((q11 * ub + q12 * vb) + e1, (q12 * ub + q22 * vb) + e2); }
+};
+
+// (u_bar, v_bar) of a cell from its four neighbours; wt is read only when WEIGHTED
+template <bool WEIGHTED>
+__device__ __forceinline__ float2 neighbour_mean(const float4& wt, float2 L, float2 R, float2 U, float2 D)
+{
+    if constexpr (WEIGHTED) return make_float2((wt.x * L.x + wt.y * R.x) + (wt.z * U.x + wt.w * D.x), (wt.x * L.y + wt.y * R.y) + (wt.z * U.y + wt.w * D.y));
+    else return make_float2(((L.x + R.x) + (U.x + D.x)) * 0.25f, ((L.y + R.y) + (U.y + D.y)) * 0.25f);
+}
+
+template <class Cell, bool WEIGHTED>
 struct SweepShape {
-    static constexpr int ROWS = ROBUST ? 8 : 16;       // rows per lane
+    static constexpr int ROWS = Cell::rows(WEIGHTED);  // rows per lane
     static constexpr int TY = SW_R / ROWS;             // lanes per column: 64 columns x TY lanes
     static constexpr int THREADS = SW_R * TY;          // 256 | 512
 };
 
-template <bool ROBUST>
-__global__ __launch_bounds__(SweepShape<ROBUST>::THREADS) void flow_sweep_kernel(FlowPtrs fins, FlowPtrs coefs, FlowPtrs fouts, int W, int H, int K, int n,
-                                                                                  SweepRobustArgs<ROBUST> ra)
+template <class Cell, bool WEIGHTED>
+__global__ __launch_bounds__((SweepShape<Cell, WEIGHTED>::THREADS)) void flow_sweep_kernel(FlowPtrs fins, FlowPtrs coefs, FlowPtrs fouts, int W, int H, int K, int n,
+                                                                                         SweepRobustArgs<WEIGHTED> ra)
 {
-    constexpr int SW_ROWS = SweepShape<ROBUST>::ROWS, TY = SweepShape<ROBUST>::TY;
+    constexpr int ROWS = SweepShape<Cell, WEIGHTED>::ROWS, TY = SweepShape<Cell, WEIGHTED>::TY;
     __shared__ float2 s[SW_R][SW_R];
     const float2* __restrict__ fin = static_cast<const float2*>(fins.p[blockIdx.z]);
-    const float4* __restrict__ coef = static_cast<const float4*>(coefs.p[blockIdx.z]);
-    float2* __restrict__ fout = static_cast<float2*>(fouts.p[blockIdx.z]);
-    const int lx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int TI = SW_R - 2 * K;
-    const int x0 = (int)blockIdx.x * TI - K, y0 = (int)blockIdx.y * TI - K;
-    const int gx = x0 + lx;
-    const int cx = min(max(gx, 0), W - 1);
-    const int lxl = (gx > 0 && lx > 0) ? lx - 1 : lx;
-    const int lxr = (gx < W - 1 && lx < SW_R - 1) ? lx + 1 : lx;
-    float4 cf[SW_ROWS];
-    float4 wt[ROBUST ? SW_ROWS : 1];
-    float2 nv[SW_ROWS];
-#pragma unroll
-    for (int j = 0; j < SW_ROWS; ++j) {
-        const int ly = ty + TY * j;
-        const int cy = min(max(y0 + ly, 0), H - 1);
-        const size_t idx = (size_t)cy * W + cx;
-        cf[j] = coef[idx];
-        if constexpr (ROBUST) wt[j] = static_cast<const float4*>(ra.wgts.p[blockIdx.z])[idx];
-        s[ly][lx] = fin[idx];
-    }
-    __syncthreads();
-    for (int sweep = 0; sweep < n; ++sweep) {
-#pragma unroll
-        for (int j = 0; j < SW_ROWS; ++j) {
-            const int ly = ty + TY * j, gy = y0 + ly;
-            const int lyu = (gy > 0 && ly > 0) ? ly - 1 : ly;
-            const int lyd = (gy < H - 1 && ly < SW_R - 1) ? ly + 1 : ly;
-            const float2 L = s[ly][lxl], R = s[ly][lxr], U = s[lyu][lx], D = s[lyd][lx];
-            float ub, vb;
-            if constexpr (ROBUST) {
-                ub = (wt[j].x * L.x + wt[j].y * R.x) + (wt[j].z * U.x + wt[j].w * D.x);
-                vb = (wt[j].x * L.y + wt[j].y * R.y) + (wt[j].z * U.y + wt[j].w * D.y);
-            } else {
-                ub = ((L.x + R.x) + (U.x + D.x)) * 0.25f;
-                vb = ((L.y + R.y) + (U.y + D.y)) * 0.25f;
-            }
-            const float t = ((cf[j].x * ub + cf[j].y * vb) + cf[j].z) * cf[j].w;
-            nv[j] = make_float2(ub - cf[j].x * t, vb - cf[j].y * t);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < SW_ROWS; ++j) s[ty + TY * j][lx] = nv[j];
-        __syncthreads();
-    }
-    if (lx < K || lx >= SW_R - K || gx >= W) return;      // (gx >= 0 here: lx >= K)
-#pragma unroll
-    for (int j = 0; j < SW_ROWS; ++j) {
-        const int ly = ty + TY * j, gy = y0 + ly;
-        if (ly >= K && ly < SW_R - K && gy < H) fout[(size_t)gy * W + gx] = s[ly][lx];
-    }
-}
-
-// The tensor form of the gradient-constancy term: the same region, LDS layout, clamping and barriers; a cell carries five values (q11, q12,
-// q22, e1, e2) instead of four, from the five planes of flow_coef_grad_kernel, and WEIGHTED adds the four n_q: nine values per cell.  Both
-// instantiations take the robust variant's shape -- 512 lanes, 8 rows per lane: 40 | 72 VGPRs of coefficients (the figures are in DESIGN.md).
-constexpr int SWG_ROWS = 8, SWG_TY = SW_R / SWG_ROWS, SWG_THREADS = SW_R * SWG_TY;
-
-template <bool WEIGHTED>
-__global__ __launch_bounds__(SWG_THREADS) void flow_sweep_grad_kernel(FlowPtrs fins, FlowPtrs coefs, FlowPtrs fouts, int W, int H, int K, int n,
-                                                                      SweepRobustArgs<WEIGHTED> ra)
-{
-    __shared__ float2 s[SW_R][SW_R];
-    const float2* __restrict__ fin = static_cast<const float2*>(fins.p[blockIdx.z]);
-    const float* __restrict__ coef = static_cast<const float*>(coefs.p[blockIdx.z]);
+    const void* __restrict__ coef = coefs.p[blockIdx.z];
     float2* __restrict__ fout = static_cast<float2*>(fouts.p[blockIdx.z]);
     const size_t plane = (size_t)W * H;
     const int lx = threadIdx.x & 63, ty = threadIdx.x >> 6;
@@ -325,47 +280,47 @@ __global__ __launch_bounds__(SWG_THREADS) void flow_sweep_grad_kernel(FlowPtrs f
     const int cx = min(max(gx, 0), W - 1);
     const int lxl = (gx > 0 && lx > 0) ? lx - 1 : lx;
     const int lxr = (gx < W - 1 && lx < SW_R - 1) ? lx + 1 : lx;
-    float q11[SWG_ROWS], q12[SWG_ROWS], q22[SWG_ROWS], e1[SWG_ROWS], e2[SWG_ROWS];
-    float4 wt[WEIGHTED ? SWG_ROWS : 1];
-    float2 nv[SWG_ROWS];
+    Cell cell[ROWS];
+    float4 wt[WEIGHTED ? ROWS : 1];
+    float2 nv[ROWS];
 #pragma unroll
-    for (int j = 0; j < SWG_ROWS; ++j) {
-        const int ly = ty + SWG_TY * j;
+    for (int j = 0; j < ROWS; ++j) {
+        const int ly = ty + TY * j;
         const int cy = min(max(y0 + ly, 0), H - 1);
         const size_t idx = (size_t)cy * W + cx;
-        q11[j] = coef[idx]; q12[j] = coef[plane + idx]; q22[j] = coef[2 * plane + idx]; e1[j] = coef[3 * plane + idx]; e2[j] = coef[4 * plane + idx];
+        cell[j].load(coef, idx, plane);
         if constexpr (WEIGHTED) wt[j] = static_cast<const float4*>(ra.wgts.p[blockIdx.z])[idx];
         s[ly][lx] = fin[idx];
     }
     __syncthreads();
     for (int sweep = 0; sweep < n; ++sweep) {
 #pragma unroll
-        for (int j = 0; j < SWG_ROWS; ++j) {
-            const int ly = ty + SWG_TY * j, gy = y0 + ly;
+        for (int j = 0; j < ROWS; ++j) {
+            const int ly = ty + TY * j, gy = y0 + ly;
             const int lyu = (gy > 0 && ly > 0) ? ly - 1 : ly;
             const int lyd = (gy < H - 1 && ly < SW_R - 1) ? ly + 1 : ly;
-            const float2 L = s[ly][lxl], R = s[ly][lxr], U = s[lyu][lx], D = s[lyd][lx];
-            float ub, vb;
-            if constexpr (WEIGHTED) {
-                ub = (wt[j].x * L.x + wt[j].y * R.x) + (wt[j].z * U.x + wt[j].w * D.x);
-                vb = (wt[j].x * L.y + wt[j].y * R.y) + (wt[j].z * U.y + wt[j].w * D.y);
-            } else {
-                ub = ((L.x + R.x) + (U.x + D.x)) * 0.25f;
-                vb = ((L.y + R.y) + (U.y + D.y)) * 0.25f;
-            }
-            nv[j] = make_float2((q11[j] * ub + q12[j] * vb) + e1[j], (q12[j] * ub + q22[j] * vb) + e2[j]);
+            const float2 m = neighbour_mean<WEIGHTED>(wt[WEIGHTED ? j : 0], s[ly][lxl], s[ly][lxr], s[lyu][lx], s[lyd][lx]);
+            nv[j] = cell[j].update(m.x, m.y);
         }
         __syncthreads();
 #pragma unroll
-        for (int j = 0; j < SWG_ROWS; ++j) s[ty + SWG_TY * j][lx] = nv[j];
+        for (int j = 0; j < ROWS; ++j) s[ty + TY * j][lx] = nv[j];
         __syncthreads();
     }
     if (lx < K || lx >= SW_R - K || gx >= W) return;      // (gx >= 0 here: lx >= K)
 #pragma unroll
-    for (int j = 0; j < SWG_ROWS; ++j) {
-        const int ly = ty + SWG_TY * j, gy = y0 + ly;
+    for (int j = 0; j < ROWS; ++j) {
+        const int ly = ty + TY * j, gy = y0 + ly;
         if (ly >= K && ly < SW_R - K && gy < H) fout[(size_t)gy * W + gx] = s[ly][lx];
     }
+}
+
+// the one place that maps a variant to an instantiation: f(grad, weighted), two std::bool_constant
+template <class F>
+void with_variant(const FlowVariant& v, F&& f)
+{
+    auto weighted = [&](auto grad) { if (v.wgt) f(grad, std::true_type{}); else f(grad, std::false_type{}); };
+    if (v.grad) weighted(std::true_type{}); else weighted(std::false_type{});
 }
 
 inline dim3 grid_64x4(int w, int h, int items) { return dim3((w + 63) / 64, (h + 3) / 4, items); }
@@ -400,23 +355,22 @@ int launch_flow_up(const FlowPtrs& coarse, int Wc, int Hc, const FlowPtrs& fine,
     return FAV_OK;
 }
 
-// wgt == nullptr: the quadratic smoothness term (eps is not read); otherwise the edge weights of eps > 0 are written next to the coefficients
-int launch_flow_coef(const FlowPtrs& A, const FlowPtrs& B, const FlowPtrs& flow0, float alpha, float eps, const FlowPtrs& coef, const FlowPtrs* wgt,
-                     int items, int W, int H, hipStream_t st, bool grad)
+int launch_flow_coef(const FlowPtrs& A, const FlowPtrs& B, const FlowPtrs& flow0, const FlowPtrs& coef, const FlowVariant& v, int items, int W, int H, hipStream_t st)
 {
     FAV_REQUIRE(size_ok(W, H) && items_ok(items), "flow coefficients: bad size %dx%d x %d", W, H, items);
-    if (grad && wgt) hipLaunchKernelGGL(flow_coef_grad_kernel<true>, grid_64x4(W, H, items), dim3(256), 0, st, A, B, flow0, alpha * alpha, coef, W, H, CoefRobustArgs<true>{eps * eps, *wgt});
-    else if (grad) hipLaunchKernelGGL(flow_coef_grad_kernel<false>, grid_64x4(W, H, items), dim3(256), 0, st, A, B, flow0, alpha * alpha, coef, W, H, CoefRobustArgs<false>{});
-    else if (wgt) hipLaunchKernelGGL(flow_coef_kernel<true>, grid_64x4(W, H, items), dim3(256), 0, st, A, B, flow0, alpha * alpha, coef, W, H, CoefRobustArgs<true>{eps * eps, *wgt});
-    else hipLaunchKernelGGL(flow_coef_kernel<false>, grid_64x4(W, H, items), dim3(256), 0, st, A, B, flow0, alpha * alpha, coef, W, H, CoefRobustArgs<false>{});
+    with_variant(v, [&](auto grad, auto weighted) {
+        constexpr bool ROBUST = decltype(weighted)::value;
+        CoefRobustArgs<ROBUST> ra;
+        if constexpr (ROBUST) ra = {v.eps * v.eps, *v.wgt};
+        hipLaunchKernelGGL(decltype(grad)::value ? flow_coef_grad_kernel<ROBUST> : flow_coef_kernel<ROBUST>, grid_64x4(W, H, items), dim3(256), 0, st, A, B, flow0,
+                           v.alpha * v.alpha, coef, W, H, ra);
+    });
     FAV_LAUNCH_CHECK("flow_coef_kernel");
     return FAV_OK;
 }
 
-// `iters` sweeps from *cur, ceil(iters / K) launches between *cur and *other (every item at once); on return *cur holds the results.
-// wgt: the normalised edge weights of the edge-preserving smoothness, or nullptr for the plain 4-neighbour mean; grad: the tensor form
-int launch_flow_sweeps(FlowPtrs* cur, FlowPtrs* other, const FlowPtrs& coef, const FlowPtrs* wgt, int items, int iters, int K, int W, int H, hipStream_t st,
-                       bool grad)
+// `iters` sweeps from *cur, ceil(iters / K) launches between *cur and *other (every item at once); on return *cur holds the results
+int launch_flow_sweeps(FlowPtrs* cur, FlowPtrs* other, const FlowPtrs& coef, const FlowVariant& v, int items, int iters, int K, int W, int H, hipStream_t st)
 {
     FAV_REQUIRE(size_ok(W, H) && items_ok(items) && iters >= 1 && K >= 1 && K <= FLOW_MAX_SWEEPS_PER_LAUNCH,
                 "flow sweeps: bad argument (%dx%d x %d, %d sweeps, %d per launch)", W, H, items, iters, K);
@@ -424,10 +378,14 @@ int launch_flow_sweeps(FlowPtrs* cur, FlowPtrs* other, const FlowPtrs& coef, con
     const dim3 grid((W + ti - 1) / ti, (H + ti - 1) / ti, items);
     FAV_REQUIRE(grid.y <= 65535, "flow sweeps: %d rows are too many", H);
     for (int done = 0; done < iters; done += K) {
-        if (grad && wgt) hipLaunchKernelGGL(flow_sweep_grad_kernel<true>, grid, dim3(SWG_THREADS), 0, st, *cur, coef, *other, W, H, K, std::min(K, iters - done), SweepRobustArgs<true>{*wgt});
-        else if (grad) hipLaunchKernelGGL(flow_sweep_grad_kernel<false>, grid, dim3(SWG_THREADS), 0, st, *cur, coef, *other, W, H, K, std::min(K, iters - done), SweepRobustArgs<false>{});
-        else if (wgt) hipLaunchKernelGGL(flow_sweep_kernel<true>, grid, dim3(SweepShape<true>::THREADS), 0, st, *cur, coef, *other, W, H, K, std::min(K, iters - done), SweepRobustArgs<true>{*wgt});
-        else hipLaunchKernelGGL(flow_sweep_kernel<false>, grid, dim3(SweepShape<false>::THREADS), 0, st, *cur, coef, *other, W, H, K, std::min(K, iters - done), SweepRobustArgs<false>{});
+        with_variant(v, [&](auto grad, auto weighted) {
+            constexpr bool WEIGHTED = decltype(weighted)::value;
+            using Cell = std::conditional_t<decltype(grad)::value, GradCell, BrightCell>;
+            SweepRobustArgs<WEIGHTED> ra;
+            if constexpr (WEIGHTED) ra = {*v.wgt};
+            hipLaunchKernelGGL((flow_sweep_kernel<Cell, WEIGHTED>), grid, dim3(SweepShape<Cell, WEIGHTED>::THREADS), 0, st, *cur, coef, *other, W, H, K,
+                               std::min(K, iters - done), ra);
+        });
         FAV_LAUNCH_CHECK("flow_sweep_kernel");
         std::swap(*cur, *other);
     }

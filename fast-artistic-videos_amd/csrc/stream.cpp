@@ -353,8 +353,7 @@ extern "C" int fav_stream_next_frame_estimate(fav_stream* s, const uint8_t* fram
                                               void* workspace, size_t workspace_bytes, float* out_rgb_f32, uint8_t* out_rgb8_hwc,
                                               fav_hipstream_t stream)
 {
-    fav_flow_opts_ex ex = {{0, 0, 0, 0.f, 0, 0.f}, FAV_FLOW_DATA_BRIGHTNESS};
-    if (flow_opts_host) ex.base = *flow_opts_host;
+    const fav_flow_opts_ex ex = flow_opts_brightness(flow_opts_host);
     return fav_stream_next_frame_estimate_ex(s, frame_rgb_hwc, prev_frame_rgb_hwc, &ex, use_structure, backward_flo, forward_flo, workspace, workspace_bytes,
                                              out_rgb_f32, out_rgb8_hwc, stream);
 }

@@ -61,7 +61,7 @@ bool parse_int(const char* s, int* out)
 
 int main(int argc, char** argv)
 {
-    fav_flow_opts_ex fx = {{0, 0, 0, 0.f, 0, 0.f}, FAV_FLOW_DATA_BRIGHTNESS};
+    fav_flow_opts_ex fx = {};      // every field 0: the defaults, the brightness term
     fav_flow_opts& fo = fx.base;
     int gpu = 0;
     std::string batch;

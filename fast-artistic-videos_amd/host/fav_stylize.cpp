@@ -337,13 +337,18 @@ FrameIn load_frame_inputs(const Opt& o, const favp::Poll& poll, int i, bool firs
     return in;
 }
 
+// the estimator's options from the -flow_* flags (main validates them)
+fav_flow_opts_ex flow_opts_of(const Opt& o)
+{
+    return {{o.i("flow_levels"), o.i("flow_warps"), o.i("flow_iters"), (float)o.d("flow_alpha"), 0, (float)o.d("flow_eps")}, o.i("flow_grad")};
+}
+
 // One video: the loop of run_fast_neural_video (core.lua:189-229) with the video CLI's callbacks (fav.lua:93-172).
 // `net` / `net_img` live on the current device; `nwriters` PNG threads.
-void run_stream(const Opt& o, fav_net* net, fav_net* net_img, int nwriters, StreamResult* res)   // nwriters: the budget; adjusted below
+void run_stream(const Opt& o, const fav_flow_opts_ex& flow_opts, fav_net* net, fav_net* net_img, int nwriters, StreamResult* res)   // nwriters: the budget; adjusted below
 {
     const bool estimate = o.i("estimate_flow") != 0;       // the flows come from the frames (and go through the fused check)
     const bool fused_check = estimate || !o.s("forward_flow_pattern").empty();
-    const fav_flow_opts_ex flow_opts{{o.i("flow_levels"), o.i("flow_warps"), o.i("flow_iters"), (float)o.d("flow_alpha"), 0, (float)o.d("flow_eps")}, o.i("flow_grad")};
     void* d_flow_ws = nullptr; size_t flow_ws_bytes = 0;
     const int border = o.s("warp_border") == "cpu" ? FAV_BORDER_CPU : FAV_BORDER_STN;
     const int num_frames = o.i("num_frames");
@@ -793,12 +798,12 @@ int main(int argc, char** argv)
     const bool estimate = o.i("estimate_flow") != 0;
     if (o.s("flow_grad") != "0" && o.s("flow_grad") != "1") die("-flow_grad must be 0 or 1, not '" + o.s("flow_grad") + "'");
     if (o.i("flow_grad") && !estimate) die("-flow_grad 1 selects the data term of the built-in flow estimator: it needs -estimate_flow 1");
+    const fav_flow_opts_ex flow_opts = flow_opts_of(o);
     if (estimate) {
         for (const char* k : {"flow_pattern", "forward_flow_pattern", "occlusions_pattern"})
             if (!o.s(k).empty()) die(std::string("-estimate_flow 1 computes both flows and the certainty from the frames: it cannot be combined with -") + k);
         if (atof(o.s("scale_factor").c_str()) != 1.0) die("-estimate_flow 1 cannot be combined with a -scale_factor other than 1");
-        const fav_flow_opts_ex fo{{o.i("flow_levels"), o.i("flow_warps"), o.i("flow_iters"), (float)o.d("flow_alpha"), 0, (float)o.d("flow_eps")}, o.i("flow_grad")};
-        if (fav_flow_workspace_bytes_ex(16, 16, &fo) == 0) die(std::string("-flow_alpha / -flow_eps / -flow_iters / -flow_warps / -flow_levels: ") + fav_last_error());
+        if (fav_flow_workspace_bytes_ex(16, 16, &flow_opts) == 0) die(std::string("-flow_alpha / -flow_eps / -flow_iters / -flow_warps / -flow_levels: ") + fav_last_error());
     }
     const bool fused_check = !o.s("forward_flow_pattern").empty();
     if (!estimate && !o.f("create_inconsistent") && (o.s("flow_pattern").empty() || (o.s("occlusions_pattern").empty() && !fused_check)))
@@ -900,7 +905,7 @@ int main(int argc, char** argv)
         Opt os = o;
         if (named) for (const char* po : path_opts) os.v[po] = favl::subst_stream(o.s(po), name);
         StreamResult r;
-        run_stream(os, net, net_img, nwriters, &r);
+        run_stream(os, flow_opts, net, net_img, nwriters, &r);
         frames += r.frames; seconds += r.seconds; cpu_seconds += r.cpu_s;
         if (o.i("timing"))
             printf("{%s\"frames\": %d, \"seconds\": %.4f, \"fps_end_to_end\": %.3f, \"wait_loader_s\": %.3f, \"h2d_gpu_d2h_s\": %.3f, \"wait_png_pool_s\": %.3f, \"setup_s\": %.3f, \"png_tail_s\": %.3f, \"png_writers\": %d, "

@@ -264,13 +264,12 @@ int run_video(std::map<std::string, std::string>& v, std::map<std::string, bool>
 // (fav_flow_pairs_rgb8), the six masks start on the library's side stream and the faces run through fav_vr_face_flow as in the file
 // mode with -forward_flow_pattern; no face, flow or certainty file exists.  Everything is enqueued on one stream.  (run_video above is
 // the reference's file contract and stays as it is; the frame's way out of the device is restated here.)
-int run_video_equi(std::map<std::string, std::string>& v, std::map<std::string, bool>& b, fav_net* vid, fav_net* img, double* seconds_out)
+int run_video_equi(std::map<std::string, std::string>& v, std::map<std::string, bool>& b, const fav_flow_opts_ex& fo, fav_net* vid, fav_net* img, double* seconds_out)
 {
     auto I = [&](const char* k) { return atoi(v[k].c_str()); };
     const bool timing = I("timing") != 0, gpu_png = v["png_encoder"] == "gpu", inconsistent = b["create_inconsistent"];
     static const int proc_order[6] = {6, 1, 2, 5, 3, 4};                                                           // :103
     const int W = I("cube_edge_length"), H = W, use_structure = I("structure"), start = I("start_frame"), count = I("num_frames");
-    const fav_flow_opts_ex fo{{0, I("flow_warps"), I("flow_iters"), (float)atof(v["flow_alpha"].c_str()), 0, (float)atof(v["flow_eps"].c_str())}, I("flow_grad")};
     hipStream_t st; hipc(hipStreamCreate(&st), "hipStreamCreate");
     fav_vr* vr = nullptr;
     fav_vr_opts o{};
@@ -426,12 +425,13 @@ int main(int argc, char** argv)
     const bool from_equi = !v["input_equi_pattern"].empty();
     if (v["flow_grad"] != "0" && v["flow_grad"] != "1") die("-flow_grad must be 0 or 1, not '" + v["flow_grad"] + "'");
     if (I("flow_grad") && !from_equi) die("-flow_grad 1 selects the data term of the built-in flow estimator: it needs -input_equi_pattern");
+    // the estimator's options from the -flow_* flags: validated here, used by run_video_equi
+    const fav_flow_opts_ex fo{{0, I("flow_warps"), I("flow_iters"), (float)atof(v["flow_alpha"].c_str()), 0, (float)atof(v["flow_eps"].c_str())}, I("flow_grad")};
     if (from_equi) {
         for (const char* k : {"input_pattern", "flow_pattern", "forward_flow_pattern", "occlusions_pattern"})
             if (!v[k].empty()) die(std::string("-input_equi_pattern makes the faces and their flows from the equirectangular frames: it cannot be combined with -") + k);
         if (I("supersample") < 1 || I("supersample") > 4) die("-supersample must be 1 .. 4, not '" + v["supersample"] + "'");
         if (I("cube_edge_length") < 16 || I("cube_edge_length") > 16384) die("-cube_edge_length must be 16 .. 16384, not '" + v["cube_edge_length"] + "'");
-        const fav_flow_opts_ex fo{{0, I("flow_warps"), I("flow_iters"), (float)atof(v["flow_alpha"].c_str()), 0, (float)atof(v["flow_eps"].c_str())}, I("flow_grad")};
         if (fav_flow_workspace_bytes_ex(16, 16, &fo) == 0) die(std::string("-flow_alpha / -flow_eps / -flow_iters / -flow_warps: ") + fav_last_error());
         if (std::max(1, I("gpus")) > 1 || I("force_dist")) die("-input_equi_pattern runs on one GPU: it cannot be combined with -gpus > 1 or -force_dist");
     }
@@ -507,7 +507,7 @@ int main(int argc, char** argv)
         std::map<std::string, std::string> vs = v;
         if (named) for (const char* po : path_opts) vs[po] = favl::subst_stream(v[po], name);
         double sec = 0;
-        frames += from_equi ? run_video_equi(vs, b, vid, img, &sec) : run_video(vs, b, vid, img, &sec);
+        frames += from_equi ? run_video_equi(vs, b, fo, vid, img, &sec) : run_video(vs, b, vid, img, &sec);
         seconds += sec;
     }
     if (dist && timing) favl::write_worker_result(v["rccl_id_file"], rank, frames, seconds);

@@ -315,64 +315,60 @@ def flow_up(coarse, h: int, w: int):
     return out
 
 
-def flow_coefficients(a_grey, b_grey, flow0, alpha: float = 15.0):
+def _flow_coef(kind: str, a_grey, b_grey, flow0, alpha: float, smooth_eps: float = 0.0):
+    """fav_flow_coefficients<kind>_f32, kind "" | "_robust" | "_grad" -> (coef, weights): coef [5][H][W] for "_grad", else [H][W][4];
+    weights [H][W][4] for "_robust" and with smooth_eps, else None.  (The plain entry takes neither smooth_eps nor weights.)"""
     torch = _torch(); _chk_f32(a_grey, "a_grey"); _chk_f32(b_grey, "b_grey"); _chk_f32(flow0, "flow0")
     h, w = a_grey.shape
-    out = torch.empty((h, w, 4), dtype=torch.float32, device=a_grey.device)
-    _check(lib().fav_flow_coefficients_f32(_p(a_grey), _p(b_grey), _p(flow0), C.c_float(alpha), _p(out), w, h, _stream()))
+    coef = torch.empty((5, h, w) if kind == "_grad" else (h, w, 4), dtype=torch.float32, device=a_grey.device)
+    weights = torch.empty((h, w, 4), dtype=torch.float32, device=a_grey.device) if kind == "_robust" or smooth_eps else None
+    args = [_p(a_grey), _p(b_grey), _p(flow0), C.c_float(alpha)] + ([C.c_float(smooth_eps), _p(coef), _p(weights)] if kind else [_p(coef)])
+    _check(getattr(lib(), f"fav_flow_coefficients{kind}_f32")(*args, w, h, _stream()))
+    return coef, weights
+
+
+def _flow_sweeps(kind: str, flow0, coef, weights, iters: int, sweeps_per_launch: int):
+    """fav_flow_sweeps<kind>_f32 (the plain entry takes no weights)"""
+    torch = _torch(); _chk_f32(flow0, "flow0"); _chk_f32(coef, "coef")
+    if weights is not None:
+        _chk_f32(weights, "weights")
+    h, w, _ = flow0.shape
+    if kind == "_grad" and (tuple(coef.shape) != (5, h, w) or (weights is not None and tuple(weights.shape) != (h, w, 4))):
+        raise FavError("flow_sweeps_grad: coef must be [5][H][W] and weights [H][W][4] for a flow [H][W][2]")
+    out, scratch = torch.empty_like(flow0), torch.empty_like(flow0)
+    args = [_p(flow0), _p(coef)] + ([_p(weights)] if kind else [])
+    _check(getattr(lib(), f"fav_flow_sweeps{kind}_f32")(*args, iters, sweeps_per_launch, _p(out), _p(scratch), w, h, _stream()))
     return out
+
+
+def flow_coefficients(a_grey, b_grey, flow0, alpha: float = 15.0):
+    return _flow_coef("", a_grey, b_grey, flow0, alpha)[0]
 
 
 def flow_sweeps(flow0, coef, iters: int, sweeps_per_launch: int = 0):
-    torch = _torch(); _chk_f32(flow0, "flow0"); _chk_f32(coef, "coef")
-    h, w, _ = flow0.shape
-    out, scratch = torch.empty_like(flow0), torch.empty_like(flow0)
-    _check(lib().fav_flow_sweeps_f32(_p(flow0), _p(coef), iters, sweeps_per_launch, _p(out), _p(scratch), w, h, _stream()))
-    return out
+    return _flow_sweeps("", flow0, coef, None, iters, sweeps_per_launch)
 
 
 def flow_coefficients_robust(a_grey, b_grey, flow0, alpha: float = 5.0, smooth_eps: float = 0.3):
     """one warp of the edge-preserving smoothness -> (coef [H][W][4] = (a, b, c, r), weights [H][W][4] = (n_l, n_r, n_u, n_d))"""
-    torch = _torch(); _chk_f32(a_grey, "a_grey"); _chk_f32(b_grey, "b_grey"); _chk_f32(flow0, "flow0")
-    h, w = a_grey.shape
-    coef = torch.empty((h, w, 4), dtype=torch.float32, device=a_grey.device)
-    weights = torch.empty((h, w, 4), dtype=torch.float32, device=a_grey.device)
-    _check(lib().fav_flow_coefficients_robust_f32(_p(a_grey), _p(b_grey), _p(flow0), C.c_float(alpha), C.c_float(smooth_eps), _p(coef), _p(weights),
-                                                  w, h, _stream()))
-    return coef, weights
+    return _flow_coef("_robust", a_grey, b_grey, flow0, alpha, smooth_eps)
 
 
 def flow_sweeps_robust(flow0, coef, weights, iters: int, sweeps_per_launch: int = 0):
-    torch = _torch(); _chk_f32(flow0, "flow0"); _chk_f32(coef, "coef"); _chk_f32(weights, "weights")
-    h, w, _ = flow0.shape
-    out, scratch = torch.empty_like(flow0), torch.empty_like(flow0)
-    _check(lib().fav_flow_sweeps_robust_f32(_p(flow0), _p(coef), _p(weights), iters, sweeps_per_launch, _p(out), _p(scratch), w, h, _stream()))
-    return out
+    _chk_f32(weights, "weights")
+    return _flow_sweeps("_robust", flow0, coef, weights, iters, sweeps_per_launch)
 
 
 def flow_coefficients_grad(a_grey, b_grey, flow0, alpha: float = 8.0, smooth_eps: float = 0.0):
     """one warp of the gradient-constancy data term -> coef [5][H][W] = the planes (q11, q12, q22, e1, e2); with smooth_eps > 0 (the
     edge-preserving smoothness) -> (coef, weights [H][W][4] = (n_l, n_r, n_u, n_d))"""
-    torch = _torch(); _chk_f32(a_grey, "a_grey"); _chk_f32(b_grey, "b_grey"); _chk_f32(flow0, "flow0")
-    h, w = a_grey.shape
-    coef = torch.empty((5, h, w), dtype=torch.float32, device=a_grey.device)
-    weights = torch.empty((h, w, 4), dtype=torch.float32, device=a_grey.device) if smooth_eps else None
-    _check(lib().fav_flow_coefficients_grad_f32(_p(a_grey), _p(b_grey), _p(flow0), C.c_float(alpha), C.c_float(smooth_eps), _p(coef), _p(weights),
-                                                w, h, _stream()))
+    coef, weights = _flow_coef("_grad", a_grey, b_grey, flow0, alpha, smooth_eps)
     return (coef, weights) if smooth_eps else coef
 
 
 def flow_sweeps_grad(flow0, coef, iters: int, sweeps_per_launch: int = 0, weights=None):
     """`iters` sweeps of the tensor form; coef [5][H][W]; weights: the [H][W][4] of the weighted mean, None for the plain mean"""
-    torch = _torch(); _chk_f32(flow0, "flow0"); _chk_f32(coef, "coef")
-    if weights is not None:
-        _chk_f32(weights, "weights")
-    h, w, _ = flow0.shape
-    if tuple(coef.shape) != (5, h, w) or (weights is not None and tuple(weights.shape) != (h, w, 4)):
-        raise FavError("flow_sweeps_grad: coef must be [5][H][W] and weights [H][W][4] for a flow [H][W][2]")
-    out, scratch = torch.empty_like(flow0), torch.empty_like(flow0)
-    _check(lib().fav_flow_sweeps_grad_f32(_p(flow0), _p(coef), _p(weights), iters, sweeps_per_launch, _p(out), _p(scratch), w, h, _stream()))
-    return out
+    return _flow_sweeps("_grad", flow0, coef, weights, iters, sweeps_per_launch)
 
 
 # ------------------------------------------------------------------------------------------------ network

@@ -3,7 +3,6 @@ premise that it survives a change of lighting that the brightness term reads as 
 _ex entries, the flags of the three executables and the resource report of the new kernels."""
 import ctypes as C
 import os
-import re
 import subprocess
 import sys
 
@@ -14,6 +13,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "uti
 import flow_model as M  # noqa: E402
 import flow_robust_model as R  # noqa: E402
 import flow_grad_model as G  # noqa: E402
+from flow_testing import kernel_resource_usage  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "fast-artistic-videos_amd")
@@ -227,23 +227,12 @@ def test_fav_stylize_vr_flow_grad_flag(favlib):
 # ------------------------------------------------------------------------------------------------ 5. the resource gate
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_gradient_term_kernels_do_not_spill(tmp_path):
-    """the compiler's kernel-resource-usage remarks for kernels_flow.hip with the Makefile's flags (as tests/test_cpu_flow_robust.py reads
-    them): the two tensor sweeps keep five (nine with the edge weights) values per cell in registers -- scratch 0 -- at two waves per SIMD
-    or better with the 32 KB LDS tile, and the two coefficient kernels do not spill either.  Measured: sweeps 128 VGPRs, occupancy 4
-    (plain mean) and 176 VGPRs, occupancy 2 (weighted mean); coefficients 53 VGPRs, occupancy 8 and 78 VGPRs, occupancy 6."""
-    p = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fhip-fp32-correctly-rounded-divide-sqrt", "-ffp-contract=off",
-                        "--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage", "-I", os.path.join(ROOT, "include"),
-                        os.path.join(PKG, "csrc", "kernels_flow.hip"), "-o", str(tmp_path / "flow.o")], capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stderr[-2000:]
-    usage, cur = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = usage.setdefault(m.group(1), {})
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).split(" ")[0]] = int(m.group(2))
-    sweeps = {k: u for k, u in usage.items() if "flow_sweep_grad_kernel" in k}
+    """the compiler's kernel-resource-usage remarks for kernels_flow.hip (flow_testing.kernel_resource_usage): the two tensor sweeps
+    keep five (nine with the edge weights) values per cell in registers -- scratch 0 -- at two waves per SIMD or better with the 32 KB
+    LDS tile, and the two coefficient kernels do not spill either.  Measured: sweeps 128 VGPRs, occupancy 4 (plain mean) and 176 VGPRs,
+    occupancy 2 (weighted mean); coefficients 53 VGPRs, occupancy 8 and 78 VGPRs, occupancy 6."""
+    usage = kernel_resource_usage(HIPCC, tmp_path)
+    sweeps = {k: u for k, u in usage.items() if "flow_sweep_kernel" in k and "GradCell" in k}
     coefs = {k: u for k, u in usage.items() if "flow_coef_grad_kernel" in k}
     assert len(sweeps) == 2 and len(coefs) == 2, sorted(usage)
     for k, u in {**sweeps, **coefs}.items():

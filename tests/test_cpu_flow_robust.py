@@ -4,7 +4,6 @@ and the resource report of the new sweep instantiation."""
 import ctypes as C
 import json
 import os
-import re
 import subprocess
 import sys
 
@@ -14,6 +13,7 @@ import pytest
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "util"))
 import flow_model as M  # noqa: E402
 import flow_robust_model as R  # noqa: E402
+from flow_testing import kernel_resource_usage  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "fast-artistic-videos_amd")
@@ -178,23 +178,12 @@ def test_fav_stylize_vr_flow_eps_flag(favlib):
 # ------------------------------------------------------------------------------------------------ 5. the resource gate
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
 def test_robust_sweep_instantiation_does_not_spill(tmp_path):
-    """the compiler's kernel-resource-usage remarks for kernels_flow.hip with the Makefile's flags (as tests/test_cpu_kernel_budget.py
-    reads them): the instantiation that carries eight values per cell keeps them in registers -- scratch 0 -- at two waves per SIMD or
-    better and with the 32 KB LDS tile of the plain one, whose own figures (176 VGPRs, occupancy 2: DESIGN.md) do not move."""
-    p = subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fhip-fp32-correctly-rounded-divide-sqrt", "-ffp-contract=off",
-                        "--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage", "-I", os.path.join(ROOT, "include"),
-                        os.path.join(PKG, "csrc", "kernels_flow.hip"), "-o", str(tmp_path / "flow.o")], capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stderr[-2000:]
-    usage, cur = {}, None
-    for line in p.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = usage.setdefault(m.group(1), {})
-        m = re.search(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1).split(" ")[0]] = int(m.group(2))
-    robust = [u for k, u in usage.items() if "flow_sweep_kernelILb1E" in k]
-    plain = [u for k, u in usage.items() if "flow_sweep_kernelILb0E" in k]
+    """the compiler's kernel-resource-usage remarks for kernels_flow.hip (flow_testing.kernel_resource_usage): the brightness
+    instantiation that carries eight values per cell keeps them in registers -- scratch 0 -- at two waves per SIMD or better and with the
+    32 KB LDS tile of the plain one, whose own figures (176 VGPRs, occupancy 2: DESIGN.md) do not move."""
+    usage = kernel_resource_usage(HIPCC, tmp_path)
+    robust = [u for k, u in usage.items() if "flow_sweep_kernel" in k and "BrightCellELb1E" in k]
+    plain = [u for k, u in usage.items() if "flow_sweep_kernel" in k and "BrightCellELb0E" in k]
     assert len(robust) == 1 and len(plain) == 1, sorted(usage)
     print("robust", robust[0], "plain", plain[0])
     assert robust[0]["ScratchSize"] == 0 and robust[0]["AGPRs"] == 0 and robust[0]["VGPRs"] <= 256 and robust[0]["Occupancy"] >= 2 and robust[0]["LDS"] == 32768, robust

@@ -7,7 +7,6 @@ input, max|GPU - M64| <= max(4 e32, 2^-20 max(1, max|M64|)).  Nothing is measure
 Measured e32 of the whole estimator on the pairs below (flow_model.warped_pair(h, w, seed 11), default options), in pixels:
 17x23 2.2e-06, 64x64 2.9e-06, 150x203 3.7e-06 (max|M64| 4.5, 5.0, 6.1) -- 4 e32 is far below the 0.02 px the issue allows."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -15,6 +14,7 @@ import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "util"))
 import flow_model as M  # noqa: E402
+from flow_testing import dev as _dev, gate_floor as _gate, run as _run, write_ppm as _write_ppm  # noqa: E402
 
 from fav_amd import synth  # noqa: E402
 
@@ -24,20 +24,6 @@ BIN = os.path.join(ROOT, "fast-artistic-videos_amd", "bin")
 VID = os.path.join(ROOT, "tests", "golden", "tiny_model.t7")
 K = 6                    # the default sweeps_per_launch
 SEED = 11
-
-
-def _dev(a, cuda):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
-
-
-def _gate(gpu, m32, m64, what):
-    e32 = float(np.abs(m32.astype(np.float64) - m64).max())
-    bound = max(4 * e32, 2.0 ** -20 * max(1.0, float(np.abs(m64).max())))
-    err = float(np.abs(gpu.astype(np.float64) - m64).max())
-    print(f"{what}: e32 {e32:.3e}  max|GPU - M64| {err:.3e}  bound {bound:.3e}")
-    assert 4 * e32 <= 0.02, (what, e32)
-    assert err <= bound, (what, err, bound)
 
 
 _pairs = {}
@@ -172,11 +158,6 @@ def test_stream_estimate_equals_flows_by_hand(favlib, cuda):
 
 
 # ------------------------------------------------------------------------------------------------ 10, 11. the executables
-def _write_ppm(path, a):
-    with open(path, "wb") as f:
-        f.write(b"P6\n%d %d\n255\n" % (a.shape[1], a.shape[0])); f.write(np.ascontiguousarray(a).tobytes())
-
-
 def _frames(n, h, w):
     """n frames of one smooth scene moving by a constant (1.5, -1) px per frame"""
     big = synth.smooth_frame(h + 16, w + 16, 77).astype(np.float64)
@@ -190,12 +171,6 @@ def _clip(d, n, h, w):
     for i, f in enumerate(frames):
         _write_ppm(str(d / f"frame_{i + 1:05d}.ppm"), f)
     return frames
-
-
-def _run(cmd):
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (cmd, r.stdout[-2000:], r.stderr[-2000:])
-    return r
 
 
 @pytest.mark.parametrize("structure,backward", [("1", False), ("0", False), ("1", True)])

@@ -7,7 +7,6 @@ fp64 model with a bound that is measured, not chosen: e32 = max|M32 - M64| of th
 computed here on the CPU at every run, and max|GPU - M64| <= 4 e32.  No floor, nothing measured against the code under test."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -17,6 +16,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "uti
 import flow_model as M  # noqa: E402
 import flow_robust_model as R  # noqa: E402
 import flow_grad_model as G  # noqa: E402
+from flow_testing import dev as _dev, gate_4e32 as _gate, run as _run, write_ppm as _write_ppm  # noqa: E402
 
 from fav_amd import synth  # noqa: E402
 
@@ -27,18 +27,6 @@ VID = os.path.join(ROOT, "tests", "golden", "tiny_model.t7")
 SEED = 11
 EPS = 0.3
 INPUTS = [("warped", h, w, 0.0) for h, w in M.SIZES] + [("scene", 96, 128, 0.0), ("scene", 96, 128, EPS)]
-
-
-def _dev(a, cuda):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
-
-
-def _gate(gpu, m32, m64, what):
-    e32 = float(np.abs(m32.astype(np.float64) - m64).max())
-    err = float(np.abs(gpu.astype(np.float64) - m64).max())
-    print(f"{what}: e32 {e32:.3e}  max|GPU - M64| {err:.3e}  bound {4 * e32:.3e}  max|M64| {np.abs(m64).max():.3g}  bit-equal to M32: {np.array_equal(gpu, m32)}")
-    assert np.isfinite(gpu).all() and err <= 4 * e32, (what, err, e32)
 
 
 _cases = {}
@@ -184,17 +172,6 @@ def test_ex_entries_with_data_term_0_are_the_old_entries(favlib, cuda):
 
 
 # ------------------------------------------------------------------------------------------------ 8. the executable
-def _write_ppm(path, a):
-    with open(path, "wb") as f:
-        f.write(b"P6\n%d %d\n255\n" % (a.shape[1], a.shape[0])); f.write(np.ascontiguousarray(a).tobytes())
-
-
-def _run(cmd):
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (cmd, r.stdout[-2000:], r.stderr[-2000:])
-    return r
-
-
 def test_cli_flow_grad_keeps_the_mask_on_a_relit_clip(favlib, cuda, tmp_path):
     """fav_stylize -estimate_flow 1 -flow_grad 1 on three 64x64 frames: shifted_pair(1, 64, 64)'s A, its B relit 0.8 B + 10, and A relit
     B + 25.  Three PNGs, the files of Stream.next_frame_estimate(..., data_term=1), and other files than without the flag.

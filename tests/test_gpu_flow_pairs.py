@@ -12,13 +12,9 @@ import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "util"))
 import flow_model as M  # noqa: E402
+from flow_testing import dev as _dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-
-def _dev(a, cuda):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
 
 
 _pairs = {}

@@ -13,7 +13,6 @@ the fp32 model there (the flows, and the coefficients and weights of the stage e
 The stage entries use the gate of tests/test_gpu_flow.py: max(4 e32, 2^-20 max(1, max|M64|))."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -22,6 +21,7 @@ import pytest
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "util"))
 import flow_model as M  # noqa: E402
 import flow_robust_model as R  # noqa: E402
+from flow_testing import dev as _dev, gate_stage_robust as _stage_gate, run as _run, write_ppm as _write_ppm  # noqa: E402
 
 from fav_amd import synth  # noqa: E402
 
@@ -33,19 +33,6 @@ K = 6                    # the default sweeps_per_launch
 SEED = 11
 EPS = 0.3
 INPUTS = [("warped", h, w) for h, w in M.SIZES] + [("scene", 96, 128)]
-
-
-def _dev(a, cuda):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
-
-
-def _stage_gate(gpu, m32, m64, what):
-    e32 = float(np.abs(m32.astype(np.float64) - m64).max())
-    bound = max(4 * e32, 2.0 ** -20 * max(1.0, float(np.abs(m64).max())))
-    err = float(np.abs(gpu.astype(np.float64) - m64).max())
-    print(f"{what}: e32 {e32:.3e}  max|GPU - M64| {err:.3e}  bound {bound:.3e}  bit-equal to M32: {np.array_equal(gpu, m32)}")
-    assert err <= bound, (what, err, bound)
 
 
 _cases = {}
@@ -186,17 +173,6 @@ def test_robust_flow_lowers_the_error_on_two_motions(favlib, cuda):
 
 
 # ------------------------------------------------------------------------------------------------ 5. the executable
-def _write_ppm(path, a):
-    with open(path, "wb") as f:
-        f.write(b"P6\n%d %d\n255\n" % (a.shape[1], a.shape[0])); f.write(np.ascontiguousarray(a).tobytes())
-
-
-def _run(cmd):
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, (cmd, r.stdout[-2000:], r.stderr[-2000:])
-    return r
-
-
 def test_cli_flow_eps_equals_the_stream_in_process(favlib, cuda, tmp_path):
     """fav_stylize -estimate_flow 1 -flow_eps 0.3 on three 64x64 frames of the two-motion scene's kind (a rectangle moving over a moving
     background): other files than with -flow_eps 0, and the files of Stream.next_frame_estimate(..., smooth_eps=0.3), byte for byte"""
