@@ -324,12 +324,24 @@ int launch_flow_up(const FlowPtrs& coarse, int Wc, int Hc, const FlowPtrs& fine,
 // (n_l, n_r, n_u, n_d), 16-byte aligned -- written by launch_flow_coef from flow0 and `eps`, read by the sweeps; nullptr: the quadratic
 // term (eps is not read).  grad: the gradient-constancy data term (tests/util/flow_grad_model.py); `coef` is then five planes [5][H][W]
 // (q11, q12, q22, e1, e2), 4-byte aligned
-struct FlowVariant { float alpha; float eps; bool grad; const FlowPtrs* wgt; };
+// prior: the matching prior (tests/util/flow_match_model.py), nullptr = off: per flow three planes [3][ph][pw] = (d.x, d.y, m) of the level
+// (shift 0, sx = sy = 1) or of level 1 when the launch is level 0's (shift 1: the parent sample, d times (sx, sy)); `coef` is then the
+// five planes with either data term, and the sweeps are the gradient term's
+constexpr int FLOW_MATCH_MAX_RADIUS = 32;
+struct FlowPrior { FlowPtrs planes; int pw, ph, shift; float sx, sy, beta, tau; };
+struct FlowVariant { float alpha; float eps; bool grad; const FlowPtrs* wgt; const FlowPrior* prior = nullptr; };
 int launch_flow_coef(const FlowPtrs& A, const FlowPtrs& B, const FlowPtrs& flow0, const FlowPtrs& coef, const FlowVariant& v, int items, int W, int H,
                      hipStream_t st);
 int launch_flow_sweeps(FlowPtrs* cur, FlowPtrs* other, const FlowPtrs& coef, const FlowVariant& v, int items, int iters, int K, int W, int H, hipStream_t st);
+// the matching prior's stages: d [H][W] of short2 (dx, dy) per item from two grey planes; the forward-backward test of two such fields into
+// the prior planes (d.x, d.y, m) of the first; the planes of the next coarser level, ceil(W/2) x ceil(H/2)
+int launch_flow_match(const FlowPtrs& A, const FlowPtrs& B, const FlowPtrs& d, int items, int W, int H, int radius, hipStream_t st);
+int launch_flow_match_check(const FlowPtrs& d_ab, const FlowPtrs& d_ba, const FlowPtrs& prior, int items, int W, int H, hipStream_t st);
+int launch_flow_prior_down(const FlowPtrs& src, int W, int H, const FlowPtrs& dst, int items, hipStream_t st);
 // the options of an entry from before data_term existed: its fav_flow_opts (or none) with the brightness term
 inline fav_flow_opts_ex flow_opts_brightness(const fav_flow_opts* o) { return {o ? *o : fav_flow_opts{0, 0, 0, 0.f, 0, 0.f}, FAV_FLOW_DATA_BRIGHTNESS}; }
+// ... and of one from before the matching prior existed: its fav_flow_opts_ex (or none) with the prior off
+inline fav_flow_opts_ex2 flow_opts_no_match(const fav_flow_opts_ex* o) { return {o ? *o : flow_opts_brightness(nullptr), 0.f, 0}; }
 // Huffman codes of the PNG encoder (png_tables.cpp): PNG_NTABLES model codes with their dynamic-block headers + the fixed code
 constexpr int PNG_NSYM = 277;            // literals 0..255, end of block 256, length symbols 257..276 (runs of 3..66)
 constexpr int PNG_NTABLES = 12;

@@ -1,6 +1,6 @@
 // flow.cpp -- the coarse-to-fine optical-flow estimator behind fav_flow_rgb8 (kernels in kernels_flow.hip; the algorithm is stated in
 // DESIGN.md, "fav_flow", and restated in numpy by tests/util/flow_model.py, for smooth_eps > 0 by tests/util/flow_robust_model.py and for the
-// gradient-constancy data term by tests/util/flow_grad_model.py):
+// gradient-constancy data term by tests/util/flow_grad_model.py, for the matching prior by tests/util/flow_match_model.py):
 // option defaults, the layout of the caller's workspace and the sequence of launches.  Nothing here allocates or synchronises.
 #include <cmath>
 
@@ -15,6 +15,8 @@ constexpr int DEFAULT_WARPS = 3, DEFAULT_ITERS = 30, DEFAULT_SWEEPS_PER_LAUNCH =
 constexpr float DEFAULT_ALPHA = 15.f, DEFAULT_ALPHA_ROBUST = 5.f;      // (robust: with smooth_eps > 0)
 constexpr float DEFAULT_ALPHA_GRAD = 8.f, DEFAULT_ALPHA_GRAD_ROBUST = 8.f;      // with the gradient-constancy data term (measured)
 constexpr float MIN_EPS = 1e-6f, MAX_EPS = 1e6f;                      // eps^2 and 1 / eps stay normal fp32 numbers
+constexpr int MATCH_LEVEL = 1, DEFAULT_MATCH_RADIUS = 16;             // the matching prior ("Matching prior": measured)
+constexpr float DEFAULT_MATCH_BETA = 225.f, MAX_MATCH_BETA = 1e6f, MATCH_TAU = 1.f, MATCH_TAU_LEVEL0 = 2.f;
 
 // The workspace of a call on `images` images and `flows` flows (fav_flow_rgb8: 2 and 1; fav_flow_pairs_rgb8: 2 n and 2 n).  The planes
 // of one kind at one level lie one behind the other, `stride` bytes apart (a multiple of 256).
@@ -26,14 +28,26 @@ struct FlowPlan {
     size_t flow0[MAX_LEVELS], flow1[MAX_LEVELS], flow_stride[MAX_LEVELS];    // the two flow buffers of a level, `flows` planes each (level 0:
                                                                              // flow1 only, the other ones are the caller's)
     size_t coef = 0, coef_stride = 0, wgt = 0, wgt_stride = 0, bytes = 0;    // wgt: the edge weights (eps > 0 only)
+    // the matching prior (beta > 0 only): `matches` match fields of level 1 (one per flow and direction: 2 for a single flow, else the
+    // flows themselves, whose opposites are in the batch), and per flow the prior planes of the levels >= 1 (level 0 reads level 1's)
+    float beta = 0.f;
+    int radius = 0, matches = 0;
+    size_t match = 0, match_stride = 0, prior[MAX_LEVELS] = {}, prior_stride[MAX_LEVELS] = {};
 };
 
 // FAV_OK or FAV_EINVAL (message set)
-int make_plan(int W, int H, const fav_flow_opts_ex* ex, int images, int flows, FlowPlan& p)
+int make_plan(int W, int H, const fav_flow_opts_ex2* ex2, int images, int flows, FlowPlan& p)
 {
-    static const fav_flow_opts_ex none = flow_opts_brightness(nullptr);
-    if (!ex) ex = &none;
+    static const fav_flow_opts_ex2 none = flow_opts_no_match(nullptr);
+    if (!ex2) ex2 = &none;
+    const fav_flow_opts_ex* ex = &ex2->ex;
     const fav_flow_opts* o = &ex->base;
+    FAV_REQUIRE(std::isfinite(ex2->match_beta) && ex2->match_beta <= MAX_MATCH_BETA, "fav_flow: match_beta must be 0 (off), negative (default) or a number up to 1e6, not %g",
+                (double)ex2->match_beta);
+    FAV_REQUIRE(ex2->match_radius >= 0 && ex2->match_radius <= FLOW_MATCH_MAX_RADIUS, "fav_flow: match_radius must be 0 (default) .. %d, not %d", FLOW_MATCH_MAX_RADIUS,
+                ex2->match_radius);
+    p.beta = ex2->match_beta < 0.f ? DEFAULT_MATCH_BETA : ex2->match_beta;
+    p.radius = ex2->match_radius ? ex2->match_radius : DEFAULT_MATCH_RADIUS;
     FAV_REQUIRE(ex->data_term == FAV_FLOW_DATA_BRIGHTNESS || ex->data_term == FAV_FLOW_DATA_GRADIENT,
                 "fav_flow: data_term must be 0 (brightness constancy) or 1 (gradient constancy), not %d", ex->data_term);
     p.v.grad = ex->data_term == FAV_FLOW_DATA_GRADIENT;
@@ -59,6 +73,7 @@ int make_plan(int W, int H, const fav_flow_opts_ex* ex, int images, int flows, F
         p.w[p.levels] = (p.w[p.levels - 1] + 1) / 2; p.h[p.levels] = (p.h[p.levels - 1] + 1) / 2;
         ++p.levels;
     }
+    FAV_REQUIRE(p.beta == 0.f || p.levels > MATCH_LEVEL, "fav_flow: the matching prior (match_beta) needs a pyramid of at least two levels, %dx%d with levels %d has one", W, H, o->levels);
     size_t off = 0;
     auto round256 = [](size_t bytes) { return (bytes + 255) / 256 * 256; };
     auto take = [&](size_t stride, int count) { const size_t at = off; off += stride * count; return at; };
@@ -68,10 +83,19 @@ int make_plan(int W, int H, const fav_flow_opts_ex* ex, int images, int flows, F
         p.pyr[l] = take(p.pyr_stride[l], images);
         p.flow0[l] = l ? take(p.flow_stride[l], flows) : 0; p.flow1[l] = take(p.flow_stride[l], flows);
     }
-    p.coef_stride = round256((size_t)W * H * (p.v.grad ? 20 : 16));
+    p.coef_stride = round256((size_t)W * H * (p.v.grad || p.beta > 0.f ? 20 : 16));
     p.coef = take(p.coef_stride, flows);
     p.wgt_stride = round256((size_t)W * H * 16);
     if (p.v.eps > 0.f) p.wgt = take(p.wgt_stride, flows);
+    if (p.beta > 0.f) {
+        p.matches = flows == 1 ? 2 : flows;
+        p.match_stride = round256((size_t)p.w[MATCH_LEVEL] * p.h[MATCH_LEVEL] * 4);
+        p.match = take(p.match_stride, p.matches);
+        for (int l = MATCH_LEVEL; l < p.levels; ++l) {
+            p.prior_stride[l] = round256((size_t)p.w[l] * p.h[l] * 12);
+            p.prior[l] = take(p.prior_stride[l], flows);
+        }
+    }
     p.bytes = off;
     return FAV_OK;
 }
@@ -94,6 +118,29 @@ int run_plan(const FlowPlan& p, const FlowPtrs& img, const int* a_of, const int*
     const FlowPtrs wgt_planes(ws + p.wgt, p.wgt_stride, p.flows);
     FlowVariant v = p.v;
     if (v.eps > 0.f) v.wgt = &wgt_planes;
+    // the matching prior: one match launch over every flow and its opposite (a single flow: the two directions of its pair; a batch: its
+    // own flows, backward k and forward k being each other's opposite), the check, and the coarser levels' planes
+    if (p.beta > 0.f) {
+        const int l = MATCH_LEVEL, half = p.flows / 2;
+        FlowPtrs mA, mB, own, opp;
+        const FlowPtrs fields(ws + p.match, p.match_stride, p.matches);
+        for (int i = 0; i < p.matches; ++i) {
+            const int j = p.flows == 1 ? 0 : i;
+            const bool swap = p.flows == 1 && i == 1;
+            mA.p[i] = ws + p.pyr[l] + (swap ? b_of[j] : a_of[j]) * p.pyr_stride[l];
+            mB.p[i] = ws + p.pyr[l] + (swap ? a_of[j] : b_of[j]) * p.pyr_stride[l];
+        }
+        for (int j = 0; j < p.flows; ++j) { own.p[j] = fields.p[j]; opp.p[j] = fields.p[p.flows == 1 ? 1 : (j + half) % p.flows]; }
+        rc = launch_flow_match(mA, mB, fields, p.matches, p.w[l], p.h[l], p.radius, st); if (rc) return rc;
+        FlowPtrs finer_prior(ws + p.prior[l], p.prior_stride[l], p.flows);
+        rc = launch_flow_match_check(own, opp, finer_prior, p.flows, p.w[l], p.h[l], st); if (rc) return rc;
+        for (int c = l + 1; c < p.levels; ++c) {
+            const FlowPtrs level(ws + p.prior[c], p.prior_stride[c], p.flows);
+            rc = launch_flow_prior_down(finer_prior, p.w[c - 1], p.h[c - 1], level, p.flows, st); if (rc) return rc;
+            finer_prior = level;
+        }
+    }
+    FlowPrior prior;
     FlowPtrs coarser;
     for (int l = p.levels - 1; l >= 0; --l) {
         FlowPtrs cur = l ? FlowPtrs(ws + p.flow0[l], p.flow_stride[l], p.flows) : out;
@@ -110,6 +157,12 @@ int run_plan(const FlowPlan& p, const FlowPtrs& img, const int* a_of, const int*
             if (cur_in_workspace) FAV_HIP(hipMemsetAsync(cur.p[0], 0, p.flow_stride[l] * p.flows, st));
             else for (int j = 0; j < p.flows; ++j) FAV_HIP(hipMemsetAsync(cur.p[j], 0, (size_t)w * h * 8, st));
         } else { rc = launch_flow_up(coarser, p.w[l + 1], p.h[l + 1], cur, p.flows, w, h, st); if (rc) return rc; }
+        if (p.beta > 0.f) {                        // level 0 reads level 1's planes at (x >> 1, y >> 1)
+            const int pl = std::max(l, MATCH_LEVEL);
+            prior = {FlowPtrs(ws + p.prior[pl], p.prior_stride[pl], p.flows), p.w[pl], p.h[pl], pl - l, (float)w / (float)p.w[pl], (float)h / (float)p.h[pl], p.beta,
+                     l ? MATCH_TAU : MATCH_TAU_LEVEL0};
+            v.prior = &prior;
+        }
         for (int k = 0; k < p.warps; ++k) {
             rc = launch_flow_coef(A, B, cur, coef, v, p.flows, w, h, st); if (rc) return rc;
             rc = launch_flow_sweeps(&cur, &other, coef, v, p.flows, p.iters, p.K, w, h, st); if (rc) return rc;
@@ -124,6 +177,12 @@ bool aligned(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p)
 }  // namespace
 
 extern "C" size_t fav_flow_workspace_bytes_ex(int W, int H, const fav_flow_opts_ex* opts_host)
+{
+    const fav_flow_opts_ex2 ex2 = flow_opts_no_match(opts_host);
+    return fav_flow_workspace_bytes_ex2(W, H, &ex2);
+}
+
+extern "C" size_t fav_flow_workspace_bytes_ex2(int W, int H, const fav_flow_opts_ex2* opts_host)
 {
     FlowPlan p;
     return make_plan(W, H, opts_host, 2, 1, p) ? 0 : p.bytes;
@@ -144,6 +203,13 @@ extern "C" int fav_flow_rgb8(const uint8_t* a_rgb_hwc, const uint8_t* b_rgb_hwc,
 
 extern "C" int fav_flow_rgb8_ex(const uint8_t* a_rgb_hwc, const uint8_t* b_rgb_hwc, int W, int H, const fav_flow_opts_ex* opts_host, float* flow_out,
                                 void* workspace, size_t workspace_bytes, fav_hipstream_t stream)
+{
+    const fav_flow_opts_ex2 ex2 = flow_opts_no_match(opts_host);
+    return fav_flow_rgb8_ex2(a_rgb_hwc, b_rgb_hwc, W, H, &ex2, flow_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int fav_flow_rgb8_ex2(const uint8_t* a_rgb_hwc, const uint8_t* b_rgb_hwc, int W, int H, const fav_flow_opts_ex2* opts_host, float* flow_out,
+                                 void* workspace, size_t workspace_bytes, fav_hipstream_t stream)
 {
     FlowPlan p;
     int rc = make_plan(W, H, opts_host, 2, 1, p); if (rc) return rc;
@@ -172,6 +238,12 @@ extern "C" int fav_flow_pairs_rgb8(const uint8_t* const* prev_rgb_hwc, const uin
 
 extern "C" size_t fav_flow_pairs_workspace_bytes_ex(int W, int H, int n_pairs, const fav_flow_opts_ex* opts_host)
 {
+    const fav_flow_opts_ex2 ex2 = flow_opts_no_match(opts_host);
+    return fav_flow_pairs_workspace_bytes_ex2(W, H, n_pairs, &ex2);
+}
+
+extern "C" size_t fav_flow_pairs_workspace_bytes_ex2(int W, int H, int n_pairs, const fav_flow_opts_ex2* opts_host)
+{
     FlowPlan p;
     if (n_pairs < 1 || n_pairs > FAV_FLOW_MAX_PAIRS) { set_error("fav_flow_pairs: n_pairs must be 1 .. %d, not %d", FAV_FLOW_MAX_PAIRS, n_pairs); return 0; }
     return make_plan(W, H, opts_host, 2 * n_pairs, 2 * n_pairs, p) ? 0 : p.bytes;
@@ -180,6 +252,14 @@ extern "C" size_t fav_flow_pairs_workspace_bytes_ex(int W, int H, int n_pairs, c
 extern "C" int fav_flow_pairs_rgb8_ex(const uint8_t* const* prev_rgb_hwc, const uint8_t* const* cur_rgb_hwc, int n_pairs, int W, int H,
                                       const fav_flow_opts_ex* opts_host, float* const* backward_flo, float* const* forward_flo, void* workspace,
                                       size_t workspace_bytes, fav_hipstream_t stream)
+{
+    const fav_flow_opts_ex2 ex2 = flow_opts_no_match(opts_host);
+    return fav_flow_pairs_rgb8_ex2(prev_rgb_hwc, cur_rgb_hwc, n_pairs, W, H, &ex2, backward_flo, forward_flo, workspace, workspace_bytes, stream);
+}
+
+extern "C" int fav_flow_pairs_rgb8_ex2(const uint8_t* const* prev_rgb_hwc, const uint8_t* const* cur_rgb_hwc, int n_pairs, int W, int H,
+                                       const fav_flow_opts_ex2* opts_host, float* const* backward_flo, float* const* forward_flo, void* workspace,
+                                       size_t workspace_bytes, fav_hipstream_t stream)
 {
     FAV_REQUIRE(n_pairs >= 1 && n_pairs <= FAV_FLOW_MAX_PAIRS, "fav_flow_pairs_rgb8: n_pairs must be 1 .. %d, not %d", FAV_FLOW_MAX_PAIRS, n_pairs);
     const int n = n_pairs;
@@ -235,16 +315,18 @@ namespace {
 // the coefficient entries: `weights` == nullptr is the quadratic smoothness term (smooth_eps is not read); grad: the gradient-constancy
 // term (coef: five planes [5][H][W], 4-byte aligned)
 int coef_entry(const char* who, const float* a_grey, const float* b_grey, const float* flow0, float alpha, float smooth_eps, float* coef, float* weights,
-               int W, int H, fav_hipstream_t stream, bool grad)
+               int W, int H, fav_hipstream_t stream, bool grad, const FlowPrior* prior = nullptr)
 {
     FAV_REQUIRE(a_grey && b_grey && flow0 && coef && W > 0 && H > 0 && std::isfinite(alpha) && alpha > 0.f, "%s: bad argument", who);
+    const bool data_grad = grad;
+    if (prior) grad = true;      // below, `grad` only says that coef is the five planes
     FAV_REQUIRE(!weights || (std::isfinite(smooth_eps) && smooth_eps >= MIN_EPS && smooth_eps <= MAX_EPS), "%s: smooth_eps must be a number in 1e-6 .. 1e6, not %g", who, (double)smooth_eps);
     FAV_REQUIRE(aligned(flow0, 8) && aligned(coef, grad ? 4 : 16) && aligned(weights, 16) && coef != weights, "%s: flow0 must be 8-byte aligned, coef %s", who,
                 grad ? "4-byte aligned, weights 16-byte aligned and distinct from coef" : weights ? "and weights 16-byte aligned and distinct" : "16-byte aligned");
     int rc = ensure_device(); if (rc) return rc;
     const FlowPtrs wgt(weights);
-    return launch_flow_coef(FlowPtrs(a_grey), FlowPtrs(b_grey), FlowPtrs(flow0), FlowPtrs(coef), {alpha, weights ? smooth_eps : 0.f, grad, weights ? &wgt : nullptr}, 1, W, H,
-                            static_cast<hipStream_t>(stream));
+    return launch_flow_coef(FlowPtrs(a_grey), FlowPtrs(b_grey), FlowPtrs(flow0), FlowPtrs(coef), {alpha, weights ? smooth_eps : 0.f, data_grad, weights ? &wgt : nullptr, prior},
+                            1, W, H, static_cast<hipStream_t>(stream));
 }
 
 // the sweep entries: `weights` == nullptr is the plain mean; grad: the tensor form (coef: five planes, 4-byte aligned)
@@ -308,3 +390,38 @@ extern "C" int fav_flow_sweeps_grad_f32(const float* flow0, const float* coef, c
     return sweeps_entry("fav_flow_sweeps_grad_f32", flow0, coef, weights, iters, sweeps_per_launch, flow_out, scratch, W, H, stream, true);
 }
 
+// ---- the matching prior's stages (tests: held to tests/util/flow_match_model.py)
+extern "C" int fav_flow_match_f32(const float* a_grey, const float* b_grey, int W, int H, int radius, int16_t* d_ab, int16_t* d_ba, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(a_grey && b_grey && d_ab && d_ba && d_ab != d_ba && W > 0 && H > 0, "fav_flow_match_f32: bad argument");
+    FAV_REQUIRE(radius >= 1 && radius <= FLOW_MATCH_MAX_RADIUS, "fav_flow_match_f32: radius must be 1 .. %d, not %d", FLOW_MATCH_MAX_RADIUS, radius);
+    FAV_REQUIRE(aligned(d_ab, 4) && aligned(d_ba, 4), "fav_flow_match_f32: the match fields must be 4-byte aligned");
+    int rc = ensure_device(); if (rc) return rc;
+    FlowPtrs A, B, d;
+    A.p[0] = const_cast<float*>(a_grey); B.p[0] = const_cast<float*>(b_grey); d.p[0] = d_ab;
+    A.p[1] = const_cast<float*>(b_grey); B.p[1] = const_cast<float*>(a_grey); d.p[1] = d_ba;
+    return launch_flow_match(A, B, d, 2, W, H, radius, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int fav_flow_match_check(const int16_t* d_ab, const int16_t* d_ba, int W, int H, float* prior, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(d_ab && d_ba && prior && W > 0 && H > 0, "fav_flow_match_check: bad argument");
+    FAV_REQUIRE(aligned(d_ab, 4) && aligned(d_ba, 4) && aligned(prior, 4), "fav_flow_match_check: the match fields and the prior must be 4-byte aligned");
+    int rc = ensure_device(); if (rc) return rc;
+    return launch_flow_match_check(FlowPtrs(d_ab), FlowPtrs(d_ba), FlowPtrs(prior), 1, W, H, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int fav_flow_coefficients_prior_f32(const float* a_grey, const float* b_grey, const float* flow0, float alpha, float smooth_eps, int data_term,
+                                               const float* prior, int Wp, int Hp, float beta, float tau, float* coef, float* weights, int W, int H,
+                                               fav_hipstream_t stream)
+{
+    const char* who = "fav_flow_coefficients_prior_f32";
+    FAV_REQUIRE(data_term == FAV_FLOW_DATA_BRIGHTNESS || data_term == FAV_FLOW_DATA_GRADIENT, "%s: data_term must be 0 or 1, not %d", who, data_term);
+    FAV_REQUIRE(prior && aligned(prior, 4) && W > 0 && H > 0, "%s: bad argument", who);
+    FAV_REQUIRE(std::isfinite(beta) && beta > 0.f && beta <= MAX_MATCH_BETA, "%s: beta must be a positive number up to 1e6, not %g", who, (double)beta);
+    FAV_REQUIRE(std::isfinite(tau) && tau >= 0.f, "%s: tau must be a number >= 0, not %g", who, (double)tau);
+    const bool same = Wp == W && Hp == H, parent = Wp == (W + 1) / 2 && Hp == (H + 1) / 2;
+    FAV_REQUIRE(same || parent, "%s: the prior must have the level's size %dx%d or the next coarser level's, not %dx%d", who, W, H, Wp, Hp);
+    const FlowPrior pr = {FlowPtrs(prior), Wp, Hp, same ? 0 : 1, (float)W / (float)Wp, (float)H / (float)Hp, beta, tau};
+    return coef_entry(who, a_grey, b_grey, flow0, alpha, smooth_eps, coef, weights, W, H, stream, data_term == FAV_FLOW_DATA_GRADIENT, &pr);
+}

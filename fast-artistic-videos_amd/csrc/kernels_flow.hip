@@ -129,6 +129,18 @@ __device__ __forceinline__ float edge_weights(const float2* __restrict__ flow0, 
     return S;
 }
 
+// (a, b, c) of the brightness term at (x, y): the only statement of the 5-point warp stencil
+__device__ __forceinline__ float3 bright_abc(const float* __restrict__ A, const float* __restrict__ B, const float2* __restrict__ flow0, int w, int h, int x, int y)
+{
+    auto bw = [&](int yy, int xx) { return warped(B, flow0, w, h, yy, xx); };
+    const float2 f0 = flow0[(size_t)y * w + x];
+    const float bc = bilinear(B, w, h, (float)x + f0.x, (float)y + f0.y);
+    const float a = (bw(y, min(x + 1, w - 1)) - bw(y, max(x - 1, 0))) * 0.5f;
+    const float b = (bw(min(y + 1, h - 1), x) - bw(max(y - 1, 0), x)) * 0.5f;
+    const float it = bc - A[(size_t)y * w + x];
+    return make_float3(a, b, (it - a * f0.x) - b * f0.y);
+}
+
 template <bool ROBUST>
 __global__ __launch_bounds__(256) void flow_coef_kernel(FlowPtrs As, FlowPtrs Bs, FlowPtrs flow0s, float alpha2, FlowPtrs coefs, int w, int h,
                                                         CoefRobustArgs<ROBUST> ra)
@@ -139,13 +151,8 @@ __global__ __launch_bounds__(256) void flow_coef_kernel(FlowPtrs As, FlowPtrs Bs
     float4* __restrict__ coef = static_cast<float4*>(coefs.p[blockIdx.z]);
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= w || y >= h) return;
-    auto bw = [&](int yy, int xx) { return warped(B, flow0, w, h, yy, xx); };
-    const float2 f0 = flow0[(size_t)y * w + x];
-    const float bc = bilinear(B, w, h, (float)x + f0.x, (float)y + f0.y);
-    const float a = (bw(y, min(x + 1, w - 1)) - bw(y, max(x - 1, 0))) * 0.5f;
-    const float b = (bw(min(y + 1, h - 1), x) - bw(max(y - 1, 0), x)) * 0.5f;
-    const float it = bc - A[(size_t)y * w + x];
-    const float c = (it - a * f0.x) - b * f0.y;
+    const float3 abc = bright_abc(A, B, flow0, w, h, x, y);
+    const float a = abc.x, b = abc.y, c = abc.z;
     float wgt = alpha2;
     if constexpr (ROBUST) wgt = (alpha2 * edge_weights(flow0, w, h, x, y, ra.eps2, static_cast<float4*>(ra.wgts.p[blockIdx.z]) + (size_t)y * w + x)) * 0.25f;
     const float r = 1.f / ((wgt + a * a) + b * b);      // one correctly rounded division (-fhip-fp32-correctly-rounded-divide-sqrt)
@@ -165,16 +172,10 @@ __global__ __launch_bounds__(256) void flow_coef_kernel(FlowPtrs As, FlowPtrs Bs
 // and reads A on its cross.  A second difference at the image border nests two clamps: clamp(clamp(x + 1) - 1) is x inside the image and
 // x - 1 on its last column, so the sample it needs is one of the 13 either way and is chosen by value.
 // The five values are planes, not a record: a wave's loads and stores are 256 contiguous bytes each, and 20 bytes per pixel need no padding.
-template <bool ROBUST>
-__global__ __launch_bounds__(256) void flow_coef_grad_kernel(FlowPtrs As, FlowPtrs Bs, FlowPtrs flow0s, float alpha2, FlowPtrs coefs, int w, int h,
-                                                             CoefRobustArgs<ROBUST> ra)
+struct DataTensor { float J11, J12, J22, h1, h2; };
+
+__device__ __forceinline__ DataTensor grad_tensor(const float* __restrict__ A, const float* __restrict__ B, const float2* __restrict__ flow0, int w, int h, int x, int y)
 {
-    const float* __restrict__ A = static_cast<const float*>(As.p[blockIdx.z]);
-    const float* __restrict__ B = static_cast<const float*>(Bs.p[blockIdx.z]);
-    const float2* __restrict__ flow0 = static_cast<const float2*>(flow0s.p[blockIdx.z]);
-    float* __restrict__ coef = static_cast<float*>(coefs.p[blockIdx.z]);
-    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= w || y >= h) return;
     auto bw = [&](int yy, int xx) { return warped(B, flow0, w, h, yy, xx); };
     const int xm = max(x - 1, 0), xp = min(x + 1, w - 1), ym = max(y - 1, 0), yp = min(y + 1, h - 1);
     const float c0 = bw(y, x);
@@ -192,18 +193,228 @@ __global__ __launch_bounds__(256) void flow_coef_grad_kernel(FlowPtrs As, FlowPt
     const float2 f0 = flow0[(size_t)y * w + x];
     const float cx = ((Bx - Ax) - ax * f0.x) - bx * f0.y;
     const float cy = ((By - Ay) - ay * f0.x) - by * f0.y;
-    const float J11 = ax * ax + ay * ay, J12 = ax * bx + ay * by, J22 = bx * bx + by * by;
-    const float h1 = ax * cx + ay * cy, h2 = bx * cx + by * cy;
+    return {ax * ax + ay * ay, ax * bx + ay * by, bx * bx + by * by, ax * cx + ay * cy, bx * cx + by * cy};
+}
+
+// the 2 x 2 system of a data tensor and the smoothness weight, solved into the five planes
+__device__ __forceinline__ void store_solved(float* __restrict__ coef, size_t n, size_t i, float wgt, const DataTensor& t)
+{
+    const float d11 = wgt + t.J11, d22 = wgt + t.J22;
+    const float det = d11 * d22 - t.J12 * t.J12;
+    coef[i] = (wgt * d22) / det;                          // five correctly rounded divisions (-fhip-fp32-correctly-rounded-divide-sqrt)
+    coef[n + i] = -((wgt * t.J12) / det);
+    coef[2 * n + i] = (wgt * d11) / det;
+    coef[3 * n + i] = -((d22 * t.h1 - t.J12 * t.h2) / det);
+    coef[4 * n + i] = -((d11 * t.h2 - t.J12 * t.h1) / det);
+}
+
+template <bool ROBUST>
+__global__ __launch_bounds__(256) void flow_coef_grad_kernel(FlowPtrs As, FlowPtrs Bs, FlowPtrs flow0s, float alpha2, FlowPtrs coefs, int w, int h,
+                                                             CoefRobustArgs<ROBUST> ra)
+{
+    const float* __restrict__ A = static_cast<const float*>(As.p[blockIdx.z]);
+    const float* __restrict__ B = static_cast<const float*>(Bs.p[blockIdx.z]);
+    const float2* __restrict__ flow0 = static_cast<const float2*>(flow0s.p[blockIdx.z]);
+    float* __restrict__ coef = static_cast<float*>(coefs.p[blockIdx.z]);
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= w || y >= h) return;
+    const DataTensor t = grad_tensor(A, B, flow0, w, h, x, y);
     float wgt = alpha2;
     if constexpr (ROBUST) wgt = (alpha2 * edge_weights(flow0, w, h, x, y, ra.eps2, static_cast<float4*>(ra.wgts.p[blockIdx.z]) + (size_t)y * w + x)) * 0.25f;
-    const float d11 = wgt + J11, d22 = wgt + J22;
-    const float det = d11 * d22 - J12 * J12;
+    store_solved(coef, (size_t)w * h, (size_t)y * w + x, wgt, t);
+}
+
+// ---- the matching prior (fav_flow_opts_ex2.match_beta > 0; DESIGN.md, "Matching prior"; restated by tests/util/flow_match_model.py).
+// Block matching at pyramid level 1 on the grey planes rounded to bytes gives an integer displacement d and a confidence m per pixel;
+// carried to every level as three planes [3][h][w] = (d.x, d.y, m), it pulls the flow towards d wherever the warp's starting flow is
+// further than tau from it:
+//   on = max(|d.x - u0|, |d.y - v0|) > tau;  bm = (beta m) on                                  (lagged: fixed for the warp's sweeps)
+//   J11 += bm, J22 += bm, h1 -= bm d.x, h2 -= bm d.y       on the data tensor of either data term (brightness: [[a a, a b], [a b, b b]],
+//                                                          h = (a c, b c)); then the stored five planes, and the sweep is GradCell's
+// Level 0 stores no planes of its own: a lane reads the parent sample (x >> 1, y >> 1) of level 1 and scales d (shift, sx, sy).
+//
+// flow_match_kernel: cost(p, d) = sum over the 7 x 7 window q around p, q clamped to the image, of |A(q) - B(clamp(q + d))|, minimised
+// over d in [-R, R]^2, ties to the first d with dy ascending (outer), dx ascending (inner).  A block owns a tile of 32 x 64 pixels and
+// stages, once, the rounded A tile (+ 3 on every side) and the B search window (+ R + 3) in LDS as bytes, both with clamped
+// coordinates; a lane owns one column and a run of 8 rows.  Per displacement it forms the 14 row sums of its column position -- each
+// one is 7 bytes of A (kept in registers, two packed words) against 7 bytes of B: three aligned LDS words, two v_alignbyte, two v_perm
+// and two v_sad_u8 -- and slides the 7-row window down its run: 14 x 7 absolute differences for 8 pixels instead of 8 x 49.  The
+// v_perm replicates the image's edge column where the window's q were clamped (the selectors are per lane, fixed for all d).  The
+// minimum lives in registers as cost << 13 | index of d, so that one v_min_u32 keeps the first of equal costs; the cost volume never
+// leaves the CU.  LDS reads (ds_read_b32: 32 banks, conflicts within a 32-lane half): a half wave is one run of 32 columns, four
+// neighbouring lanes share a word (broadcast) and the eight distinct words are consecutive, so every read is conflict-free.
+constexpr int MT_W = 32, MT_H = 64, MT_RUN = 8, MT_HALF = 3, MT_ROWS = MT_RUN + 2 * MT_HALF;
+constexpr int MT_MAX_R = FLOW_MATCH_MAX_RADIUS;
+constexpr int MT_A_PITCH = (MT_W + 2 * MT_HALF + 5 + 3) & ~3;                          // a lane reads 12 bytes from byte lx & ~3 on
+constexpr int MT_A_BYTES = (MT_H + 2 * MT_HALF) * MT_A_PITCH;
+constexpr int mt_b_pitch(int R) { return (MT_W + 2 * R + 2 * MT_HALF + 5 + 3) & ~3; }   // likewise, from (lx + dx + R) & ~3 on
+constexpr int MT_B_BYTES = (MT_H + 2 * MT_MAX_R + 2 * MT_HALF) * mt_b_pitch(MT_MAX_R);
+
+__device__ __forceinline__ uint32_t grey_byte(const float* __restrict__ g, int w, int h, int y, int x)
+{
+    const float v = g[(size_t)min(max(y, 0), h - 1) * w + min(max(x, 0), w - 1)];
+    return (uint32_t)fminf(fmaxf(rintf(v), 0.f), 255.f);
+}
+
+// bytes [o, o + 8) of an LDS row given as words, o = 4 wo + s: the low and the high word
+__device__ __forceinline__ void eight_bytes(const uint32_t* __restrict__ row, int wo, int s, uint32_t& lo, uint32_t& hi)
+{
+    const uint32_t w0 = row[wo], w1 = row[wo + 1], w2 = row[wo + 2];
+    lo = __builtin_amdgcn_alignbyte(w1, w0, s);
+    hi = __builtin_amdgcn_alignbyte(w2, w1, s);
+}
+
+__global__ __launch_bounds__(256) void flow_match_kernel(FlowPtrs As, FlowPtrs Bs, FlowPtrs ds, int w, int h, int R)
+{
+    __shared__ uint32_t sA[MT_A_BYTES / 4];
+    __shared__ uint32_t sB[MT_B_BYTES / 4];
+    const float* __restrict__ A = static_cast<const float*>(As.p[blockIdx.z]);
+    const float* __restrict__ B = static_cast<const float*>(Bs.p[blockIdx.z]);
+    short2* __restrict__ dout = static_cast<short2*>(ds.p[blockIdx.z]);
+    const int tx0 = blockIdx.x * MT_W, ty0 = blockIdx.y * MT_H;
+    const int bpitch = mt_b_pitch(R), bpw = bpitch >> 2, brows = MT_H + 2 * R + 2 * MT_HALF;
+    const int wx0 = tx0 - R - MT_HALF, wy0 = ty0 - R - MT_HALF;      // image coordinates of window byte (0, 0)
+    // stage: a lane packs four bytes into a word
+    for (int i = threadIdx.x; i < MT_A_BYTES / 4; i += 256) {
+        const int ry = i / (MT_A_PITCH / 4), cx = (i % (MT_A_PITCH / 4)) * 4;
+        uint32_t v = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v |= grey_byte(A, w, h, ty0 - MT_HALF + ry, tx0 - MT_HALF + cx + k) << (8 * k);
+        sA[i] = v;
+    }
+    for (int i = threadIdx.x; i < brows * bpw; i += 256) {
+        const int ry = i / bpw, cx = (i % bpw) * 4;
+        uint32_t v = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v |= grey_byte(B, w, h, wy0 + ry, wx0 + cx + k) << (8 * k);
+        sB[i] = v;
+    }
+    __syncthreads();
+    const int lx = threadIdx.x & (MT_W - 1), run = threadIdx.x / MT_W;
+    const int gx = tx0 + lx, gy0 = ty0 + run * MT_RUN;
+    const int xe = min(gx, w - 1);                                   // lanes right of the image work on its last column and store nothing
+    const int cmin = max(xe - MT_HALF, 0);                           // the window's columns clamp(xe - 3 .. xe + 3) all lie in [cmin, cmin + 6]
+    uint32_t sel_lo = 0, sel_hi = 0x0c000000u;                       // v_perm selectors: byte clamp(xe + o) - cmin of the eight; 0x0c = zero
+#pragma unroll
+    for (int o = 0; o < 7; ++o) {
+        const uint32_t pick = (uint32_t)(min(max(xe + o - MT_HALF, 0), w - 1) - cmin);
+        if (o < 4) sel_lo |= pick << (8 * o); else sel_hi |= pick << (8 * (o - 4));
+    }
+    // A: the lane's 14 rows of 7 bytes (the tile was staged with clamped coordinates: columns lx .. lx + 6 are clamp(gx - 3 .. gx + 3))
+    uint32_t a_lo[MT_ROWS], a_hi[MT_ROWS];
+    int brow[MT_ROWS];                                               // word offset of the lane's B row r at dy = -R
+#pragma unroll
+    for (int r = 0; r < MT_ROWS; ++r) {
+        const int ly = min(gy0 + r, h - 1 + MT_HALF) - ty0;          // staged row of image row clamp(gy0 - 3 + r) (rows below the image: its last)
+        eight_bytes(sA + ly * (MT_A_PITCH / 4), lx >> 2, lx & 3, a_lo[r], a_hi[r]);
+        a_hi[r] &= 0x00ffffffu;
+        const int cy = min(max(gy0 - MT_HALF + r, 0), h - 1);
+        brow[r] = (cy - R - wy0) * bpw;
+    }
+    const int bo0 = cmin - wx0 - R;                                  // byte offset of the lane's eight bytes in a window row at dx = -R
+    const int side = 2 * R + 1;
+    uint32_t best[MT_RUN];
+#pragma unroll
+    for (int k = 0; k < MT_RUN; ++k) best[k] = 0xffffffffu;
+    for (int dyi = 0; dyi < side; ++dyi) {
+        const uint32_t* __restrict__ base = sB + dyi * bpw;
+        for (int dxi = 0; dxi < side; ++dxi) {
+            const int bo = bo0 + dxi, wo = bo >> 2, s = bo & 3;
+            uint32_t hrow[MT_ROWS];
+#pragma unroll
+            for (int r = 0; r < MT_ROWS; ++r) {
+                uint32_t lo, hi;
+                eight_bytes(base + brow[r], wo, s, lo, hi);
+                const uint32_t plo = __builtin_amdgcn_perm(hi, lo, sel_lo), phi = __builtin_amdgcn_perm(hi, lo, sel_hi);
+                hrow[r] = __builtin_amdgcn_sad_u8(plo, a_lo[r], __builtin_amdgcn_sad_u8(phi, a_hi[r], 0u));
+            }
+            const uint32_t idx = (uint32_t)(dyi * side + dxi);
+            uint32_t cost = ((hrow[0] + hrow[1]) + (hrow[2] + hrow[3])) + ((hrow[4] + hrow[5]) + hrow[6]);
+#pragma unroll
+            for (int k = 0; k < MT_RUN; ++k) {
+                if (k) cost = cost + hrow[k + 6] - hrow[k - 1];
+                best[k] = min(best[k], (cost << 13) | idx);
+            }
+        }
+    }
+    if (gx >= w) return;
+#pragma unroll
+    for (int k = 0; k < MT_RUN; ++k) {
+        const int gy = gy0 + k;
+        if (gy < h) {
+            const int idx = (int)(best[k] & 0x1fffu);
+            dout[(size_t)gy * w + gx] = make_short2((short)(idx % side - R), (short)(idx / side - R));
+        }
+    }
+}
+
+// the forward-backward test of two match fields, and the level-1 prior of the flow "from A to B": planes (d.x, d.y, m), m = 1 when
+// t = p + d_AB(p) lies inside the image and max(|d_AB(p) + d_BA(t)|) <= 1
+__global__ __launch_bounds__(256) void flow_match_check_kernel(FlowPtrs dabs, FlowPtrs dbas, FlowPtrs priors, int w, int h)
+{
+    const short2* __restrict__ dab = static_cast<const short2*>(dabs.p[blockIdx.z]);
+    const short2* __restrict__ dba = static_cast<const short2*>(dbas.p[blockIdx.z]);
+    float* __restrict__ prior = static_cast<float*>(priors.p[blockIdx.z]);
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= w || y >= h) return;
+    const short2 d = dab[(size_t)y * w + x];
+    const int tx = x + d.x, ty = y + d.y;
+    float m = 0.f;
+    if (tx >= 0 && tx < w && ty >= 0 && ty < h) {
+        const short2 b = dba[(size_t)ty * w + tx];
+        m = max(abs(d.x + b.x), abs(d.y + b.y)) <= 1 ? 1.f : 0.f;
+    }
     const size_t n = (size_t)w * h, i = (size_t)y * w + x;
-    coef[i] = (wgt * d22) / det;                          // five correctly rounded divisions (-fhip-fp32-correctly-rounded-divide-sqrt)
-    coef[n + i] = -((wgt * J12) / det);
-    coef[2 * n + i] = (wgt * d11) / det;
-    coef[3 * n + i] = -((d22 * h1 - J12 * h2) / det);
-    coef[4 * n + i] = -((d11 * h2 - J12 * h1) / det);
+    prior[i] = (float)d.x; prior[n + i] = (float)d.y; prior[2 * n + i] = m;
+}
+
+// the prior of the next coarser level: s = (m00 + m01) + (m10 + m11); m = s 0.25; d = the m-weighted mean times (sx, sy), 0 where s = 0
+__global__ __launch_bounds__(256) void flow_prior_down_kernel(FlowPtrs srcs, int w, int h, FlowPtrs dsts, int wd, int hd, float sx, float sy)
+{
+    const float* __restrict__ src = static_cast<const float*>(srcs.p[blockIdx.z]);
+    float* __restrict__ dst = static_cast<float*>(dsts.p[blockIdx.z]);
+    const int ox = blockIdx.x * 64 + (threadIdx.x & 63), oy = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (ox >= wd || oy >= hd) return;
+    const int x0 = 2 * ox, x1 = min(2 * ox + 1, w - 1), y0 = 2 * oy, y1 = min(2 * oy + 1, h - 1);
+    const size_t n = (size_t)w * h, i00 = (size_t)y0 * w + x0, i01 = (size_t)y0 * w + x1, i10 = (size_t)y1 * w + x0, i11 = (size_t)y1 * w + x1;
+    const float m00 = src[2 * n + i00], m01 = src[2 * n + i01], m10 = src[2 * n + i10], m11 = src[2 * n + i11];
+    const float s = (m00 + m01) + (m10 + m11);
+    const float tx = (m00 * src[i00] + m01 * src[i01]) + (m10 * src[i10] + m11 * src[i11]);
+    const float ty = (m00 * src[n + i00] + m01 * src[n + i01]) + (m10 * src[n + i10] + m11 * src[n + i11]);
+    const size_t nd = (size_t)wd * hd, o = (size_t)oy * wd + ox;
+    dst[o] = s > 0.f ? (tx / s) * sx : 0.f;
+    dst[nd + o] = s > 0.f ? (ty / s) * sy : 0.f;
+    dst[2 * nd + o] = s * 0.25f;
+}
+
+// the coefficients of a warp with the prior, either data term: always the five planes
+template <bool GRAD, bool ROBUST>
+__global__ __launch_bounds__(256) void flow_coef_prior_kernel(FlowPtrs As, FlowPtrs Bs, FlowPtrs flow0s, float alpha2, FlowPtrs coefs, int w, int h,
+                                                              FlowPrior pr, CoefRobustArgs<ROBUST> ra)
+{
+    const float* __restrict__ A = static_cast<const float*>(As.p[blockIdx.z]);
+    const float* __restrict__ B = static_cast<const float*>(Bs.p[blockIdx.z]);
+    const float2* __restrict__ flow0 = static_cast<const float2*>(flow0s.p[blockIdx.z]);
+    float* __restrict__ coef = static_cast<float*>(coefs.p[blockIdx.z]);
+    const float* __restrict__ prior = static_cast<const float*>(pr.planes.p[blockIdx.z]);
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= w || y >= h) return;
+    DataTensor t;
+    if constexpr (GRAD) t = grad_tensor(A, B, flow0, w, h, x, y);
+    else {
+        const float3 abc = bright_abc(A, B, flow0, w, h, x, y);
+        t = {abc.x * abc.x, abc.x * abc.y, abc.y * abc.y, abc.x * abc.z, abc.y * abc.z};
+    }
+    const size_t pn = (size_t)pr.pw * pr.ph, pi = (size_t)min(y >> pr.shift, pr.ph - 1) * pr.pw + min(x >> pr.shift, pr.pw - 1);
+    const float dx = prior[pi] * pr.sx, dy = prior[pn + pi] * pr.sy, m = prior[2 * pn + pi];
+    const float2 f0 = flow0[(size_t)y * w + x];
+    const float on = fmaxf(fabsf(dx - f0.x), fabsf(dy - f0.y)) > pr.tau ? 1.f : 0.f;
+    const float bm = (pr.beta * m) * on;
+    t.J11 = t.J11 + bm; t.J22 = t.J22 + bm;
+    t.h1 = t.h1 - bm * dx; t.h2 = t.h2 - bm * dy;
+    float wgt = alpha2;
+    if constexpr (ROBUST) wgt = (alpha2 * edge_weights(flow0, w, h, x, y, ra.eps2, static_cast<float4*>(ra.wgts.p[blockIdx.z]) + (size_t)y * w + x)) * 0.25f;
+    store_solved(coef, (size_t)w * h, (size_t)y * w + x, wgt, t);
 }
 
 // ---- the sweeps, temporally blocked.
@@ -315,11 +526,12 @@ __global__ __launch_bounds__((SweepShape<Cell, WEIGHTED>::THREADS)) void flow_sw
     }
 }
 
-// the one place that maps a variant to an instantiation: f(grad, weighted), two std::bool_constant
+// the one place that maps a variant to an instantiation: f(grad, weighted, prior), three std::bool_constant
 template <class F>
 void with_variant(const FlowVariant& v, F&& f)
 {
-    auto weighted = [&](auto grad) { if (v.wgt) f(grad, std::true_type{}); else f(grad, std::false_type{}); };
+    auto prior = [&](auto grad, auto weighted) { if (v.prior) f(grad, weighted, std::true_type{}); else f(grad, weighted, std::false_type{}); };
+    auto weighted = [&](auto grad) { if (v.wgt) prior(grad, std::true_type{}); else prior(grad, std::false_type{}); };
     if (v.grad) weighted(std::true_type{}); else weighted(std::false_type{});
 }
 
@@ -358,14 +570,44 @@ int launch_flow_up(const FlowPtrs& coarse, int Wc, int Hc, const FlowPtrs& fine,
 int launch_flow_coef(const FlowPtrs& A, const FlowPtrs& B, const FlowPtrs& flow0, const FlowPtrs& coef, const FlowVariant& v, int items, int W, int H, hipStream_t st)
 {
     FAV_REQUIRE(size_ok(W, H) && items_ok(items), "flow coefficients: bad size %dx%d x %d", W, H, items);
-    with_variant(v, [&](auto grad, auto weighted) {
-        constexpr bool ROBUST = decltype(weighted)::value;
+    with_variant(v, [&](auto grad, auto weighted, auto prior) {
+        constexpr bool GRAD = decltype(grad)::value, ROBUST = decltype(weighted)::value;
         CoefRobustArgs<ROBUST> ra;
         if constexpr (ROBUST) ra = {v.eps * v.eps, *v.wgt};
-        hipLaunchKernelGGL(decltype(grad)::value ? flow_coef_grad_kernel<ROBUST> : flow_coef_kernel<ROBUST>, grid_64x4(W, H, items), dim3(256), 0, st, A, B, flow0,
-                           v.alpha * v.alpha, coef, W, H, ra);
+        if constexpr (decltype(prior)::value)
+            hipLaunchKernelGGL((flow_coef_prior_kernel<GRAD, ROBUST>), grid_64x4(W, H, items), dim3(256), 0, st, A, B, flow0, v.alpha * v.alpha, coef, W, H, *v.prior, ra);
+        else
+            hipLaunchKernelGGL(GRAD ? flow_coef_grad_kernel<ROBUST> : flow_coef_kernel<ROBUST>, grid_64x4(W, H, items), dim3(256), 0, st, A, B, flow0,
+                               v.alpha * v.alpha, coef, W, H, ra);
     });
     FAV_LAUNCH_CHECK("flow_coef_kernel");
+    return FAV_OK;
+}
+
+int launch_flow_match(const FlowPtrs& A, const FlowPtrs& B, const FlowPtrs& d, int items, int W, int H, int radius, hipStream_t st)
+{
+    FAV_REQUIRE(size_ok(W, H) && items_ok(items) && radius >= 1 && radius <= FLOW_MATCH_MAX_RADIUS, "flow match: bad argument (%dx%d x %d, radius %d)", W, H, items, radius);
+    const dim3 grid((W + MT_W - 1) / MT_W, (H + MT_H - 1) / MT_H, items);
+    FAV_REQUIRE(grid.y <= 65535, "flow match: %d rows are too many", H);
+    hipLaunchKernelGGL(flow_match_kernel, grid, dim3(256), 0, st, A, B, d, W, H, radius);
+    FAV_LAUNCH_CHECK("flow_match_kernel");
+    return FAV_OK;
+}
+
+int launch_flow_match_check(const FlowPtrs& d_ab, const FlowPtrs& d_ba, const FlowPtrs& prior, int items, int W, int H, hipStream_t st)
+{
+    FAV_REQUIRE(size_ok(W, H) && items_ok(items), "flow match check: bad size %dx%d x %d", W, H, items);
+    hipLaunchKernelGGL(flow_match_check_kernel, grid_64x4(W, H, items), dim3(256), 0, st, d_ab, d_ba, prior, W, H);
+    FAV_LAUNCH_CHECK("flow_match_check_kernel");
+    return FAV_OK;
+}
+
+int launch_flow_prior_down(const FlowPtrs& src, int W, int H, const FlowPtrs& dst, int items, hipStream_t st)
+{
+    FAV_REQUIRE(size_ok(W, H) && items_ok(items), "flow prior down: bad size %dx%d x %d", W, H, items);
+    const int wd = (W + 1) / 2, hd = (H + 1) / 2;
+    hipLaunchKernelGGL(flow_prior_down_kernel, grid_64x4(wd, hd, items), dim3(256), 0, st, src, W, H, dst, wd, hd, (float)wd / (float)W, (float)hd / (float)H);
+    FAV_LAUNCH_CHECK("flow_prior_down_kernel");
     return FAV_OK;
 }
 
@@ -378,9 +620,9 @@ int launch_flow_sweeps(FlowPtrs* cur, FlowPtrs* other, const FlowPtrs& coef, con
     const dim3 grid((W + ti - 1) / ti, (H + ti - 1) / ti, items);
     FAV_REQUIRE(grid.y <= 65535, "flow sweeps: %d rows are too many", H);
     for (int done = 0; done < iters; done += K) {
-        with_variant(v, [&](auto grad, auto weighted) {
+        with_variant(v, [&](auto grad, auto weighted, auto prior) {
             constexpr bool WEIGHTED = decltype(weighted)::value;
-            using Cell = std::conditional_t<decltype(grad)::value, GradCell, BrightCell>;
+            using Cell = std::conditional_t<decltype(grad)::value || decltype(prior)::value, GradCell, BrightCell>;      // (with the prior: the five planes)
             SweepRobustArgs<WEIGHTED> ra;
             if constexpr (WEIGHTED) ra = {*v.wgt};
             hipLaunchKernelGGL((flow_sweep_kernel<Cell, WEIGHTED>), grid, dim3(SweepShape<Cell, WEIGHTED>::THREADS), 0, st, *cur, coef, *other, W, H, K,

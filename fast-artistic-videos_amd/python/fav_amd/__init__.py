@@ -65,6 +65,10 @@ def lib() -> C.CDLL:
     L.fav_flow_workspace_bytes_ex.argtypes = [C.c_int, C.c_int, C.c_void_p]
     L.fav_flow_pairs_workspace_bytes_ex.restype = C.c_size_t
     L.fav_flow_pairs_workspace_bytes_ex.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.fav_flow_workspace_bytes_ex2.restype = C.c_size_t
+    L.fav_flow_workspace_bytes_ex2.argtypes = [C.c_int, C.c_int, C.c_void_p]
+    L.fav_flow_pairs_workspace_bytes_ex2.restype = C.c_size_t
+    L.fav_flow_pairs_workspace_bytes_ex2.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
     _lib = L
     return L
 
@@ -90,6 +94,8 @@ EXPORTS = [
     "fav_flow_coefficients_robust_f32", "fav_flow_sweeps_robust_f32",
     "fav_flow_workspace_bytes_ex", "fav_flow_rgb8_ex", "fav_flow_pairs_workspace_bytes_ex", "fav_flow_pairs_rgb8_ex",
     "fav_stream_next_frame_estimate_ex", "fav_flow_coefficients_grad_f32", "fav_flow_sweeps_grad_f32",
+    "fav_flow_workspace_bytes_ex2", "fav_flow_rgb8_ex2", "fav_flow_pairs_workspace_bytes_ex2", "fav_flow_pairs_rgb8_ex2",
+    "fav_stream_next_frame_estimate_ex2", "fav_flow_match_f32", "fav_flow_match_check", "fav_flow_coefficients_prior_f32",
     "fav_vr_equi_to_faces_rgb8",
 ]
 
@@ -232,10 +238,24 @@ def _flow_opts_ex(opts) -> "_FlowOptsEx":
     return _FlowOptsEx(_flow_opts({k: v for k, v in opts.items() if k not in _DATA_KEYS}), term)
 
 
+class _FlowOptsEx2(C.Structure):
+    _fields_ = [("ex", _FlowOptsEx), ("match_beta", C.c_float), ("match_radius", C.c_int)]
+
+
+_MATCH_KEYS = {"match_beta", "match_radius"}
+
+
+def _flow_opts_ex2(opts) -> "_FlowOptsEx2":
+    """fav_flow_opts_ex2 of the flow options: those of _flow_opts_ex plus match_beta= (0 = off, negative = the default weight) and
+    match_radius= (0 = default), the matching prior; every Python entry goes through the _ex2 entries of the library"""
+    return _FlowOptsEx2(_flow_opts_ex({k: v for k, v in opts.items() if k not in _MATCH_KEYS}), float(opts.get("match_beta", 0.0)),
+                        int(opts.get("match_radius", 0)))
+
+
 def flow_workspace_bytes(w: int, h: int, **opts) -> int:
-    """fav_flow_workspace_bytes_ex (host only); raises on a bad size or option"""
-    o = _flow_opts_ex(opts)
-    n = lib().fav_flow_workspace_bytes_ex(w, h, C.cast(C.pointer(o), C.c_void_p))
+    """fav_flow_workspace_bytes_ex2 (host only); raises on a bad size or option"""
+    o = _flow_opts_ex2(opts)
+    n = lib().fav_flow_workspace_bytes_ex2(w, h, C.cast(C.pointer(o), C.c_void_p))
     if n == 0:
         _check(-1)
     return n
@@ -244,17 +264,18 @@ def flow_workspace_bytes(w: int, h: int, **opts) -> int:
 def flow_rgb8(a, b, **opts):
     """fav_flow_rgb8: the flow w "from a to b", b(p + w(p)) ~ a(p), of two u8 [H][W][3] frames -> .flo payload [H][W][2] (u, v).
     opts: levels, warps, iters, alpha, sweeps_per_launch (0 / absent = default); smooth_eps > 0 turns the edge-preserving smoothness on;
-    data_term=1 / gradient_data=True takes the data term on the image gradients (frames whose lighting changes)."""
+    data_term=1 / gradient_data=True takes the data term on the image gradients (frames whose lighting changes); match_beta != 0 turns
+    the block-matching prior on (negative: the default weight), match_radius is its search radius at half resolution."""
     torch = _torch()
     if not (a.is_cuda and b.is_cuda and a.dtype == torch.uint8 and b.dtype == torch.uint8 and a.is_contiguous() and b.is_contiguous() and
             a.dim() == 3 and a.shape[2] == 3 and a.shape == b.shape):
         raise FavError("flow_rgb8: a and b must be contiguous uint8 CUDA tensors [H][W][3] of one size")
     h, w = a.shape[0], a.shape[1]
-    o = _flow_opts_ex(opts)
+    o = _flow_opts_ex2(opts)
     nb = flow_workspace_bytes(w, h, **opts)
     ws = torch.empty(nb, dtype=torch.uint8, device=a.device)
     out = torch.empty((h, w, 2), dtype=torch.float32, device=a.device)
-    _check(lib().fav_flow_rgb8_ex(_p(a), _p(b), w, h, C.byref(o), _p(out), _p(ws), C.c_size_t(nb), _stream()))
+    _check(lib().fav_flow_rgb8_ex2(_p(a), _p(b), w, h, C.byref(o), _p(out), _p(ws), C.c_size_t(nb), _stream()))
     return out
 
 
@@ -262,9 +283,9 @@ FLOW_MAX_PAIRS = 8
 
 
 def flow_pairs_workspace_bytes(w: int, h: int, n_pairs: int, **opts) -> int:
-    """fav_flow_pairs_workspace_bytes_ex (host only); raises on a bad size, pair count or option"""
-    o = _flow_opts_ex(opts)
-    n = lib().fav_flow_pairs_workspace_bytes_ex(w, h, n_pairs, C.cast(C.pointer(o), C.c_void_p))
+    """fav_flow_pairs_workspace_bytes_ex2 (host only); raises on a bad size, pair count or option"""
+    o = _flow_opts_ex2(opts)
+    n = lib().fav_flow_pairs_workspace_bytes_ex2(w, h, n_pairs, C.cast(C.pointer(o), C.c_void_p))
     if n == 0:
         _check(-1)
     return n
@@ -273,7 +294,8 @@ def flow_pairs_workspace_bytes(w: int, h: int, n_pairs: int, **opts) -> int:
 def flow_pairs(prev_list, cur_list, opts=None):
     """fav_flow_pairs_rgb8: both flows of every (prev[k], cur[k]) in one batched call -> (backward_list, forward_list), .flo payloads
     [H][W][2]: backward[k] is flow_rgb8(cur[k], prev[k]), forward[k] is flow_rgb8(prev[k], cur[k]), bit for bit.
-    opts: a dict of levels, warps, iters, alpha, sweeps_per_launch, smooth_eps, data_term / gradient_data (0 / absent = default)."""
+    opts: a dict of levels, warps, iters, alpha, sweeps_per_launch, smooth_eps, data_term / gradient_data, match_beta, match_radius
+    (0 / absent = default)."""
     torch = _torch()
     opts = dict(opts or {})
     n = len(prev_list)
@@ -282,13 +304,13 @@ def flow_pairs(prev_list, cur_list, opts=None):
                                                t.shape == imgs[0].shape for t in imgs):
         raise FavError("flow_pairs: prev_list and cur_list must be equally long lists of contiguous uint8 CUDA tensors [H][W][3] of one size")
     h, w = imgs[0].shape[0], imgs[0].shape[1]
-    o = _flow_opts_ex(opts)
+    o = _flow_opts_ex2(opts)
     nb = flow_pairs_workspace_bytes(w, h, n, **opts)
     ws = torch.empty(nb, dtype=torch.uint8, device=imgs[0].device)
     bw = [torch.empty((h, w, 2), dtype=torch.float32, device=imgs[0].device) for _ in range(n)]
     fw = [torch.empty((h, w, 2), dtype=torch.float32, device=imgs[0].device) for _ in range(n)]
     arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
-    _check(lib().fav_flow_pairs_rgb8_ex(arr(prev_list), arr(cur_list), n, w, h, C.byref(o), arr(bw), arr(fw), _p(ws), C.c_size_t(nb), _stream()))
+    _check(lib().fav_flow_pairs_rgb8_ex2(arr(prev_list), arr(cur_list), n, w, h, C.byref(o), arr(bw), arr(fw), _p(ws), C.c_size_t(nb), _stream()))
     return bw, fw
 
 
@@ -364,6 +386,44 @@ def flow_coefficients_grad(a_grey, b_grey, flow0, alpha: float = 8.0, smooth_eps
     edge-preserving smoothness) -> (coef, weights [H][W][4] = (n_l, n_r, n_u, n_d))"""
     coef, weights = _flow_coef("_grad", a_grey, b_grey, flow0, alpha, smooth_eps)
     return (coef, weights) if smooth_eps else coef
+
+
+def flow_match(a_grey, b_grey, radius: int = 16):
+    """fav_flow_match_f32: the block-matching fields of two grey planes [H][W], both directions -> (d_ab, d_ba), int16 [H][W][2] (dx, dy)"""
+    torch = _torch(); _chk_f32(a_grey, "a_grey"); _chk_f32(b_grey, "b_grey")
+    if a_grey.dim() != 2 or a_grey.shape != b_grey.shape:
+        raise FavError("flow_match: a_grey and b_grey must be [H][W] of one size")
+    h, w = a_grey.shape
+    d_ab = torch.empty((h, w, 2), dtype=torch.int16, device=a_grey.device); d_ba = torch.empty_like(d_ab)
+    _check(lib().fav_flow_match_f32(_p(a_grey), _p(b_grey), w, h, int(radius), _p(d_ab), _p(d_ba), _stream()))
+    return d_ab, d_ba
+
+
+def flow_match_check(d_ab, d_ba, want_prior: bool = False):
+    """fav_flow_match_check: the forward-backward test of two match fields -> m [H][W] (0 | 1, fp32); want_prior: the three planes
+    [3][H][W] = (d_ab.x, d_ab.y, m) that fav_flow_coefficients_prior_f32 takes"""
+    torch = _torch()
+    if not (d_ab.is_cuda and d_ba.is_cuda and d_ab.dtype == torch.int16 and d_ba.dtype == torch.int16 and d_ab.is_contiguous() and d_ba.is_contiguous() and
+            d_ab.dim() == 3 and d_ab.shape[2] == 2 and d_ab.shape == d_ba.shape):
+        raise FavError("flow_match_check: d_ab and d_ba must be contiguous int16 CUDA tensors [H][W][2] of one size")
+    h, w, _ = d_ab.shape
+    prior = torch.empty((3, h, w), dtype=torch.float32, device=d_ab.device)
+    _check(lib().fav_flow_match_check(_p(d_ab), _p(d_ba), w, h, _p(prior), _stream()))
+    return prior if want_prior else prior[2]
+
+
+def flow_coefficients_prior(a_grey, b_grey, flow0, prior, alpha: float, beta: float = 225.0, tau: float = 1.0, smooth_eps: float = 0.0, data_term: int = 0):
+    """fav_flow_coefficients_prior_f32: one warp's coefficients with the matching prior `prior` [3][Hp][Wp] (the level's own size, or
+    the next coarser level's: level 0 reading level 1) -> coef [5][H][W] (smooth_eps == 0) or (coef, weights [H][W][4])"""
+    torch = _torch(); _chk_f32(a_grey, "a_grey"); _chk_f32(b_grey, "b_grey"); _chk_f32(flow0, "flow0"); _chk_f32(prior, "prior")
+    h, w = a_grey.shape
+    if prior.dim() != 3 or prior.shape[0] != 3 or tuple(flow0.shape) != (h, w, 2) or b_grey.shape != a_grey.shape:
+        raise FavError("flow_coefficients_prior: prior must be [3][Hp][Wp], flow0 [H][W][2], the grey planes [H][W]")
+    coef = torch.empty((5, h, w), dtype=torch.float32, device=a_grey.device)
+    weights = torch.empty((h, w, 4), dtype=torch.float32, device=a_grey.device) if smooth_eps > 0 else None
+    _check(lib().fav_flow_coefficients_prior_f32(_p(a_grey), _p(b_grey), _p(flow0), C.c_float(alpha), C.c_float(smooth_eps), int(data_term), _p(prior),
+                                                 prior.shape[2], prior.shape[1], C.c_float(beta), C.c_float(tau), _p(coef), _p(weights), w, h, _stream()))
+    return (coef, weights) if smooth_eps > 0 else coef
 
 
 def flow_sweeps_grad(flow0, coef, iters: int, sweeps_per_launch: int = 0, weights=None):
@@ -546,12 +606,12 @@ class Stream:
         Returns (f32, u8, backward_flo, forward_flo)."""
         torch = _torch()
         f, u = self._outs(frame_u8_hwc.device, want_f32, want_u8)
-        o = _flow_opts_ex(flow_opts)
+        o = _flow_opts_ex2(flow_opts)
         nb = flow_pairs_workspace_bytes(self.W, self.H, 1, **flow_opts) if batched else flow_workspace_bytes(self.W, self.H, **flow_opts)
         ws = torch.empty(nb, dtype=torch.uint8, device=frame_u8_hwc.device)
         bw = torch.empty((self.H, self.W, 2), dtype=torch.float32, device=frame_u8_hwc.device)
         fw = torch.empty_like(bw)
-        _check(lib().fav_stream_next_frame_estimate_ex(self.h, _p(frame_u8_hwc), _p(prev_frame_u8_hwc), C.byref(o), 1 if use_structure else 0,
+        _check(lib().fav_stream_next_frame_estimate_ex2(self.h, _p(frame_u8_hwc), _p(prev_frame_u8_hwc), C.byref(o), 1 if use_structure else 0,
                                                        _p(bw), _p(fw), _p(ws), C.c_size_t(nb), _p(f), _p(u), _stream()))
         return f, u, bw, fw
 

@@ -152,6 +152,35 @@ size_t fav_flow_pairs_workspace_bytes_ex(int W, int H, int n_pairs, const fav_fl
 int fav_flow_pairs_rgb8_ex(const uint8_t* const* prev_rgb_hwc, const uint8_t* const* cur_rgb_hwc, int n_pairs, int W, int H,
                            const fav_flow_opts_ex* opts_host, float* const* backward_flo, float* const* forward_flo,
                            void* workspace, size_t workspace_bytes, fav_hipstream_t stream);
+/* The options with the MATCHING PRIOR ("Matching prior"; restated by tests/util/flow_match_model.py): fav_flow_opts_ex (which
+ * keeps its 28 bytes) plus match_beta and match_radius.  match_beta 0 = off: the _ex entry's launches, workspace and bits.  With
+ * match_beta > 0 (up to 1e6; negative = the default, 225) both frames are block-matched at pyramid level 1 -- integer sums of absolute
+ * differences over 7 x 7 windows of the rounded grey, displacements in [-match_radius, match_radius]^2 (1..32; 0 = the default, 16, i.e.
+ * +-32 px at full size), forward-backward checked -- and wherever a warp's starting flow is further than a threshold from a confirmed
+ * match the data term gains a quadratic pull of weight match_beta towards it: objects that move further than their own size, which the
+ * pyramid alone loses, are recovered, at the price of about 0.1 px where nothing moves far (the matches are integers at half
+ * resolution), so it is off by default.  It combines with smooth_eps and data_term.  A pyramid of a single level has no level 1:
+ * FAV_EINVAL.  The workspace grows by the match fields, the prior's pyramid and, with the brightness term, 4 bytes of coefficients per
+ * pixel and flow.  Every _ex entry is its _ex2 twin with match_beta 0. */
+typedef struct fav_flow_opts_ex2 { fav_flow_opts_ex ex; float match_beta; int match_radius; } fav_flow_opts_ex2;
+size_t fav_flow_workspace_bytes_ex2(int W, int H, const fav_flow_opts_ex2* opts_host);
+int fav_flow_rgb8_ex2(const uint8_t* a_rgb_hwc, const uint8_t* b_rgb_hwc, int W, int H, const fav_flow_opts_ex2* opts_host,
+                      float* flow_out, void* workspace, size_t workspace_bytes, fav_hipstream_t stream);
+size_t fav_flow_pairs_workspace_bytes_ex2(int W, int H, int n_pairs, const fav_flow_opts_ex2* opts_host);
+int fav_flow_pairs_rgb8_ex2(const uint8_t* const* prev_rgb_hwc, const uint8_t* const* cur_rgb_hwc, int n_pairs, int W, int H,
+                            const fav_flow_opts_ex2* opts_host, float* const* backward_flo, float* const* forward_flo,
+                            void* workspace, size_t workspace_bytes, fav_hipstream_t stream);
+/* the prior's stages on their own.  fav_flow_match_f32: two grey planes [H][W] -> the match fields of both directions, d_ab / d_ba
+ * [H][W][2] int16 (dx, dy), 4-byte aligned (radius 1..32).  fav_flow_match_check: the forward-backward test of d_ab against d_ba ->
+ * prior, THREE PLANES [3][H][W] fp32 (d_ab.x, d_ab.y, m) with m 0 | 1.  fav_flow_coefficients_prior_f32: one warp's coefficients with
+ * a prior -- coef is the five planes of fav_flow_coefficients_grad_f32 with either data_term; prior [3][Hp][Wp] is the level's own
+ * (Wp = W, Hp = H) or the next coarser level's (Wp = ceil(W/2), Hp = ceil(H/2): level 0 reading level 1); beta in (0, 1e6], tau >= 0 the
+ * gate (the estimator: 1, at level 0: 2); weights NULL or as in the _grad_ entry. */
+int fav_flow_match_f32(const float* a_grey, const float* b_grey, int W, int H, int radius, int16_t* d_ab, int16_t* d_ba, fav_hipstream_t stream);
+int fav_flow_match_check(const int16_t* d_ab, const int16_t* d_ba, int W, int H, float* prior, fav_hipstream_t stream);
+int fav_flow_coefficients_prior_f32(const float* a_grey, const float* b_grey, const float* flow0, float alpha, float smooth_eps, int data_term,
+                                    const float* prior, int Wp, int Hp, float beta, float tau, float* coef, float* weights, int W, int H,
+                                    fav_hipstream_t stream);
 /* the estimator's stages on their own (operator-level entries, as fav_scale_bicubic_f32 is one): the grey image [H][W]; one pyramid step
  * to ceil(W/2) x ceil(H/2); the x2 flow upsampling between two level sizes; the coefficients (a, b, c, r) of one warp around flow0,
  * [H][W][4], 16-byte aligned; `iters` Jacobi sweeps from flow0 into flow_out (scratch: a second flow buffer [H][W][2]; flow0 is not
@@ -335,6 +364,11 @@ int fav_stream_next_frame_estimate_ex(fav_stream* s, const uint8_t* frame_rgb_hw
                                       const fav_flow_opts_ex* flow_opts_host, int use_structure, float* backward_flo, float* forward_flo,
                                       void* workspace, size_t workspace_bytes, float* out_rgb_f32, uint8_t* out_rgb8_hwc,
                                       fav_hipstream_t stream);
+/* ... and with the matching prior (fav_flow_opts_ex2); workspace sizes from the _ex2 queries */
+int fav_stream_next_frame_estimate_ex2(fav_stream* s, const uint8_t* frame_rgb_hwc, const uint8_t* prev_frame_rgb_hwc,
+                                       const fav_flow_opts_ex2* flow_opts_host, int use_structure, float* backward_flo, float* forward_flo,
+                                       void* workspace, size_t workspace_bytes, float* out_rgb_f32, uint8_t* out_rgb8_hwc,
+                                       fav_hipstream_t stream);
 /* optional look-ahead: start computing the consistency mask of a FUTURE frame on an internal side stream (the mask
  * depends only on that frame and its two flows, not on the recurrent state), so the order-preserving 4-argument
  * structure pass overlaps the network of the current frame.  The inputs must already be complete on `stream`.  The next
