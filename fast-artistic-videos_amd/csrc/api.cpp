@@ -7,7 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "fav_internal.h"
+#include "dev_owned.h"
 
 #include <dlfcn.h>
 
@@ -175,13 +175,12 @@ extern "C" int fav_temporal_loss_host(const float* prev_rgb, const float* cur_rg
     FAV_REQUIRE(prev_rgb && cur_rgb && backward_flo && cert_pgm && loss_host && H > 0 && W > 0, "fav_temporal_loss_host: bad argument");
     int rc = ensure_device(); if (rc) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    double* part = nullptr;
-    FAV_HIP(hipMalloc(reinterpret_cast<void**>(&part), 256 * sizeof(double)));
-    rc = launch_temporal_loss(prev_rgb, cur_rgb, backward_flo, cert_pgm, border_mode, H, W, part, st);
+    dev_ptr<double> part;
+    rc = dev_alloc(part, 256); if (rc) return rc;
+    rc = launch_temporal_loss(prev_rgb, cur_rgb, backward_flo, cert_pgm, border_mode, H, W, part.get(), st);
     double h[256];
-    if (!rc && hipMemcpyAsync(h, part, sizeof h, hipMemcpyDeviceToHost, st) != hipSuccess) rc = hip_fail(hipGetLastError(), "hipMemcpyAsync");
+    if (!rc && hipMemcpyAsync(h, part.get(), sizeof h, hipMemcpyDeviceToHost, st) != hipSuccess) rc = hip_fail(hipGetLastError(), "hipMemcpyAsync");
     if (!rc && hipStreamSynchronize(st) != hipSuccess) rc = hip_fail(hipGetLastError(), "hipStreamSynchronize");
-    (void)hipFree(part);
     if (rc) return rc;
     double s = 0.0;
     for (int i = 0; i < 256; ++i) s += h[i];

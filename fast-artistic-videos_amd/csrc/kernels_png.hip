@@ -34,7 +34,7 @@
 #include <utility>
 #include <vector>
 
-#include "fav_internal.h"
+#include "dev_owned.h"
 
 namespace fav {
 namespace {
@@ -496,11 +496,10 @@ const PngTable* png_tables_for_device(int device)
     for (auto& kv : cache) if (kv.first == device) return kv.second;
     const std::vector<PngTable>& t = png_tables();
     for (const PngTable& x : t) if (x.hdr_bits == 0xFFFFFFFFu) return nullptr;
-    PngTable* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), t.size() * sizeof(PngTable)) != hipSuccess) return nullptr;
-    if (hipMemcpy(d, t.data(), t.size() * sizeof(PngTable), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return nullptr; }
-    cache.emplace_back(device, d);
-    return d;
+    dev_ptr<PngTable> d;
+    if (dev_upload(d, t)) return nullptr;
+    cache.emplace_back(device, d.get());
+    return d.release();      // (kept for the life of the process)
 }
 
 // x^(8 n) tables (4 x 256 words), built on the host with the same arithmetic the kernels use
@@ -526,11 +525,10 @@ const uint32_t* crc_tables_for_device(int device)
     std::lock_guard<std::mutex> lock(mu);
     for (auto& kv : cache) if (kv.first == device) return kv.second;
     const std::vector<uint32_t> t = crc_pow_tables();
-    uint32_t* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), t.size() * 4) != hipSuccess) return nullptr;
-    if (hipMemcpy(d, t.data(), t.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return nullptr; }
-    cache.emplace_back(device, d);
-    return d;
+    dev_ptr<uint32_t> d;
+    if (dev_upload(d, t)) return nullptr;
+    cache.emplace_back(device, d.get());
+    return d.release();      // (kept for the life of the process)
 }
 }  // namespace
 

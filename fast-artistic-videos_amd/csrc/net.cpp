@@ -93,9 +93,10 @@ int fav_net::alloc(size_t bytes, float** out)
     }
     if (slab_left < bytes) {
         const size_t sz = std::max(bytes, (size_t)256 << 20);
-        void* sp = nullptr;
-        FAV_HIP(hipMalloc(&sp, sz));
-        slabs.push_back(sp); slab_cur = static_cast<char*>(sp); slab_left = sz;
+        dev_ptr<void> sp;
+        const int rc = dev_alloc(sp, sz); if (rc) return rc;
+        slab_cur = static_cast<char*>(sp.get()); slab_left = sz;
+        slabs.push_back(std::move(sp));
     }
     DevBuf b; b.bytes = bytes; b.p = slab_cur;
     slab_cur += bytes; slab_left -= bytes;
@@ -128,11 +129,11 @@ int fav_net::timed_conv(const ConvLaunch& c, const Layer& L, ConvKernel kernel)
     ProfRec r; r.conv = conv_index;
     // (no system-scope fence at the event: the default one flushes the caches around every timed kernel -- 6 us on either side of each
     // convolution in the rocprofv3 trace, 0.18 ms per 1280x720 frame)
-    FAV_HIP(hipEventCreateWithFlags(&r.a, hipEventDisableSystemFence)); FAV_HIP(hipEventCreateWithFlags(&r.b, hipEventDisableSystemFence));
-    FAV_HIP(hipEventRecord(r.a, st));
+    if (event_create(r.a, hipEventDisableSystemFence) || event_create(r.b, hipEventDisableSystemFence)) return FAV_EHIP;
+    FAV_HIP(hipEventRecord(r.a.get(), st));
     int rc = k.launch(cs, st);
-    FAV_HIP(hipEventRecord(r.b, st));
-    prof_pending.push_back(r);
+    FAV_HIP(hipEventRecord(r.b.get(), st));
+    prof_pending.push_back(std::move(r));
     if ((int)prof_ms.size() <= conv_index) { prof_ms.resize(conv_index + 1, 0.0); prof_macs.resize(conv_index + 1, 0.0); prof_n.resize(conv_index + 1, 0); prof_tile.resize(conv_index + 1, 0); }
     prof_macs[conv_index] = (double)c.OH * c.OW * L.cout * L.cin * L.k * L.k;      // useful MACs only
     if (L.transposed) prof_macs[conv_index] /= (double)(L.stride * L.stride);       // (every output pixel meets k^2 / s^2 taps)
@@ -438,7 +439,7 @@ int fav_net::forward_padded(const float* in8, int H, int W, float* out_planar, f
 
 int fav_net::forward_padded_unordered(const float* in8, int H, int W, float* out_planar, float* out_raw, hipStream_t stream)
 {
-    if (sk_err_host && *reinterpret_cast<volatile unsigned*>(sk_err_host)) {      // reported by an earlier launch of this net
+    if (sk_err_host && *static_cast<volatile unsigned*>(sk_err_host.get())) {      // reported by an earlier launch of this net
         *sk_err_host = 0;
         shared_device = true;
         set_error("a stream-K hand-off between convolution blocks timed out in an earlier launch of this network: its result was "
@@ -448,8 +449,7 @@ int fav_net::forward_padded_unordered(const float* in8, int H, int W, float* out
     if (H != curH || W != curW) {
         if (!bufs.empty()) {
             FAV_HIP(hipDeviceSynchronize());
-            for (void* sp : slabs) (void)hipFree(sp);
-            slabs.clear(); slab_cur = nullptr; slab_left = 0;
+            slabs.clear(); slab_cur = nullptr; slab_left = 0;      // (frees them)
             bufs.clear();
         }
         curH = H; curW = W;
@@ -473,14 +473,6 @@ int fav_net::forward_padded_unordered(const float* in8, int H, int W, float* out
 // ================================================================================================
 // C ABI: network
 // ================================================================================================
-static int finish_create(fav_net* net, fav_net** out)
-{
-    int rc = net->upload();
-    if (rc) { delete net; return rc; }
-    *out = net;
-    return FAV_OK;
-}
-
 extern "C" int fav_net_create(const char* t7_path_host, int device, fav_net** out)
 {
     FAV_REQUIRE(t7_path_host && out, "fav_net_create: null argument");
@@ -489,8 +481,9 @@ extern "C" int fav_net_create(const char* t7_path_host, int device, fav_net** ou
     std::unique_ptr<fav_net> net(new fav_net());
     net->device = device;
     rc = t7_parse_model(t7_path_host, net->layers);
-    if (rc) return rc;
-    return finish_create(net.release(), out);
+    if (!rc) rc = net->upload();
+    if (!rc) *out = net.release();
+    return rc;
     FAV_ABI_CATCH("fav_net_create")
 }
 
@@ -519,8 +512,9 @@ extern "C" int fav_net_create_from_blob(const void* blob_host, size_t bytes, int
     std::unique_ptr<fav_net> net(new fav_net());
     net->device = device;
     rc = blob_unpack(blob_host, bytes, net->layers);
-    if (rc) return rc;
-    return finish_create(net.release(), out);
+    if (!rc) rc = net->upload();
+    if (!rc) *out = net.release();
+    return rc;
     FAV_ABI_CATCH("fav_net_create_from_blob")
 }
 
@@ -529,7 +523,7 @@ extern "C" void fav_net_destroy(fav_net* net) { delete net; }
 extern "C" int fav_net_check(fav_net* net)
 {
     FAV_REQUIRE(net, "fav_net_check: null net");
-    if (net->sk_err_host && *reinterpret_cast<volatile unsigned*>(net->sk_err_host)) {
+    if (net->sk_err_host && *static_cast<volatile unsigned*>(net->sk_err_host.get())) {
         *net->sk_err_host = 0;
         net->shared_device = true;      // from now on: data-parallel grids, which need no co-resident blocks
         set_error("a stream-K hand-off between convolution blocks timed out: the frame(s) computed since the last check are wrong "
@@ -569,11 +563,10 @@ extern "C" int fav_net_profile_read_host(fav_net* net, int capacity, int* count,
     FAV_REQUIRE(net && count && ms_sum && launches && macs_per_launch && ntile, "fav_net_profile_read_host: null argument");
     FAV_HIP(hipSetDevice(net->device));
     for (auto& r : net->prof_pending) {
-        FAV_HIP(hipEventSynchronize(r.b));
+        FAV_HIP(hipEventSynchronize(r.b.get()));
         float ms = 0.f;
-        FAV_HIP(hipEventElapsedTime(&ms, r.a, r.b));
+        FAV_HIP(hipEventElapsedTime(&ms, r.a.get(), r.b.get()));
         net->prof_ms[r.conv] += ms; net->prof_n[r.conv] += 1;
-        (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b);
     }
     net->prof_pending.clear();
     const int n = (int)net->prof_ms.size();
@@ -616,11 +609,11 @@ extern "C" int fav_net_forward(fav_net* net, const float* in7, float* out3, int 
     const size_t bytes = (size_t)(H + 2 * net->pad) * (W + 2 * net->pad) * 8 * sizeof(float);
     if (net->stage_bytes < bytes) {
         FAV_HIP(hipDeviceSynchronize());
-        (void)hipFree(net->stage); net->stage = nullptr; net->stage_bytes = 0;
-        FAV_HIP(hipMalloc(reinterpret_cast<void**>(&net->stage), bytes));
+        net->stage.reset(); net->stage_bytes = 0;
+        int rc = dev_alloc(net->stage, bytes / sizeof(float)); if (rc) return rc;
         net->stage_bytes = bytes;
     }
-    float* in8 = net->stage;
+    float* in8 = net->stage.get();
     int rc = launch_nchw_to_nhwc_pad(in7, net->in_channels, H, W, net->pad, 8, in8, st); if (rc) return rc;
     return net->forward_padded(in8, H, W, nullptr, out3, st);
 }

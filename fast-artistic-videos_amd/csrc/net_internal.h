@@ -5,7 +5,7 @@
 #include <cstring>
 #include <vector>
 
-#include "fav_internal.h"
+#include "dev_owned.h"
 
 namespace fav {
 
@@ -78,7 +78,6 @@ struct Tuning {
 const Tuning& tuning();
 
 // net_model.cpp
-int dev_upload(const std::vector<float>& h, size_t pad_to, float** out);
 void repack_weights(const Layer& L, int cinp, int coutp, int kpad, std::vector<float>& out);
 bool only_tail(const std::vector<Layer>& ls, size_t from, bool& has_tanh, float& mul);      // nothing but Tanh / MulConstant / Identity from ls[from] on
 
@@ -94,12 +93,17 @@ struct fav_net {
     long long params = 0;
     std::vector<fav::DevConvW> convs;  // traversal order
     std::vector<fav::DevIN> ins;
+    // Device memory that lives as long as the net has ONE owner list: dev_new / dev_put (net_model.cpp) allocate, append the allocation to
+    // `owned` and hand out a raw view.  convs, ins and the scalars below keep those views, so the launch records read plain pointers
+    std::vector<fav::dev_ptr<void>> owned;
+    template <class T> int dev_new(T** view, size_t n, bool zeroed = false);
+    template <class T> int dev_put(T** view, const std::vector<T>& h, size_t pad_to = 0);
     float* ones = nullptr; float* zeros = nullptr;
     float* sk_ws = nullptr; unsigned* sk_flags = nullptr; unsigned sk_epoch = 0;   // stream-K hand-off state
     float* ks_ws = nullptr; int* ks_cnt = nullptr;                                    // meeting places of the F(4x4) Winograd kernel's stream-K launches
     // a residual block whose join stays pending (run(), L_RES): its last convolution lays its output out under the skip tensor
     struct LazyOut { bool active = false; int pitch = 0, rows = 0, shave = 0, conv_index = -1; } lazy;
-    unsigned* sk_err_host = nullptr; unsigned* sk_err_dev = nullptr;               // host-mapped: a hand-off wait timed out
+    fav::host_ptr<unsigned> sk_err_host; unsigned* sk_err_dev = nullptr;           // host-mapped: a hand-off wait timed out (sk_err_dev: its device address)
     bool shared_device = false;     // data-parallel grids only: set by the caller (fav_net_set_shared_device) or by a timed-out hand-off
     int precision = 0;              // 0 = fp32 (parity mode), 1 = bf16 operands in the halo-resident 3x3 convolutions (fast mode)
     int acc_parity = 0;             // which half of the InstanceNorm accumulators this forward adds to (the consumers zero the other half)
@@ -110,25 +114,17 @@ struct fav_net {
     int curH = 0, curW = 0;
     std::vector<fav::DevBuf> bufs;
     // ... carved out of a few large slabs: sixty hipMalloc calls cost the first frame of a run 10 ms (profiles/e2e_r04s_startup.log)
-    std::vector<void*> slabs; char* slab_cur = nullptr; size_t slab_left = 0;
+    std::vector<fav::dev_ptr<void>> slabs; char* slab_cur = nullptr; size_t slab_left = 0;
     size_t cursor = 0;
     hipStream_t st = nullptr;
-    float* stage = nullptr; size_t stage_bytes = 0;   // NCHW-boundary staging (fav_net_forward)
+    fav::dev_ptr<float> stage; size_t stage_bytes = 0;   // NCHW-boundary staging (fav_net_forward)
     // optional per-convolution event timing (bench.py roofline)
     bool profiling = false;
-    struct ProfRec { hipEvent_t a, b; int conv; };
+    struct ProfRec { fav::event_h a, b; int conv; };
     std::vector<ProfRec> prof_pending;
     std::vector<double> prof_ms, prof_macs; std::vector<int> prof_n, prof_tile;
 
-    ~fav_net()
-    {
-        (void)hipSetDevice(device);
-        (void)hipFree(stage);
-        for (auto& c : convs) { (void)hipFree(c.wgt); (void)hipFree(c.bias); (void)hipFree(c.wgt16); for (float* p : c.packed) (void)hipFree(p); }
-        for (auto& i : ins) { (void)hipFree(i.gamma); (void)hipFree(i.beta); (void)hipFree(i.scale); (void)hipFree(i.shift); (void)hipFree(i.acc); }
-        for (void* sp : slabs) (void)hipFree(sp);
-        (void)hipFree(ones); (void)hipFree(zeros); (void)hipFree(sk_ws); (void)hipFree(sk_flags); (void)hipFree(ks_ws); (void)hipFree(ks_cnt); if (sk_err_host) (void)hipHostFree(sk_err_host);
-    }
+    ~fav_net() { (void)hipSetDevice(device); }      // (the members free themselves, on the net's device)
     // net_model.cpp
     int upload_layers(std::vector<fav::Layer>& ls, int& chan_pitch, int& maxc);
     int upload();

@@ -14,16 +14,6 @@
 
 namespace fav {
 
-int dev_upload(const std::vector<float>& h, size_t pad_to, float** out)
-{
-    const size_t n = std::max(pad_to, h.size());
-    std::vector<float> tmp(n, 0.f);
-    std::copy(h.begin(), h.end(), tmp.begin());
-    FAV_HIP(hipMalloc(reinterpret_cast<void**>(out), (n ? n : 1) * sizeof(float)));
-    if (n) FAV_HIP(hipMemcpy(*out, tmp.data(), n * sizeof(float), hipMemcpyHostToDevice));
-    return FAV_OK;
-}
-
 // repack [cout][cin][k][k] -> [coutp][kpad].  K order of the implicit GEMM (must match FAV_TAP_SETUP):
 //   cinp >= 32: k = ((ci/32)*taps + tap)*32 + ci%32   (channel slice outermost: consecutive K-steps shift by one tap)
 //   cinp <  32: k = tap*cinp + ci                     (several taps per 32-wide K slice)
@@ -197,12 +187,29 @@ bool only_tail(const std::vector<Layer>& ls, size_t from, bool& has_tanh, float&
 
 using namespace fav;
 
+// n elements (zeroed on request) | h, zero-padded to pad_to elements: owned by the net, *view = the allocation
+template <class T> int fav_net::dev_new(T** view, size_t n, bool zeroed)
+{
+    dev_ptr<T> d;
+    const int rc = dev_alloc(d, n); if (rc) return rc;
+    if (zeroed) FAV_HIP(hipMemset(d.get(), 0, n * sizeof(T)));
+    owned.emplace_back(); owned.back().reset(*view = d.release());
+    return FAV_OK;
+}
+template <class T> int fav_net::dev_put(T** view, const std::vector<T>& h, size_t pad_to)
+{
+    dev_ptr<T> d;
+    const int rc = dev_upload(d, h, pad_to); if (rc) return rc;
+    owned.emplace_back(); owned.back().reset(*view = d.release());
+    return FAV_OK;
+}
+
 int fav_net::upload_layers(std::vector<Layer>& ls, int& chan_pitch, int& maxc)
 {
     for (Layer& L : ls) {
         if (L.type == L_CONV) {
             L.dev_index = (int)convs.size();
-            convs.emplace_back();                 // registered first: the destructor frees whatever a failed upload leaves behind
+            convs.emplace_back();
             DevConvW& d = convs.back();
             if (L.cin > chan_pitch || (chan_pitch != 8 && L.cin != chan_pitch)) {
                 set_error("network: conv expects %d input channels, producer has %d", L.cin, chan_pitch); return FAV_EFORMAT; }
@@ -226,14 +233,13 @@ int fav_net::upload_layers(std::vector<Layer>& ls, int& chan_pitch, int& maxc)
             int rc = FAV_OK;
             if (!phase) {                   // (the phase kernel reads its own packing only: no generic weight matrix for it)
                 repack_weights(L, s.cin_pitch, s.coutp, d.kpad, w);
-                rc = dev_upload(w, 0, &d.wgt); if (rc) return rc;
+                rc = dev_put(&d.wgt, w); if (rc) return rc;
             }
-            rc = dev_upload(L.b, (size_t)s.coutp, &d.bias); if (rc) return rc;
+            rc = dev_put(&d.bias, L.b, (size_t)s.coutp); if (rc) return rc;
             if (conv3_halo_eligible(s)) {      // bf16 copy for the fast mode (round to nearest even)
                 std::vector<unsigned short> w16(w.size());
                 for (size_t i = 0; i < w.size(); ++i) { unsigned b; memcpy(&b, &w[i], 4); w16[i] = (unsigned short)((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16); }
-                FAV_HIP(hipMalloc(reinterpret_cast<void**>(&d.wgt16), w16.size() * 2));
-                FAV_HIP(hipMemcpy(d.wgt16, w16.data(), w16.size() * 2, hipMemcpyHostToDevice));
+                rc = dev_put(&d.wgt16, w16); if (rc) return rc;
             }
             if (L.transposed && (L.k > TCONV_MAX_K || L.stride < 2 || L.stride > TCONV_MAX_S || L.pad > L.k - 1 || L.adj < 0 || L.adj >= L.stride)) {
                 set_error("network: SpatialFullConvolution is supported for k <= %d, stride <= %d, pad <= k - 1, adj < stride (models_video.lua:81-89,99-102), got k=%d s=%d pad=%d adj=%d",
@@ -243,7 +249,7 @@ int fav_net::upload_layers(std::vector<Layer>& ls, int& chan_pitch, int& maxc)
             for (const ConvKernelInfo& k : CONV_KERNEL_TABLE)
                 if (k.pack && k.eligible(with_input(s, k.pack_state))) {
                     k.pack(L.w.data(), s, w);
-                    rc = dev_upload(w, 0, &d.packed[k.kernel]); if (rc) return rc;
+                    rc = dev_put(&d.packed[k.kernel], w); if (rc) return rc;
                 }
             chan_pitch = L.cout;
             maxc = std::max(maxc, std::max(s.coutp, s.cin_pitch));
@@ -252,13 +258,10 @@ int fav_net::upload_layers(std::vector<Layer>& ls, int& chan_pitch, int& maxc)
             L.dev_index = (int)ins.size();
             ins.emplace_back();
             DevIN& d = ins.back();
-            int rc = dev_upload(L.gamma, 0, &d.gamma); if (rc) return rc;
-            rc = dev_upload(L.beta, 0, &d.beta); if (rc) return rc;
-            FAV_HIP(hipMalloc(reinterpret_cast<void**>(&d.scale), L.gamma.size() * sizeof(float)));
-            FAV_HIP(hipMalloc(reinterpret_cast<void**>(&d.shift), L.gamma.size() * sizeof(float)));
+            int rc = dev_put(&d.gamma, L.gamma); if (rc) return rc;
+            rc = dev_put(&d.beta, L.beta); if (rc) return rc;
             d.acc_bytes = 2 * stat_acc_words((int)L.gamma.size()) * sizeof(long long);
-            FAV_HIP(hipMalloc(reinterpret_cast<void**>(&d.acc), d.acc_bytes));
-            FAV_HIP(hipMemset(d.acc, 0, d.acc_bytes));
+            if (dev_new(&d.scale, L.gamma.size()) || dev_new(&d.shift, L.gamma.size()) || dev_new(&d.acc, d.acc_bytes / sizeof(long long), true)) return FAV_EHIP;
         } else if (L.type == L_BN) {
             if ((int)L.mean.size() != chan_pitch) { set_error("network: SpatialBatchNormalization(%zu) after %d channels", L.mean.size(), chan_pitch); return FAV_EFORMAT; }
             // evaluate mode: a fixed per-channel affine, folded into the consumer's load like InstanceNorm's
@@ -270,8 +273,8 @@ int fav_net::upload_layers(std::vector<Layer>& ls, int& chan_pitch, int& maxc)
             L.dev_index = (int)ins.size();
             ins.emplace_back();
             DevIN& d = ins.back();
-            int rc = dev_upload(sc, 0, &d.scale); if (rc) return rc;
-            rc = dev_upload(sh, 0, &d.shift); if (rc) return rc;
+            int rc = dev_put(&d.scale, sc); if (rc) return rc;
+            rc = dev_put(&d.shift, sh); if (rc) return rc;
         } else if (L.type == L_RES) {
             int cp = chan_pitch;
             int rc = upload_layers(L.block, cp, maxc); if (rc) return rc;
@@ -308,16 +311,11 @@ int fav_net::upload()
     rc = upload_layers(exec, chan, maxc); if (rc) return rc;
     params = count_params(layers);
     std::vector<float> o((size_t)maxc, 1.f), z((size_t)maxc, 0.f);
-    rc = dev_upload(o, 0, &ones); if (rc) return rc;
-    rc = dev_upload(z, 0, &zeros); if (rc) return rc;
-    FAV_HIP(hipMalloc(reinterpret_cast<void**>(&sk_ws), conv_streamk_workspace_bytes()));
-    FAV_HIP(hipMalloc(reinterpret_cast<void**>(&sk_flags), conv_streamk_grid() * sizeof(unsigned)));
-    FAV_HIP(hipMemset(sk_flags, 0, conv_streamk_grid() * sizeof(unsigned)));
-    FAV_HIP(hipMalloc(reinterpret_cast<void**>(&ks_ws), conv3_wino4_ksplit_bytes()));
-    FAV_HIP(hipMalloc(reinterpret_cast<void**>(&ks_cnt), 256 * sizeof(int)));
-    FAV_HIP(hipMemset(ks_cnt, 0, 256 * sizeof(int)));
-    FAV_HIP(hipHostMalloc(reinterpret_cast<void**>(&sk_err_host), sizeof(unsigned), hipHostMallocMapped));
+    if (dev_put(&ones, o) || dev_put(&zeros, z) ||
+        dev_new(&sk_ws, conv_streamk_workspace_bytes() / sizeof(float)) || dev_new(&sk_flags, (size_t)conv_streamk_grid(), true) ||
+        dev_new(&ks_ws, conv3_wino4_ksplit_bytes() / sizeof(float)) || dev_new(&ks_cnt, 256, true) ||
+        host_alloc(sk_err_host, 1, hipHostMallocMapped)) return FAV_EHIP;
     *sk_err_host = 0;
-    FAV_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&sk_err_dev), sk_err_host, 0));
+    FAV_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&sk_err_dev), sk_err_host.get(), 0));
     return FAV_OK;
 }

@@ -9,7 +9,7 @@
 
 #include <unistd.h>
 
-#include "fav_internal.h"
+#include "dev_owned.h"
 
 using namespace fav;
 
@@ -24,65 +24,56 @@ struct fav_stream {
                                  // convolutions, two x2 upsamplings).  The reference keeps and saves the LARGER image and warps it
                                  // with the flow's size (BilinearSamplerBDHW.lua:71: the output takes the grid's size), so does this
     fav_stream_opts opts{};
-    float* state = nullptr;      // last_frame_stylized: [3][Ho][Wo] float RGB, unclamped (fav.lua:169)
+    dev_ptr<float> state;        // last_frame_stylized: [3][Ho][Wo] float RGB, unclamped (fav.lua:169)
     bool has_state = false;
     unsigned frame_counter = 0;  // 1-based index of the frame being stylised (key of the uniform-random fill)
-    float* in8 = nullptr;        // padded NHWC8 network input
+    dev_ptr<float> in8;          // padded NHWC8 network input
     // -scale_factor (fav_stream_set_single_image_size): frames without a prior run at sHs x sWs (0: unscaled).  The scaled padded input
     // and the network's planar output at that size (sHo x sWo) live here from the call that sets the size on
     int sHs = 0, sWs = 0, sHo = 0, sWo = 0;
-    float* scaled_in8 = nullptr; float* scaled_out = nullptr;
+    dev_ptr<float> scaled_in8, scaled_out;
     bool last_scaled = false;    // the last frame ran at the scaled size: in8 does not hold its input
-    float* cert_tmp = nullptr; float* cert = nullptr;
-    uint8_t* mask = nullptr;     // certainty as the checker writes it (u8 {0,255})
-    int* q0_main = nullptr;      // the XCD the caller's queue deals block 0 of a launch to (written by prep_input_kernel, read by the look-ahead mask's long-lived kernels)
-    void* ws = nullptr; size_t ws_bytes = 0;
-    void* png_ws = nullptr; size_t png_ws_bytes = 0;      // workspace of fav_stream_encode_png (allocated on first use)
+    dev_ptr<float> cert_tmp, cert;
+    dev_ptr<uint8_t> mask;       // certainty as the checker writes it (u8 {0,255})
+    dev_ptr<int> q0_main;        // the XCD the caller's queue deals block 0 of a launch to (written by prep_input_kernel, read by the look-ahead mask's long-lived kernels)
+    dev_ptr<void> ws; size_t ws_bytes = 0;
+    dev_ptr<void> png_ws; size_t png_ws_bytes = 0;        // workspace of fav_stream_encode_png (allocated on first use)
     // fav_stream_encode_png_async: the encoder's kernels run on a queue of their own, next to the NEXT frame's network (they fill the
     // tails of its grids instead of standing in front of it).  The state is double-buffered from then on: frame i + 1 is written into
     // the other buffer while frame i's is being encoded, and the frame that comes back to a buffer waits for that buffer's encoder
-    hipStream_t png_q = nullptr; hipEvent_t ev_png_in = nullptr;
-    float* state_other = nullptr;                         // the buffer `state` is not (null until the first asynchronous encode)
-    hipEvent_t png_done = nullptr, png_done_other = nullptr;      // the last encode that read `state` / `state_other` ...
+    queue_h png_q; event_h ev_png_in;
+    dev_ptr<float> state_other;                           // the buffer `state` is not (null until the first asynchronous encode)
+    event_h png_done, png_done_other;                             // the last encode that read `state` / `state_other` ...
     bool png_pending = false, png_pending_other = false;          // ... if nothing has waited for it yet
     // look-ahead mask (fav_stream_prefetch_mask)
     // two side queues with their own structure workspaces: the masks of frames i+1 and i+2 are computed concurrently
     // (each 4-argument mask contains a ~3 ms sequential fp32 chain, CMatrix::avg), three look-ahead slots
     static constexpr int NSIDE = 2, NPREF = 4;
-    hipStream_t side[NSIDE] = {nullptr, nullptr}; void* side_ws[NSIDE] = {nullptr, nullptr}; hipEvent_t ev_in = nullptr;
-    float* side_cert_tmp[NSIDE] = {nullptr, nullptr};      // scratch of the certainty preparation (erosion input) on each side queue
-    struct Pref { uint8_t* mask = nullptr; float* cert = nullptr; hipEvent_t done = nullptr; bool valid = false;
+    queue_h side[NSIDE]; dev_ptr<void> side_ws[NSIDE]; event_h ev_in;      // (only the NSIDE_USED queues that can be indexed exist)
+    struct Pref { dev_ptr<uint8_t> mask; dev_ptr<float> cert; event_h done; bool valid = false;
                   const void *frame = nullptr, *bw = nullptr, *fw = nullptr; int structure = 0;
                   uint32_t retired = 0; };       // host-ordered: retire sequence of the (mask, cert) buffers now in this slot (0: never read)
     Pref pref[NPREF]; int pref_next = 0, side_next = 0;
     // host-ordered look-ahead (fav_stream_set_host_ordered): no event ever enters the caller's queue or the side queues; a one-thread
     // kernel behind the mask pipeline stores a sequence number into host-mapped memory, which fav_stream_next_frame_flow polls
     bool host_ordered = false;
-    uint32_t* done_host = nullptr;      // [NPREF], hipHostMalloc
+    host_ptr<uint32_t> done_host;       // [NPREF] (+ retired_host)
     uint32_t pref_seq[NPREF] = {0, 0, 0, 0}; uint32_t seq_counter = 0;
     // ... and nothing orders a side queue behind the caller's queue either, so the buffers a consumed look-ahead swaps OUT of the stream
     // (read by the previous frames' kernels on the caller's queue) must not be rewritten by a later look-ahead before those kernels are
     // through: the consuming call first enqueues a one-thread kernel on the caller's queue that stores a retire sequence number into
     // host-mapped memory (everything enqueued before it has then finished), and a look-ahead into a slot waits ON THE HOST for the
     // sequence number of the buffers it holds (with NPREF slots and two frames of look-ahead that frame finished long ago: no wait)
-    uint32_t* retired_host = nullptr; uint32_t retire_counter = 0;
+    uint32_t* retired_host = nullptr; uint32_t retire_counter = 0;      // (a view into done_host's allocation, on its own 64-byte line)
     hipStream_t last_st = nullptr; bool ran = false;       // the HIP stream of the last forward (forgotten by the destructor)
     ~fav_stream()
     {
         if (net) (void)hipSetDevice(net_device(net));
         if (net && ran) net_forget_stream(net, last_st);
-        if (png_q) { (void)hipStreamSynchronize(png_q); (void)hipStreamDestroy(png_q); }
-        if (ev_png_in) (void)hipEventDestroy(ev_png_in);
-        if (png_done) (void)hipEventDestroy(png_done);
-        if (png_done_other) (void)hipEventDestroy(png_done_other);
-        (void)hipFree(state_other);
-        for (int i = 0; i < NSIDE; ++i) { if (side[i]) { (void)hipStreamSynchronize(side[i]); (void)hipStreamDestroy(side[i]); } (void)hipFree(side_ws[i]); }
-        if (ev_in) (void)hipEventDestroy(ev_in);
-        if (done_host) (void)hipHostFree(done_host);       // (retired_host lives in the same allocation)
-        for (auto& pf : pref) { if (pf.done) (void)hipEventDestroy(pf.done); (void)hipFree(pf.mask); (void)hipFree(pf.cert); }
-        for (int i = 0; i < NSIDE; ++i) (void)hipFree(side_cert_tmp[i]);
-        (void)hipFree(scaled_in8); (void)hipFree(scaled_out);
-        (void)hipFree(q0_main); (void)hipFree(state); (void)hipFree(in8); (void)hipFree(cert_tmp); (void)hipFree(cert); (void)hipFree(mask); (void)hipFree(ws); (void)hipFree(png_ws);
+        // the one ordering the members' own destruction (reverse declaration order) would not give: the stream's queues are drained and
+        // destroyed BEFORE any buffer or host flag their kernels touch is freed, wherever those are declared
+        png_q.reset();
+        for (auto& q : side) q.reset();
     }
 };
 
@@ -97,16 +88,19 @@ static const int NSIDE_USED = getenv("FAV_SIDE_QUEUES") ? std::max(1, std::min(2
 // the look-ahead mask's long-lived kernels (the recursive-filter passes) are packed onto the reserved CUs (launch_structure's pack_cus;
 // FAV_SIDE_PACK=0: one block per wave, the form of rounds 4-5)
 static const int SIDE_PACK = diag_env("FAV_SIDE_PACK") ? std::max(0, atoi(diag_env("FAV_SIDE_PACK"))) : -1;
-static hipError_t create_side_stream(hipStream_t* st)
+static int create_side_stream(queue_h& out)
 {
     // (confining the side queues with a CU mask -- hipExtStreamCreateWithCUMask -- measured slower than leaving the CUs free, rounds 2-3)
     // FAV_SIDE_CU_MASK=<comma-separated bit numbers>: experiment, round 6
     if (const char* m = diag_env("FAV_SIDE_CU_MASK")) {
         uint32_t words[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         for (const char* p = m; *p;) { const int b = atoi(p); if (b >= 0 && b < 256) words[b / 32] |= 1u << (b % 32); while (*p && *p != ',') ++p; if (*p == ',') ++p; }
-        return hipExtStreamCreateWithCUMask(st, 8, words);
+        hipStream_t q = nullptr;
+        FAV_HIP(hipExtStreamCreateWithCUMask(&q, 8, words));
+        out.reset(q);
+        return FAV_OK;
     }
-    return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
+    return queue_create(out, "side queues");
 }
 
 extern "C" int fav_stream_create(fav_net* net, int H, int W, const fav_stream_opts* o, fav_stream** out)
@@ -117,28 +111,24 @@ extern "C" int fav_stream_create(fav_net* net, int H, int W, const fav_stream_op
     int Ho, Wo; net_out_size(net, H, W, &Ho, &Wo);
     FAV_REQUIRE(Ho >= 1 && Wo >= 1, "frame size %dx%d is too small for the architecture", W, H);
     FAV_HIP(hipSetDevice(net_device(net)));
-    fav_stream* s = new fav_stream();
+    std::unique_ptr<fav_stream> s(new fav_stream());      // (every failure below is a plain return: the handles free what exists by then)
     s->net = net; s->H = H; s->W = W; s->Ho = Ho; s->Wo = Wo;
     if (o) s->opts = *o; else { s->opts.border_mode = FAV_BORDER_STN; s->opts.occlusions_min_filter = 7; s->opts.invert_occlusion = 0; s->opts.fix_occlusions = 0; s->opts.fill_random = 0; s->opts.seed = 0; }
     if (s->opts.occlusions_min_filter < 1) s->opts.occlusions_min_filter = 1;
     const size_t n = (size_t)H * W;
     s->ws_bytes = structure_workspace_bytes(W, H);
-    if (hipMalloc(reinterpret_cast<void**>(&s->state), (size_t)3 * Ho * Wo * 4) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&s->in8), (size_t)(H + 2 * pad) * (W + 2 * pad) * 32) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&s->cert_tmp), n * 4) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&s->cert), n * 4) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&s->mask), n) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&s->q0_main), 64) != hipSuccess || hipMemset(s->q0_main, 0, 64) != hipSuccess ||
-        hipEventCreateWithFlags(&s->ev_in, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess ||
-        hipMalloc(&s->ws, s->ws_bytes) != hipSuccess) { delete s; return hip_fail(hipErrorOutOfMemory, "hipMalloc(stream buffers)"); }
+    const unsigned ef = hipEventDisableTiming | hipEventDisableSystemFence;
+    const char* what = "hipMalloc(stream buffers)";
+    if (dev_alloc(s->state, (size_t)3 * Ho * Wo, what) || dev_alloc(s->in8, (size_t)(H + 2 * pad) * (W + 2 * pad) * 8, what) ||
+        dev_alloc(s->cert_tmp, n, what) || dev_alloc(s->cert, n, what) || dev_alloc(s->mask, n, what) || dev_alloc(s->q0_main, 16, what) ||
+        event_create(s->ev_in, ef, what) || dev_alloc(s->ws, s->ws_bytes, what)) return FAV_EHIP;
+    FAV_HIP(hipMemset(s->q0_main.get(), 0, 16 * sizeof(int)));
     for (auto& pf : s->pref)
-        if (hipMalloc(reinterpret_cast<void**>(&pf.mask), n) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&pf.cert), n * 4) != hipSuccess || hipEventCreateWithFlags(&pf.done, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess) {
-            delete s; return hip_fail(hipErrorOutOfMemory, "look-ahead slots"); }
-    for (int i = 0; i < fav_stream::NSIDE; ++i)
-        if (create_side_stream(&s->side[i]) != hipSuccess || hipMalloc(&s->side_ws[i], s->ws_bytes) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&s->side_cert_tmp[i]), n * 4) != hipSuccess) {
-            delete s; return hip_fail(hipErrorOutOfMemory, "side queues"); }
-    *out = s;
+        if (dev_alloc(pf.mask, n, "look-ahead slots") || dev_alloc(pf.cert, n, "look-ahead slots") || event_create(pf.done, ef, "look-ahead slots")) return FAV_EHIP;
+    // the side queues a look-ahead can ever be dealt to (fav_stream_prefetch_mask: q < NSIDE_USED), each with its structure workspace
+    for (int i = 0; i < NSIDE_USED; ++i)
+        if (create_side_stream(s->side[i]) || dev_alloc(s->side_ws[i], s->ws_bytes, "side queues")) return FAV_EHIP;
+    *out = s.release();
     return FAV_OK;
 }
 
@@ -159,7 +149,7 @@ static int state_for_writing(fav_stream* s, hipStream_t st)
 {
     if (!s->state_other) return FAV_OK;
     swap_state_buffers(s);
-    if (s->png_pending) { FAV_HIP(hipStreamWaitEvent(st, s->png_done, 0)); s->png_pending = false; }
+    if (s->png_pending) { FAV_HIP(hipStreamWaitEvent(st, s->png_done.get(), 0)); s->png_pending = false; }
     return FAV_OK;
 }
 
@@ -174,8 +164,8 @@ static int stream_finish(fav_stream* s, float* out_rgb_f32, uint8_t* out_rgb8_hw
 {
     const size_t n = (size_t)s->Ho * s->Wo;
     s->has_state = true;
-    if (out_rgb_f32) FAV_HIP(hipMemcpyAsync(out_rgb_f32, s->state, 3 * n * 4, hipMemcpyDeviceToDevice, st));
-    if (out_rgb8_hwc) return launch_quantize_rgb8(s->state, out_rgb8_hwc, s->Ho, s->Wo, st);
+    if (out_rgb_f32) FAV_HIP(hipMemcpyAsync(out_rgb_f32, s->state.get(), 3 * n * 4, hipMemcpyDeviceToDevice, st));
+    if (out_rgb8_hwc) return launch_quantize_rgb8(s->state.get(), out_rgb8_hwc, s->Ho, s->Wo, st);
     return FAV_OK;
 }
 
@@ -188,23 +178,23 @@ extern "C" int fav_stream_first_frame(fav_stream* s, const uint8_t* frame_rgb_hw
     ++s->frame_counter;
     fav_net* fn = s->img_net ? s->img_net : s->net;      // image model: 3 content channels (the zero prior / mask planes meet zero weights)
     if (s->sHs) {      // core.lua:127-130,150-152: resampled before the model, the result resampled back to H x W (= Ho x Wo) into the state
-        int rc = launch_scale_prep(frame_rgb_hwc, s->H, s->W, s->sHs, s->sWs, net_pad(s->net), s->scaled_in8, st,
+        int rc = launch_scale_prep(frame_rgb_hwc, s->H, s->W, s->sHs, s->sWs, net_pad(s->net), s->scaled_in8.get(), st,
                                    s->img_net ? 0 : s->opts.fill_random, s->opts.seed, s->frame_counter);
         if (rc) return rc;
         s->last_st = st; s->ran = true; s->last_scaled = true;
         rc = state_for_writing(s, st); if (rc) return rc;
-        rc = net_forward_padded(fn, s->scaled_in8, s->sHs, s->sWs, s->scaled_out, st);
-        if (!rc) rc = launch_scale_planar(s->scaled_out, s->state, 3, s->sHo, s->sWo, s->Ho, s->Wo, st);
+        rc = net_forward_padded(fn, s->scaled_in8.get(), s->sHs, s->sWs, s->scaled_out.get(), st);
+        if (!rc) rc = launch_scale_planar(s->scaled_out.get(), s->state.get(), 3, s->sHo, s->sWo, s->Ho, s->Wo, st);
         if (rc) { state_writing_failed(s); return rc; }
         return stream_finish(s, out_rgb_f32, out_rgb8_hwc, st);
     }
     // the image model sees only the three content channels (core.lua:146): no fill there
-    int rc = launch_prep_input(frame_rgb_hwc, nullptr, 0, 0, nullptr, nullptr, s->opts.border_mode, s->H, s->W, net_pad(s->net), s->in8, st,
+    int rc = launch_prep_input(frame_rgb_hwc, nullptr, 0, 0, nullptr, nullptr, s->opts.border_mode, s->H, s->W, net_pad(s->net), s->in8.get(), st,
                                s->img_net ? 0 : s->opts.fill_random, s->opts.seed, s->frame_counter);
     if (rc) return rc;
     s->last_st = st; s->ran = true; s->last_scaled = false;
     rc = state_for_writing(s, st); if (rc) return rc;
-    rc = net_forward_padded(fn, s->in8, s->H, s->W, s->state, st); if (rc) { state_writing_failed(s); return rc; }
+    rc = net_forward_padded(fn, s->in8.get(), s->H, s->W, s->state.get(), st); if (rc) { state_writing_failed(s); return rc; }
     return stream_finish(s, out_rgb_f32, out_rgb8_hwc, st);
 }
 
@@ -229,9 +219,9 @@ extern "C" int fav_stream_set_single_image_size(fav_stream* s, int Hs, int Ws)
 {
     FAV_REQUIRE(s, "fav_stream_set_single_image_size: null stream");
     FAV_HIP(hipSetDevice(net_device(s->net)));
-    if (Hs == 0 && Ws == 0) {      // back to the unscaled path (hipFree waits for the frames that still read the buffers)
-        (void)hipFree(s->scaled_in8); (void)hipFree(s->scaled_out);
-        s->scaled_in8 = s->scaled_out = nullptr; s->sHs = s->sWs = s->sHo = s->sWo = 0;
+    if (Hs == 0 && Ws == 0) {      // back to the unscaled path (freeing waits for the frames that still read the buffers)
+        s->scaled_in8.reset(); s->scaled_out.reset();
+        s->sHs = s->sWs = s->sHo = s->sWo = 0;
         return FAV_OK;
     }
     if (s->Ho != s->H || s->Wo != s->W) {
@@ -247,12 +237,21 @@ extern "C" int fav_stream_set_single_image_size(fav_stream* s, int Hs, int Ws)
         int Hi, Wi; net_out_size(s->img_net, Hs, Ws, &Hi, &Wi);
         FAV_REQUIRE(Hi == Ho && Wi == Wo, "fav_stream_set_single_image_size: the image model maps %dx%d to %dx%d, the video model to %dx%d", Ws, Hs, Wi, Hi, Wo, Ho);
     }
-    float* in8 = nullptr; float* out = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&in8), (size_t)(Hs + 2 * pad) * (Ws + 2 * pad) * 32) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&out), (size_t)3 * Ho * Wo * 4) != hipSuccess) {
-        (void)hipFree(in8); return hip_fail(hipErrorOutOfMemory, "hipMalloc(scaled single-image buffers)"); }
-    (void)hipFree(s->scaled_in8); (void)hipFree(s->scaled_out);
-    s->scaled_in8 = in8; s->scaled_out = out; s->sHs = Hs; s->sWs = Ws; s->sHo = Ho; s->sWo = Wo;
+    dev_ptr<float> in8, out;      // both or neither: the stream keeps its old pair when either allocation fails
+    const char* what = "hipMalloc(scaled single-image buffers)";
+    if (dev_alloc(in8, (size_t)(Hs + 2 * pad) * (Ws + 2 * pad) * 8, what) || dev_alloc(out, (size_t)3 * Ho * Wo, what)) return FAV_EHIP;
+    s->scaled_in8 = std::move(in8); s->scaled_out = std::move(out); s->sHs = Hs; s->sWs = Ws; s->sHo = Ho; s->sWo = Wo;      // (freeing the old pair waits for the frames that still read it)
+    return FAV_OK;
+}
+
+// host-ordered mode: the HOST waits until done() sees the sequence number that a one-thread kernel on queue `q` stores into host-mapped
+// memory, and asks the queue every 2048 spins (0.1 s) whether it has failed (`what` names it in the error text)
+template <class Done> static int host_wait(Done done, hipStream_t q, const char* what)
+{
+    for (int spins = 0; !done(); ++spins) {
+        usleep(50);
+        if ((spins & 2047) == 2047) { const hipError_t e = hipStreamQuery(q); if (e != hipSuccess && e != hipErrorNotReady) return hip_fail(e, what); }
+    }
     return FAV_OK;
 }
 
@@ -267,16 +266,16 @@ static int stream_next(fav_stream* s, const uint8_t* frame, const float* bw, con
         TraceRange tr_pre("fav:certainty+warp+assemble");
         if (!cert_ready)
             rc = launch_cert_prepare(mask, bw, s->opts.invert_occlusion, s->opts.fix_occlusions, s->opts.border_mode,
-                                     s->opts.occlusions_min_filter, s->cert_tmp, s->cert, s->H, s->W, st);
+                                     s->opts.occlusions_min_filter, s->cert_tmp.get(), s->cert.get(), s->H, s->W, st);
         if (rc) return rc;
         ++s->frame_counter;
-        rc = launch_prep_input(frame, s->state, s->Ho, s->Wo, bw, s->cert, s->opts.border_mode, s->H, s->W, net_pad(s->net), s->in8, st,
-                               s->opts.fill_random, s->opts.seed, s->frame_counter, s->q0_main);
+        rc = launch_prep_input(frame, s->state.get(), s->Ho, s->Wo, bw, s->cert.get(), s->opts.border_mode, s->H, s->W, net_pad(s->net), s->in8.get(), st,
+                               s->opts.fill_random, s->opts.seed, s->frame_counter, s->q0_main.get());
         if (rc) return rc;
     }
     s->last_st = st; s->ran = true; s->last_scaled = false;
     rc = state_for_writing(s, st); if (rc) return rc;       // (the prior was read from the previous state above)
-    { TraceRange tr_net("fav:network"); rc = net_forward_padded(s->net, s->in8, s->H, s->W, s->state, st); }
+    { TraceRange tr_net("fav:network"); rc = net_forward_padded(s->net, s->in8.get(), s->H, s->W, s->state.get(), st); }
     if (rc) { state_writing_failed(s); return rc; }
     return stream_finish(s, out_f32, out_u8, st);
 }
@@ -288,8 +287,8 @@ extern "C" int fav_stream_next_frame_cert(fav_stream* s, const uint8_t* frame_rg
     FAV_REQUIRE(s && frame_rgb_hwc && backward_flo && cert_pgm, "fav_stream_next_frame_cert: null argument");
     FAV_HIP(hipSetDevice(net_device(s->net)));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    FAV_HIP(hipMemcpyAsync(s->mask, cert_pgm, (size_t)s->H * s->W, hipMemcpyDeviceToDevice, st));
-    return stream_next(s, frame_rgb_hwc, backward_flo, s->mask, out_rgb_f32, out_rgb8_hwc, st);
+    FAV_HIP(hipMemcpyAsync(s->mask.get(), cert_pgm, (size_t)s->H * s->W, hipMemcpyDeviceToDevice, st));
+    return stream_next(s, frame_rgb_hwc, backward_flo, s->mask.get(), out_rgb_f32, out_rgb8_hwc, st);
 }
 
 extern "C" int fav_stream_next_frame_flow(fav_stream* s, const uint8_t* frame_rgb_hwc, const float* backward_flo,
@@ -308,40 +307,37 @@ extern "C" int fav_stream_next_frame_flow(fav_stream* s, const uint8_t* frame_rg
                 // the mask pipeline of this slot ends in a store of its sequence number to host-mapped memory: wait for it HERE, on the
                 // host (it was started a frame ago: normally no wait at all), then enqueue -- no dependency between the queues
                 const int slot = (int)(&pf - s->pref);
-                volatile uint32_t* flag = &s->done_host[slot];
-                for (int spins = 0; *flag != s->pref_seq[slot]; ++spins) {
-                    usleep(50);
-                    if ((spins & 2047) == 2047) { const hipError_t e = hipStreamQuery(s->side[0]); if (e != hipSuccess && e != hipErrorNotReady) return hip_fail(e, "look-ahead queue"); }
-                }
+                volatile uint32_t* flag = s->done_host.get() + slot;
+                int rcw = host_wait([&] { return *flag == s->pref_seq[slot]; }, s->side[0].get(), "look-ahead queue"); if (rcw) return rcw;
                 // the buffers about to leave the stream were read by kernels already in the caller's queue: mark the point behind them
                 pf.retired = ++s->retire_counter;
                 int rcf = launch_store_flag(s->retired_host, pf.retired, st); if (rcf) return rcf;
-            } else FAV_HIP(hipStreamWaitEvent(st, pf.done, 0));
+            } else FAV_HIP(hipStreamWaitEvent(st, pf.done.get(), 0));
             std::swap(s->mask, pf.mask);
             std::swap(s->cert, pf.cert);          // mask -> certainty (options, erosion) was done on the side queue as well
-            return stream_next(s, frame_rgb_hwc, backward_flo, s->mask, out_rgb_f32, out_rgb8_hwc, st, true);
+            return stream_next(s, frame_rgb_hwc, backward_flo, s->mask.get(), out_rgb_f32, out_rgb8_hwc, st, true);
         }
     // not prefetched: compute inline on the caller's stream (own workspace)
     TraceRange tr_mask("fav:consistency mask");
     const float* structure = nullptr; const float* avg = nullptr;
     if (use_structure) {
-        int rc = launch_structure(frame_rgb_hwc, s->W, s->H, s->ws, s->ws_bytes, &structure, &avg, st); if (rc) return rc;
+        int rc = launch_structure(frame_rgb_hwc, s->W, s->H, s->ws.get(), s->ws_bytes, &structure, &avg, st); if (rc) return rc;
     }
     // check + certainty options + erosion + input assembly in ONE tile kernel (round 5; the mask byte and the eroded certainty of every pixel
     // are still written: fav_stream_last_mask); FAV_NO_CHECK_PREP: the check and the assembly as two launches (rounds 3-4)
     static const bool fused_prep = diag_env("FAV_NO_CHECK_PREP") == nullptr;      // (tuning: read once)
     if (fused_prep && s->has_state) {
         ++s->frame_counter;
-        int rcp = launch_check_prep(frame_rgb_hwc, s->state, s->Ho, s->Wo, backward_flo, forward_flo, structure, avg, s->mask, s->cert,
+        int rcp = launch_check_prep(frame_rgb_hwc, s->state.get(), s->Ho, s->Wo, backward_flo, forward_flo, structure, avg, s->mask.get(), s->cert.get(),
                                     s->opts.invert_occlusion, s->opts.fix_occlusions, s->opts.border_mode, s->opts.occlusions_min_filter,
-                                    s->H, s->W, net_pad(s->net), s->in8, st, s->opts.fill_random, s->opts.seed, s->frame_counter);
+                                    s->H, s->W, net_pad(s->net), s->in8.get(), st, s->opts.fill_random, s->opts.seed, s->frame_counter);
         if (rcp) return rcp;
-        return stream_next(s, frame_rgb_hwc, backward_flo, s->mask, out_rgb_f32, out_rgb8_hwc, st, true, true);
+        return stream_next(s, frame_rgb_hwc, backward_flo, s->mask.get(), out_rgb_f32, out_rgb8_hwc, st, true, true);
     }
-    int rc = launch_check_cert(backward_flo, forward_flo, structure, avg, s->mask, s->opts.invert_occlusion, s->opts.fix_occlusions, s->opts.border_mode,
-                               s->opts.occlusions_min_filter, s->cert, s->H, s->W, st);
+    int rc = launch_check_cert(backward_flo, forward_flo, structure, avg, s->mask.get(), s->opts.invert_occlusion, s->opts.fix_occlusions, s->opts.border_mode,
+                               s->opts.occlusions_min_filter, s->cert.get(), s->H, s->W, st);
     if (rc) return rc;
-    return stream_next(s, frame_rgb_hwc, backward_flo, s->mask, out_rgb_f32, out_rgb8_hwc, st, true);
+    return stream_next(s, frame_rgb_hwc, backward_flo, s->mask.get(), out_rgb_f32, out_rgb8_hwc, st, true);
 }
 
 // -estimate_flow: both flows from the two frames on the caller's queue, then the frame as above (never prefetched: the flows do not exist
@@ -402,32 +398,29 @@ extern "C" int fav_stream_prefetch_mask(fav_stream* s, const uint8_t* frame_rgb_
     fav_stream::Pref& pf = s->pref[s->pref_next];
     s->pref_next = (s->pref_next + 1) % fav_stream::NPREF;
     const int q = s->side_next; s->side_next = (s->side_next + 1) % NSIDE_USED;
-    hipStream_t sd = s->side[q];
+    hipStream_t sd = s->side[q].get();
     if (!s->host_ordered) {
-        FAV_HIP(hipEventRecord(s->ev_in, st));                 // inputs are complete at this point of the caller's stream
-        FAV_HIP(hipStreamWaitEvent(sd, s->ev_in, 0));          // (work enqueued on `stream` AFTER this call is not waited for)
+        FAV_HIP(hipEventRecord(s->ev_in.get(), st));                 // inputs are complete at this point of the caller's stream
+        FAV_HIP(hipStreamWaitEvent(sd, s->ev_in.get(), 0));          // (work enqueued on `stream` AFTER this call is not waited for)
     } else if (pf.retired) {                                   // host-ordered: the caller has SEEN the inputs complete (fav.h) ...
         // ... and the slot's buffers were read by frames on the caller's queue: those must be through before a side queue rewrites them
         volatile uint32_t* flag = s->retired_host;
-        for (int spins = 0; (int32_t)(*flag - pf.retired) < 0; ++spins) {
-            usleep(50);
-            if ((spins & 2047) == 2047) { const hipError_t e = hipStreamQuery(st); if (e != hipSuccess && e != hipErrorNotReady) return hip_fail(e, "look-ahead: the caller's queue"); }
-        }
+        int rcw = host_wait([&] { return (int32_t)(*flag - pf.retired) >= 0; }, st, "look-ahead: the caller's queue"); if (rcw) return rcw;
         pf.retired = 0;
     }
     const float* structure = nullptr; const float* avg = nullptr;
     if (use_structure) {
-        int rc = launch_structure(frame_rgb_hwc, s->W, s->H, s->side_ws[q], s->ws_bytes, &structure, &avg, sd, SIDE_PACK >= 0 ? SIDE_PACK : SIDE_CUS, s->q0_main); if (rc) return rc;
+        int rc = launch_structure(frame_rgb_hwc, s->W, s->H, s->side_ws[q].get(), s->ws_bytes, &structure, &avg, sd, SIDE_PACK >= 0 ? SIDE_PACK : SIDE_CUS, s->q0_main.get()); if (rc) return rc;
     }
     // mask + certainty of the frame (mask options, fix_occlusions warp of ones, erosion): depends on the flows and the stream's options only
-    int rc = launch_check_cert(backward_flo, forward_flo, structure, avg, pf.mask, s->opts.invert_occlusion, s->opts.fix_occlusions, s->opts.border_mode,
-                               s->opts.occlusions_min_filter, pf.cert, s->H, s->W, sd);
+    int rc = launch_check_cert(backward_flo, forward_flo, structure, avg, pf.mask.get(), s->opts.invert_occlusion, s->opts.fix_occlusions, s->opts.border_mode,
+                               s->opts.occlusions_min_filter, pf.cert.get(), s->H, s->W, sd);
     if (rc) return rc;
     if (s->host_ordered) {
         const int slot = (int)(&pf - s->pref);
         s->pref_seq[slot] = ++s->seq_counter;
-        rc = launch_store_flag(&s->done_host[slot], s->pref_seq[slot], sd); if (rc) return rc;
-    } else FAV_HIP(hipEventRecord(pf.done, sd));
+        rc = launch_store_flag(s->done_host.get() + slot, s->pref_seq[slot], sd); if (rc) return rc;
+    } else FAV_HIP(hipEventRecord(pf.done.get(), sd));
     pf.valid = true; pf.frame = frame_rgb_hwc; pf.bw = backward_flo; pf.fw = forward_flo; pf.structure = use_structure != 0;
     return FAV_OK;
 }
@@ -436,7 +429,7 @@ extern "C" int fav_stream_get_state(fav_stream* s, float* state_rgb_f32, fav_hip
 {
     FAV_REQUIRE(s && state_rgb_f32 && s->has_state, "fav_stream_get_state: no state");
     FAV_HIP(hipSetDevice(net_device(s->net)));
-    FAV_HIP(hipMemcpyAsync(state_rgb_f32, s->state, (size_t)3 * s->Ho * s->Wo * 4, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    FAV_HIP(hipMemcpyAsync(state_rgb_f32, s->state.get(), (size_t)3 * s->Ho * s->Wo * 4, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
     return FAV_OK;
 }
 
@@ -444,8 +437,8 @@ extern "C" int fav_stream_set_state(fav_stream* s, const float* state_rgb_f32, f
 {
     FAV_REQUIRE(s && state_rgb_f32, "fav_stream_set_state: null argument");
     FAV_HIP(hipSetDevice(net_device(s->net)));
-    if (s->png_pending) { FAV_HIP(hipStreamWaitEvent(static_cast<hipStream_t>(stream), s->png_done, 0)); s->png_pending = false; }
-    FAV_HIP(hipMemcpyAsync(s->state, state_rgb_f32, (size_t)3 * s->Ho * s->Wo * 4, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    if (s->png_pending) { FAV_HIP(hipStreamWaitEvent(static_cast<hipStream_t>(stream), s->png_done.get(), 0)); s->png_pending = false; }
+    FAV_HIP(hipMemcpyAsync(s->state.get(), state_rgb_f32, (size_t)3 * s->Ho * s->Wo * 4, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
     s->has_state = true;
     return FAV_OK;
 }
@@ -455,8 +448,8 @@ extern "C" int fav_stream_wait_png(fav_stream* s, fav_hipstream_t stream)
     FAV_REQUIRE(s, "fav_stream_wait_png: null stream");
     FAV_HIP(hipSetDevice(net_device(s->net)));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (s->png_pending) FAV_HIP(hipStreamWaitEvent(st, s->png_done, 0));
-    if (s->png_pending_other) FAV_HIP(hipStreamWaitEvent(st, s->png_done_other, 0));
+    if (s->png_pending) FAV_HIP(hipStreamWaitEvent(st, s->png_done.get(), 0));
+    if (s->png_pending_other) FAV_HIP(hipStreamWaitEvent(st, s->png_done_other.get(), 0));
     return FAV_OK;
 }
 
@@ -465,8 +458,7 @@ static int ensure_png_ws(fav_stream* s)
 {
     if (s->png_ws) return FAV_OK;
     s->png_ws_bytes = png_workspace_bytes(s->Wo, s->Ho);
-    FAV_HIP(hipMalloc(&s->png_ws, s->png_ws_bytes));
-    return FAV_OK;
+    return dev_alloc(s->png_ws, s->png_ws_bytes);
 }
 
 extern "C" int fav_stream_encode_png(fav_stream* s, void* png_out, size_t capacity, uint32_t* png_bytes_out, fav_hipstream_t stream)
@@ -475,7 +467,7 @@ extern "C" int fav_stream_encode_png(fav_stream* s, void* png_out, size_t capaci
     FAV_HIP(hipSetDevice(net_device(s->net)));
     { int rc = ensure_png_ws(s); if (rc) return rc; }
     if (s->png_q) { int rc = fav_stream_wait_png(s, stream); if (rc) return rc; }      // (one workspace: behind the asynchronous encodes)
-    return launch_png_encode(nullptr, s->state, s->Wo, s->Ho, png_out, capacity, png_bytes_out, s->png_ws, s->png_ws_bytes, static_cast<hipStream_t>(stream));
+    return launch_png_encode(nullptr, s->state.get(), s->Wo, s->Ho, png_out, capacity, png_bytes_out, s->png_ws.get(), s->png_ws_bytes, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int fav_stream_encode_png_async(fav_stream* s, void* png_out, size_t capacity, uint32_t* png_bytes_out, fav_hipstream_t stream)
@@ -487,34 +479,21 @@ extern "C" int fav_stream_encode_png_async(fav_stream* s, void* png_out, size_t 
     if (!s->png_q) {
         // all or nothing: a stream with the queue but without the second state buffer would let the next frame overwrite what is being encoded
         const unsigned ef = hipEventDisableTiming | hipEventDisableSystemFence;
-        hipStream_t q = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr; float* other = nullptr;
-        const hipError_t e = [&]() -> hipError_t {
-            hipError_t r;
-            if ((r = hipStreamCreateWithFlags(&q, hipStreamNonBlocking)) != hipSuccess) return r;
-            if ((r = hipEventCreateWithFlags(&e0, ef)) != hipSuccess) return r;
-            if ((r = hipEventCreateWithFlags(&e1, ef)) != hipSuccess) return r;
-            if ((r = hipEventCreateWithFlags(&e2, ef)) != hipSuccess) return r;
-            return hipMalloc(reinterpret_cast<void**>(&other), (size_t)3 * s->Ho * s->Wo * 4);
-        }();
-        if (e != hipSuccess) {
-            if (q) (void)hipStreamDestroy(q);
-            if (e0) (void)hipEventDestroy(e0);
-            if (e1) (void)hipEventDestroy(e1);
-            if (e2) (void)hipEventDestroy(e2);
-            (void)hipFree(other);
-            return hip_fail(e, "fav_stream_encode_png_async: encoder queue / second state buffer");
-        }
-        s->png_q = q; s->ev_png_in = e0; s->png_done = e1; s->png_done_other = e2; s->state_other = other;
+        const char* what = "fav_stream_encode_png_async: encoder queue / second state buffer";
+        queue_h q; event_h e0, e1, e2; dev_ptr<float> other;
+        if (queue_create(q, what) || event_create(e0, ef, what) || event_create(e1, ef, what) || event_create(e2, ef, what) ||
+            dev_alloc(other, (size_t)3 * s->Ho * s->Wo, what)) return FAV_EHIP;
+        s->png_q = std::move(q); s->ev_png_in = std::move(e0); s->png_done = std::move(e1); s->png_done_other = std::move(e2); s->state_other = std::move(other);
         // from now on the encoder's kernels run NEXT TO the following frame's network, like the look-ahead masks do: the network's
         // persistent grids leave them SIDE_CUS CUs and the generic kernel's hand-off between co-resident blocks is off (timed_conv)
         net_reserve_cus(s->net, SIDE_CUS);
         if (s->img_net) net_reserve_cus(s->img_net, SIDE_CUS);
     }
-    FAV_HIP(hipEventRecord(s->ev_png_in, st));                 // the frame is complete at this point of the caller's queue
-    FAV_HIP(hipStreamWaitEvent(s->png_q, s->ev_png_in, 0));
-    int rc = launch_png_encode(nullptr, s->state, s->Wo, s->Ho, png_out, capacity, png_bytes_out, s->png_ws, s->png_ws_bytes, s->png_q);
+    FAV_HIP(hipEventRecord(s->ev_png_in.get(), st));                 // the frame is complete at this point of the caller's queue
+    FAV_HIP(hipStreamWaitEvent(s->png_q.get(), s->ev_png_in.get(), 0));
+    int rc = launch_png_encode(nullptr, s->state.get(), s->Wo, s->Ho, png_out, capacity, png_bytes_out, s->png_ws.get(), s->png_ws_bytes, s->png_q.get());
     if (rc) return rc;
-    FAV_HIP(hipEventRecord(s->png_done, s->png_q));
+    FAV_HIP(hipEventRecord(s->png_done.get(), s->png_q.get()));
     s->png_pending = true;
     return FAV_OK;
 }
@@ -524,9 +503,9 @@ extern "C" int fav_stream_set_host_ordered(fav_stream* s, int on)
     FAV_REQUIRE(s, "fav_stream_set_host_ordered: null stream");
     FAV_HIP(hipSetDevice(net_device(s->net)));
     if (on && !s->done_host) {
-        FAV_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->done_host), 128, hipHostMallocDefault));
-        for (int i = 0; i < 32; ++i) s->done_host[i] = 0u;
-        s->retired_host = s->done_host + 16;               // its own 64-byte line
+        int rc = host_alloc(s->done_host, 32, hipHostMallocDefault); if (rc) return rc;
+        for (int i = 0; i < 32; ++i) s->done_host.get()[i] = 0u;
+        s->retired_host = s->done_host.get() + 16;         // its own 64-byte line
     }
     for (auto& pf : s->pref) { pf.valid = false; pf.retired = 0; }     // look-aheads in flight in the other mode are dropped (their queues drain on their own)
     s->host_ordered = on != 0;
@@ -545,7 +524,7 @@ extern "C" int fav_stream_get_input_f32(const fav_stream* s, float* in7, fav_hip
     FAV_REQUIRE(s && in7 && s->frame_counter > 0, "fav_stream_get_input_f32: no frame has been assembled yet");
     FAV_REQUIRE(!s->last_scaled, "fav_stream_get_input_f32: the last frame ran at the scaled single-image size (this view is the H x W input)");
     FAV_HIP(hipSetDevice(net_device(s->net)));
-    return launch_unpad_input(s->in8, s->H, s->W, net_pad(s->net), in7, static_cast<hipStream_t>(stream));
+    return launch_unpad_input(s->in8.get(), s->H, s->W, net_pad(s->net), in7, static_cast<hipStream_t>(stream));
 }
 
-extern "C" const uint8_t* fav_stream_last_mask(const fav_stream* s) { return s ? s->mask : nullptr; }
+extern "C" const uint8_t* fav_stream_last_mask(const fav_stream* s) { return s ? s->mask.get() : nullptr; }

@@ -17,7 +17,7 @@
 #include <cstring>
 #include <vector>
 
-#include "fav_internal.h"
+#include "dev_owned.h"
 
 using namespace fav;
 
@@ -137,13 +137,6 @@ void gradient_masks(int H, int W, int gw, int gh, std::vector<double> g[4])
     }
 }
 
-int upload(const std::vector<float>& h, float** d)
-{
-    FAV_HIP(hipMalloc(reinterpret_cast<void**>(d), h.size() * sizeof(float)));
-    FAV_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    return FAV_OK;
-}
-
 }  // namespace
 
 struct fav_vr {
@@ -151,48 +144,36 @@ struct fav_vr {
     int H = 0, W = 0;                     // hplus, wplus
     fav_vr_opts o{};
     size_t n = 0;
-    float* map[4] = {nullptr, nullptr, nullptr, nullptr};      // left, right, top, bottom: [2][H][W]
-    float* mask[4] = {nullptr, nullptr, nullptr, nullptr};     // warp(ones, map): [H][W]
-    float* mask_all = nullptr; float* mask_all_div = nullptr;
-    float* grad[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // left, right, top, bottom, left_right, all (fp32)
-    float* anti_all = nullptr;            // fp32(1 - grad_all)
-    float* equi_map = nullptr;
-    float* last[6] = {}; float* prev[6] = {}; float* filt[6] = {};
+    dev_ptr<float> map[4];                // left, right, top, bottom: [2][H][W]
+    dev_ptr<float> mask[4];               // warp(ones, map): [H][W]
+    dev_ptr<float> mask_all, mask_all_div;
+    dev_ptr<float> grad[6];               // left, right, top, bottom, left_right, all (fp32)
+    dev_ptr<float> anti_all;              // fp32(1 - grad_all)
+    dev_ptr<float> equi_map;
+    dev_ptr<float> last[6], prev[6], filt[6];
     bool have_last[6] = {}; bool have_prev = false;
-    float* tmp_rot = nullptr; float* tmp_warp = nullptr; float* border = nullptr; float* lfw = nullptr; float* prior = nullptr;
-    float* flow_lua = nullptr; float* cert_tmp = nullptr; float* cert = nullptr; float* in8 = nullptr;
-    float* strip = nullptr; float* equi = nullptr; float* cube = nullptr;
+    dev_ptr<float> tmp_rot, tmp_warp, border, lfw, prior;
+    dev_ptr<float> flow_lua, cert_tmp, cert, in8;
+    dev_ptr<float> strip, equi, cube;
     int FH = 0, FW = 0;                   // filtered face size
     int cube_h = 0, cube_w = 0;
     // the consistency check on the device (fav_vr_face_flow): mask of a check made on the caller's stream, the mask the last face used
     // (that one or a look-ahead slot's), and the structure workspaces of the checker's 4-argument mode -- one per queue, each allocated
     // by the first structure-mode face that runs on it
-    uint8_t* mask_u8 = nullptr; const uint8_t* last_mask = nullptr;
-    void* ws = nullptr; void* side_ws = nullptr;
+    dev_ptr<uint8_t> mask_u8; const uint8_t* last_mask = nullptr;
+    dev_ptr<void> ws, side_ws;
     // look-ahead (fav_vr_prefetch_mask): one side stream, one slot per face of a frame (slot = mode); everything here is created by the
     // first look-ahead
-    hipStream_t side = nullptr; hipEvent_t ev_in = nullptr;
+    queue_h side; event_h ev_in;
     struct Pending {
-        uint8_t* mask = nullptr; float* cert_tmp = nullptr; hipEvent_t done = nullptr;
+        dev_ptr<uint8_t> mask; dev_ptr<float> cert_tmp; event_h done;
         bool valid = false; int i = 0; const uint8_t* frame = nullptr; const float* bw = nullptr; const float* fw = nullptr; bool structure = false;
     };
     Pending pend[6];
     ~fav_vr()
     {
         if (vid) (void)hipSetDevice(net_device(vid));
-        if (side) { (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); }
-        if (ev_in) (void)hipEventDestroy(ev_in);
-        for (auto& p : pend) { if (p.done) (void)hipEventDestroy(p.done); (void)hipFree(p.mask); (void)hipFree(p.cert_tmp); }
-        (void)hipFree(mask_u8); (void)hipFree(ws); (void)hipFree(side_ws);
-        for (auto p : map) (void)hipFree(p);
-        for (auto p : mask) (void)hipFree(p);
-        for (auto p : grad) (void)hipFree(p);
-        for (auto p : last) (void)hipFree(p);
-        for (auto p : prev) (void)hipFree(p);
-        for (auto p : filt) (void)hipFree(p);
-        float* rest[] = {mask_all, mask_all_div, anti_all, equi_map, tmp_rot, tmp_warp, border, lfw, prior, flow_lua, cert_tmp, cert,
-                         in8, strip, equi, cube};
-        for (auto p : rest) (void)hipFree(p);
+        side.reset();      // drained and destroyed BEFORE the look-ahead slots and static masks its kernels touch are freed (the members go after this body)
     }
 };
 
@@ -246,71 +227,68 @@ extern "C" int fav_vr_create(fav_net* video_net, fav_net* image_net_or_null, int
         FAV_REQUIRE(Ho == hplus && Wo == wplus, "fav_vr_create: the image model changes the face size");
     }
     FAV_HIP(hipSetDevice(net_device(video_net)));
-    fav_vr* v = new fav_vr();
+    std::unique_ptr<fav_vr> v(new fav_vr());      // (every failure below is a plain return: the handles free what exists by then)
     v->vid = video_net; v->img = image_net_or_null; v->H = hplus; v->W = wplus; v->o = o;
     if (v->o.occlusions_min_filter < 1) v->o.occlusions_min_filter = 1;
     const size_t n = (size_t)hplus * wplus; v->n = n;
     const int pad = net_pad(video_net);
-    auto fail = [&](int rc) { delete v; return rc; };
-    auto dmalloc = [&](float** p, size_t floats) { return hipMalloc(reinterpret_cast<void**>(p), floats * sizeof(float)) == hipSuccess; };
+    int rc = FAV_OK;
     // ---- static maps and masks (fast_artistic_video_vr.lua:164-198)
     const int crop[4] = {o.overlap_w, o.overlap_w, o.overlap_h, o.overlap_h};
-    std::vector<float> ones(n, 1.f); float* d_ones = nullptr;
-    int rc = upload(ones, &d_ones); if (rc) return fail(rc);
-    for (int k = 0; k < 4; ++k) {
-        std::vector<float> m; perspective_map(k, hplus, wplus, crop[k], m);
-        rc = upload(m, &v->map[k]); if (rc) { (void)hipFree(d_ones); return fail(rc); }
-        if (!dmalloc(&v->mask[k], n)) { (void)hipFree(d_ones); return fail(hip_fail(hipErrorOutOfMemory, "vr masks")); }
-        rc = launch_warp(d_ones, v->map[k], v->mask[k], 1, 1, hplus, wplus, hplus, wplus, o.border_mode, nullptr);
-        if (rc) { (void)hipFree(d_ones); return fail(rc); }
+    {
+        std::vector<float> ones(n, 1.f); dev_ptr<float> d_ones;
+        rc = dev_upload(d_ones, ones); if (rc) return rc;
+        for (int k = 0; k < 4; ++k) {
+            std::vector<float> m; perspective_map(k, hplus, wplus, crop[k], m);
+            if (dev_upload(v->map[k], m) || dev_alloc(v->mask[k], n, "vr masks")) return FAV_EHIP;
+            rc = launch_warp(d_ones.get(), v->map[k].get(), v->mask[k].get(), 1, 1, hplus, wplus, hplus, wplus, o.border_mode, nullptr); if (rc) return rc;
+        }
+        FAV_HIP(hipDeviceSynchronize());
     }
-    FAV_HIP(hipDeviceSynchronize());
-    (void)hipFree(d_ones);
     {   // mask_all_div = max(l + r + t + b, 1), mask_all = min(.., 1) (:176-177) -- tiny, done on the host in fp32
         std::vector<float> mk[4], div(n), all(n);
-        for (int k = 0; k < 4; ++k) { mk[k].resize(n); FAV_HIP(hipMemcpy(mk[k].data(), v->mask[k], n * 4, hipMemcpyDeviceToHost)); }
+        for (int k = 0; k < 4; ++k) { mk[k].resize(n); FAV_HIP(hipMemcpy(mk[k].data(), v->mask[k].get(), n * 4, hipMemcpyDeviceToHost)); }
         for (size_t i = 0; i < n; ++i) {
             volatile float s = mk[0][i] + mk[1][i]; s = s + mk[2][i]; s = s + mk[3][i];      // left + right + top + bottom
             div[i] = s > 1.f ? (float)s : 1.f; all[i] = s < 1.f ? (float)s : 1.f;
         }
-        rc = upload(div, &v->mask_all_div); if (rc) return fail(rc);
-        rc = upload(all, &v->mask_all); if (rc) return fail(rc);
+        if (dev_upload(v->mask_all_div, div) || dev_upload(v->mask_all, all)) return FAV_EHIP;
     }
     {   // gradient masks (:179-187), doubles cast to fp32 when used (:type(dtype))
         std::vector<double> g[4];
         gradient_masks(hplus, wplus, o.overlap_w - 10, o.overlap_h - 10, g);
         std::vector<float> f(n), anti(n);
-        for (int k = 0; k < 4; ++k) { for (size_t i = 0; i < n; ++i) f[i] = (float)g[k][i]; rc = upload(f, &v->grad[k]); if (rc) return fail(rc); }
+        for (int k = 0; k < 4; ++k) { for (size_t i = 0; i < n; ++i) f[i] = (float)g[k][i]; rc = dev_upload(v->grad[k], f); if (rc) return rc; }
         for (size_t i = 0; i < n; ++i) f[i] = (float)std::fmax(g[0][i], g[1][i]);
-        rc = upload(f, &v->grad[4]); if (rc) return fail(rc);
+        rc = dev_upload(v->grad[4], f); if (rc) return rc;
         for (size_t i = 0; i < n; ++i) {
             const double a = std::fmax(std::fmax(g[0][i], g[1][i]), std::fmax(g[2][i], g[3][i]));
             f[i] = (float)a; anti[i] = (float)(1.0 - a);                        // :456: csub in double, then :type(dtype)
         }
-        rc = upload(f, &v->grad[5]); if (rc) return fail(rc);
-        rc = upload(anti, &v->anti_all); if (rc) return fail(rc);
+        if (dev_upload(v->grad[5], f) || dev_upload(v->anti_all, anti)) return FAV_EHIP;
     }
     const int r = o.median_filter / 2;
     v->FH = hplus - 2 * r; v->FW = wplus - 2 * r;
     const int ovw = o.overlap_w / 2 - r, ovh = o.overlap_h / 2 - r;               // :515-516
     const int ch = hplus - 2 * ovh, cw = wplus - 2 * ovw;                          // crop {ov+1, plus-ov}
-    if (ovw < 0 || ovh < 0 || hplus - ovh > v->FH || wplus - ovw > v->FW) { delete v; set_error("fav_vr_create: overlap/2 must be >= 3*floor(median/2) for the cube-map crop"); return FAV_EINVAL; }
+    FAV_REQUIRE(ovw >= 0 && ovh >= 0 && hplus - ovh <= v->FH && wplus - ovw <= v->FW, "fav_vr_create: overlap/2 must be >= 3*floor(median/2) for the cube-map crop");
     v->cube_h = (ch == cw) ? ch : 0; v->cube_w = (ch == cw) ? 6 * cw : 0;       // rotated top/bottom faces need square crops
-    bool ok = true;
-    for (int k = 0; k < 6; ++k) ok = ok && dmalloc(&v->last[k], 3 * n) && dmalloc(&v->prev[k], 3 * n) && dmalloc(&v->filt[k], 3 * (size_t)v->FH * v->FW);
-    ok = ok && dmalloc(&v->tmp_rot, 3 * n) && dmalloc(&v->tmp_warp, 3 * n) && dmalloc(&v->border, 3 * n) && dmalloc(&v->lfw, 3 * n) &&
-         dmalloc(&v->prior, 3 * n) && dmalloc(&v->flow_lua, 2 * n) && dmalloc(&v->cert_tmp, n) && dmalloc(&v->cert, n) &&
-         dmalloc(&v->in8, (size_t)(hplus + 2 * pad) * (wplus + 2 * pad) * 8);
-    ok = ok && hipMalloc(reinterpret_cast<void**>(&v->mask_u8), n) == hipSuccess;
-    if (v->cube_w) ok = ok && dmalloc(&v->cube, 3 * (size_t)v->cube_h * v->cube_w);
+    auto dmalloc = [&](dev_ptr<float>& p, size_t floats) { if (!rc) rc = dev_alloc(p, floats, "hipMalloc(vr buffers)"); };      // (nothing more once one has failed)
+    for (int k = 0; k < 6; ++k) { dmalloc(v->last[k], 3 * n); dmalloc(v->prev[k], 3 * n); dmalloc(v->filt[k], 3 * (size_t)v->FH * v->FW); }
+    dmalloc(v->tmp_rot, 3 * n); dmalloc(v->tmp_warp, 3 * n); dmalloc(v->border, 3 * n); dmalloc(v->lfw, 3 * n);
+    dmalloc(v->prior, 3 * n); dmalloc(v->flow_lua, 2 * n); dmalloc(v->cert_tmp, n); dmalloc(v->cert, n);
+    dmalloc(v->in8, (size_t)(hplus + 2 * pad) * (wplus + 2 * pad) * 8);
+    if (!rc) rc = dev_alloc(v->mask_u8, n, "hipMalloc(vr buffers)");
+    if (v->cube_w) dmalloc(v->cube, 3 * (size_t)v->cube_h * v->cube_w);
+    if (rc) return rc;
     if (o.out_equi_w > 0 && o.out_equi_h > 0) {
         std::vector<float> m;
         equirect_map(hplus - 2 * r, wplus - 2 * r, o.overlap_w - r, o.overlap_h - r, o.out_equi_w, o.out_equi_h, m);   // :191-192
-        rc = upload(m, &v->equi_map); if (rc) return fail(rc);
-        ok = ok && dmalloc(&v->strip, 3 * (size_t)v->FH * 6 * v->FW) && dmalloc(&v->equi, 3 * (size_t)o.out_equi_w * o.out_equi_h);
+        rc = dev_upload(v->equi_map, m); if (rc) return rc;
+        dmalloc(v->strip, 3 * (size_t)v->FH * 6 * v->FW); dmalloc(v->equi, 3 * (size_t)o.out_equi_w * o.out_equi_h);
+        if (rc) return rc;
     }
-    if (!ok) return fail(hip_fail(hipErrorOutOfMemory, "hipMalloc(vr buffers)"));
-    *out = v;
+    *out = v.release();
     return FAV_OK;
 }
 
@@ -322,11 +300,11 @@ static int add_border(fav_vr* v, const float* src, int rot, int map_k, bool divi
     const float* s = src;
     if (rot) {
         FAV_REQUIRE(v->H == v->W, "cube-map faces must be square for the rotated neighbours");
-        int rc = launch_vr_rotate(src, v->tmp_rot, v->H, v->W, rot, st); if (rc) return rc;
-        s = v->tmp_rot;
+        int rc = launch_vr_rotate(src, v->tmp_rot.get(), v->H, v->W, rot, st); if (rc) return rc;
+        s = v->tmp_rot.get();
     }
-    int rc = launch_warp(s, v->map[map_k], v->tmp_warp, 1, 3, v->H, v->W, v->H, v->W, v->o.border_mode, st); if (rc) return rc;
-    return launch_vr_accum(v->border, v->tmp_warp, divide ? v->mask_all_div : nullptr, v->n, first ? 1 : 0, st);
+    int rc = launch_warp(s, v->map[map_k].get(), v->tmp_warp.get(), 1, 3, v->H, v->W, v->H, v->W, v->o.border_mode, st); if (rc) return rc;
+    return launch_vr_accum(v->border.get(), v->tmp_warp.get(), divide ? v->mask_all_div.get() : nullptr, v->n, first ? 1 : 0, st);
 }
 
 static bool vr_temporal(const fav_vr* v, int i) { return i >= 7 && !v->o.create_inconsistent; }
@@ -336,23 +314,23 @@ static void border_masks(const fav_vr* v, int mode, const float* m[4])
 {
     enum { L = 0, R = 1, T = 2, B = 3 };
     const bool bd = !v->o.create_inconsistent_border;
-    m[0] = bd && (mode == 1 || mode >= 3) ? v->mask[L] : nullptr;
-    m[1] = bd && (mode >= 2) ? v->mask[R] : nullptr;
-    m[2] = bd && (mode >= 4) ? v->mask[T] : nullptr;
-    m[3] = bd && (mode >= 4) ? v->mask[B] : nullptr;
+    m[0] = bd && (mode == 1 || mode >= 3) ? v->mask[L].get() : nullptr;
+    m[1] = bd && (mode >= 2) ? v->mask[R].get() : nullptr;
+    m[2] = bd && (mode >= 4) ? v->mask[T].get() : nullptr;
+    m[3] = bd && (mode >= 4) ? v->mask[B].get() : nullptr;
 }
 
 // the checker on queue `q`: makeOptFlow_deepflow.sh:59 `consistencyChecker backward forward reliable [frame]` -> mask, and
 // cert_tmp = max(mask / 255, border masks).  The structure plane is launch_structure in its stand-alone operator form (as
 // fav_consistency_u8 calls it) on `*ws`, the workspace of this queue.
-static int check_cert(fav_vr* v, int mode, const uint8_t* frame, const float* bw, const float* fw, bool use_structure, void** ws,
+static int check_cert(fav_vr* v, int mode, const uint8_t* frame, const float* bw, const float* fw, bool use_structure, dev_ptr<void>& ws,
                       uint8_t* mask, float* cert_tmp, hipStream_t q)
 {
     const float* structure = nullptr; const float* avg = nullptr;
     if (use_structure) {
         const size_t ws_bytes = fav_consistency_workspace_bytes(v->W, v->H, 1);
-        if (!*ws) FAV_HIP(hipMalloc(ws, ws_bytes));
-        int rc = launch_structure(frame, v->W, v->H, *ws, ws_bytes, &structure, &avg, q); if (rc) return rc;
+        if (!ws) { int rc = dev_alloc(ws, ws_bytes); if (rc) return rc; }
+        int rc = launch_structure(frame, v->W, v->H, ws.get(), ws_bytes, &structure, &avg, q); if (rc) return rc;
     }
     const float* m[4]; border_masks(v, mode, m);
     return launch_vr_check_cert(bw, fw, structure, avg, m[0], m[1], m[2], m[3], mask, cert_tmp, v->H, v->W, q);
@@ -389,71 +367,71 @@ static int vr_face(fav_vr* v, int i, const uint8_t* frame_rgb_hwc, const float* 
     if (temporal && cs.flow) FAV_REQUIRE(cs.fw, "%s: face %d needs the forward flow (forward_flo is NULL)", cs.who, i);
     fav_vr::Pending* ahead = take_pending(v, i, frame_rgb_hwc, backward_flo, cs.fw, temporal && cs.flow, cs.structure);
     if (single) {
-        rc = launch_vr_prep(frame_rgb_hwc, nullptr, nullptr, v->img ? 0 : v->o.fill_random, v->o.seed, (unsigned)i, H, W, pad, v->in8, st);
+        rc = launch_vr_prep(frame_rgb_hwc, nullptr, nullptr, v->img ? 0 : v->o.fill_random, v->o.seed, (unsigned)i, H, W, pad, v->in8.get(), st);
         if (rc) return rc;
-        rc = net_forward_padded(v->img ? v->img : v->vid, v->in8, H, W, v->last[mode], st); if (rc) return rc;
+        rc = net_forward_padded(v->img ? v->img : v->vid, v->in8.get(), H, W, v->last[mode].get(), st); if (rc) return rc;
     } else {
         if (temporal) FAV_REQUIRE(backward_flo && (cs.flow || cs.cert_pgm) && v->have_prev, "%s: face %d needs the flow, the certainty and a finished previous frame", cs.who, i);
         for (int k = 0; k < mode && !v->o.create_inconsistent_border; ++k)
             FAV_REQUIRE(v->have_last[k], "%s: faces must be processed in order (face %d of this frame is missing)", cs.who, k);
         // ---- func_load_cert (:204-237) + min filter (core.lua:207)
         const bool bd = !v->o.create_inconsistent_border;
-        const float* cert_tmp = v->cert_tmp;
+        const float* cert_tmp = v->cert_tmp.get();
         if (temporal && cs.flow) {
             if (ahead) {                                                          // computed ahead of time on the side stream
-                FAV_HIP(hipStreamWaitEvent(st, ahead->done, 0));
-                cert_tmp = ahead->cert_tmp; v->last_mask = ahead->mask;
+                FAV_HIP(hipStreamWaitEvent(st, ahead->done.get(), 0));
+                cert_tmp = ahead->cert_tmp.get(); v->last_mask = ahead->mask.get();
             } else {
-                rc = check_cert(v, mode, frame_rgb_hwc, backward_flo, cs.fw, cs.structure, &v->ws, v->mask_u8, v->cert_tmp, st); if (rc) return rc;
-                v->last_mask = v->mask_u8;
+                rc = check_cert(v, mode, frame_rgb_hwc, backward_flo, cs.fw, cs.structure, v->ws, v->mask_u8.get(), v->cert_tmp.get(), st); if (rc) return rc;
+                v->last_mask = v->mask_u8.get();
             }
         } else {
             const float* m[4]; border_masks(v, mode, m);
-            rc = launch_vr_cert(temporal ? cs.cert_pgm : nullptr, m[0], m[1], m[2], m[3], v->cert_tmp, n, st); if (rc) return rc;
+            rc = launch_vr_cert(temporal ? cs.cert_pgm : nullptr, m[0], m[1], m[2], m[3], v->cert_tmp.get(), n, st); if (rc) return rc;
         }
-        rc = launch_min_filter_f32(cert_tmp, v->cert, H, W, v->o.occlusions_min_filter, st); if (rc) return rc;
+        rc = launch_min_filter_f32(cert_tmp, v->cert.get(), H, W, v->o.occlusions_min_filter, st); if (rc) return rc;
         // ---- func_make_last_frame_warped (:239-302)
         bool have_border = false;
         if (bd) {
-            float** S = v->last;
-            if (mode == 1)      { rc = add_border(v, S[0], 0, L, false, true, st); }
-            else if (mode == 2) { rc = add_border(v, S[0], 0, R, false, true, st); }
-            else if (mode == 3) { rc = add_border(v, S[1], 0, L, false, true, st); if (!rc) rc = add_border(v, S[2], 0, R, false, false, st); }
+            const dev_ptr<float>* S = v->last;
+            if (mode == 1)      { rc = add_border(v, S[0].get(), 0, L, false, true, st); }
+            else if (mode == 2) { rc = add_border(v, S[0].get(), 0, R, false, true, st); }
+            else if (mode == 3) { rc = add_border(v, S[1].get(), 0, L, false, true, st); if (!rc) rc = add_border(v, S[2].get(), 0, R, false, false, st); }
             else if (mode == 4) {
-                rc = add_border(v, S[1], 1, L, true, true, st);
-                if (!rc) rc = add_border(v, S[2], 2, R, true, false, st);
-                if (!rc) rc = add_border(v, S[3], 0, T, true, false, st);
-                if (!rc) rc = add_border(v, S[0], 3, B, true, false, st);
+                rc = add_border(v, S[1].get(), 1, L, true, true, st);
+                if (!rc) rc = add_border(v, S[2].get(), 2, R, true, false, st);
+                if (!rc) rc = add_border(v, S[3].get(), 0, T, true, false, st);
+                if (!rc) rc = add_border(v, S[0].get(), 3, B, true, false, st);
             } else if (mode == 5) {
-                rc = add_border(v, S[1], 2, L, true, true, st);
-                if (!rc) rc = add_border(v, S[2], 1, R, true, false, st);
-                if (!rc) rc = add_border(v, S[0], 3, T, true, false, st);
-                if (!rc) rc = add_border(v, S[3], 0, B, true, false, st);
+                rc = add_border(v, S[1].get(), 2, L, true, true, st);
+                if (!rc) rc = add_border(v, S[2].get(), 1, R, true, false, st);
+                if (!rc) rc = add_border(v, S[0].get(), 3, T, true, false, st);
+                if (!rc) rc = add_border(v, S[3].get(), 0, B, true, false, st);
             }
             if (rc) return rc;
             have_border = mode >= 1;
         }
-        if (!have_border) FAV_HIP(hipMemsetAsync(v->border, 0, 3 * n * sizeof(float), st));
-        const float* prior = v->border;
+        if (!have_border) FAV_HIP(hipMemsetAsync(v->border.get(), 0, 3 * n * sizeof(float), st));
+        const float* prior = v->border.get();
         if (temporal) {
-            rc = launch_vr_flo_to_lua(backward_flo, v->flow_lua, n, st); if (rc) return rc;
-            rc = launch_warp(v->prev[mode], v->flow_lua, v->lfw, 1, 3, H, W, H, W, v->o.border_mode, st); if (rc) return rc;
-            if (mode == 0) prior = v->lfw;
+            rc = launch_vr_flo_to_lua(backward_flo, v->flow_lua.get(), n, st); if (rc) return rc;
+            rc = launch_warp(v->prev[mode].get(), v->flow_lua.get(), v->lfw.get(), 1, 3, H, W, H, W, v->o.border_mode, st); if (rc) return rc;
+            if (mode == 0) prior = v->lfw.get();
             else {
                 // grad_masks = {right, left, left_right, all, all}; masks = {left, right, left + right, all, all}   (:286-287)
-                const float* g = mode == 1 ? v->grad[1] : mode == 2 ? v->grad[0] : mode == 3 ? v->grad[4] : v->grad[5];
-                const float* m = mode == 1 ? v->mask[L] : mode == 2 ? v->mask[R] : mode == 3 ? v->mask[L] : v->mask_all;
-                const float* m2 = mode == 3 ? v->mask[R] : nullptr;
-                rc = launch_vr_prior(v->lfw, v->border, g, v->cert, m, m2, v->prior, n, st); if (rc) return rc;
-                prior = v->prior;
+                const float* g = mode == 1 ? v->grad[1].get() : mode == 2 ? v->grad[0].get() : mode == 3 ? v->grad[4].get() : v->grad[5].get();
+                const float* m = mode == 1 ? v->mask[L].get() : mode == 2 ? v->mask[R].get() : mode == 3 ? v->mask[L].get() : v->mask_all.get();
+                const float* m2 = mode == 3 ? v->mask[R].get() : nullptr;
+                rc = launch_vr_prior(v->lfw.get(), v->border.get(), g, v->cert.get(), m, m2, v->prior.get(), n, st); if (rc) return rc;
+                prior = v->prior.get();
             }
         }
         // ---- run_next_image (core.lua:161-180)
-        rc = launch_vr_prep(frame_rgb_hwc, prior, v->cert, v->o.fill_random, v->o.seed, (unsigned)i, H, W, pad, v->in8, st); if (rc) return rc;
-        rc = net_forward_padded(v->vid, v->in8, H, W, v->last[mode], st); if (rc) return rc;
+        rc = launch_vr_prep(frame_rgb_hwc, prior, v->cert.get(), v->o.fill_random, v->o.seed, (unsigned)i, H, W, pad, v->in8.get(), st); if (rc) return rc;
+        rc = net_forward_padded(v->vid, v->in8.get(), H, W, v->last[mode].get(), st); if (rc) return rc;
     }
     v->have_last[mode] = true;
-    if (out_rgb_f32) FAV_HIP(hipMemcpyAsync(out_rgb_f32, v->last[mode], 3 * n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (out_rgb_f32) FAV_HIP(hipMemcpyAsync(out_rgb_f32, v->last[mode].get(), 3 * n * sizeof(float), hipMemcpyDeviceToDevice, st));
     return FAV_OK;
 }
 
@@ -483,19 +461,16 @@ extern "C" int fav_vr_prefetch_mask(fav_vr* v, int i, const uint8_t* frame_rgb_h
     FAV_HIP(hipSetDevice(net_device(v->vid)));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const unsigned ef = hipEventDisableTiming | hipEventDisableSystemFence;
-    if (!v->side) FAV_HIP(hipStreamCreateWithFlags(&v->side, hipStreamNonBlocking));
-    if (!v->ev_in) FAV_HIP(hipEventCreateWithFlags(&v->ev_in, ef));
+    if ((!v->side && queue_create(v->side)) || (!v->ev_in && event_create(v->ev_in, ef))) return FAV_EHIP;
     const int mode = (i - 1) % 6;
     fav_vr::Pending& p = v->pend[mode];
     p.valid = false;
-    if (!p.mask) FAV_HIP(hipMalloc(reinterpret_cast<void**>(&p.mask), v->n));
-    if (!p.cert_tmp) FAV_HIP(hipMalloc(reinterpret_cast<void**>(&p.cert_tmp), v->n * sizeof(float)));
-    if (!p.done) FAV_HIP(hipEventCreateWithFlags(&p.done, ef));
-    FAV_HIP(hipEventRecord(v->ev_in, st));
-    FAV_HIP(hipStreamWaitEvent(v->side, v->ev_in, 0));                           // (work enqueued on `stream` after this call is not waited for)
-    int rc = check_cert(v, mode, frame_rgb_hwc, backward_flo, forward_flo, use_structure != 0, &v->side_ws, p.mask, p.cert_tmp, v->side);
+    if ((!p.mask && dev_alloc(p.mask, v->n)) || (!p.cert_tmp && dev_alloc(p.cert_tmp, v->n)) || (!p.done && event_create(p.done, ef))) return FAV_EHIP;
+    FAV_HIP(hipEventRecord(v->ev_in.get(), st));
+    FAV_HIP(hipStreamWaitEvent(v->side.get(), v->ev_in.get(), 0));               // (work enqueued on `stream` after this call is not waited for)
+    int rc = check_cert(v, mode, frame_rgb_hwc, backward_flo, forward_flo, use_structure != 0, v->side_ws, p.mask.get(), p.cert_tmp.get(), v->side.get());
     if (rc) return rc;
-    FAV_HIP(hipEventRecord(p.done, v->side));
+    FAV_HIP(hipEventRecord(p.done.get(), v->side.get()));
     p.valid = true; p.i = i; p.frame = frame_rgb_hwc; p.bw = backward_flo; p.fw = forward_flo; p.structure = use_structure != 0;
     return FAV_OK;
 }
@@ -509,7 +484,7 @@ extern "C" int fav_vr_finish_frame(fav_vr* v, uint8_t* equi_rgb8_hwc, uint8_t* c
     FAV_HIP(hipSetDevice(net_device(v->vid)));
     hipStream_t st = static_cast<hipStream_t>(stream);
     enum { L = 0, R = 1, T = 2, B = 3 };
-    float** S = v->last;
+    const dev_ptr<float>* S = v->last;
     // blend_other_sides (:454-509): {source face, rotation, map} x 4 per face, summed as combineSides does
     struct Src { int face, rot, map; };
     static const Src plan[6][4] = {
@@ -522,31 +497,31 @@ extern "C" int fav_vr_finish_frame(fav_vr* v, uint8_t* equi_rgb8_hwc, uint8_t* c
     };
     int rc;
     for (int f = 0; f < 6; ++f) {
-        for (int q = 0; q < 4; ++q) { rc = add_border(v, S[plan[f][q].face], plan[f][q].rot, plan[f][q].map, true, q == 0, st); if (rc) return rc; }
-        rc = launch_vr_blend(S[f], v->border, v->grad[5], v->anti_all, v->prev[f], v->n, st); if (rc) return rc;
+        for (int q = 0; q < 4; ++q) { rc = add_border(v, S[plan[f][q].face].get(), plan[f][q].rot, plan[f][q].map, true, q == 0, st); if (rc) return rc; }
+        rc = launch_vr_blend(S[f].get(), v->border.get(), v->grad[5].get(), v->anti_all.get(), v->prev[f].get(), v->n, st); if (rc) return rc;
     }
     v->have_prev = true;
     for (int k = 0; k < 6; ++k) v->have_last[k] = false;
     // :529-536 median filter of every blended face
     for (int f = 0; f < 6; ++f) {
-        if (v->o.median_filter > 0) { rc = launch_vr_median(v->prev[f], v->filt[f], v->H, v->W, v->o.median_filter, st); if (rc) return rc; }
-        else FAV_HIP(hipMemcpyAsync(v->filt[f], v->prev[f], 3 * v->n * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (v->o.median_filter > 0) { rc = launch_vr_median(v->prev[f].get(), v->filt[f].get(), v->H, v->W, v->o.median_filter, st); if (rc) return rc; }
+        else FAV_HIP(hipMemcpyAsync(v->filt[f].get(), v->prev[f].get(), 3 * v->n * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     const int FH = v->FH, FW = v->FW;
     if (equi_rgb8_hwc) {                                                         // :538-541
         FAV_REQUIRE(v->equi_map, "fav_vr_finish_frame: created without an equirectangular output size");
         const int rot[6] = {0, 0, 0, 0, 3, 3};
-        for (int f = 0; f < 6; ++f) { rc = launch_vr_strip(v->filt[f], FH, FW, 0, 0, FH, FW, rot[f], v->strip, FH, 6 * FW, f * FW, st); if (rc) return rc; }
-        rc = launch_warp(v->strip, v->equi_map, v->equi, 1, 3, FH, 6 * FW, v->o.out_equi_h, v->o.out_equi_w, v->o.border_mode, st); if (rc) return rc;
-        rc = launch_quantize_rgb8(v->equi, equi_rgb8_hwc, v->o.out_equi_h, v->o.out_equi_w, st); if (rc) return rc;
+        for (int f = 0; f < 6; ++f) { rc = launch_vr_strip(v->filt[f].get(), FH, FW, 0, 0, FH, FW, rot[f], v->strip.get(), FH, 6 * FW, f * FW, st); if (rc) return rc; }
+        rc = launch_warp(v->strip.get(), v->equi_map.get(), v->equi.get(), 1, 3, FH, 6 * FW, v->o.out_equi_h, v->o.out_equi_w, v->o.border_mode, st); if (rc) return rc;
+        rc = launch_quantize_rgb8(v->equi.get(), equi_rgb8_hwc, v->o.out_equi_h, v->o.out_equi_w, st); if (rc) return rc;
     }
     if (cubemap_rgb8_hwc) {                                                      // :542-552: faces 4, 1, rot90(5), rotMinus90(6), 3, 2
         FAV_REQUIRE(v->cube, "fav_vr_finish_frame: the cube-map strip needs square cropped faces");
         const int r = v->o.median_filter / 2, ovw = v->o.overlap_w / 2 - r, ovh = v->o.overlap_h / 2 - r;
         const int ch = v->H - 2 * ovh, cw = v->W - 2 * ovw;
         const int order[6] = {3, 0, 4, 5, 2, 1}, rot[6] = {0, 0, 1, 2, 0, 0};
-        for (int q = 0; q < 6; ++q) { rc = launch_vr_strip(v->filt[order[q]], FH, FW, ovh, ovw, ch, cw, rot[q], v->cube, v->cube_h, v->cube_w, q * cw, st); if (rc) return rc; }
-        rc = launch_quantize_rgb8(v->cube, cubemap_rgb8_hwc, v->cube_h, v->cube_w, st); if (rc) return rc;
+        for (int q = 0; q < 6; ++q) { rc = launch_vr_strip(v->filt[order[q]].get(), FH, FW, ovh, ovw, ch, cw, rot[q], v->cube.get(), v->cube_h, v->cube_w, q * cw, st); if (rc) return rc; }
+        rc = launch_quantize_rgb8(v->cube.get(), cubemap_rgb8_hwc, v->cube_h, v->cube_w, st); if (rc) return rc;
     }
     return FAV_OK;
 }
@@ -571,12 +546,12 @@ extern "C" int fav_vr_get_f32(const fav_vr* v, int which, int k, float* out_dev,
     FAV_REQUIRE(v && out_dev && k >= 0 && k < 6, "fav_vr_get_f32: bad argument");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const float* src = nullptr; size_t cnt = 0;
-    if (which == 0) { src = v->last[k]; cnt = 3 * v->n; }
-    else if (which == 1) { src = v->prev[k]; cnt = 3 * v->n; }
-    else if (which == 2) { src = v->filt[k]; cnt = 3 * (size_t)v->FH * v->FW; }
-    else if (which == 3) { src = v->equi; cnt = v->equi ? 3 * (size_t)v->o.out_equi_w * v->o.out_equi_h : 0; }
-    else if (which == 4) { src = v->cube; cnt = v->cube ? 3 * (size_t)v->cube_h * v->cube_w : 0; }
-    else if (which == 5) { src = v->cert; cnt = v->n; }
+    if (which == 0) { src = v->last[k].get(); cnt = 3 * v->n; }
+    else if (which == 1) { src = v->prev[k].get(); cnt = 3 * v->n; }
+    else if (which == 2) { src = v->filt[k].get(); cnt = 3 * (size_t)v->FH * v->FW; }
+    else if (which == 3) { src = v->equi.get(); cnt = v->equi ? 3 * (size_t)v->o.out_equi_w * v->o.out_equi_h : 0; }
+    else if (which == 4) { src = v->cube.get(); cnt = v->cube ? 3 * (size_t)v->cube_h * v->cube_w : 0; }
+    else if (which == 5) { src = v->cert.get(); cnt = v->n; }
     FAV_REQUIRE(src && cnt, "fav_vr_get_f32: nothing of kind %d", which);
     FAV_HIP(hipMemcpyAsync(out_dev, src, cnt * sizeof(float), hipMemcpyDeviceToDevice, st));
     return FAV_OK;
