@@ -150,6 +150,47 @@ extern "C" int fav_png_encode_f32(const float* rgb_planar, int W, int H, void* p
     return launch_png_encode(nullptr, rgb_planar, W, H, png_out, capacity, png_bytes_out, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
+// ---- YUV4MPEG2: 8-bit YCbCr planes <-> RGB (kernels_yuv.hip)
+int fav::yuv_format_check(const char* who, int W, int H, const fav_yuv_format* f)
+{
+    FAV_REQUIRE(f, "%s: null format", who);
+    FAV_REQUIRE(W > 0 && H > 0 && (long long)W * H <= (1ll << 28), "%s: bad frame size %dx%d", who, W, H);
+    FAV_REQUIRE(f->chroma == FAV_YUV_420 || f->chroma == FAV_YUV_444, "%s: chroma must be 0 (4:2:0) or 1 (4:4:4), not %d", who, f->chroma);
+    FAV_REQUIRE(f->chroma == FAV_YUV_444 || f->siting == FAV_YUV_SITING_CENTER || f->siting == FAV_YUV_SITING_LEFT,
+                "%s: siting must be 0 (centre, C420jpeg) or 1 (left, C420mpeg2), not %d", who, f->siting);
+    FAV_REQUIRE(f->matrix == FAV_YUV_BT601 || f->matrix == FAV_YUV_BT709, "%s: matrix must be 0 (BT.601) or 1 (BT.709), not %d", who, f->matrix);
+    return FAV_OK;
+}
+
+extern "C" size_t fav_yuv_frame_bytes(int W, int H, const fav_yuv_format* fmt_host)
+{
+    return yuv_format_check("fav_yuv_frame_bytes", W, H, fmt_host) ? 0 : yuv_frame_bytes(W, H, *fmt_host);
+}
+
+extern "C" int fav_yuv_to_rgb8(const uint8_t* yuv, int W, int H, const fav_yuv_format* fmt_host, uint8_t* rgb_hwc, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(yuv && rgb_hwc, "fav_yuv_to_rgb8: null pointer");
+    int rc = yuv_format_check("fav_yuv_to_rgb8", W, H, fmt_host); if (rc) return rc;
+    rc = ensure_device(); if (rc) return rc;
+    return launch_yuv_to_rgb8(yuv, W, H, *fmt_host, rgb_hwc, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int fav_rgb8_to_yuv(const uint8_t* rgb_hwc, int W, int H, const fav_yuv_format* fmt_host, uint8_t* yuv, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(rgb_hwc && yuv, "fav_rgb8_to_yuv: null pointer");
+    int rc = yuv_format_check("fav_rgb8_to_yuv", W, H, fmt_host); if (rc) return rc;
+    rc = ensure_device(); if (rc) return rc;
+    return launch_rgb_to_yuv(rgb_hwc, nullptr, W, H, *fmt_host, yuv, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int fav_rgb_f32_to_yuv(const float* rgb_planar, int W, int H, const fav_yuv_format* fmt_host, uint8_t* yuv, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(rgb_planar && yuv, "fav_rgb_f32_to_yuv: null pointer");
+    int rc = yuv_format_check("fav_rgb_f32_to_yuv", W, H, fmt_host); if (rc) return rc;
+    rc = ensure_device(); if (rc) return rc;
+    return launch_rgb_to_yuv(nullptr, rgb_planar, W, H, *fmt_host, yuv, static_cast<hipStream_t>(stream));
+}
+
 extern "C" int fav_assemble_input_f32(const float* frame_rgb, const float* warped_rgb, const float* cert, float* in7, int H,
                                       int W, fav_hipstream_t stream)
 {
@@ -354,4 +395,104 @@ extern "C" int fav_write_png_rgb8_host(const char* path, const uint8_t* rgb_hwc,
     const bool ok = fwrite(out.data(), 1, out.size(), f) == out.size();
     if (fclose(f) != 0 || !ok) { set_error("write to %s failed", path); return FAV_EIO; }
     return FAV_OK;
+}
+
+// ---- YUV4MPEG2 stream header (include/fav.h says which tags are taken); host-only
+static bool y4m_int(const char* s, const char* end, int* out)      // [s, end) is a decimal number below 2^30
+{
+    if (s == end || end - s > 9) return false;
+    int v = 0;
+    for (; s != end; ++s) { if (*s < '0' || *s > '9') return false; v = v * 10 + (*s - '0'); }
+    *out = v;
+    return true;
+}
+
+static bool y4m_ratio(const std::string& tag, int* num, int* den)   // "<letter><num>:<den>"
+{
+    const size_t c = tag.find(':');
+    return c != std::string::npos && y4m_int(tag.data() + 1, tag.data() + c, num) && y4m_int(tag.data() + c + 1, tag.data() + tag.size(), den);
+}
+
+extern "C" int fav_y4m_parse_header_host(const char* line, size_t len, fav_y4m_header* out)
+{
+    FAV_REQUIRE(line && out, "fav_y4m_parse_header_host: null argument");
+    size_t n = 0;
+    while (n < len && n < FAV_Y4M_MAX_HEADER && line[n] != '\n') ++n;
+    FAV_REQUIRE(n < FAV_Y4M_MAX_HEADER, "Y4M header: longer than %d bytes", FAV_Y4M_MAX_HEADER);
+    FAV_REQUIRE(n >= 9 && !memcmp(line, "YUV4MPEG2", 9) && (n == 9 || line[9] == ' '), "Y4M header: the stream does not start with YUV4MPEG2");
+    fav_y4m_header h;
+    memset(&h, 0, sizeof h);
+    h.aspect_num = -1;
+    bool have_w = false, have_h = false;
+    std::string xt;
+    for (size_t p = 9; p < n;) {
+        if (line[p] == ' ') { ++p; continue; }
+        size_t e = p;
+        while (e < n && line[e] != ' ') ++e;
+        const std::string tag(line + p, e - p);
+        p = e;
+        switch (tag[0]) {
+        case 'W': FAV_REQUIRE(y4m_int(tag.data() + 1, tag.data() + tag.size(), &h.W) && h.W > 0, "Y4M header: bad tag %s", tag.c_str()); have_w = true; break;
+        case 'H': FAV_REQUIRE(y4m_int(tag.data() + 1, tag.data() + tag.size(), &h.H) && h.H > 0, "Y4M header: bad tag %s", tag.c_str()); have_h = true; break;
+        case 'F': FAV_REQUIRE(y4m_ratio(tag, &h.fps_num, &h.fps_den) && h.fps_den > 0, "Y4M header: bad tag %s", tag.c_str()); break;
+        case 'A': FAV_REQUIRE(y4m_ratio(tag, &h.aspect_num, &h.aspect_den), "Y4M header: bad tag %s", tag.c_str()); break;
+        case 'I':
+            if (tag == "It" || tag == "Ib" || tag == "Im") { set_error("Y4M header: interlaced material (tag %s) is not supported", tag.c_str()); return FAV_EUNSUPPORTED; }
+            FAV_REQUIRE(tag == "Ip" || tag == "I?", "Y4M header: bad tag %s", tag.c_str());
+            h.interlace = tag[1];
+            break;
+        case 'C':
+            if (tag == "C420" || tag == "C420jpeg") { h.fmt.chroma = FAV_YUV_420; h.fmt.siting = FAV_YUV_SITING_CENTER; }
+            else if (tag == "C420mpeg2") { h.fmt.chroma = FAV_YUV_420; h.fmt.siting = FAV_YUV_SITING_LEFT; }
+            else if (tag == "C444") { h.fmt.chroma = FAV_YUV_444; h.fmt.siting = FAV_YUV_SITING_CENTER; }
+            else { set_error("Y4M header: colour space %s is not supported (8-bit C420, C420jpeg, C420mpeg2 and C444 are)", tag.c_str()); return FAV_EUNSUPPORTED; }
+            break;
+        case 'X':
+            if (tag.compare(0, 12, "XCOLORRANGE=") == 0) {
+                FAV_REQUIRE(tag == "XCOLORRANGE=FULL" || tag == "XCOLORRANGE=LIMITED", "Y4M header: bad tag %s", tag.c_str());
+                h.fmt.full_range = tag == "XCOLORRANGE=FULL";
+            }
+            xt += (xt.empty() ? "" : " ") + tag;
+            break;
+        default: FAV_REQUIRE(false, "Y4M header: unknown tag %s", tag.c_str());
+        }
+    }
+    FAV_REQUIRE(have_w && have_h, "Y4M header: the %s tag is missing", have_w ? "H" : "W");
+    FAV_REQUIRE((long long)h.W * h.H <= (1ll << 28), "Y4M header: %dx%d frames are too large", h.W, h.H);
+    h.fmt.matrix = h.H >= 720 ? FAV_YUV_BT709 : FAV_YUV_BT601;      // the stream carries none: the usual player heuristic
+    memcpy(h.xtags, xt.c_str(), xt.size() + 1);                     // (shorter than the line, which is shorter than the array)
+    *out = h;
+    return FAV_OK;
+}
+
+extern "C" int fav_y4m_format_header_host(const fav_y4m_header* h, char* buf_host, size_t capacity)
+{
+    FAV_REQUIRE(h && buf_host, "fav_y4m_format_header_host: null argument");
+    int rc = yuv_format_check("fav_y4m_format_header_host", h->W, h->H, &h->fmt); if (rc) return rc;
+    FAV_REQUIRE(h->interlace == 0 || h->interlace == 'p' || h->interlace == '?', "fav_y4m_format_header_host: interlace must be 0, 'p' or '?'");
+    FAV_REQUIRE(memchr(h->xtags, 0, sizeof h->xtags) != nullptr, "fav_y4m_format_header_host: xtags is not terminated");
+    std::string s = "YUV4MPEG2 W" + std::to_string(h->W) + " H" + std::to_string(h->H);
+    if (h->fps_den > 0) s += " F" + std::to_string(h->fps_num) + ":" + std::to_string(h->fps_den);
+    if (h->interlace) s += std::string(" I") + (char)h->interlace;
+    if (h->aspect_num >= 0) s += " A" + std::to_string(h->aspect_num) + ":" + std::to_string(h->aspect_den);
+    s += h->fmt.chroma == FAV_YUV_444 ? " C444" : h->fmt.siting == FAV_YUV_SITING_LEFT ? " C420mpeg2" : " C420jpeg";
+    const char* const range = h->fmt.full_range ? "XCOLORRANGE=FULL" : "XCOLORRANGE=LIMITED";
+    bool range_written = false;
+    const std::string xt = h->xtags;
+    for (size_t p = 0; p < xt.size();) {
+        if (xt[p] == ' ') { ++p; continue; }
+        size_t e = xt.find(' ', p);
+        if (e == std::string::npos) e = xt.size();
+        const std::string tag = xt.substr(p, e - p);
+        p = e;
+        FAV_REQUIRE(tag[0] == 'X' && tag.find('\n') == std::string::npos, "fav_y4m_format_header_host: '%s' in xtags is no X tag", tag.c_str());
+        if (tag.compare(0, 12, "XCOLORRANGE=") == 0) { if (!range_written) s += std::string(" ") + range; range_written = true; }
+        else s += " " + tag;
+    }
+    if (!range_written && h->fmt.full_range) s += std::string(" ") + range;
+    s += "\n";
+    FAV_REQUIRE(s.size() <= FAV_Y4M_MAX_HEADER, "fav_y4m_format_header_host: the header would be longer than %d bytes", FAV_Y4M_MAX_HEADER);
+    FAV_REQUIRE(s.size() < capacity, "fav_y4m_format_header_host: %zu bytes do not fit the caller's buffer", s.size() + 1);
+    memcpy(buf_host, s.c_str(), s.size() + 1);
+    return (int)s.size();
 }

@@ -357,6 +357,12 @@ size_t png_workspace_bytes(int W, int H);
 uint32_t png_crc32_combine_host(uint32_t crc_a, uint32_t crc_b, uint32_t len_b);
 int launch_png_encode(const uint8_t* rgb_hwc, const float* rgb_planar, int W, int H, void* png_out, size_t capacity, uint32_t* png_bytes,
                       void* workspace, size_t ws_bytes, hipStream_t st);
+// 8-bit YCbCr planes <-> RGB (kernels_yuv.hip); the format has been validated (yuv_format_check, api.cpp).  launch_rgb_to_yuv takes
+// exactly one of rgb_hwc / rgb_planar.
+size_t yuv_frame_bytes(int W, int H, const fav_yuv_format& f);
+int yuv_format_check(const char* who, int W, int H, const fav_yuv_format* f);
+int launch_yuv_to_rgb8(const uint8_t* yuv, int W, int H, const fav_yuv_format& f, uint8_t* rgb_hwc, hipStream_t st);
+int launch_rgb_to_yuv(const uint8_t* rgb_hwc, const float* rgb_planar, int W, int H, const fav_yuv_format& f, uint8_t* yuv, hipStream_t st);
 int launch_check_cert(const float* backward_flo, const float* forward_flo, const float* structure, const float* avg, uint8_t* mask_out,
                       int invert, int fix_occ, int border, int r, float* cert, int H, int W, hipStream_t st);
 // ... and the input assembly on top of it (launch_check_cert + launch_prep_input in one launch; round 5)

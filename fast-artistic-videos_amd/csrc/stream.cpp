@@ -470,6 +470,18 @@ extern "C" int fav_stream_encode_png(fav_stream* s, void* png_out, size_t capaci
     return launch_png_encode(nullptr, s->state.get(), s->Wo, s->Ho, png_out, capacity, png_bytes_out, s->png_ws.get(), s->png_ws_bytes, static_cast<hipStream_t>(stream));
 }
 
+// the current stylised frame as the planes of a YUV4MPEG2 frame (kernels_yuv.hip): one launch on the caller's queue, no workspace
+extern "C" int fav_stream_encode_yuv(fav_stream* s, const fav_yuv_format* fmt_host, uint8_t* yuv_out, size_t capacity, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(s && s->has_state, "fav_stream_encode_yuv: no stylised frame yet");
+    FAV_REQUIRE(yuv_out, "fav_stream_encode_yuv: null output");
+    { int rc = yuv_format_check("fav_stream_encode_yuv", s->Wo, s->Ho, fmt_host); if (rc) return rc; }
+    const size_t need = yuv_frame_bytes(s->Wo, s->Ho, *fmt_host);
+    FAV_REQUIRE(capacity >= need, "fav_stream_encode_yuv: a %dx%d frame takes %zu bytes, the buffer holds %zu", s->Wo, s->Ho, need, capacity);
+    FAV_HIP(hipSetDevice(net_device(s->net)));
+    return launch_rgb_to_yuv(nullptr, s->state.get(), s->Wo, s->Ho, *fmt_host, yuv_out, static_cast<hipStream_t>(stream));
+}
+
 extern "C" int fav_stream_encode_png_async(fav_stream* s, void* png_out, size_t capacity, uint32_t* png_bytes_out, fav_hipstream_t stream)
 {
     FAV_REQUIRE(s && s->has_state, "fav_stream_encode_png_async: no stylised frame yet");

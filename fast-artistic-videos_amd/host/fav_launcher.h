@@ -37,6 +37,8 @@
 namespace favl {
 
 [[noreturn]] inline void die(const std::string& m) { fprintf(stderr, "%s\n", m.c_str()); exit(1); }
+// where the messages go: stdout, unless the caller's stdout carries data (fav_stylize -output_y4m -)
+inline FILE*& msg() { static FILE* f = stdout; return f; }
 
 inline std::string subst_stream(std::string v, const std::string& name)
 {
@@ -311,7 +313,7 @@ inline void print_aggregate(const std::string& dir, int world, size_t nstreams)
         per += (r ? ", " : "") + std::to_string(fr ? fr / std::max(sc, 1e-9) : 0.0);
     }
     const double ms = frames ? 1e3 * cpu / frames : 0.0;
-    printf("{\"gpus\": %d, \"streams\": %zu, \"frames\": %d, \"seconds\": %.4f, \"fps_end_to_end\": %.3f, \"fps_per_gpu\": [%s], "
+    fprintf(msg(), "{\"gpus\": %d, \"streams\": %zu, \"frames\": %d, \"seconds\": %.4f, \"fps_end_to_end\": %.3f, \"fps_per_gpu\": [%s], "
            "\"host_cpu_ms_per_frame\": %.3f, \"host_ceiling\": %s, "
            "\"weights\": \"rank 0 parsed the .t7, ncclBroadcast of the packed blob\", \"weight_broadcast_ms\": %.3f, \"rccl_comm_init_ms\": %.1f}\n",
            world, nstreams, frames, secs, secs > 0 ? frames / secs : 0.0, per.c_str(), ms, host_ceiling_json(ms, "measured: CPU seconds of all workers / frames").c_str(),
@@ -365,7 +367,7 @@ inline void load_models_dist(int rank, int world, const std::string& idf, int de
     const double bms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb).count();
     if (fav_net_create_from_blob(blob.data(), blob.size(), device, net)) die(fav_last_error());
     if (!blob_img.empty() && fav_net_create_from_blob(blob_img.data(), blob_img.size(), device, net_img)) die(fav_last_error());
-    printf("[rank %d/%d gpu %d] weights: %zu B%s via ncclBroadcast from rank 0 in %.2f ms (communicator up in %.0f ms); %zu stream(s), %d PNG writers\n", rank, world, device,
+    fprintf(msg(), "[rank %d/%d gpu %d] weights: %zu B%s via ncclBroadcast from rank 0 in %.2f ms (communicator up in %.0f ms); %zu stream(s), %d PNG writers\n", rank, world, device,
            blob.size(), blob_img.empty() ? "" : " (+ image model)", bms, ims, nstreams, nwriters);
     if (times) { times->bcast_ms = bms; times->init_ms = ims; }
     hipStreamDestroy(bst);

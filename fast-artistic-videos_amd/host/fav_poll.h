@@ -32,6 +32,7 @@ namespace favp {
 struct Poll {
     double timeout_s = 600.0;   // -poll_timeout
     double settle_s = 1.0;      // -poll_settle
+    FILE* out = stdout;         // where the `Waiting for file` line goes (fav_stylize -output_y4m -: stderr, stdout carries the video)
 };
 
 enum WaitResult { WAIT_OK = 0, WAIT_TIMEOUT = 1 };
@@ -66,7 +67,7 @@ inline WaitResult wait_for_file(const std::string& path, const Poll& p)
             remaining = p.settle_s - std::max(age, watched);                 // until the earlier of the two acceptances
         } else {
             seen_size = -1;
-            if (!announced) { printf("Waiting for file \"%s\"\n", path.c_str()); fflush(stdout); announced = true; }
+            if (!announced) { fprintf(p.out, "Waiting for file \"%s\"\n", path.c_str()); fflush(p.out); announced = true; }
         }
         if (std::chrono::duration<double>(clk::now() - t0).count() > p.timeout_s) return WAIT_TIMEOUT;
         const double nap = std::min(0.05, std::max(0.001, remaining + 0.0005));

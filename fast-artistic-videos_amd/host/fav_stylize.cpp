@@ -31,6 +31,17 @@
 // instead of the grey levels, for video whose lighting changes; 0 = off, the default; only with -estimate_flow 1); -flow_match <0|1>
 // (fav_flow_opts_ex2.match_beta: the block-matching prior for objects that move further than their own size; 0 = off, the default; only
 // with -estimate_flow 1).
+// -input_y4m <path|-> INSTEAD of -input_pattern: the frames are those of a YUV4MPEG2 stream (`ffmpeg ... -f yuv4mpegpipe -`), frame i is
+//   its i-th frame (1-based), read sequentially (a pipe's short reads included); the planes are uploaded and converted on the device
+//   (fav_yuv_to_rgb8) into the buffer the PPM payload otherwise fills.  The stream ending at a frame boundary ends the clip like a missing
+//   next file; ending INSIDE a frame is an error that names the frame, after the complete frames before it have been written.
+// -output_y4m <path|-> INSTEAD of PNG files (-output_prefix and -png_* are unused): the input's header with the stylised frames' size
+//   (without -input_y4m: F25:1 Ip A1:1), then per frame `FRAME` and the planes the device wrote into pinned memory
+//   (fav_stream_encode_yuv), in order.  With `-` every message goes to stderr: stdout carries the stream and nothing else.
+// -y4m_matrix <auto|bt601|bt709>, -y4m_range <auto|limited|full>: override what the input's header says or lacks (auto: XCOLORRANGE,
+//   else limited; BT.709 from 720 rows on, else BT.601 -- Y4M carries no matrix); -y4m_format <420jpeg|420mpeg2|444>: the output's
+//   sampling when it is not to be the input's (without -input_y4m the default is 420jpeg).
+//   Refused: -backward with -input_y4m, -continue_with other than 1 with either, `-` with more than one -streams entry.
 //
 // Several videos on several GPUs (BASELINE config 4; the reference runs one `th` process per video, stylizeVideo_deepflow.sh:87-96,
 // and its only device hook is utils.setup_gpu, fast_artistic_video/utils.lua:43-66):
@@ -72,6 +83,7 @@
 #include "../../include/fav.h"
 #include "fav_launcher.h"
 #include "fav_poll.h"
+#include "fav_y4m.h"
 
 namespace {
 
@@ -238,7 +250,8 @@ struct FrameIn {           // everything frame i needs from disk
     int index = 0; bool ok = false; bool single = false;
     uint8_t* frame = nullptr; int W = 0, H = 0;
     float* bw = nullptr; float* fw = nullptr; uint8_t* cert = nullptr;
-    void release() { fav_free_host(frame); fav_free_host(bw); fav_free_host(fw); fav_free_host(cert); frame = nullptr; bw = fw = nullptr; cert = nullptr; }
+    uint8_t* yuv = nullptr;          // -input_y4m: the frame's planes instead of `frame`
+    void release() { fav_free_host(frame); fav_free_host(bw); fav_free_host(fw); fav_free_host(cert); free(yuv); frame = yuv = nullptr; bw = fw = nullptr; cert = nullptr; }
 };
 
 
@@ -299,22 +312,33 @@ double process_cpu_seconds()
     return ru.ru_utime.tv_sec + ru.ru_stime.tv_sec + 1e-6 * (ru.ru_utime.tv_usec + ru.ru_stime.tv_usec);
 }
 
-struct Pinned { uint8_t* frame = nullptr; float* bw = nullptr; float* fw = nullptr; uint8_t* cert = nullptr; };
+struct Pinned { uint8_t* frame = nullptr; float* bw = nullptr; float* fw = nullptr; uint8_t* cert = nullptr; uint8_t* yuv = nullptr; };
 
 // Everything frame i needs from disk (fast_artistic_video.lua:93-110,153-158): the frame, and for a frame with a predecessor the backward
 // flow plus either the certainty file (the reference's path: polled, fav.lua:102) or the forward flow (fused check).
 // pd != null: decode straight into that pinned staging set of pin_px pixels (no allocation, no second copy)
-FrameIn load_frame_inputs(const Opt& o, const favp::Poll& poll, int i, bool first_of_run, const Pinned* pd, size_t pin_px)
+// y4m != null (-input_y4m): the frame is the stream's i-th, W x H its header's size, y4m_bytes a frame's payload
+FrameIn load_frame_inputs(const Opt& o, const favp::Poll& poll, int i, bool first_of_run, const Pinned* pd, size_t pin_px,
+                          favy::Reader* y4m = nullptr, size_t y4m_bytes = 0)
 {
     const bool estimate = o.i("estimate_flow") != 0;
     const bool fused_check = !o.s("forward_flow_pattern").empty();
     FrameIn in; in.index = pd ? -i - 1 : i;              // negative index marks "pinned, do not free"
-    const std::string fp = fmt_int(o.s("input_pattern"), i);
-    if (!file_exists(fp)) return in;                                                                     // fav.lua:93-97 -> nil -> break
-    int ch;
-    if (pd) { check(fav_read_pnm_into_host(fp.c_str(), pd->frame, pin_px * 3, &in.W, &in.H, &ch), fp.c_str()); in.frame = pd->frame; }
-    else check(fav_read_pnm_host(fp.c_str(), &in.frame, &in.W, &in.H, &ch), fp.c_str());
-    if (ch != 3) die(fp + ": expected a colour (P6) frame");
+    if (y4m) {
+        in.yuv = pd ? pd->yuv : static_cast<uint8_t*>(malloc(y4m_bytes));
+        if (!in.yuv) die("out of host memory");
+        // anything but a complete frame ends the clip here; run_stream reports a stream that ended inside a frame once the frames
+        // before it are written
+        if (y4m->read_frame(i, in.yuv) != favy::Reader::FRAME) { if (!pd) { free(in.yuv); in.yuv = nullptr; } return in; }
+        in.W = y4m->header().W; in.H = y4m->header().H;
+    } else {
+        const std::string fp = fmt_int(o.s("input_pattern"), i);
+        if (!file_exists(fp)) return in;                                                                 // fav.lua:93-97 -> nil -> break
+        int ch;
+        if (pd) { check(fav_read_pnm_into_host(fp.c_str(), pd->frame, pin_px * 3, &in.W, &in.H, &ch), fp.c_str()); in.frame = pd->frame; }
+        else check(fav_read_pnm_host(fp.c_str(), &in.frame, &in.W, &in.H, &ch), fp.c_str());
+        if (ch != 3) die(fp + ": expected a colour (P6) frame");
+    }
     in.single = (i == 1) || o.f("create_inconsistent") || first_of_run;                                 // fav.lua:172
     if (!in.single && !estimate) {
         const std::string fl = flow_name(o.s("flow_pattern"), i - 1, i);                               // fav.lua:100,154
@@ -346,6 +370,21 @@ fav_flow_opts_ex2 flow_opts_of(const Opt& o)
             o.i("flow_match") ? -1.f : 0.f, 0};
 }
 
+// The format of a Y4M stream's frames.  from_header: what the input's header says (null: there is no Y4M input -- 4:2:0 with centre
+// siting, limited range, BT.709 from 720 rows on, else BT.601: the heuristic players use, Y4M carries no matrix); -y4m_matrix and
+// -y4m_range override either; -y4m_format sets the OUTPUT's sampling.  main has validated the three options.
+fav_yuv_format y4m_format_of(const Opt& o, const fav_yuv_format* from_header, int H, bool output)
+{
+    fav_yuv_format f = from_header ? *from_header : fav_yuv_format{FAV_YUV_420, FAV_YUV_SITING_CENTER, H >= 720 ? FAV_YUV_BT709 : FAV_YUV_BT601, 0};
+    if (o.s("y4m_matrix") != "auto") f.matrix = o.s("y4m_matrix") == "bt709" ? FAV_YUV_BT709 : FAV_YUV_BT601;
+    if (o.s("y4m_range") != "auto") f.full_range = o.s("y4m_range") == "full";
+    if (output && !o.s("y4m_format").empty()) {
+        f.chroma = o.s("y4m_format") == "444" ? FAV_YUV_444 : FAV_YUV_420;
+        f.siting = o.s("y4m_format") == "420mpeg2" ? FAV_YUV_SITING_LEFT : FAV_YUV_SITING_CENTER;
+    }
+    return f;
+}
+
 // One video: the loop of run_fast_neural_video (core.lua:189-229) with the video CLI's callbacks (fav.lua:93-172).
 // `net` / `net_img` live on the current device; `nwriters` PNG threads.
 void run_stream(const Opt& o, const fav_flow_opts_ex2& flow_opts, fav_net* net, fav_net* net_img, int nwriters, StreamResult* res)   // nwriters: the budget; adjusted below
@@ -357,15 +396,35 @@ void run_stream(const Opt& o, const fav_flow_opts_ex2& flow_opts, fav_net* net, 
     const int num_frames = o.i("num_frames");
     const bool backward = o.f("backward");
     const int start = backward ? num_frames - 1 : o.i("continue_with"), end = backward ? 1 : num_frames, inc = backward ? -1 : 1;   // core:189-191
-    favp::Poll poll; poll.timeout_s = o.d("poll_timeout"); poll.settle_s = std::max(0.0, o.d("poll_settle"));
+    favp::Poll poll; poll.timeout_s = o.d("poll_timeout"); poll.settle_s = std::max(0.0, o.d("poll_settle")); poll.out = favl::msg();
+
+    // -input_y4m: one sequential reader behind the loader threads; -output_y4m: planes instead of PNG files, written in order
+    const bool y4m_in = !o.s("input_y4m").empty(), y4m_out = !o.s("output_y4m").empty();
+    favy::Reader y4m_reader; favy::Writer y4m_writer;
+    fav_yuv_format fmt_in{}, fmt_out{};
+    size_t y4m_in_bytes = 0, y4m_out_bytes = 0;
+    if (y4m_in) {
+        const std::string err = y4m_reader.open(o.s("input_y4m"));
+        if (!err.empty()) die(err);
+        const fav_y4m_header& h = y4m_reader.header();
+        fmt_in = y4m_format_of(o, &h.fmt, h.H, false);
+        y4m_in_bytes = fav_yuv_frame_bytes(h.W, h.H, &fmt_in);
+        if (!y4m_in_bytes) die(std::string("-input_y4m: ") + fav_last_error());
+        y4m_reader.set_frame_bytes(y4m_in_bytes);
+    }
 
     size_t pin_px = 0;                       // capacity of a pinned staging set in pixels (0: none yet)
-    auto load = [&](int i, bool first_of_run, const Pinned* pd) { return load_frame_inputs(o, poll, i, first_of_run, pd, pin_px); };
+    auto load = [&](int i, bool first_of_run, const Pinned* pd) {
+        return load_frame_inputs(o, poll, i, first_of_run, pd, pin_px, y4m_in ? &y4m_reader : nullptr, y4m_in_bytes);
+    };
 
     // -png_encoder gpu (default): the PNG file's bytes are produced on the device (fav_stream_encode_png: Sub filter + fixed-Huffman /
     // run-length deflate per row + Adler-32 / CRC-32 combine), leave as ONE exact-size DMA and the writer thread only write()s them;
     // -png_encoder host: the 8-bit frame is downloaded and deflated by zlib on the writer threads (-png_level; ~25 ms per frame and core)
-    const bool gpu_png = o.s("png_encoder") == "gpu";
+    // -output_y4m: no PNG at all.  The planes are written by the frame's last kernel straight into a pinned output slot
+    // (fav_stream_encode_yuv), the host learns of them through an event on the compute queue -- the event-ordered path of
+    // -png_encoder host, minus its download -- and ONE writer thread write()s the slots in frame order.
+    const bool gpu_png = !y4m_out && o.s("png_encoder") == "gpu";
     const bool png_overlap = o.i("png_overlap") != 0;
     // QUIET synchronisation (gpu_png, no 4-argument look-ahead): nothing but kernels ever enters the compute queue.  On this runtime
     // a marker behind long-running kernels (hipEventRecord on the compute stream) or a device-side dependency between queues
@@ -381,6 +440,7 @@ void run_stream(const Opt& o, const fav_flow_opts_ex2& flow_opts, fav_net* net, 
     int cur_device = 0; (void)hipGetDevice(&cur_device);
     const double cpu0 = process_cpu_seconds();
     if (gpu_png && o.i("writers") <= 0) nwriters = std::min(nwriters, 4);      // they only write() finished files: 0.5 ms per frame
+    if (y4m_out) nwriters = 1;               // a stream's frames leave in order: the pool's queue is first in, first out
     Pool writers(nwriters, cur_device);
     // compute queue; upload queue (the next frame's inputs travel while this frame computes); download queue (the 8-bit frame leaves
     // while the next frame computes: on the compute queue the 2.8 MB copy held back the next frame's kernels for its whole duration)
@@ -401,7 +461,7 @@ void run_stream(const Opt& o, const fav_flow_opts_ex2& flow_opts, fav_net* net, 
     fav_stream* fs = nullptr;
     int W = 0, H = 0;                        // frame size
     int Wo = 0, Ho = 0;                      // size of the stylised frames: the network's output (H x W when both are multiples of 4)
-    struct Dev { uint8_t* frame = nullptr; uint8_t* cert = nullptr; float* bw = nullptr; float* fw = nullptr; };
+    struct Dev { uint8_t* frame = nullptr; uint8_t* cert = nullptr; float* bw = nullptr; float* fw = nullptr; uint8_t* yuv = nullptr; };
     Dev dev[NDEV];
     uint8_t* d_out8s[2] = {nullptr, nullptr};    // frames alternate: frame i + 2 is enqueued after the host has seen frame i's download complete
     // gpu_png: device PNG buffers (two, alternating like d_out8s), their sizes on the device and in pinned host memory, and per pinned
@@ -449,11 +509,12 @@ void run_stream(const Opt& o, const fav_flow_opts_ex2& flow_opts, fav_net* net, 
     Pinned pin[DEPTH + 1];
     bool pinned_ready = false;
     auto load_pinned = [&](int i, bool first_of_run, int set) {
-        if (pinned_ready && !pin[set].frame) {           // first use of this staging set: pinned here, by the loader thread that owns it
+        if (pinned_ready && !pin[set].frame && !pin[set].yuv) {      // first use of this staging set: pinned here, by the loader thread that owns it
             Pinned& p = pin[set];
-            if (estimate) { if (hipHostMalloc((void**)&p.frame, pin_px * 3, hipHostMallocDefault)) die("hipHostMalloc failed"); }      // frames only
-            else if (hipHostMalloc((void**)&p.frame, pin_px * 3, hipHostMallocDefault) || hipHostMalloc((void**)&p.bw, pin_px * 8, hipHostMallocDefault) ||
-                (fused_check ? hipHostMalloc((void**)&p.fw, pin_px * 8, hipHostMallocDefault) : hipHostMalloc((void**)&p.cert, pin_px, hipHostMallocDefault))) die("hipHostMalloc failed");
+            if (y4m_in ? hipHostMalloc((void**)&p.yuv, y4m_in_bytes, hipHostMallocDefault) : hipHostMalloc((void**)&p.frame, pin_px * 3, hipHostMallocDefault)) die("hipHostMalloc failed");
+            if (!estimate &&                                     // (-estimate_flow: frames only)
+                (hipHostMalloc((void**)&p.bw, pin_px * 8, hipHostMallocDefault) ||
+                 (fused_check ? hipHostMalloc((void**)&p.fw, pin_px * 8, hipHostMallocDefault) : hipHostMalloc((void**)&p.cert, pin_px, hipHostMallocDefault)))) die("hipHostMalloc failed");
         }
         return load(i, first_of_run, pinned_ready ? &pin[set] : nullptr);
     };
@@ -485,7 +546,10 @@ void run_stream(const Opt& o, const fav_flow_opts_ex2& flow_opts, fav_net* net, 
     int done = 0, dset = 0;
     auto upload = [&](const FrameIn& f, int set) {                // async H2D of one frame's inputs (pinned -> device) on the copy queue
         const size_t n = (size_t)W * H; const Dev& dv = dev[set];
-        hipMemcpyAsync(dv.frame, f.frame, n * 3, hipMemcpyHostToDevice, st_copy);
+        if (f.yuv) {          // -input_y4m: the planes travel, and become the P6 payload on the device, still on the upload queue
+            hipMemcpyAsync(dv.yuv, f.yuv, y4m_in_bytes, hipMemcpyHostToDevice, st_copy);
+            check(fav_yuv_to_rgb8(dv.yuv, W, H, &fmt_in, dv.frame, st_copy), "fav_yuv_to_rgb8");
+        } else hipMemcpyAsync(dv.frame, f.frame, n * 3, hipMemcpyHostToDevice, st_copy);
         if (f.bw) hipMemcpyAsync(dv.bw, f.bw, n * 8, hipMemcpyHostToDevice, st_copy);
         if (f.fw) hipMemcpyAsync(dv.fw, f.fw, n * 8, hipMemcpyHostToDevice, st_copy);
         if (f.cert) hipMemcpyAsync(dv.cert, f.cert, n, hipMemcpyHostToDevice, st_copy);
@@ -512,15 +576,26 @@ void run_stream(const Opt& o, const fav_flow_opts_ex2& flow_opts, fav_net* net, 
         check(fav_net_check(net), "stylising a frame");      // a stream-K hand-off that timed out: fail at THIS frame, before its PNG exists
         if (net_img) check(fav_net_check(net_img), "stylising a frame");
         const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - pd.t0).count();
-        if (pd.single) printf("Elapsed time for stylizing frame independently:%g\n", ms / 1000.0);           // core:155
-        else printf("Elapsed time for stylizing frame:%g\n", ms / 1000.0);                                   // core:177
+        if (pd.single) fprintf(favl::msg(), "Elapsed time for stylizing frame independently:%g\n", ms / 1000.0);           // core:155
+        else fprintf(favl::msg(), "Elapsed time for stylizing frame:%g\n", ms / 1000.0);                                   // core:177
         char nm[4096]; snprintf(nm, sizeof nm, "%s-%05d.png", o.s("output_prefix").c_str(), pd.index);       // fav.lua:161
-        printf("Writing output image to %s\n", nm);
-        mkdirs_for(nm);
+        if (y4m_out) snprintf(nm, sizeof nm, "%s (frame %d)", o.s("output_y4m").c_str(), pd.index);
+        fprintf(favl::msg(), "Writing output image to %s\n", nm);
+        if (!y4m_out) mkdirs_for(nm);
         const int lvl = o.i("png_level");
         const std::string path = nm; uint8_t* hb = pd.hb; const int w_ = Wo, h_ = Ho;
         Slots* sl = &slots;
-        if (gpu_png) {
+        if (y4m_out) {
+            // the planes are in the pinned slot (the event above covers them): `FRAME` and the payload, behind the frames before it
+            favy::Writer* wr = &y4m_writer; const size_t nbytes = y4m_out_bytes;
+            std::atomic<long long>* cw = &cpu_writers_us;
+            writers.submit([hb, path, nbytes, wr, sl, cw] {
+                const double c0 = thread_cpu_seconds();
+                if (!wr->frame(hb, nbytes)) { fprintf(stderr, "cannot write %s\n", path.c_str()); exit(1); }
+                *cw += (long long)(1e6 * (thread_cpu_seconds() - c0));
+                sl->give(hb);
+            });
+        } else if (gpu_png) {
             // the size word has arrived (ev_done): ONE DMA of exactly the file's bytes, then the writer thread only write()s
             const uint32_t nbytes = h_png_size[pd.ev];
             if (nbytes < 57 || nbytes > png_cap) die("fav_stream_encode_png returned an impossible size");
@@ -599,13 +674,25 @@ void run_stream(const Opt& o, const fav_flow_opts_ex2& flow_opts, fav_net* net, 
                 png_cap = fav_png_capacity(Wo, Ho);
                 for (int k = 0; k < 2; ++k) if (hipMalloc((void**)&d_png[k], png_cap) || hipMalloc((void**)&d_png_size[k], 16)) die("hipMalloc failed");
                 if (hipHostMalloc((void**)&h_png_size, 64, hipHostMallocDefault) != hipSuccess) die("hipHostMalloc failed");
+            } else if (y4m_out) {
+                // the stream's header: the input's (or F25:1 Ip A1:1) with the stylised frames' size and the output's format
+                fav_y4m_header oh;
+                if (y4m_in) oh = y4m_reader.header();
+                else { memset(&oh, 0, sizeof oh); oh.fps_num = 25; oh.fps_den = 1; oh.interlace = 'p'; oh.aspect_num = oh.aspect_den = 1; }
+                fmt_out = y4m_format_of(o, y4m_in ? &fmt_in : nullptr, Ho, true);
+                oh.W = Wo; oh.H = Ho; oh.fmt = fmt_out;
+                y4m_out_bytes = fav_yuv_frame_bytes(Wo, Ho, &fmt_out);
+                if (!y4m_out_bytes) die(std::string("-output_y4m: ") + fav_last_error());
+                if (o.s("output_y4m") != "-") mkdirs_for(o.s("output_y4m"));
+                if (!y4m_writer.open(o.s("output_y4m"))) die("Could not open " + o.s("output_y4m") + " for writing");
+                if (!y4m_writer.header(oh)) die("cannot write the stream header to " + o.s("output_y4m") + ": " + fav_last_error());
             } else if (hipMalloc((void**)&d_out8s[0], no * 3) || hipMalloc((void**)&d_out8s[1], no * 3)) die("hipMalloc failed");
             for (auto& dv : dev)
                 if (hipMalloc((void**)&dv.frame, n * 3) || hipMalloc((void**)&dv.cert, n) || hipMalloc((void**)&dv.bw, n * 8) ||
-                    hipMalloc((void**)&dv.fw, n * 8)) die("hipMalloc failed");
+                    hipMalloc((void**)&dv.fw, n * 8) || (y4m_in && hipMalloc((void**)&dv.yuv, y4m_in_bytes))) die("hipMalloc failed");
             // pinned memory is paid for by the page (~0.2 ms per MB): two output slots now, the others when the pool first falls behind;
             // every loader thread pins its own staging set on first use, in parallel with this thread's set-up
-            slot_bytes = gpu_png ? png_cap : no * 3;
+            slot_bytes = y4m_out ? y4m_out_bytes : gpu_png ? png_cap : no * 3;
             for (int k = 0; k < std::min(2, nslots); ++k) slots.add(new_slot());
             pin_px = n; pinned_ready = true;
             if (have_resume) {
@@ -660,7 +747,7 @@ void run_stream(const Opt& o, const fav_flow_opts_ex2& flow_opts, fav_net* net, 
         tr_mark(0);      // (the look-ahead is topped up BEHIND the frame's enqueue, also for the first frame: its enqueue is 15 ms of one-time
                          //  work -- activation arena, code objects -- that now runs while the loaders read and pin frames 2, 3, ...)
         if (quiet && wait_event_sleeping(ev_up[dset], 50) != hipSuccess) die("GPU error while uploading a frame");      // requested a frame ago: already there
-        uint8_t* const d_out8 = gpu_png ? nullptr : d_out8s[done & 1];
+        uint8_t* const d_out8 = (gpu_png || y4m_out) ? nullptr : d_out8s[done & 1];
         const bool teval = !o.s("temporal_eval_file").empty();
         if (teval && !d_prev) { if (hipMalloc((void**)&d_prev, (size_t)W * H * 12) || hipMalloc((void**)&d_cur, (size_t)W * H * 12)) die("hipMalloc failed"); }
         if (teval && !cur.single) check(fav_stream_get_state(fs, d_prev, st), "fav_stream_get_state");
@@ -702,7 +789,8 @@ void run_stream(const Opt& o, const fav_flow_opts_ex2& flow_opts, fav_net* net, 
             if (quiet && png_overlap) check(fav_stream_encode_png_async(fs, d_png[now.ev], png_cap, &h_png_size[now.ev], st), "fav_stream_encode_png_async");
             else check(fav_stream_encode_png(fs, d_png[now.ev], png_cap, quiet ? &h_png_size[now.ev] : d_png_size[now.ev], st), "fav_stream_encode_png");
         }
-        if (!quiet) hipEventRecord(ev_out[now.ev], st);  // the frame's 8-bit image / PNG is complete on the compute queue ...
+        if (y4m_out) check(fav_stream_encode_yuv(fs, &fmt_out, hb, y4m_out_bytes, st), "fav_stream_encode_yuv");      // into the pinned slot
+        if (!quiet && !y4m_out) hipEventRecord(ev_out[now.ev], st);  // the frame's 8-bit image / PNG is complete on the compute queue ...
         tr_mark(2);                                      // PNG encode enqueued
         top_up();                                        // behind frame i's kernels: the 0.45 ms this waits for the upload are not in front of them
         const auto tg = std::chrono::steady_clock::now();
@@ -715,7 +803,8 @@ void run_stream(const Opt& o, const fav_flow_opts_ex2& flow_opts, fav_net* net, 
                     std::chrono::duration<double, std::milli>(t0 - t_begin).count(), tr_ms[0], tr_ms[1], tr_ms[2], tr_ms[3]);
         if (loop_trace && !loop_trace_start && done >= 100 && done < 112)
             fprintf(stderr, "loop trace frame %d: look-ahead %.3f  frame enqueued %.3f  encode enqueued %.3f  previous frame finished %.3f ms\n", i, tr_ms[0], tr_ms[1], tr_ms[2], tr_ms[3]);
-        if (!quiet) {
+        if (y4m_out) hipEventRecord(ev_done[now.ev], st);    // nothing to download: the planes are in host memory when this event fires
+        else if (!quiet) {
             hipStreamWaitEvent(st_down, ev_out[now.ev], 0);  // ... and leaves on the download queue
             if (gpu_png) hipMemcpyAsync(&h_png_size[now.ev], d_png_size[now.ev], 4, hipMemcpyDeviceToHost, st_down);      // (the bytes follow in finish(), exactly `size` of them)
             else hipMemcpyAsync(hb, d_out8, (size_t)Wo * Ho * 3, hipMemcpyDeviceToHost, st_down);
@@ -731,8 +820,13 @@ void run_stream(const Opt& o, const fav_flow_opts_ex2& flow_opts, fav_net* net, 
     const auto t_tail = std::chrono::steady_clock::now();       // the GPU is done: what follows is the PNG pool draining
     for (auto& pr : inflight) pr.second.get();
     for (auto& r : ready) if (r.index >= 0) r.release();
-    fflush(stdout);
+    fflush(favl::msg());
     writers.wait_below(0);
+    if (y4m_in && y4m_reader.failed_at()) {              // the complete frames before it are written: now it is an error
+        fflush(favl::msg());
+        die(o.s("input_y4m") + (y4m_reader.failure() == favy::Reader::TRUNCATED ? ": the stream ends inside frame " : ": no FRAME marker (or a read error) at frame ") +
+            std::to_string(y4m_reader.failed_at()));
+    }
     if (!temporal.empty()) {                             // core.lua:231-238 layout: values joined by ';', then the mean
         FILE* f = fopen(o.s("temporal_eval_file").c_str(), "a");
         if (!f) die("cannot open " + o.s("temporal_eval_file"));
@@ -753,9 +847,9 @@ void run_stream(const Opt& o, const fav_flow_opts_ex2& flow_opts, fav_net* net, 
     for (auto& kv : slot_ev) hipEventDestroy(kv.second);
     fav_stream_destroy(fs);
     hipFree(d_prev); hipFree(d_cur); hipFree(d_flow_ws);
-    hipFree(d_out8s[0]); hipFree(d_out8s[1]); for (auto& dv : dev) { hipFree(dv.frame); hipFree(dv.cert); hipFree(dv.bw); hipFree(dv.fw); }
+    hipFree(d_out8s[0]); hipFree(d_out8s[1]); for (auto& dv : dev) { hipFree(dv.frame); hipFree(dv.cert); hipFree(dv.bw); hipFree(dv.fw); hipFree(dv.yuv); }
     for (auto p : h_out) hipHostFree(p);
-    for (auto& p : pin) { hipHostFree(p.frame); hipHostFree(p.bw); hipHostFree(p.fw); hipHostFree(p.cert); }
+    for (auto& p : pin) { hipHostFree(p.frame); hipHostFree(p.bw); hipHostFree(p.fw); hipHostFree(p.cert); hipHostFree(p.yuv); }
     for (auto& e : ev_up) hipEventDestroy(e);
     for (auto& e : ev_done) hipEventDestroy(e);
     for (auto& e : ev_out) hipEventDestroy(e);
@@ -779,6 +873,7 @@ int main(int argc, char** argv)
            // additive
            {"forward_flow_pattern", ""}, {"structure", "1"}, {"warp_border", "stn"}, {"poll_timeout", "3600"}, {"poll_settle", "1.0"},
            {"png_level", "1"}, {"png_encoder", "gpu"}, {"png_overlap", "0"}, {"writers", "0"}, {"timing", "0"}, {"temporal_eval_file", ""}, {"seed", "1"}, {"precision", "fp32"},
+           {"input_y4m", ""}, {"output_y4m", ""}, {"y4m_matrix", "auto"}, {"y4m_range", "auto"}, {"y4m_format", ""},
            {"estimate_flow", "0"}, {"flow_alpha", "0"}, {"flow_eps", "0"}, {"flow_grad", "0"}, {"flow_match", "0"}, {"flow_iters", "0"}, {"flow_warps", "0"}, {"flow_levels", "0"},
            {"streams", ""}, {"gpus", "1"}, {"force_dist", "0"}, {"dry_run", "0"}, {"shared_gpu", "0"}, {"pin_workers", "1"},
            // internal (set by the launcher for its workers)
@@ -796,7 +891,20 @@ int main(int argc, char** argv)
         if (a + 1 >= argc) die("missing value for -" + k);
         o.v[k] = argv[++a];
     }
-    if (o.s("input_pattern").empty()) die("Must give -input_pattern");                                      // fav.lua:177-179
+    // YUV4MPEG2 streams in and / or out: everything that cannot work is refused here, before any device is opened
+    const bool y4m_in = !o.s("input_y4m").empty(), y4m_out = !o.s("output_y4m").empty();
+    if (o.s("output_y4m") == "-") favl::msg() = stderr;                                                     // stdout carries the stream and nothing else
+    if (y4m_in && !o.s("input_pattern").empty()) die("-input_y4m is given INSTEAD of -input_pattern: the frames come from one or the other, not both");
+    if (y4m_in && o.f("backward")) die("-backward cannot be combined with -input_y4m: a stream is read from its first frame to its last");
+    if ((y4m_in || y4m_out) && o.s("continue_with") != "1")
+        die("-continue_with " + o.s("continue_with") + " cannot be combined with -input_y4m / -output_y4m: a stream starts at its first frame");
+    if ((o.s("input_y4m") == "-" || o.s("output_y4m") == "-") && favl::split_list(o.s("streams")).size() > 1)
+        die("-input_y4m - / -output_y4m - is ONE stream (stdin / stdout): it cannot be combined with more than one -streams entry");
+    if (o.s("y4m_matrix") != "auto" && o.s("y4m_matrix") != "bt601" && o.s("y4m_matrix") != "bt709") die("-y4m_matrix must be auto, bt601 or bt709, not '" + o.s("y4m_matrix") + "'");
+    if (o.s("y4m_range") != "auto" && o.s("y4m_range") != "limited" && o.s("y4m_range") != "full") die("-y4m_range must be auto, limited or full, not '" + o.s("y4m_range") + "'");
+    if (!o.s("y4m_format").empty() && o.s("y4m_format") != "420jpeg" && o.s("y4m_format") != "420mpeg2" && o.s("y4m_format") != "444")
+        die("-y4m_format must be 420jpeg, 420mpeg2 or 444, not '" + o.s("y4m_format") + "'");
+    if (!y4m_in && o.s("input_pattern").empty()) die("Must give -input_pattern");                           // fav.lua:177-179
     if (o.s("estimate_flow") != "0" && o.s("estimate_flow") != "1") die("-estimate_flow must be 0 or 1, not '" + o.s("estimate_flow") + "'");
     const bool estimate = o.i("estimate_flow") != 0;
     if (o.s("flow_grad") != "0" && o.s("flow_grad") != "1") die("-flow_grad must be 0 or 1, not '" + o.s("flow_grad") + "'");
@@ -824,15 +932,16 @@ int main(int argc, char** argv)
     if (o.s("fill_occlusions") != "vgg-mean" && o.s("fill_occlusions") != "uniform-random") die("-fill_occlusions must be vgg-mean or uniform-random");
     if (o.s("png_encoder") != "gpu" && o.s("png_encoder") != "host") die("-png_encoder must be gpu (the file's bytes are produced on the device) or host (zlib, -png_level)");
     if (o.s("precision") != "fp32" && o.s("precision") != "bf16") die("-precision must be fp32 (parity mode) or bf16 (bf16 operands in the 3x3 residual convolutions)");
+    if (o.i("load_probe") > 0 && y4m_in) die("-load_probe probes the file loaders: it cannot be combined with -input_y4m");
     if (o.i("load_probe") > 0) {
-        favp::Poll poll; poll.timeout_s = o.d("poll_timeout"); poll.settle_s = std::max(0.0, o.d("poll_settle"));
+        favp::Poll poll; poll.timeout_s = o.d("poll_timeout"); poll.settle_s = std::max(0.0, o.d("poll_settle")); poll.out = favl::msg();
         const auto t0 = std::chrono::steady_clock::now();
         FrameIn in = load_frame_inputs(o, poll, o.i("load_probe"), false, nullptr, 0);
         auto fnv = [](const void* p, size_t n) { unsigned long long h = 1469598103934665603ull; const uint8_t* b = (const uint8_t*)p;
                                                  if (!p) return 0ull; for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; } return h; };
         const size_t n = (size_t)in.W * in.H;
         size_t cert255 = 0; if (in.cert) for (size_t i = 0; i < n; ++i) cert255 += in.cert[i] == 255;
-        printf("{\"ok\": %s, \"W\": %d, \"H\": %d, \"seconds\": %.3f, \"frame\": \"%016llx\", \"cert\": \"%016llx\", \"cert_255\": %zu, \"bw\": \"%016llx\", \"fw\": \"%016llx\"}\n",
+        fprintf(favl::msg(), "{\"ok\": %s, \"W\": %d, \"H\": %d, \"seconds\": %.3f, \"frame\": \"%016llx\", \"cert\": \"%016llx\", \"cert_255\": %zu, \"bw\": \"%016llx\", \"fw\": \"%016llx\"}\n",
                in.ok ? "true" : "false", in.W, in.H, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(),
                fnv(in.frame, n * 3), fnv(in.cert, n), cert255, fnv(in.bw, n * 8), fnv(in.fw, n * 8));
         return in.ok ? 0 : 1;
@@ -843,9 +952,10 @@ int main(int argc, char** argv)
     if (!named) streams.push_back("");
     int world = std::max(1, o.i("gpus"));
     const int rank = o.i("worker_rank");
-    static const char* const path_opts[] = {"input_pattern", "flow_pattern", "forward_flow_pattern", "occlusions_pattern", "output_prefix", "temporal_eval_file"};
-    if (named && streams.size() > 1 && o.s("output_prefix").find("%S") == std::string::npos)
-        die("-streams: -output_prefix must contain %S (the streams would overwrite each other's frames)");
+    static const char* const path_opts[] = {"input_pattern", "flow_pattern", "forward_flow_pattern", "occlusions_pattern", "output_prefix", "temporal_eval_file",
+                                            "input_y4m", "output_y4m"};
+    if (named && streams.size() > 1 && o.s(y4m_out ? "output_y4m" : "output_prefix").find("%S") == std::string::npos)
+        die(std::string("-streams: -") + (y4m_out ? "output_y4m" : "output_prefix") + " must contain %S (the streams would overwrite each other's frames)");
 
     // ------------------------------------------------------------------------------------------ launcher
     if (rank < 0 && (world > 1 || o.i("force_dist"))) {
@@ -858,7 +968,7 @@ int main(int argc, char** argv)
             if (o.i("gpu") + world > ndev) die("-gpus " + o.s("gpus") + " from -gpu " + o.s("gpu") + ": only " + std::to_string(ndev) + " devices");
         }
         if (dry)      // what the host can sustain at most, whatever the GPUs do (the 8-GPU run explains itself)
-            printf("{\"host_ceiling\": %s}\n", favl::host_ceiling_json(o.s("png_encoder") == "gpu" ? favl::HOST_CPU_MS_PER_FRAME_GPU_PNG : favl::HOST_CPU_MS_PER_FRAME_HOST_PNG,
+            fprintf(favl::msg(), "{\"host_ceiling\": %s}\n", favl::host_ceiling_json(o.s("png_encoder") == "gpu" ? favl::HOST_CPU_MS_PER_FRAME_GPU_PNG : favl::HOST_CPU_MS_PER_FRAME_HOST_PNG,
                                                                        "default: measured on the project's MI355X box at 1280x720, fused 3-argument check").c_str());
         std::string xdir;
         const int worst = favl::spawn_workers(argc, argv, world, o.i("pin_workers") != 0, &xdir);
@@ -883,7 +993,7 @@ int main(int argc, char** argv)
             for (const char* po : path_opts) js += std::string(", \"") + po + "\": " + favl::json_str(named ? favl::subst_stream(o.s(po), mine[k]) : o.s(po));
             js += "}";
         }
-        printf("%s]}\n", js.c_str());
+        fprintf(favl::msg(), "%s]}\n", js.c_str());
         return 0;
     }
 
@@ -902,8 +1012,8 @@ int main(int argc, char** argv)
     }
     check(fav_net_set_precision(net, o.s("precision") == "bf16" ? FAV_PRECISION_BF16_OPERANDS : FAV_PRECISION_FP32), "fav_net_set_precision");
     if (o.i("shared_gpu")) { check(fav_net_set_shared_device(net, 1), "fav_net_set_shared_device"); if (net_img) check(fav_net_set_shared_device(net_img, 1), "fav_net_set_shared_device"); }
-    printf("Model loaded.\n");
-    if (net_img) printf("Model loaded.\n");
+    fprintf(favl::msg(), "Model loaded.\n");
+    if (net_img) fprintf(favl::msg(), "Model loaded.\n");
 
     int frames = 0; double seconds = 0, cpu_seconds = 0;
     for (const std::string& name : mine) {
@@ -913,7 +1023,7 @@ int main(int argc, char** argv)
         run_stream(os, flow_opts, net, net_img, nwriters, &r);
         frames += r.frames; seconds += r.seconds; cpu_seconds += r.cpu_s;
         if (o.i("timing"))
-            printf("{%s\"frames\": %d, \"seconds\": %.4f, \"fps_end_to_end\": %.3f, \"wait_loader_s\": %.3f, \"h2d_gpu_d2h_s\": %.3f, \"wait_png_pool_s\": %.3f, \"setup_s\": %.3f, \"png_tail_s\": %.3f, \"png_writers\": %d, "
+            fprintf(favl::msg(), "{%s\"frames\": %d, \"seconds\": %.4f, \"fps_end_to_end\": %.3f, \"wait_loader_s\": %.3f, \"h2d_gpu_d2h_s\": %.3f, \"wait_png_pool_s\": %.3f, \"setup_s\": %.3f, \"png_tail_s\": %.3f, \"png_writers\": %d, "
                    "\"png_encoder\": \"%s\", \"host_cpu_ms_per_frame\": %.3f, \"cpu_ms_per_frame_loaders\": %.3f, \"cpu_ms_per_frame_writers\": %.3f, \"cpu_ms_per_frame_writers_waiting_for_the_copy\": %.3f, \"cpu_ms_per_frame_main\": %.3f, "
                    "\"png_mb_per_frame\": %.3f, \"usable_cpus\": %d}\n",
                    named ? ("\"stream\": " + favl::json_str(name) + ", \"gpu\": " + std::to_string(device) + ", ").c_str() : "",
@@ -923,9 +1033,9 @@ int main(int argc, char** argv)
     }
     check(fav_net_check(net), "at exit");
     if (net_img) check(fav_net_check(net_img), "at exit (image model)");
-    if (o.i("timing")) printf("thread CPU seconds (live threads, whole process): %s\n", thread_cpu_report().c_str());
+    if (o.i("timing")) fprintf(favl::msg(), "thread CPU seconds (live threads, whole process): %s\n", thread_cpu_report().c_str());
     if (dist && o.i("timing")) favl::write_worker_result(o.s("rccl_id_file"), rank, frames, seconds, cpu_seconds, dist_times);
-    fflush(stdout);
+    fflush(favl::msg());
     fav_net_destroy(net); fav_net_destroy(net_img);
     return 0;
 }

@@ -69,6 +69,8 @@ def lib() -> C.CDLL:
     L.fav_flow_workspace_bytes_ex2.argtypes = [C.c_int, C.c_int, C.c_void_p]
     L.fav_flow_pairs_workspace_bytes_ex2.restype = C.c_size_t
     L.fav_flow_pairs_workspace_bytes_ex2.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.fav_yuv_frame_bytes.restype = C.c_size_t
+    L.fav_yuv_frame_bytes.argtypes = [C.c_int, C.c_int, C.c_void_p]
     _lib = L
     return L
 
@@ -97,6 +99,8 @@ EXPORTS = [
     "fav_flow_workspace_bytes_ex2", "fav_flow_rgb8_ex2", "fav_flow_pairs_workspace_bytes_ex2", "fav_flow_pairs_rgb8_ex2",
     "fav_stream_next_frame_estimate_ex2", "fav_flow_match_f32", "fav_flow_match_check", "fav_flow_coefficients_prior_f32",
     "fav_vr_equi_to_faces_rgb8",
+    "fav_yuv_frame_bytes", "fav_yuv_to_rgb8", "fav_rgb8_to_yuv", "fav_rgb_f32_to_yuv", "fav_stream_encode_yuv",
+    "fav_y4m_parse_header_host", "fav_y4m_format_header_host",
 ]
 
 
@@ -440,8 +444,24 @@ class Net:
         else:
             _check(lib().fav_net_create(t7_path.encode(), device, C.byref(h)))
         self.h, self.device = h, device
+        self._users, self._close_pending = 0, False
+
+    # A fav_stream / fav_vr reads its network when it is destroyed (~fav_stream, ~fav_vr select the network's device), so the network must
+    # outlive the objects built on it.  Reference counting sees to that as long as finalisers run in order, but the garbage collector
+    # finalises the members of a reference cycle in ANY order (a test's frame kept alive by a caught exception is such a cycle): a Net
+    # that is closed while Streams / VRs still use it is therefore destroyed when the last of them has been.
+    def _retain(self):
+        self._users += 1
+
+    def _release(self):
+        self._users -= 1
+        if self._users == 0 and self._close_pending:
+            self.close()
 
     def close(self):
+        if getattr(self, "_users", 0) > 0:
+            self._close_pending = True
+            return
         if getattr(self, "h", None) and lib is not None:
             try:
                 lib().fav_net_destroy(self.h)
@@ -548,10 +568,12 @@ class Stream:
     def __init__(self, net: Net, h: int, w: int, border: int = BORDER_STN, min_filter_r: int = 7,
                  invert_occlusion: bool = False, fix_occlusions: bool = False, fill_random: bool = False, seed: int = 1):
         self.net, self.H, self.W = net, h, w
+        self._img = None
         o = _Opts(border, min_filter_r, int(invert_occlusion), int(fix_occlusions), int(fill_random), seed)
         hd = C.c_void_p()
         _check(lib().fav_stream_create(net.h, h, w, C.byref(o), C.byref(hd)))
         self.h = hd
+        net._retain()
         ho, wo = C.c_int(), C.c_int()
         _check(lib().fav_stream_output_size(hd, C.byref(ho), C.byref(wo)))
         self.Ho, self.Wo = ho.value, wo.value          # size of the stylised frames (= H x W when both are multiples of 4)
@@ -563,12 +585,19 @@ class Stream:
             except Exception:      # interpreter shutdown
                 pass
             self.h = None
+            self.net._release()
+            if self._img is not None:
+                self._img._release()
 
     __del__ = close
 
     def set_image_net(self, img_net: Optional[Net]):
-        self._img = img_net      # keep alive
         _check(lib().fav_stream_set_image_net(self.h, img_net.h if img_net is not None else None))
+        if img_net is not None:
+            img_net._retain()
+        if self._img is not None:
+            self._img._release()
+        self._img = img_net      # keep alive
 
     def set_single_image_size(self, hs: int, ws: int):
         """-scale_factor: frames without a prior run at hs x ws and are scaled back to H x W (0, 0: the unscaled path)"""
@@ -652,6 +681,10 @@ class Stream:
         """fav_stream_wait_png: the current stream waits for the asynchronous encodes issued so far"""
         _check(lib().fav_stream_wait_png(self.h, _stream()))
 
+    def encode_yuv_into(self, out, fmt: "YuvFormat", capacity: Optional[int] = None):
+        """fav_stream_encode_yuv: the current stylised frame as the planes of a Y4M frame, enqueued on the current stream (no sync)"""
+        _check(lib().fav_stream_encode_yuv(self.h, C.byref(fmt), _p(out), C.c_size_t(out.numel() if capacity is None else capacity), _stream()))
+
     def last_input(self):
         """[7][H][W] network input of the last frame (content | prior | certainty), un-padded copy of the fused kernel's output"""
         torch = _torch()
@@ -694,6 +727,82 @@ def png_encode(img, from_stream: "Stream" = None) -> bytes:
     torch.cuda.synchronize()
     n = int(nbytes.item())
     return bytes(out[:n].cpu().numpy().tobytes())
+
+
+# ---- YUV4MPEG2: 8-bit YCbCr planes <-> RGB (fav_yuv_*, fav_y4m_*)
+YUV_420, YUV_444 = 0, 1
+YUV_SITING_CENTER, YUV_SITING_LEFT = 0, 1
+YUV_BT601, YUV_BT709 = 0, 1
+
+
+class YuvFormat(C.Structure):
+    """fav_yuv_format"""
+    _fields_ = [("chroma", C.c_int), ("siting", C.c_int), ("matrix", C.c_int), ("full_range", C.c_int)]
+
+    def __repr__(self):
+        return f"YuvFormat(chroma={self.chroma}, siting={self.siting}, matrix={self.matrix}, full_range={self.full_range})"
+
+
+class Y4mHeader(C.Structure):
+    """fav_y4m_header"""
+    _fields_ = [("W", C.c_int), ("H", C.c_int), ("fps_num", C.c_int), ("fps_den", C.c_int), ("aspect_num", C.c_int),
+                ("aspect_den", C.c_int), ("interlace", C.c_int), ("fmt", YuvFormat), ("xtags", C.c_char * 1024)]
+
+
+def yuv_format(chroma: int = YUV_420, siting: int = YUV_SITING_CENTER, matrix: int = YUV_BT601, full_range: bool = False) -> YuvFormat:
+    return YuvFormat(chroma, siting, matrix, int(full_range))
+
+
+def yuv_frame_bytes(w: int, h: int, fmt: YuvFormat) -> int:
+    """bytes of one frame's payload; raises on a bad size or format"""
+    n = lib().fav_yuv_frame_bytes(w, h, C.byref(fmt))
+    if n == 0:
+        raise FavError(lib().fav_last_error().decode(errors="replace"))
+    return n
+
+
+def yuv_to_rgb8(yuv, w: int, h: int, fmt: YuvFormat, out=None):
+    """fav_yuv_to_rgb8: a frame's planes (flat u8 tensor) -> [H][W][3] u8.  out: a u8 tensor of at least H*W*3 elements to write into"""
+    torch = _torch()
+    assert yuv.dtype == torch.uint8 and yuv.is_contiguous() and yuv.numel() >= yuv_frame_bytes(w, h, fmt)
+    if out is None:
+        out = torch.empty((h, w, 3), dtype=torch.uint8, device=yuv.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= h * w * 3
+    _check(lib().fav_yuv_to_rgb8(_p(yuv), w, h, C.byref(fmt), _p(out), _stream()))
+    return out
+
+
+def rgb_to_yuv(img, fmt: YuvFormat, out=None):
+    """fav_rgb8_to_yuv for a u8 [H][W][3] tensor, fav_rgb_f32_to_yuv for a float [3][H][W] tensor (image.save's quantisation in front)
+    -> the frame's planes, flat u8.  out: a u8 tensor of at least fav_yuv_frame_bytes elements to write into"""
+    torch = _torch()
+    assert img.is_contiguous()
+    u8 = img.dtype == torch.uint8
+    h, w = (img.shape[0], img.shape[1]) if u8 else (img.shape[1], img.shape[2])
+    n = yuv_frame_bytes(w, h, fmt)
+    if out is None:
+        out = torch.empty(n, dtype=torch.uint8, device=img.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= n
+    if not u8:
+        _chk_f32(img, "img")
+    _check((lib().fav_rgb8_to_yuv if u8 else lib().fav_rgb_f32_to_yuv)(_p(img), w, h, C.byref(fmt), _p(out), _stream()))
+    return out
+
+
+def y4m_parse_header(line: bytes) -> Y4mHeader:
+    """fav_y4m_parse_header_host (no device needed); raises FavError with the library's message"""
+    h = Y4mHeader()
+    _check(lib().fav_y4m_parse_header_host(line, C.c_size_t(len(line)), C.byref(h)))
+    return h
+
+
+def y4m_format_header(h: Y4mHeader) -> bytes:
+    """fav_y4m_format_header_host (no device needed): the header line, newline included"""
+    buf = C.create_string_buffer(1100)
+    n = lib().fav_y4m_format_header_host(C.byref(h), buf, C.c_size_t(len(buf)))
+    if n <= 0:
+        _check(n if n else -1)
+    return buf.raw[:n]
 
 
 def png_tables():
@@ -773,6 +882,9 @@ class VR:
         hd = C.c_void_p()
         _check(lib().fav_vr_create(net.h, image_net.h if image_net is not None else None, hplus, wplus, C.byref(o), C.byref(hd)))
         self.h = hd
+        net._retain()
+        if image_net is not None:
+            image_net._retain()
         sz = [C.c_int() for _ in range(6)]
         _check(lib().fav_vr_output_sizes(self.h, *[C.byref(x) for x in sz]))
         self.equi_w, self.equi_h, self.cube_w, self.cube_h, self.filt_w, self.filt_h = [x.value for x in sz]
@@ -784,6 +896,9 @@ class VR:
             except Exception:      # interpreter shutdown
                 pass
             self.h = None
+            self.net._release()
+            if self.img is not None:
+                self.img._release()
 
     __del__ = close
 

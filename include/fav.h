@@ -529,6 +529,58 @@ int fav_stream_encode_png_async(fav_stream* s, void* png_out, size_t capacity, u
 /* makes `stream` wait (on the device) for the asynchronous encodes issued so far */
 int fav_stream_wait_png(fav_stream* s, fav_hipstream_t stream);
 
+/* ---- YUV4MPEG2 (Y4M) video streams: 8-bit YCbCr planes <-> RGB on the GPU ---------------------------------------------------------
+ * Stands in for the first and the last stage of every driver of the reference (stylizeVideo_deepflow.sh: `ffmpeg -i video
+ * frame_%05d.ppm` ... `ffmpeg -i out-%05d.png video`): with `ffmpeg -f yuv4mpegpipe` on either side of fav_stylize -input_y4m /
+ * -output_y4m the frames travel through pipes as planes, and the conversion ffmpeg would do on the CPU runs here.
+ * A frame is the Y4M payload: plane Y [H][W], then Cb, then Cr, contiguous, 8 bits per sample; the chroma planes are [H][W] for 4:4:4 and
+ * [ceil(H/2)][ceil(W/2)] for 4:2:0 (odd sizes are legal: a missing partner is the replicated edge sample).  The arithmetic -- fp32, one
+ * stated order of operations, restated by tests/util/yuv_model.py and matched byte for byte -- is in DESIGN.md, "Y4M in and out":
+ * (Kr, Kb) of BT.601 / BT.709; limited range Y 16..235, C 16..240, or full range; bytes are floor(x + 0.5) clamped to [0, 255] (limited
+ * input outside 16..235 is legal and simply clamped after conversion); 4:2:0 chroma is interpolated bilinearly on the way in and
+ * averaged over 2 x 2 (centre siting) / filtered 1-2-1 along x and averaged over two rows (left siting) on the way out.
+ * Device pointers, caller-owned buffers of fav_yuv_frame_bytes / W*H*3 bytes with no alignment requirement, nothing allocated, no
+ * synchronisation, nothing outside the buffers read or written.  A size below 1 x 1 or above 2^28 pixels, a null pointer or a field of
+ * the format outside its values: FAV_EINVAL. */
+enum fav_yuv_chroma { FAV_YUV_420 = 0, FAV_YUV_444 = 1 };
+enum fav_yuv_siting { FAV_YUV_SITING_CENTER = 0 /* C420jpeg */, FAV_YUV_SITING_LEFT = 1 /* C420mpeg2 */ };
+enum fav_yuv_matrix { FAV_YUV_BT601 = 0, FAV_YUV_BT709 = 1 };
+typedef struct fav_yuv_format { int chroma;   /* FAV_YUV_420 | FAV_YUV_444 */
+                                int siting;   /* FAV_YUV_SITING_CENTER (C420jpeg) | FAV_YUV_SITING_LEFT (C420mpeg2); ignored for 444 */
+                                int matrix;   /* FAV_YUV_BT601 | FAV_YUV_BT709 */
+                                int full_range; } fav_yuv_format;
+/* bytes of one frame's payload (0 with a message: bad size or format) */
+size_t fav_yuv_frame_bytes(int W, int H, const fav_yuv_format* fmt_host);
+/* planes -> [H][W][3] u8, the layout fav_stream_* takes as frame_rgb_hwc */
+int fav_yuv_to_rgb8(const uint8_t* yuv, int W, int H, const fav_yuv_format* fmt_host, uint8_t* rgb_hwc, fav_hipstream_t stream);
+/* [H][W][3] u8 -> planes */
+int fav_rgb8_to_yuv(const uint8_t* rgb_hwc, int W, int H, const fav_yuv_format* fmt_host, uint8_t* yuv, fav_hipstream_t stream);
+/* planar float RGB [3][H][W] (what fav_stream_get_state returns) -> planes, image.save's quantisation (clamp to [0,1], x255, truncate:
+ * fav_png_encode_f32's) fused in front: the planes are the conversion of exactly the bytes the PNG would have held */
+int fav_rgb_f32_to_yuv(const float* rgb_planar, int W, int H, const fav_yuv_format* fmt_host, uint8_t* yuv, fav_hipstream_t stream);
+/* the stream's current stylised frame (the recurrent state, Ho x Wo) as planes.  yuv_out: device memory or host-mapped pinned memory
+ * (complete when the stream reaches the point after the call -- use an event WITH the system-scope fence) of `capacity` >=
+ * fav_yuv_frame_bytes(Wo, Ho, fmt) bytes; a smaller capacity is FAV_EINVAL and nothing is written. */
+int fav_stream_encode_yuv(fav_stream* s, const fav_yuv_format* fmt_host, uint8_t* yuv_out, size_t capacity, fav_hipstream_t stream);
+/* The stream header of YUV4MPEG2, host-only (no device needed): the magic `YUV4MPEG2`, then space-separated tags in any order, ended by
+ * '\n'; at most FAV_Y4M_MAX_HEADER bytes.  `line` holds the header up to or including the newline (len bytes).
+ *   W, H   required;  F<num>:<den> and A<num>:<den> are kept (fps_den 0 / aspect_num -1: the tag was absent and is not written back)
+ *   I      absent, Ip or I? (kept in `interlace` as 0, 'p', '?'); It, Ib, Im: FAV_EUNSUPPORTED
+ *   C      absent, C420, C420jpeg: 4:2:0, centre siting; C420mpeg2: 4:2:0, left siting; C444; every other tag (C420paldv, C422, C420p10,
+ *          C444alpha, Cmono, ...): FAV_EUNSUPPORTED with a message that names the tag
+ *   X...   kept verbatim, in order, space-separated, in `xtags`; XCOLORRANGE=FULL / =LIMITED also sets fmt.full_range (default: limited)
+ * Y4M carries no matrix: the parser sets BT.709 when H >= 720, else BT.601 (the usual player heuristic); the caller may override it.
+ * Anything malformed (magic, a missing W or H, a number that is none, an unknown tag letter, too long): FAV_EINVAL.
+ * The formatter writes `YUV4MPEG2 W H F I A C X...` and the newline into buf_host and returns the number of bytes (> 0), or a negative
+ * fav_status.  The X tags are written as kept, except XCOLORRANGE, which is written from fmt.full_range: in place where the tag was, or
+ * appended (=FULL only) where it was not.  Parsing what the formatter wrote gives the header back.
+ * A frame is `FRAME`, optional parameters, '\n', then fav_yuv_frame_bytes bytes. */
+#define FAV_Y4M_MAX_HEADER 1024
+typedef struct fav_y4m_header { int W, H; int fps_num, fps_den; int aspect_num, aspect_den; int interlace; fav_yuv_format fmt;
+                                char xtags[FAV_Y4M_MAX_HEADER]; } fav_y4m_header;
+int fav_y4m_parse_header_host(const char* line, size_t len, fav_y4m_header* out);
+int fav_y4m_format_header_host(const fav_y4m_header* h, char* buf_host, size_t capacity);
+
 #ifdef __cplusplus
 }
 #endif
