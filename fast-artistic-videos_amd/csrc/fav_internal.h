@@ -342,6 +342,11 @@ int launch_flow_prior_down(const FlowPtrs& src, int W, int H, const FlowPtrs& ds
 inline fav_flow_opts_ex flow_opts_brightness(const fav_flow_opts* o) { return {o ? *o : fav_flow_opts{0, 0, 0, 0.f, 0, 0.f}, FAV_FLOW_DATA_BRIGHTNESS}; }
 // ... and of one from before the matching prior existed: its fav_flow_opts_ex (or none) with the prior off
 inline fav_flow_opts_ex2 flow_opts_no_match(const fav_flow_opts_ex* o) { return {o ? *o : flow_opts_brightness(nullptr), 0.f, 0}; }
+// the median filter between warps (tests/util/flow_median_model.py): u and v of every item, each replaced by the median of its
+// size x size window (size 3 | 5, indices clamped to the image), from src into dst; src and dst are distinct buffers
+int launch_flow_median(const FlowPtrs& src, const FlowPtrs& dst, int items, int W, int H, int size, hipStream_t st);
+// ... and the options of an entry from before the median filter existed: its fav_flow_opts_ex2 (or none) with the filter off
+inline fav_flow_opts_ex3 flow_opts_no_median(const fav_flow_opts_ex2* o) { return {o ? *o : flow_opts_no_match(nullptr), 0}; }
 // Huffman codes of the PNG encoder (png_tables.cpp): PNG_NTABLES model codes with their dynamic-block headers + the fixed code
 constexpr int PNG_NSYM = 277;            // literals 0..255, end of block 256, length symbols 257..276 (runs of 3..66)
 constexpr int PNG_NTABLES = 12;

@@ -1,6 +1,7 @@
 // flow.cpp -- the coarse-to-fine optical-flow estimator behind fav_flow_rgb8 (kernels in kernels_flow.hip; the algorithm is stated in
 // DESIGN.md, "fav_flow", and restated in numpy by tests/util/flow_model.py, for smooth_eps > 0 by tests/util/flow_robust_model.py and for the
-// gradient-constancy data term by tests/util/flow_grad_model.py, for the matching prior by tests/util/flow_match_model.py):
+// gradient-constancy data term by tests/util/flow_grad_model.py, for the matching prior by tests/util/flow_match_model.py, for the median
+// filter between warps by tests/util/flow_median_model.py):
 // option defaults, the layout of the caller's workspace and the sequence of launches.  Nothing here allocates or synchronises.
 #include <cmath>
 
@@ -33,15 +34,19 @@ struct FlowPlan {
     float beta = 0.f;
     int radius = 0, matches = 0;
     size_t match = 0, match_stride = 0, prior[MAX_LEVELS] = {}, prior_stride[MAX_LEVELS] = {};
+    int median = 0;      // 3 | 5: the window of the median filter behind every warp's sweeps; it owns no part of the workspace
 };
 
 // FAV_OK or FAV_EINVAL (message set)
-int make_plan(int W, int H, const fav_flow_opts_ex2* ex2, int images, int flows, FlowPlan& p)
+int make_plan(int W, int H, const fav_flow_opts_ex3* ex3, int images, int flows, FlowPlan& p)
 {
-    static const fav_flow_opts_ex2 none = flow_opts_no_match(nullptr);
-    if (!ex2) ex2 = &none;
+    static const fav_flow_opts_ex3 none = flow_opts_no_median(nullptr);
+    if (!ex3) ex3 = &none;
+    const fav_flow_opts_ex2* ex2 = &ex3->ex2;
     const fav_flow_opts_ex* ex = &ex2->ex;
     const fav_flow_opts* o = &ex->base;
+    FAV_REQUIRE(ex3->median == 0 || ex3->median == 3 || ex3->median == 5, "fav_flow: median must be 0 (off), 3 or 5 (the side of the window), not %d", ex3->median);
+    p.median = ex3->median;
     FAV_REQUIRE(std::isfinite(ex2->match_beta) && ex2->match_beta <= MAX_MATCH_BETA, "fav_flow: match_beta must be 0 (off), negative (default) or a number up to 1e6, not %g",
                 (double)ex2->match_beta);
     FAV_REQUIRE(ex2->match_radius >= 0 && ex2->match_radius <= FLOW_MATCH_MAX_RADIUS, "fav_flow: match_radius must be 0 (default) .. %d, not %d", FLOW_MATCH_MAX_RADIUS,
@@ -112,8 +117,9 @@ int run_plan(const FlowPlan& p, const FlowPtrs& img, const int* a_of, const int*
         rc = launch_flow_down(finer, p.w[l - 1], p.h[l - 1], level, p.images, st); if (rc) return rc;
         finer = level;
     }
-    // coarse to fine.  Every warp ends ceil(iters / K) buffer swaps later: level 0 starts in the buffers that leave the results in `out`
-    const int swaps = p.warps * ((p.iters + p.K - 1) / p.K);
+    // coarse to fine.  Every warp ends ceil(iters / K) buffer swaps later, and one more with the median filter (it goes from the buffer the
+    // sweeps ended in into the other one): level 0 starts in the buffers that leave the results in `out`
+    const int swaps = p.warps * ((p.iters + p.K - 1) / p.K + (p.median ? 1 : 0));
     const FlowPtrs coef(ws + p.coef, p.coef_stride, p.flows);
     const FlowPtrs wgt_planes(ws + p.wgt, p.wgt_stride, p.flows);
     FlowVariant v = p.v;
@@ -166,6 +172,10 @@ int run_plan(const FlowPlan& p, const FlowPtrs& img, const int* a_of, const int*
         for (int k = 0; k < p.warps; ++k) {
             rc = launch_flow_coef(A, B, cur, coef, v, p.flows, w, h, st); if (rc) return rc;
             rc = launch_flow_sweeps(&cur, &other, coef, v, p.flows, p.iters, p.K, w, h, st); if (rc) return rc;
+            if (p.median) {
+                rc = launch_flow_median(cur, other, p.flows, w, h, p.median, st); if (rc) return rc;
+                std::swap(cur, other);
+            }
         }
         coarser = cur;
     }
@@ -183,6 +193,12 @@ extern "C" size_t fav_flow_workspace_bytes_ex(int W, int H, const fav_flow_opts_
 }
 
 extern "C" size_t fav_flow_workspace_bytes_ex2(int W, int H, const fav_flow_opts_ex2* opts_host)
+{
+    const fav_flow_opts_ex3 ex3 = flow_opts_no_median(opts_host);
+    return fav_flow_workspace_bytes_ex3(W, H, &ex3);
+}
+
+extern "C" size_t fav_flow_workspace_bytes_ex3(int W, int H, const fav_flow_opts_ex3* opts_host)
 {
     FlowPlan p;
     return make_plan(W, H, opts_host, 2, 1, p) ? 0 : p.bytes;
@@ -209,6 +225,13 @@ extern "C" int fav_flow_rgb8_ex(const uint8_t* a_rgb_hwc, const uint8_t* b_rgb_h
 }
 
 extern "C" int fav_flow_rgb8_ex2(const uint8_t* a_rgb_hwc, const uint8_t* b_rgb_hwc, int W, int H, const fav_flow_opts_ex2* opts_host, float* flow_out,
+                                 void* workspace, size_t workspace_bytes, fav_hipstream_t stream)
+{
+    const fav_flow_opts_ex3 ex3 = flow_opts_no_median(opts_host);
+    return fav_flow_rgb8_ex3(a_rgb_hwc, b_rgb_hwc, W, H, &ex3, flow_out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int fav_flow_rgb8_ex3(const uint8_t* a_rgb_hwc, const uint8_t* b_rgb_hwc, int W, int H, const fav_flow_opts_ex3* opts_host, float* flow_out,
                                  void* workspace, size_t workspace_bytes, fav_hipstream_t stream)
 {
     FlowPlan p;
@@ -244,6 +267,12 @@ extern "C" size_t fav_flow_pairs_workspace_bytes_ex(int W, int H, int n_pairs, c
 
 extern "C" size_t fav_flow_pairs_workspace_bytes_ex2(int W, int H, int n_pairs, const fav_flow_opts_ex2* opts_host)
 {
+    const fav_flow_opts_ex3 ex3 = flow_opts_no_median(opts_host);
+    return fav_flow_pairs_workspace_bytes_ex3(W, H, n_pairs, &ex3);
+}
+
+extern "C" size_t fav_flow_pairs_workspace_bytes_ex3(int W, int H, int n_pairs, const fav_flow_opts_ex3* opts_host)
+{
     FlowPlan p;
     if (n_pairs < 1 || n_pairs > FAV_FLOW_MAX_PAIRS) { set_error("fav_flow_pairs: n_pairs must be 1 .. %d, not %d", FAV_FLOW_MAX_PAIRS, n_pairs); return 0; }
     return make_plan(W, H, opts_host, 2 * n_pairs, 2 * n_pairs, p) ? 0 : p.bytes;
@@ -259,6 +288,14 @@ extern "C" int fav_flow_pairs_rgb8_ex(const uint8_t* const* prev_rgb_hwc, const 
 
 extern "C" int fav_flow_pairs_rgb8_ex2(const uint8_t* const* prev_rgb_hwc, const uint8_t* const* cur_rgb_hwc, int n_pairs, int W, int H,
                                        const fav_flow_opts_ex2* opts_host, float* const* backward_flo, float* const* forward_flo, void* workspace,
+                                       size_t workspace_bytes, fav_hipstream_t stream)
+{
+    const fav_flow_opts_ex3 ex3 = flow_opts_no_median(opts_host);
+    return fav_flow_pairs_rgb8_ex3(prev_rgb_hwc, cur_rgb_hwc, n_pairs, W, H, &ex3, backward_flo, forward_flo, workspace, workspace_bytes, stream);
+}
+
+extern "C" int fav_flow_pairs_rgb8_ex3(const uint8_t* const* prev_rgb_hwc, const uint8_t* const* cur_rgb_hwc, int n_pairs, int W, int H,
+                                       const fav_flow_opts_ex3* opts_host, float* const* backward_flo, float* const* forward_flo, void* workspace,
                                        size_t workspace_bytes, fav_hipstream_t stream)
 {
     FAV_REQUIRE(n_pairs >= 1 && n_pairs <= FAV_FLOW_MAX_PAIRS, "fav_flow_pairs_rgb8: n_pairs must be 1 .. %d, not %d", FAV_FLOW_MAX_PAIRS, n_pairs);
@@ -388,6 +425,18 @@ extern "C" int fav_flow_sweeps_grad_f32(const float* flow0, const float* coef, c
                                         float* scratch, int W, int H, fav_hipstream_t stream)
 {
     return sweeps_entry("fav_flow_sweeps_grad_f32", flow0, coef, weights, iters, sweeps_per_launch, flow_out, scratch, W, H, stream, true);
+}
+
+// ---- the median filter on its own (tests: equal to tests/util/flow_median_model.py value for value)
+extern "C" int fav_flow_median_f32(const float* flow_in, float* flow_out, int W, int H, int size, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(flow_in && flow_out && W > 0 && H > 0 && (long long)W * H <= (1ll << 28), "fav_flow_median_f32: bad argument");
+    FAV_REQUIRE(size == 3 || size == 5, "fav_flow_median_f32: size must be 3 or 5 (the side of the window), not %d", size);
+    FAV_REQUIRE(aligned(flow_in, 8) && aligned(flow_out, 8), "fav_flow_median_f32: flows must be 8-byte aligned");
+    const uintptr_t in = reinterpret_cast<uintptr_t>(flow_in), out = reinterpret_cast<uintptr_t>(flow_out), bytes = (uintptr_t)W * H * 8;
+    FAV_REQUIRE(in + bytes <= out || out + bytes <= in, "fav_flow_median_f32: flow_in and flow_out overlap (the filter is not in place)");
+    int rc = ensure_device(); if (rc) return rc;
+    return launch_flow_median(FlowPtrs(flow_in), FlowPtrs(flow_out), 1, W, H, size, static_cast<hipStream_t>(stream));
 }
 
 // ---- the matching prior's stages (tests: held to tests/util/flow_match_model.py)

@@ -526,6 +526,88 @@ __global__ __launch_bounds__((SweepShape<Cell, WEIGHTED>::THREADS)) void flow_sw
     }
 }
 
+// ---- median filtering of the flow between warps (fav_flow_opts_ex3.median = 3 | 5; DESIGN.md, "Median filtering"; restated by
+// tests/util/flow_median_model.py).  After the sweeps of a warp u and v are replaced, each on its own, by the median of their
+// (2R + 1)^2 window, R = median / 2, neighbour indices clamped to the image.  Nothing is computed, only selected: the result equals
+// a sort's middle element value for value.
+// A block owns a tile of 64 x 16 pixels and stages it with a halo of R (coordinates clamped to the image: the replicated border) in
+// LDS as float2; a lane owns one column and the rows ty + 4 j.  Per pixel it reads its window -- a wave is one row of 64 columns, so
+// at any window offset and any row pitch consecutive lanes read consecutive float2: the 32 lanes of a ds_read_b64's conflict group
+// cover 256 contiguous bytes, all 64 banks once, and the 16 lanes of a group of ds_read2_b64 (what the compiler makes of two taps)
+// 128 contiguous bytes, its 32 banks once: conflict-free either way, no padding -- and runs a fixed selection network on it in
+// registers, first for u, then for v: 19 compare-exchanges for 9 values,
+// 99 for 25 (the classical median networks; every table below sorts all 2^n inputs of zeros and ones to the right middle wire,
+// which by the 0-1 principle is every input).  The tables are unrolled, so every array index is a constant and nothing goes to scratch.
+// A compare-exchange is a permutation of its two inputs (a < b picks both sides), so no value is duplicated or lost, -0 / +0 included.
+constexpr int MED_TW = 64, MED_TH = 16, MED_TY = 4;
+constexpr unsigned char MED9_NET[19][2] = {{1, 2}, {4, 5}, {7, 8}, {0, 1}, {3, 4}, {6, 7}, {1, 2}, {4, 5}, {7, 8}, {0, 3}, {5, 8}, {4, 7}, {3, 6}, {1, 4}, {2, 5},
+                                           {4, 7}, {4, 2}, {6, 4}, {4, 2}};
+constexpr unsigned char MED25_NET[99][2] = {
+    {0, 1}, {3, 4}, {2, 4}, {2, 3}, {6, 7}, {5, 7}, {5, 6}, {9, 10}, {8, 10}, {8, 9}, {12, 13}, {11, 13}, {11, 12}, {15, 16}, {14, 16}, {14, 15}, {18, 19},
+    {17, 19}, {17, 18}, {21, 22}, {20, 22}, {20, 21}, {23, 24}, {2, 5}, {3, 6}, {0, 6}, {0, 3}, {4, 7}, {1, 7}, {1, 4}, {11, 14}, {8, 14}, {8, 11}, {12, 15},
+    {9, 15}, {9, 12}, {13, 16}, {10, 16}, {10, 13}, {20, 23}, {17, 23}, {17, 20}, {21, 24}, {18, 24}, {18, 21}, {19, 22}, {8, 17}, {9, 18}, {0, 18}, {0, 9},
+    {10, 19}, {1, 19}, {1, 10}, {11, 20}, {2, 20}, {2, 11}, {12, 21}, {3, 21}, {3, 12}, {13, 22}, {4, 22}, {4, 13}, {14, 23}, {5, 23}, {5, 14}, {15, 24},
+    {6, 24}, {6, 15}, {7, 16}, {7, 19}, {13, 21}, {15, 23}, {7, 13}, {7, 15}, {1, 9}, {3, 11}, {5, 17}, {11, 17}, {9, 17}, {4, 10}, {6, 12}, {7, 14}, {4, 6},
+    {4, 7}, {12, 14}, {10, 14}, {6, 7}, {10, 12}, {6, 10}, {6, 17}, {12, 17}, {7, 17}, {7, 10}, {12, 18}, {7, 12}, {10, 18}, {12, 20}, {10, 20}, {10, 12}};
+
+// the smaller of the two into a, the larger into b
+__device__ __forceinline__ void compare_exchange(float& a, float& b)
+{
+    const bool lt = a < b;
+    const float lo = lt ? a : b, hi = lt ? b : a;
+    a = lo; b = hi;
+}
+
+// the middle element of p's (2R + 1)^2 values (p is permuted)
+template <int R>
+__device__ __forceinline__ float median_select(float (&p)[(2 * R + 1) * (2 * R + 1)])
+{
+    static_assert(R == 1 || R == 2, "a 3 x 3 or a 5 x 5 window");
+    if constexpr (R == 1) {
+#pragma unroll
+        for (int i = 0; i < 19; ++i) compare_exchange(p[MED9_NET[i][0]], p[MED9_NET[i][1]]);
+        return p[4];
+    } else {
+#pragma unroll
+        for (int i = 0; i < 99; ++i) compare_exchange(p[MED25_NET[i][0]], p[MED25_NET[i][1]]);
+        return p[12];
+    }
+}
+
+template <int R>
+__global__ __launch_bounds__(256) void flow_median_kernel(FlowPtrs srcs, FlowPtrs dsts, int w, int h)
+{
+    constexpr int S = 2 * R + 1, COLS = MED_TW + 2 * R, ROWS = MED_TH + 2 * R;
+    __shared__ float2 s[ROWS][COLS];
+    const float2* __restrict__ src = static_cast<const float2*>(srcs.p[blockIdx.z]);
+    float2* __restrict__ dst = static_cast<float2*>(dsts.p[blockIdx.z]);
+    const int tx0 = blockIdx.x * MED_TW, ty0 = blockIdx.y * MED_TH;
+    for (int i = threadIdx.x; i < ROWS * COLS; i += 256) {
+        const int ry = i / COLS, cx = i - ry * COLS;
+        const int cy = min(max(ty0 - R + ry, 0), h - 1), ccx = min(max(tx0 - R + cx, 0), w - 1);
+        s[ry][cx] = src[(size_t)cy * w + ccx];
+    }
+    __syncthreads();
+    const int lx = threadIdx.x & 63, ty = threadIdx.x >> 6, gx = tx0 + lx;
+    if (gx >= w) return;
+#pragma unroll
+    for (int j = 0; j < MED_TH / MED_TY; ++j) {
+        const int ly = ty + MED_TY * j, gy = ty0 + ly;
+        if (gy < h) {
+            float u[S * S], v[S * S];      // window sample (dy, dx) is staged cell (ly + dy, lx + dx)
+#pragma unroll
+            for (int dy = 0; dy < S; ++dy)
+#pragma unroll
+                for (int dx = 0; dx < S; ++dx) {
+                    const float2 t = s[ly + dy][lx + dx];
+                    u[dy * S + dx] = t.x; v[dy * S + dx] = t.y;
+                }
+            const float mu = median_select<R>(u), mv = median_select<R>(v);
+            dst[(size_t)gy * w + gx] = make_float2(mu, mv);
+        }
+    }
+}
+
 // the one place that maps a variant to an instantiation: f(grad, weighted, prior), three std::bool_constant
 template <class F>
 void with_variant(const FlowVariant& v, F&& f)
@@ -631,6 +713,18 @@ int launch_flow_sweeps(FlowPtrs* cur, FlowPtrs* other, const FlowPtrs& coef, con
         FAV_LAUNCH_CHECK("flow_sweep_kernel");
         std::swap(*cur, *other);
     }
+    return FAV_OK;
+}
+
+// the size x size median (size 3 | 5) of every item's u and v, from src into dst (never in place)
+int launch_flow_median(const FlowPtrs& src, const FlowPtrs& dst, int items, int W, int H, int size, hipStream_t st)
+{
+    FAV_REQUIRE(size_ok(W, H) && items_ok(items) && (size == 3 || size == 5), "flow median: bad argument (%dx%d x %d, window %d)", W, H, items, size);
+    for (int j = 0; j < items; ++j) FAV_REQUIRE(src.p[j] && dst.p[j] && src.p[j] != dst.p[j], "flow median: item %d is filtered in place or missing", j);
+    const dim3 grid((W + MED_TW - 1) / MED_TW, (H + MED_TH - 1) / MED_TH, items);
+    FAV_REQUIRE(grid.y <= 65535, "flow median: %d rows are too many", H);
+    hipLaunchKernelGGL(size == 3 ? flow_median_kernel<1> : flow_median_kernel<2>, grid, dim3(256), 0, st, src, dst, W, H);
+    FAV_LAUNCH_CHECK("flow_median_kernel");
     return FAV_OK;
 }
 

@@ -369,18 +369,28 @@ extern "C" int fav_stream_next_frame_estimate_ex2(fav_stream* s, const uint8_t* 
                                                   void* workspace, size_t workspace_bytes, float* out_rgb_f32, uint8_t* out_rgb8_hwc,
                                                   fav_hipstream_t stream)
 {
+    const fav_flow_opts_ex3 ex3 = flow_opts_no_median(flow_opts_host);
+    return fav_stream_next_frame_estimate_ex3(s, frame_rgb_hwc, prev_frame_rgb_hwc, &ex3, use_structure, backward_flo, forward_flo, workspace, workspace_bytes,
+                                              out_rgb_f32, out_rgb8_hwc, stream);
+}
+
+extern "C" int fav_stream_next_frame_estimate_ex3(fav_stream* s, const uint8_t* frame_rgb_hwc, const uint8_t* prev_frame_rgb_hwc,
+                                                  const fav_flow_opts_ex3* flow_opts_host, int use_structure, float* backward_flo, float* forward_flo,
+                                                  void* workspace, size_t workspace_bytes, float* out_rgb_f32, uint8_t* out_rgb8_hwc,
+                                                  fav_hipstream_t stream)
+{
     FAV_REQUIRE(s && frame_rgb_hwc && prev_frame_rgb_hwc && backward_flo && forward_flo, "fav_stream_next_frame_estimate: null argument");
     FAV_HIP(hipSetDevice(net_device(s->net)));
-    const size_t pair_bytes = fav_flow_pairs_workspace_bytes_ex2(s->W, s->H, 1, flow_opts_host);      // (0: a bad option; the single call reports it)
+    const size_t pair_bytes = fav_flow_pairs_workspace_bytes_ex3(s->W, s->H, 1, flow_opts_host);      // (0: a bad option; the single call reports it)
     int rc;
     if (pair_bytes && workspace_bytes >= pair_bytes) {
-        rc = fav_flow_pairs_rgb8_ex2(&prev_frame_rgb_hwc, &frame_rgb_hwc, 1, s->W, s->H, flow_opts_host, &backward_flo, &forward_flo, workspace,
+        rc = fav_flow_pairs_rgb8_ex3(&prev_frame_rgb_hwc, &frame_rgb_hwc, 1, s->W, s->H, flow_opts_host, &backward_flo, &forward_flo, workspace,
                                      workspace_bytes, stream);
         if (rc) return rc;
     } else {
-        rc = fav_flow_rgb8_ex2(frame_rgb_hwc, prev_frame_rgb_hwc, s->W, s->H, flow_opts_host, backward_flo, workspace, workspace_bytes, stream);
+        rc = fav_flow_rgb8_ex3(frame_rgb_hwc, prev_frame_rgb_hwc, s->W, s->H, flow_opts_host, backward_flo, workspace, workspace_bytes, stream);
         if (rc) return rc;
-        rc = fav_flow_rgb8_ex2(prev_frame_rgb_hwc, frame_rgb_hwc, s->W, s->H, flow_opts_host, forward_flo, workspace, workspace_bytes, stream);
+        rc = fav_flow_rgb8_ex3(prev_frame_rgb_hwc, frame_rgb_hwc, s->W, s->H, flow_opts_host, forward_flo, workspace, workspace_bytes, stream);
         if (rc) return rc;
     }
     return fav_stream_next_frame_flow(s, frame_rgb_hwc, backward_flo, forward_flo, use_structure, out_rgb_f32, out_rgb8_hwc, stream);

@@ -10,6 +10,8 @@
 //                        for frames whose lighting changes
 //            -match <0|1> block-matching prior for objects that move further than their own size (fav_flow_opts_ex2.match_beta: the
 //                        default weight; 0 = off, the default);  -match_radius <n>  its search radius at half resolution (1..32; 0 = 16)
+//            -median <0|3|5> median filtering of the flow after every warp, the side of the window (fav_flow_opts_ex3.median; 0 = off,
+//                        the default)
 //
 // The .flo is written under a temporary name and renamed into place, so a polling consumer never reads a partial file.
 #include <hip/hip_runtime.h>
@@ -31,7 +33,7 @@ namespace {
 
 [[noreturn]] void usage(const std::string& why)
 {
-    fprintf(stderr, "%s\nusage: fav_flow [-alpha x] [-eps x] [-grad 0|1] [-match 0|1] [-match_radius n] [-iters n] [-warps n] [-levels n] [-gpu n] <img1.ppm> <img2.ppm> <out.flo> [downscale]\n"
+    fprintf(stderr, "%s\nusage: fav_flow [-alpha x] [-eps x] [-grad 0|1] [-match 0|1] [-match_radius n] [-median 0|3|5] [-iters n] [-warps n] [-levels n] [-gpu n] <img1.ppm> <img2.ppm> <out.flo> [downscale]\n"
                     "       fav_flow [options] -batch <list.txt>      (one \"img1 img2 out.flo\" per line)\n", why.c_str());
     exit(2);
 }
@@ -63,7 +65,8 @@ bool parse_int(const char* s, int* out)
 
 int main(int argc, char** argv)
 {
-    fav_flow_opts_ex2 fx2 = {};    // every field 0: the defaults, the brightness term, no matching prior
+    fav_flow_opts_ex3 fx3 = {};    // every field 0: the defaults, the brightness term, no matching prior, no median filter
+    fav_flow_opts_ex2& fx2 = fx3.ex2;
     fav_flow_opts_ex& fx = fx2.ex;
     fav_flow_opts& fo = fx.base;
     int gpu = 0;
@@ -81,6 +84,7 @@ int main(int argc, char** argv)
             else if (k == "-grad") { if (strcmp(v, "0") != 0 && strcmp(v, "1") != 0) usage(std::string("-grad must be 0 or 1, not '") + v + "'"); fx.data_term = v[0] - '0'; }
             else if (k == "-match") { if (strcmp(v, "0") != 0 && strcmp(v, "1") != 0) usage(std::string("-match must be 0 or 1, not '") + v + "'"); fx2.match_beta = v[0] == '1' ? -1.f : 0.f; }
             else if (k == "-match_radius") ok = parse_int(v, &fx2.match_radius);
+            else if (k == "-median") { if (strcmp(v, "0") != 0 && strcmp(v, "3") != 0 && strcmp(v, "5") != 0) usage(std::string("-median must be 0, 3 or 5, not '") + v + "'"); fx3.median = v[0] - '0'; }
             else if (k == "-iters") ok = parse_int(v, &fo.iters);
             else if (k == "-warps") ok = parse_int(v, &fo.warps);
             else if (k == "-levels") ok = parse_int(v, &fo.levels);
@@ -107,7 +111,7 @@ int main(int argc, char** argv)
         if (pos.size() < 3 || pos.size() > 4) usage("expected <img1.ppm> <img2.ppm> <out.flo> [downscale]");
         jobs.push_back({pos[0], pos[1], pos[2]});        // pos[3]: run-deepflow.sh's downscale factor, of no use here
     }
-    if (fav_flow_workspace_bytes_ex2(64, 64, &fx2) == 0) die(fav_last_error());      // the options, before any file or device is touched
+    if (fav_flow_workspace_bytes_ex3(64, 64, &fx3) == 0) die(fav_last_error());      // the options, before any file or device is touched
 
     if (fav_device_count() <= 0) die(std::string("ERROR: ") + fav_last_error());
     if (hipSetDevice(gpu) != hipSuccess) die("cannot select GPU " + std::to_string(gpu));
@@ -122,7 +126,7 @@ int main(int argc, char** argv)
         if (W != W2 || H != H2) die(j.a + ", " + j.b + ": the two frames differ in size");
         const size_t n = (size_t)W * H;
         if (W != cw || H != ch) {
-            ws_bytes = fav_flow_workspace_bytes_ex2(W, H, &fx2);
+            ws_bytes = fav_flow_workspace_bytes_ex3(W, H, &fx3);
             if (!ws_bytes) die(fav_last_error());
             hipFree(d_a); hipFree(d_b); hipFree(d_flow); hipFree(d_ws);
             if (hipMalloc((void**)&d_a, n * 3) || hipMalloc((void**)&d_b, n * 3) || hipMalloc((void**)&d_flow, n * 8) || hipMalloc(&d_ws, ws_bytes)) die("hipMalloc failed");
@@ -130,7 +134,7 @@ int main(int argc, char** argv)
         }
         if (hipMemcpy(d_a, a, n * 3, hipMemcpyHostToDevice) || hipMemcpy(d_b, b, n * 3, hipMemcpyHostToDevice)) die("upload failed");
         fav_free_host(a); fav_free_host(b);
-        if (fav_flow_rgb8_ex2(d_a, d_b, W, H, &fx2, d_flow, d_ws, ws_bytes, nullptr)) die(fav_last_error());
+        if (fav_flow_rgb8_ex3(d_a, d_b, W, H, &fx3, d_flow, d_ws, ws_bytes, nullptr)) die(fav_last_error());
         if (hipMemcpy(h_flow.data(), d_flow, n * 8, hipMemcpyDeviceToHost) != hipSuccess) die("GPU error while estimating " + j.out);
         if (!write_flo(j.out, h_flow.data(), W, H)) die("cannot write " + j.out);
     }

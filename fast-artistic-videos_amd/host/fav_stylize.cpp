@@ -30,7 +30,8 @@
 // edge-preserving smoothness, 0 = off, the default); -flow_grad <0|1> (fav_flow_opts_ex.data_term: the data term on the image gradients
 // instead of the grey levels, for video whose lighting changes; 0 = off, the default; only with -estimate_flow 1); -flow_match <0|1>
 // (fav_flow_opts_ex2.match_beta: the block-matching prior for objects that move further than their own size; 0 = off, the default; only
-// with -estimate_flow 1).
+// with -estimate_flow 1); -flow_median <0|3|5> (fav_flow_opts_ex3.median: median filtering of the flow after every warp, the side of the
+// window; 0 = off, the default; only with -estimate_flow 1).
 // -input_y4m <path|-> INSTEAD of -input_pattern: the frames are those of a YUV4MPEG2 stream (`ffmpeg ... -f yuv4mpegpipe -`), frame i is
 //   its i-th frame (1-based), read sequentially (a pipe's short reads included); the planes are uploaded and converted on the device
 //   (fav_yuv_to_rgb8) into the buffer the PPM payload otherwise fills.  The stream ending at a frame boundary ends the clip like a missing
@@ -364,10 +365,11 @@ FrameIn load_frame_inputs(const Opt& o, const favp::Poll& poll, int i, bool firs
 }
 
 // the estimator's options from the -flow_* flags (main validates them)
-fav_flow_opts_ex2 flow_opts_of(const Opt& o)
+fav_flow_opts_ex3 flow_opts_of(const Opt& o)
 {
-    return {{{o.i("flow_levels"), o.i("flow_warps"), o.i("flow_iters"), (float)o.d("flow_alpha"), 0, (float)o.d("flow_eps")}, o.i("flow_grad")},
-            o.i("flow_match") ? -1.f : 0.f, 0};
+    return {{{{o.i("flow_levels"), o.i("flow_warps"), o.i("flow_iters"), (float)o.d("flow_alpha"), 0, (float)o.d("flow_eps")}, o.i("flow_grad")},
+             o.i("flow_match") ? -1.f : 0.f, 0},
+            o.i("flow_median")};
 }
 
 // The format of a Y4M stream's frames.  from_header: what the input's header says (null: there is no Y4M input -- 4:2:0 with centre
@@ -387,7 +389,7 @@ fav_yuv_format y4m_format_of(const Opt& o, const fav_yuv_format* from_header, in
 
 // One video: the loop of run_fast_neural_video (core.lua:189-229) with the video CLI's callbacks (fav.lua:93-172).
 // `net` / `net_img` live on the current device; `nwriters` PNG threads.
-void run_stream(const Opt& o, const fav_flow_opts_ex2& flow_opts, fav_net* net, fav_net* net_img, int nwriters, StreamResult* res)   // nwriters: the budget; adjusted below
+void run_stream(const Opt& o, const fav_flow_opts_ex3& flow_opts, fav_net* net, fav_net* net_img, int nwriters, StreamResult* res)   // nwriters: the budget; adjusted below
 {
     const bool estimate = o.i("estimate_flow") != 0;       // the flows come from the frames (and go through the fused check)
     const bool fused_check = estimate || !o.s("forward_flow_pattern").empty();
@@ -703,7 +705,7 @@ void run_stream(const Opt& o, const fav_flow_opts_ex2& flow_opts, fav_net* net, 
                 hipStreamSynchronize(st); hipFree(d_state);
             }
             if (estimate) {
-                flow_ws_bytes = fav_flow_pairs_workspace_bytes_ex2(W, H, 1, &flow_opts);      // room for both flows at once: the batch of one
+                flow_ws_bytes = fav_flow_pairs_workspace_bytes_ex3(W, H, 1, &flow_opts);      // room for both flows at once: the batch of one
                 if (!flow_ws_bytes) die(std::string("-estimate_flow: ") + fav_last_error());
                 if (hipMalloc(&d_flow_ws, flow_ws_bytes) != hipSuccess) die("hipMalloc failed");
                 if (!cur.single) {                       // -continue_with: the frame before the first one is read as well, into the set "before" dset
@@ -756,7 +758,7 @@ void run_stream(const Opt& o, const fav_flow_opts_ex2& flow_opts, fav_net* net, 
         } else if (estimate) {
             // the previous frame in processing order is still in the device set before this one: with one frame of look-ahead the
             // uploads only ever touch the set after it
-            check(fav_stream_next_frame_estimate_ex2(fs, dc.frame, dev[(dset + NDEV - 1) % NDEV].frame, &flow_opts, o.i("structure"), dc.bw, dc.fw,
+            check(fav_stream_next_frame_estimate_ex3(fs, dc.frame, dev[(dset + NDEV - 1) % NDEV].frame, &flow_opts, o.i("structure"), dc.bw, dc.fw,
                                                  d_flow_ws, flow_ws_bytes, nullptr, d_out8, st), "fav_stream_next_frame_estimate");
         } else if (fused_check) {
             check(fav_stream_next_frame_flow(fs, dc.frame, dc.bw, dc.fw, o.i("structure"), nullptr, d_out8, st), "fav_stream_next_frame_flow");
@@ -874,7 +876,7 @@ int main(int argc, char** argv)
            {"forward_flow_pattern", ""}, {"structure", "1"}, {"warp_border", "stn"}, {"poll_timeout", "3600"}, {"poll_settle", "1.0"},
            {"png_level", "1"}, {"png_encoder", "gpu"}, {"png_overlap", "0"}, {"writers", "0"}, {"timing", "0"}, {"temporal_eval_file", ""}, {"seed", "1"}, {"precision", "fp32"},
            {"input_y4m", ""}, {"output_y4m", ""}, {"y4m_matrix", "auto"}, {"y4m_range", "auto"}, {"y4m_format", ""},
-           {"estimate_flow", "0"}, {"flow_alpha", "0"}, {"flow_eps", "0"}, {"flow_grad", "0"}, {"flow_match", "0"}, {"flow_iters", "0"}, {"flow_warps", "0"}, {"flow_levels", "0"},
+           {"estimate_flow", "0"}, {"flow_alpha", "0"}, {"flow_eps", "0"}, {"flow_grad", "0"}, {"flow_match", "0"}, {"flow_median", "0"}, {"flow_iters", "0"}, {"flow_warps", "0"}, {"flow_levels", "0"},
            {"streams", ""}, {"gpus", "1"}, {"force_dist", "0"}, {"dry_run", "0"}, {"shared_gpu", "0"}, {"pin_workers", "1"},
            // internal (set by the launcher for its workers)
            {"worker_rank", "-1"}, {"worker_world", "0"}, {"rccl_id_file", ""},
@@ -911,12 +913,14 @@ int main(int argc, char** argv)
     if (o.i("flow_grad") && !estimate) die("-flow_grad 1 selects the data term of the built-in flow estimator: it needs -estimate_flow 1");
     if (o.s("flow_match") != "0" && o.s("flow_match") != "1") die("-flow_match must be 0 or 1, not '" + o.s("flow_match") + "'");
     if (o.i("flow_match") && !estimate) die("-flow_match 1 turns on the matching prior of the built-in flow estimator: it needs -estimate_flow 1");
-    const fav_flow_opts_ex2 flow_opts = flow_opts_of(o);
+    if (o.s("flow_median") != "0" && o.s("flow_median") != "3" && o.s("flow_median") != "5") die("-flow_median must be 0, 3 or 5, not '" + o.s("flow_median") + "'");
+    if (o.i("flow_median") && !estimate) die("-flow_median " + o.s("flow_median") + " turns on the median filter of the built-in flow estimator: it needs -estimate_flow 1");
+    const fav_flow_opts_ex3 flow_opts = flow_opts_of(o);
     if (estimate) {
         for (const char* k : {"flow_pattern", "forward_flow_pattern", "occlusions_pattern"})
             if (!o.s(k).empty()) die(std::string("-estimate_flow 1 computes both flows and the certainty from the frames: it cannot be combined with -") + k);
         if (atof(o.s("scale_factor").c_str()) != 1.0) die("-estimate_flow 1 cannot be combined with a -scale_factor other than 1");
-        if (fav_flow_workspace_bytes_ex2(64, 64, &flow_opts) == 0) die(std::string("-flow_alpha / -flow_eps / -flow_iters / -flow_warps / -flow_levels: ") + fav_last_error());
+        if (fav_flow_workspace_bytes_ex3(64, 64, &flow_opts) == 0) die(std::string("-flow_alpha / -flow_eps / -flow_iters / -flow_warps / -flow_levels: ") + fav_last_error());
     }
     const bool fused_check = !o.s("forward_flow_pattern").empty();
     if (!estimate && !o.f("create_inconsistent") && (o.s("flow_pattern").empty() || (o.s("occlusions_pattern").empty() && !fused_check)))

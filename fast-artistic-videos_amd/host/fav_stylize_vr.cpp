@@ -14,7 +14,7 @@
 // INSTEAD of face, flow and certainty files (naming any of -input_pattern, -flow_pattern, -forward_flow_pattern, -occlusions_pattern next
 // to it is an error).  Every frame is turned into six faces of -cube_edge_length <n> (768) pixels with -overlap_pixel_w / _h of margin
 // (fav_vr_equi_to_faces_rgb8, -supersample <1..4>, default 2; the reference script's pair is 768 / 128), both flows of all six faces are
-// estimated in one batched call (fav_flow_pairs_rgb8_ex2; -flow_alpha, -flow_eps, -flow_grad, -flow_match, -flow_warps, -flow_iters as in fav_stylize, 0 = default) and the faces
+// estimated in one batched call (fav_flow_pairs_rgb8_ex3; -flow_alpha, -flow_eps, -flow_grad, -flow_match, -flow_median, -flow_warps, -flow_iters as in fav_stylize, 0 = default) and the faces
 // run as with -forward_flow_pattern.  One GPU.  (-estimate_flow is NOT a flag here: the flows follow from there being no face files.)
 // Additive flags: -precision <fp32|bf16>, -warp_border <stn|cpu>, -poll_timeout <sec>, -poll_settle <sec> (host/fav_poll.h), -png_level <0..9>, -seed <n> (uniform-random fill), -timing <0|1>,
 // and -- several 360-degree videos on several GPUs (BASELINE config 5; the faces of one frame depend on each other through the
@@ -264,7 +264,7 @@ int run_video(std::map<std::string, std::string>& v, std::map<std::string, bool>
 // (fav_flow_pairs_rgb8), the six masks start on the library's side stream and the faces run through fav_vr_face_flow as in the file
 // mode with -forward_flow_pattern; no face, flow or certainty file exists.  Everything is enqueued on one stream.  (run_video above is
 // the reference's file contract and stays as it is; the frame's way out of the device is restated here.)
-int run_video_equi(std::map<std::string, std::string>& v, std::map<std::string, bool>& b, const fav_flow_opts_ex2& fo, fav_net* vid, fav_net* img, double* seconds_out)
+int run_video_equi(std::map<std::string, std::string>& v, std::map<std::string, bool>& b, const fav_flow_opts_ex3& fo, fav_net* vid, fav_net* img, double* seconds_out)
 {
     auto I = [&](const char* k) { return atoi(v[k].c_str()); };
     const bool timing = I("timing") != 0, gpu_png = v["png_encoder"] == "gpu", inconsistent = b["create_inconsistent"];
@@ -293,7 +293,7 @@ int run_video_equi(std::map<std::string, std::string>& v, std::map<std::string, 
     }
     void* d_flow_ws = nullptr; size_t flow_ws_bytes = 0;
     if (!inconsistent) {
-        flow_ws_bytes = fav_flow_pairs_workspace_bytes_ex2(W, H, 6, &fo);
+        flow_ws_bytes = fav_flow_pairs_workspace_bytes_ex3(W, H, 6, &fo);
         if (!flow_ws_bytes) die(std::string("-input_equi_pattern: ") + fav_last_error());
         hipc(hipMalloc(&d_flow_ws, flow_ws_bytes), "hipMalloc");
     }
@@ -326,7 +326,7 @@ int run_video_equi(std::map<std::string, std::string>& v, std::map<std::string, 
         const bool temporal = n > 0 && !inconsistent;
         const int i0 = n * 6 + 1;                                              // the frame's first face, 1-based and frame-major
         if (temporal) {
-            check(fav_flow_pairs_rgb8_ex2(d_faces[prev], d_faces[cur], 6, W, H, &fo, d_bw, d_fw, d_flow_ws, flow_ws_bytes, st), "fav_flow_pairs_rgb8_ex2");
+            check(fav_flow_pairs_rgb8_ex3(d_faces[prev], d_faces[cur], 6, W, H, &fo, d_bw, d_fw, d_flow_ws, flow_ws_bytes, st), "fav_flow_pairs_rgb8_ex3");
             for (int k = 0; k < 6; ++k) check(fav_vr_prefetch_mask(vr, i0 + k, d_faces[cur][k], d_bw[k], d_fw[k], use_structure, st), "fav_vr_prefetch_mask");
         }
         hipc(hipStreamSynchronize(st), "sync");                                // the copy has left the host buffer
@@ -396,7 +396,7 @@ int run_video_equi(std::map<std::string, std::string>& v, std::map<std::string, 
 int main(int argc, char** argv)
 {
     std::map<std::string, std::string> v = {
-        {"input_pattern", ""}, {"input_equi_pattern", ""}, {"cube_edge_length", "768"}, {"supersample", "2"}, {"flow_alpha", "0"}, {"flow_eps", "0"}, {"flow_grad", "0"}, {"flow_match", "0"}, {"flow_warps", "0"}, {"flow_iters", "0"},
+        {"input_pattern", ""}, {"input_equi_pattern", ""}, {"cube_edge_length", "768"}, {"supersample", "2"}, {"flow_alpha", "0"}, {"flow_eps", "0"}, {"flow_grad", "0"}, {"flow_match", "0"}, {"flow_median", "0"}, {"flow_warps", "0"}, {"flow_iters", "0"},
         {"flow_pattern", ""}, {"occlusions_pattern", ""}, {"forward_flow_pattern", ""}, {"structure", "1"}, {"model_img", ""}, {"model_vid", ""},
         {"start_frame", "1"}, {"continue_with", "1"}, {"num_frames", "9999"}, {"occlusions_min_filter", "7"},
         {"fill_occlusions", "vgg-mean"}, {"overlap_pixel_w", "20"}, {"overlap_pixel_h", "20"}, {"output_prefix", "out"},
@@ -428,14 +428,17 @@ int main(int argc, char** argv)
     // the estimator's options from the -flow_* flags: validated here, used by run_video_equi
     if (v["flow_match"] != "0" && v["flow_match"] != "1") die("-flow_match must be 0 or 1, not '" + v["flow_match"] + "'");
     if (I("flow_match") && !from_equi) die("-flow_match 1 turns on the matching prior of the built-in flow estimator: it needs -input_equi_pattern");
-    const fav_flow_opts_ex2 fo{{{0, I("flow_warps"), I("flow_iters"), (float)atof(v["flow_alpha"].c_str()), 0, (float)atof(v["flow_eps"].c_str())}, I("flow_grad")},
-                               I("flow_match") ? -1.f : 0.f, 0};
+    if (v["flow_median"] != "0" && v["flow_median"] != "3" && v["flow_median"] != "5") die("-flow_median must be 0, 3 or 5, not '" + v["flow_median"] + "'");
+    if (I("flow_median") && !from_equi) die("-flow_median " + v["flow_median"] + " turns on the median filter of the built-in flow estimator: it needs -input_equi_pattern");
+    const fav_flow_opts_ex3 fo{{{{0, I("flow_warps"), I("flow_iters"), (float)atof(v["flow_alpha"].c_str()), 0, (float)atof(v["flow_eps"].c_str())}, I("flow_grad")},
+                                I("flow_match") ? -1.f : 0.f, 0},
+                               I("flow_median")};
     if (from_equi) {
         for (const char* k : {"input_pattern", "flow_pattern", "forward_flow_pattern", "occlusions_pattern"})
             if (!v[k].empty()) die(std::string("-input_equi_pattern makes the faces and their flows from the equirectangular frames: it cannot be combined with -") + k);
         if (I("supersample") < 1 || I("supersample") > 4) die("-supersample must be 1 .. 4, not '" + v["supersample"] + "'");
         if (I("cube_edge_length") < 16 || I("cube_edge_length") > 16384) die("-cube_edge_length must be 16 .. 16384, not '" + v["cube_edge_length"] + "'");
-        if (fav_flow_workspace_bytes_ex2(64, 64, &fo) == 0) die(std::string("-flow_alpha / -flow_eps / -flow_iters / -flow_warps: ") + fav_last_error());
+        if (fav_flow_workspace_bytes_ex3(64, 64, &fo) == 0) die(std::string("-flow_alpha / -flow_eps / -flow_iters / -flow_warps: ") + fav_last_error());
         if (std::max(1, I("gpus")) > 1 || I("force_dist")) die("-input_equi_pattern runs on one GPU: it cannot be combined with -gpus > 1 or -force_dist");
     }
     if (!from_equi && v["input_pattern"].empty()) die("Must give -input_pattern");                                  // :564-566

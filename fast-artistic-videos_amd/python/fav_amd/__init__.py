@@ -69,6 +69,10 @@ def lib() -> C.CDLL:
     L.fav_flow_workspace_bytes_ex2.argtypes = [C.c_int, C.c_int, C.c_void_p]
     L.fav_flow_pairs_workspace_bytes_ex2.restype = C.c_size_t
     L.fav_flow_pairs_workspace_bytes_ex2.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
+    L.fav_flow_workspace_bytes_ex3.restype = C.c_size_t
+    L.fav_flow_workspace_bytes_ex3.argtypes = [C.c_int, C.c_int, C.c_void_p]
+    L.fav_flow_pairs_workspace_bytes_ex3.restype = C.c_size_t
+    L.fav_flow_pairs_workspace_bytes_ex3.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.fav_yuv_frame_bytes.restype = C.c_size_t
     L.fav_yuv_frame_bytes.argtypes = [C.c_int, C.c_int, C.c_void_p]
     _lib = L
@@ -98,6 +102,8 @@ EXPORTS = [
     "fav_stream_next_frame_estimate_ex", "fav_flow_coefficients_grad_f32", "fav_flow_sweeps_grad_f32",
     "fav_flow_workspace_bytes_ex2", "fav_flow_rgb8_ex2", "fav_flow_pairs_workspace_bytes_ex2", "fav_flow_pairs_rgb8_ex2",
     "fav_stream_next_frame_estimate_ex2", "fav_flow_match_f32", "fav_flow_match_check", "fav_flow_coefficients_prior_f32",
+    "fav_flow_workspace_bytes_ex3", "fav_flow_rgb8_ex3", "fav_flow_pairs_workspace_bytes_ex3", "fav_flow_pairs_rgb8_ex3",
+    "fav_stream_next_frame_estimate_ex3", "fav_flow_median_f32",
     "fav_vr_equi_to_faces_rgb8",
     "fav_yuv_frame_bytes", "fav_yuv_to_rgb8", "fav_rgb8_to_yuv", "fav_rgb_f32_to_yuv", "fav_stream_encode_yuv",
     "fav_y4m_parse_header_host", "fav_y4m_format_header_host",
@@ -256,10 +262,20 @@ def _flow_opts_ex2(opts) -> "_FlowOptsEx2":
                         int(opts.get("match_radius", 0)))
 
 
+class _FlowOptsEx3(C.Structure):
+    _fields_ = [("ex2", _FlowOptsEx2), ("median", C.c_int)]
+
+
+def _flow_opts_ex3(opts) -> "_FlowOptsEx3":
+    """fav_flow_opts_ex3 of the flow options: those of _flow_opts_ex2 plus median= (0 = off, 3 or 5: the side of the window of the median
+    filter behind every warp); every Python entry goes through the _ex3 entries of the library"""
+    return _FlowOptsEx3(_flow_opts_ex2({k: v for k, v in opts.items() if k != "median"}), int(opts.get("median", 0)))
+
+
 def flow_workspace_bytes(w: int, h: int, **opts) -> int:
-    """fav_flow_workspace_bytes_ex2 (host only); raises on a bad size or option"""
-    o = _flow_opts_ex2(opts)
-    n = lib().fav_flow_workspace_bytes_ex2(w, h, C.cast(C.pointer(o), C.c_void_p))
+    """fav_flow_workspace_bytes_ex3 (host only); raises on a bad size or option"""
+    o = _flow_opts_ex3(opts)
+    n = lib().fav_flow_workspace_bytes_ex3(w, h, C.cast(C.pointer(o), C.c_void_p))
     if n == 0:
         _check(-1)
     return n
@@ -269,17 +285,18 @@ def flow_rgb8(a, b, **opts):
     """fav_flow_rgb8: the flow w "from a to b", b(p + w(p)) ~ a(p), of two u8 [H][W][3] frames -> .flo payload [H][W][2] (u, v).
     opts: levels, warps, iters, alpha, sweeps_per_launch (0 / absent = default); smooth_eps > 0 turns the edge-preserving smoothness on;
     data_term=1 / gradient_data=True takes the data term on the image gradients (frames whose lighting changes); match_beta != 0 turns
-    the block-matching prior on (negative: the default weight), match_radius is its search radius at half resolution."""
+    the block-matching prior on (negative: the default weight), match_radius is its search radius at half resolution; median=3 | 5
+    replaces the flow by its 3 x 3 | 5 x 5 median after every warp."""
     torch = _torch()
     if not (a.is_cuda and b.is_cuda and a.dtype == torch.uint8 and b.dtype == torch.uint8 and a.is_contiguous() and b.is_contiguous() and
             a.dim() == 3 and a.shape[2] == 3 and a.shape == b.shape):
         raise FavError("flow_rgb8: a and b must be contiguous uint8 CUDA tensors [H][W][3] of one size")
     h, w = a.shape[0], a.shape[1]
-    o = _flow_opts_ex2(opts)
+    o = _flow_opts_ex3(opts)
     nb = flow_workspace_bytes(w, h, **opts)
     ws = torch.empty(nb, dtype=torch.uint8, device=a.device)
     out = torch.empty((h, w, 2), dtype=torch.float32, device=a.device)
-    _check(lib().fav_flow_rgb8_ex2(_p(a), _p(b), w, h, C.byref(o), _p(out), _p(ws), C.c_size_t(nb), _stream()))
+    _check(lib().fav_flow_rgb8_ex3(_p(a), _p(b), w, h, C.byref(o), _p(out), _p(ws), C.c_size_t(nb), _stream()))
     return out
 
 
@@ -287,9 +304,9 @@ FLOW_MAX_PAIRS = 8
 
 
 def flow_pairs_workspace_bytes(w: int, h: int, n_pairs: int, **opts) -> int:
-    """fav_flow_pairs_workspace_bytes_ex2 (host only); raises on a bad size, pair count or option"""
-    o = _flow_opts_ex2(opts)
-    n = lib().fav_flow_pairs_workspace_bytes_ex2(w, h, n_pairs, C.cast(C.pointer(o), C.c_void_p))
+    """fav_flow_pairs_workspace_bytes_ex3 (host only); raises on a bad size, pair count or option"""
+    o = _flow_opts_ex3(opts)
+    n = lib().fav_flow_pairs_workspace_bytes_ex3(w, h, n_pairs, C.cast(C.pointer(o), C.c_void_p))
     if n == 0:
         _check(-1)
     return n
@@ -298,8 +315,8 @@ def flow_pairs_workspace_bytes(w: int, h: int, n_pairs: int, **opts) -> int:
 def flow_pairs(prev_list, cur_list, opts=None):
     """fav_flow_pairs_rgb8: both flows of every (prev[k], cur[k]) in one batched call -> (backward_list, forward_list), .flo payloads
     [H][W][2]: backward[k] is flow_rgb8(cur[k], prev[k]), forward[k] is flow_rgb8(prev[k], cur[k]), bit for bit.
-    opts: a dict of levels, warps, iters, alpha, sweeps_per_launch, smooth_eps, data_term / gradient_data, match_beta, match_radius
-    (0 / absent = default)."""
+    opts: a dict of levels, warps, iters, alpha, sweeps_per_launch, smooth_eps, data_term / gradient_data, match_beta, match_radius,
+    median (0 / absent = default)."""
     torch = _torch()
     opts = dict(opts or {})
     n = len(prev_list)
@@ -308,14 +325,26 @@ def flow_pairs(prev_list, cur_list, opts=None):
                                                t.shape == imgs[0].shape for t in imgs):
         raise FavError("flow_pairs: prev_list and cur_list must be equally long lists of contiguous uint8 CUDA tensors [H][W][3] of one size")
     h, w = imgs[0].shape[0], imgs[0].shape[1]
-    o = _flow_opts_ex2(opts)
+    o = _flow_opts_ex3(opts)
     nb = flow_pairs_workspace_bytes(w, h, n, **opts)
     ws = torch.empty(nb, dtype=torch.uint8, device=imgs[0].device)
     bw = [torch.empty((h, w, 2), dtype=torch.float32, device=imgs[0].device) for _ in range(n)]
     fw = [torch.empty((h, w, 2), dtype=torch.float32, device=imgs[0].device) for _ in range(n)]
     arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() for t in ts])
-    _check(lib().fav_flow_pairs_rgb8_ex2(arr(prev_list), arr(cur_list), n, w, h, C.byref(o), arr(bw), arr(fw), _p(ws), C.c_size_t(nb), _stream()))
+    _check(lib().fav_flow_pairs_rgb8_ex3(arr(prev_list), arr(cur_list), n, w, h, C.byref(o), arr(bw), arr(fw), _p(ws), C.c_size_t(nb), _stream()))
     return bw, fw
+
+
+def flow_median(flow, size: int):
+    """fav_flow_median_f32: u and v of a flow [H][W][2], each replaced by the median of its size x size window (size 3 | 5, indices
+    clamped to the image) -> a new tensor"""
+    torch = _torch(); _chk_f32(flow, "flow")
+    if flow.dim() != 3 or flow.shape[2] != 2:
+        raise FavError("flow_median: flow must be [H][W][2]")
+    h, w, _ = flow.shape
+    out = torch.empty_like(flow)
+    _check(lib().fav_flow_median_f32(_p(flow), _p(out), w, h, int(size), _stream()))
+    return out
 
 
 def flow_grey(rgb_hwc):
@@ -635,12 +664,12 @@ class Stream:
         Returns (f32, u8, backward_flo, forward_flo)."""
         torch = _torch()
         f, u = self._outs(frame_u8_hwc.device, want_f32, want_u8)
-        o = _flow_opts_ex2(flow_opts)
+        o = _flow_opts_ex3(flow_opts)
         nb = flow_pairs_workspace_bytes(self.W, self.H, 1, **flow_opts) if batched else flow_workspace_bytes(self.W, self.H, **flow_opts)
         ws = torch.empty(nb, dtype=torch.uint8, device=frame_u8_hwc.device)
         bw = torch.empty((self.H, self.W, 2), dtype=torch.float32, device=frame_u8_hwc.device)
         fw = torch.empty_like(bw)
-        _check(lib().fav_stream_next_frame_estimate_ex2(self.h, _p(frame_u8_hwc), _p(prev_frame_u8_hwc), C.byref(o), 1 if use_structure else 0,
+        _check(lib().fav_stream_next_frame_estimate_ex3(self.h, _p(frame_u8_hwc), _p(prev_frame_u8_hwc), C.byref(o), 1 if use_structure else 0,
                                                        _p(bw), _p(fw), _p(ws), C.c_size_t(nb), _p(f), _p(u), _stream()))
         return f, u, bw, fw
 

@@ -170,6 +170,27 @@ size_t fav_flow_pairs_workspace_bytes_ex2(int W, int H, int n_pairs, const fav_f
 int fav_flow_pairs_rgb8_ex2(const uint8_t* const* prev_rgb_hwc, const uint8_t* const* cur_rgb_hwc, int n_pairs, int W, int H,
                             const fav_flow_opts_ex2* opts_host, float* const* backward_flo, float* const* forward_flo,
                             void* workspace, size_t workspace_bytes, fav_hipstream_t stream);
+/* The options with the MEDIAN FILTER ("Median filtering"; restated by tests/util/flow_median_model.py): fav_flow_opts_ex2 (which
+ * keeps its 36 bytes) plus median.  median 0 = off: the _ex2 entry's launches and bits.  median 3 or 5 is the side of a window: after the
+ * sweeps of every warp at every level -- the last warp of level 0 included -- u and v are replaced, each on its own, by the median of their
+ * 3 x 3 (the 5th smallest of 9) or 5 x 5 (the 13th smallest of 25) neighbourhood, neighbour indices clamped to the image (Sun, Roth and
+ * Black, "Secrets of optical flow estimation", 2010).  The filtered flow is what the next warp linearises around, what the next finer
+ * level upsamples and, at level 0, what the caller receives.  A median removes the isolated outliers of a warp step, which the linear
+ * smoothness term only spreads, and keeps motion boundaries; it is pure selection, so the stage equals a sort value for value.  What it
+ * gains and costs is measured in DESIGN.md; it is off by default.  It combines with smooth_eps, data_term and match_beta.  Any other
+ * value is FAV_EINVAL (workspace query: 0) with a message that names it.  The filter alternates between the two flow buffers a level
+ * already has: the workspace is the _ex2 entry's, byte for byte.  Every _ex2 entry is its _ex3 twin with median 0. */
+typedef struct fav_flow_opts_ex3 { fav_flow_opts_ex2 ex2; int median; } fav_flow_opts_ex3;
+size_t fav_flow_workspace_bytes_ex3(int W, int H, const fav_flow_opts_ex3* opts_host);
+int fav_flow_rgb8_ex3(const uint8_t* a_rgb_hwc, const uint8_t* b_rgb_hwc, int W, int H, const fav_flow_opts_ex3* opts_host,
+                      float* flow_out, void* workspace, size_t workspace_bytes, fav_hipstream_t stream);
+size_t fav_flow_pairs_workspace_bytes_ex3(int W, int H, int n_pairs, const fav_flow_opts_ex3* opts_host);
+int fav_flow_pairs_rgb8_ex3(const uint8_t* const* prev_rgb_hwc, const uint8_t* const* cur_rgb_hwc, int n_pairs, int W, int H,
+                            const fav_flow_opts_ex3* opts_host, float* const* backward_flo, float* const* forward_flo,
+                            void* workspace, size_t workspace_bytes, fav_hipstream_t stream);
+/* the filter on its own: flow_in -> flow_out, both [H][W][2], 8-byte aligned, size 3 or 5.  Not in place: buffers that overlap, or another
+ * size, are FAV_EINVAL with a message. */
+int fav_flow_median_f32(const float* flow_in, float* flow_out, int W, int H, int size, fav_hipstream_t stream);
 /* the prior's stages on their own.  fav_flow_match_f32: two grey planes [H][W] -> the match fields of both directions, d_ab / d_ba
  * [H][W][2] int16 (dx, dy), 4-byte aligned (radius 1..32).  fav_flow_match_check: the forward-backward test of d_ab against d_ba ->
  * prior, THREE PLANES [3][H][W] fp32 (d_ab.x, d_ab.y, m) with m 0 | 1.  fav_flow_coefficients_prior_f32: one warp's coefficients with
@@ -367,6 +388,11 @@ int fav_stream_next_frame_estimate_ex(fav_stream* s, const uint8_t* frame_rgb_hw
 /* ... and with the matching prior (fav_flow_opts_ex2); workspace sizes from the _ex2 queries */
 int fav_stream_next_frame_estimate_ex2(fav_stream* s, const uint8_t* frame_rgb_hwc, const uint8_t* prev_frame_rgb_hwc,
                                        const fav_flow_opts_ex2* flow_opts_host, int use_structure, float* backward_flo, float* forward_flo,
+                                       void* workspace, size_t workspace_bytes, float* out_rgb_f32, uint8_t* out_rgb8_hwc,
+                                       fav_hipstream_t stream);
+/* ... and with the median filter between warps (fav_flow_opts_ex3); workspace sizes from the _ex3 queries (the _ex2 sizes) */
+int fav_stream_next_frame_estimate_ex3(fav_stream* s, const uint8_t* frame_rgb_hwc, const uint8_t* prev_frame_rgb_hwc,
+                                       const fav_flow_opts_ex3* flow_opts_host, int use_structure, float* backward_flo, float* forward_flo,
                                        void* workspace, size_t workspace_bytes, float* out_rgb_f32, uint8_t* out_rgb8_hwc,
                                        fav_hipstream_t stream);
 /* optional look-ahead: start computing the consistency mask of a FUTURE frame on an internal side stream (the mask
