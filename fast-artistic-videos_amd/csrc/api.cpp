@@ -191,6 +191,21 @@ extern "C" int fav_rgb_f32_to_yuv(const float* rgb_planar, int W, int H, const f
     return launch_rgb_to_yuv(nullptr, rgb_planar, W, H, *fmt_host, yuv, static_cast<hipStream_t>(stream));
 }
 
+// ---- scene changes: the block-histogram distance of two frames (kernels_scene.hip)
+extern "C" size_t fav_scene_change_workspace_bytes(void) { return scene_change_workspace_bytes(); }
+
+extern "C" int fav_scene_change_rgb8(const uint8_t* prev_rgb_hwc, const uint8_t* cur_rgb_hwc, int W, int H, void* workspace, size_t workspace_bytes,
+                                     fav_scene_change* result, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(prev_rgb_hwc && cur_rgb_hwc && workspace && result, "fav_scene_change_rgb8: null pointer");
+    FAV_REQUIRE(W >= 4 && H >= 4 && (long long)W * H <= (1ll << 28), "fav_scene_change_rgb8: bad frame size %dx%d (4 x 4 cells: both sides at least 4, at most 2^28 pixels)", W, H);
+    FAV_REQUIRE(workspace_bytes >= scene_change_workspace_bytes(), "fav_scene_change_rgb8: the workspace holds %zu bytes, fav_scene_change_workspace_bytes() is %zu",
+                workspace_bytes, scene_change_workspace_bytes());
+    FAV_REQUIRE(((uintptr_t)workspace & 15u) == 0 && ((uintptr_t)result & 3u) == 0, "fav_scene_change_rgb8: the workspace must be 16-byte aligned, the result 4-byte aligned");
+    int rc = ensure_device(); if (rc) return rc;
+    return launch_scene_change(prev_rgb_hwc, cur_rgb_hwc, W, H, workspace, result, static_cast<hipStream_t>(stream));
+}
+
 extern "C" int fav_assemble_input_f32(const float* frame_rgb, const float* warped_rgb, const float* cert, float* in7, int H,
                                       int W, fav_hipstream_t stream)
 {

@@ -368,6 +368,10 @@ size_t yuv_frame_bytes(int W, int H, const fav_yuv_format& f);
 int yuv_format_check(const char* who, int W, int H, const fav_yuv_format* f);
 int launch_yuv_to_rgb8(const uint8_t* yuv, int W, int H, const fav_yuv_format& f, uint8_t* rgb_hwc, hipStream_t st);
 int launch_rgb_to_yuv(const uint8_t* rgb_hwc, const float* rgb_planar, int W, int H, const fav_yuv_format& f, uint8_t* yuv, hipStream_t st);
+// the block-histogram distance of two RGB8 frames (kernels_scene.hip; tests/util/scene_model.py): the workspace is zeroed by the call,
+// the 17 integers go to `result` (device or host-mapped memory); W, H >= 4 and W * H <= 2^28 have been checked (api.cpp)
+size_t scene_change_workspace_bytes();
+int launch_scene_change(const uint8_t* prev_rgb_hwc, const uint8_t* cur_rgb_hwc, int W, int H, void* workspace, fav_scene_change* result, hipStream_t st);
 int launch_check_cert(const float* backward_flo, const float* forward_flo, const float* structure, const float* avg, uint8_t* mask_out,
                       int invert, int fix_occ, int border, int r, float* cert, int H, int W, hipStream_t st);
 // ... and the input assembly on top of it (launch_check_cert + launch_prep_input in one launch; round 5)

@@ -43,6 +43,15 @@
 //   else limited; BT.709 from 720 rows on, else BT.601 -- Y4M carries no matrix); -y4m_format <420jpeg|420mpeg2|444>: the output's
 //   sampling when it is not to be the input's (without -input_y4m the default is 420jpeg).
 //   Refused: -backward with -input_y4m, -continue_with other than 1 with either, `-` with more than one -streams entry.
+// -scene_cut <T> (0, default: off; T in (0, 1]; only with -estimate_flow 1): restart the recurrence at scene changes.  Frame i, in
+//   processing order, is a CUT when score(frame i-1, frame i) > T, the score being fav_scene_change_rgb8's block-histogram distance
+//   total / (2 W H) in [0, 1] (include/fav.h).  A cut frame takes the path of a frame without a prior (fav_stream_first_frame: the image
+//   model when -model_img names one, no flow estimated, 0 in -temporal_eval_file); the frame after it continues from its result.  The
+//   measure is enqueued behind the upload of frame i, one frame ahead, into host-mapped memory: the host reads it a frame later and never
+//   waits for a network.  Dissolves and fades are not detected; a flash is a cut.  Refused: without -estimate_flow 1, with
+//   -create_inconsistent, a value outside [0, 1].
+// -scene_cut_log <path> (only with -scene_cut): one line per frame, `index total score cut` (cut = 0 | 1; the first frame is
+//   `index 0 0 0`), written when the frame is decided.
 //
 // Several videos on several GPUs (BASELINE config 4; the reference runs one `th` process per video, stylizeVideo_deepflow.sh:87-96,
 // and its only device hook is utils.setup_gpu, fast_artistic_video/utils.lua:43-66):
@@ -475,6 +484,19 @@ void run_stream(const Opt& o, const fav_flow_opts_ex3& flow_opts, fav_net* net, 
     std::atomic<long long> png_bytes_total{0}, cpu_loaders_us{0}, cpu_writers_us{0}, cpu_writer_sync_us{0};
     const double cpu_main0 = thread_cpu_seconds();
     float *d_prev = nullptr, *d_cur = nullptr; std::vector<double> temporal;      // -temporal_eval_file
+    // -scene_cut: per device input set one host-mapped record that fav_scene_change_rgb8 fills behind the set's upload.  The host
+    // needs `total` only, which the measure's last kernel stores last: it is set to SCENE_PENDING (no total exceeds 2^29) when the
+    // measure is enqueued and polled when the frame's turn comes, a frame later -- like the PNG's size word, without an event.
+    const double scene_T = o.d("scene_cut");
+    const bool scene = scene_T > 0.0;
+    constexpr uint32_t SCENE_PENDING = 0xFFFFFFFFu;
+    fav_scene_change* h_scene = nullptr; void* d_scene_ws = nullptr;
+    FILE* scene_log = nullptr;
+    if (!o.s("scene_cut_log").empty()) {
+        mkdirs_for(o.s("scene_cut_log"));
+        scene_log = fopen(o.s("scene_cut_log").c_str(), "w");
+        if (!scene_log) die("cannot open " + o.s("scene_cut_log"));
+    }
     const int nslots = nwriters + 2;   // pinned output slots in flight to the PNG pool (deflate ~55 ms/frame/thread)
     std::vector<uint8_t*> h_out;       // allocated on demand, at most nslots
     size_t slot_bytes = 0;
@@ -704,6 +726,10 @@ void run_stream(const Opt& o, const fav_flow_opts_ex3& flow_opts, fav_net* net, 
                 check(fav_stream_set_state(fs, d_state, st), "fav_stream_set_state");
                 hipStreamSynchronize(st); hipFree(d_state);
             }
+            if (scene) {
+                if (hipHostMalloc((void**)&h_scene, NDEV * sizeof(fav_scene_change), hipHostMallocDefault) != hipSuccess ||
+                    hipMalloc(&d_scene_ws, fav_scene_change_workspace_bytes()) != hipSuccess) die("hipMalloc failed");
+            }
             if (estimate) {
                 flow_ws_bytes = fav_flow_pairs_workspace_bytes_ex3(W, H, 1, &flow_opts);      // room for both flows at once: the batch of one
                 if (!flow_ws_bytes) die(std::string("-estimate_flow: ") + fav_last_error());
@@ -738,6 +764,11 @@ void run_stream(const Opt& o, const fav_flow_opts_ex3& flow_opts, fav_net* net, 
             const int nset = (dset + 1 + (int)ahead.size()) % NDEV;
             const Dev& dn = dev[nset];
             upload(nxt, nset);
+            if (scene) {         // behind the upload, on its queue: the frame before `nxt` in processing order is in the set before it
+                h_scene[nset].total = SCENE_PENDING;
+                check(fav_scene_change_rgb8(dev[(nset + NDEV - 1) % NDEV].frame, dn.frame, W, H, d_scene_ws, fav_scene_change_workspace_bytes(),
+                                            &h_scene[nset], st_copy), "fav_scene_change_rgb8");
+            }
             if (fused_check && !estimate && !nxt.single && (!quiet || o.i("structure") != 0)) {
                 // quiet: the look-ahead may only start on inputs the host has seen arrive (0.35 ms of DMA; the GPU is busy with frame i-1)
                 if (quiet && wait_event_sleeping(ev_up[nset], 50) != hipSuccess) die("GPU error while uploading a frame");
@@ -749,6 +780,24 @@ void run_stream(const Opt& o, const fav_flow_opts_ex3& flow_opts, fav_net* net, 
         tr_mark(0);      // (the look-ahead is topped up BEHIND the frame's enqueue, also for the first frame: its enqueue is 15 ms of one-time
                          //  work -- activation arena, code objects -- that now runs while the loaders read and pin frames 2, 3, ...)
         if (quiet && wait_event_sleeping(ev_up[dset], 50) != hipSuccess) die("GPU error while uploading a frame");      // requested a frame ago: already there
+        if (scene) {             // is frame i a cut?  Its measure was enqueued a frame ago, behind its upload
+            uint32_t total = 0; double score = 0.0; bool cut = false;
+            if (done > 0) {          // (the first frame has nothing in front of it)
+                volatile uint32_t* tw = &h_scene[dset].total;
+                for (int spins = 0; *tw == SCENE_PENDING; ++spins) {
+                    usleep(50);
+                    if ((spins & 2047) == 2047) {             // every ~0.1 s: has the GPU faulted? (a query, not a marker)
+                        const hipError_t e = hipStreamQuery(st_copy);
+                        if (e != hipSuccess && e != hipErrorNotReady) die("GPU error while measuring a scene change");
+                    }
+                }
+                total = *tw;
+                score = (double)total / (2.0 * (double)W * (double)H);
+                cut = score > scene_T;
+            }
+            if (cut) cur.single = true;          // the path of a frame without a prior: image model, no flow, the recurrence starts afresh
+            if (scene_log) fprintf(scene_log, "%d %u %.6f %d\n", i, total, score, cut ? 1 : 0);
+        }
         uint8_t* const d_out8 = (gpu_png || y4m_out) ? nullptr : d_out8s[done & 1];
         const bool teval = !o.s("temporal_eval_file").empty();
         if (teval && !d_prev) { if (hipMalloc((void**)&d_prev, (size_t)W * H * 12) || hipMalloc((void**)&d_cur, (size_t)W * H * 12)) die("hipMalloc failed"); }
@@ -849,6 +898,9 @@ void run_stream(const Opt& o, const fav_flow_opts_ex3& flow_opts, fav_net* net, 
     for (auto& kv : slot_ev) hipEventDestroy(kv.second);
     fav_stream_destroy(fs);
     hipFree(d_prev); hipFree(d_cur); hipFree(d_flow_ws);
+    if (scene_log) fclose(scene_log);
+    if (h_scene) hipHostFree(h_scene);
+    hipFree(d_scene_ws);
     hipFree(d_out8s[0]); hipFree(d_out8s[1]); for (auto& dv : dev) { hipFree(dv.frame); hipFree(dv.cert); hipFree(dv.bw); hipFree(dv.fw); hipFree(dv.yuv); }
     for (auto p : h_out) hipHostFree(p);
     for (auto& p : pin) { hipHostFree(p.frame); hipHostFree(p.bw); hipHostFree(p.fw); hipHostFree(p.cert); hipHostFree(p.yuv); }
@@ -876,6 +928,7 @@ int main(int argc, char** argv)
            {"forward_flow_pattern", ""}, {"structure", "1"}, {"warp_border", "stn"}, {"poll_timeout", "3600"}, {"poll_settle", "1.0"},
            {"png_level", "1"}, {"png_encoder", "gpu"}, {"png_overlap", "0"}, {"writers", "0"}, {"timing", "0"}, {"temporal_eval_file", ""}, {"seed", "1"}, {"precision", "fp32"},
            {"input_y4m", ""}, {"output_y4m", ""}, {"y4m_matrix", "auto"}, {"y4m_range", "auto"}, {"y4m_format", ""},
+           {"scene_cut", "0"}, {"scene_cut_log", ""},
            {"estimate_flow", "0"}, {"flow_alpha", "0"}, {"flow_eps", "0"}, {"flow_grad", "0"}, {"flow_match", "0"}, {"flow_median", "0"}, {"flow_iters", "0"}, {"flow_warps", "0"}, {"flow_levels", "0"},
            {"streams", ""}, {"gpus", "1"}, {"force_dist", "0"}, {"dry_run", "0"}, {"shared_gpu", "0"}, {"pin_workers", "1"},
            // internal (set by the launcher for its workers)
@@ -909,6 +962,16 @@ int main(int argc, char** argv)
     if (!y4m_in && o.s("input_pattern").empty()) die("Must give -input_pattern");                           // fav.lua:177-179
     if (o.s("estimate_flow") != "0" && o.s("estimate_flow") != "1") die("-estimate_flow must be 0 or 1, not '" + o.s("estimate_flow") + "'");
     const bool estimate = o.i("estimate_flow") != 0;
+    {   // -scene_cut: the recurrence restarts where the picture changes by more than T (0: off)
+        const std::string sc = o.s("scene_cut");
+        char* end = nullptr;
+        const double T = strtod(sc.c_str(), &end);
+        if (sc.empty() || end == sc.c_str() || *end != '\0' || !std::isfinite(T) || T < 0.0 || T > 1.0) die("-scene_cut must be a number in [0, 1] (0: off), not '" + sc + "'");
+        if (T > 0.0 && !estimate)
+            die("-scene_cut " + sc + " needs -estimate_flow 1: with flows from files the look-ahead has already started a frame's mask when the cut is known");
+        if (T > 0.0 && o.f("create_inconsistent")) die("-scene_cut " + sc + " cannot be combined with -create_inconsistent: no frame has a prior there");
+        if (!o.s("scene_cut_log").empty() && T == 0.0) die("-scene_cut_log needs -scene_cut: without it no frame is measured");
+    }
     if (o.s("flow_grad") != "0" && o.s("flow_grad") != "1") die("-flow_grad must be 0 or 1, not '" + o.s("flow_grad") + "'");
     if (o.i("flow_grad") && !estimate) die("-flow_grad 1 selects the data term of the built-in flow estimator: it needs -estimate_flow 1");
     if (o.s("flow_match") != "0" && o.s("flow_match") != "1") die("-flow_match must be 0 or 1, not '" + o.s("flow_match") + "'");
@@ -960,6 +1023,8 @@ int main(int argc, char** argv)
                                             "input_y4m", "output_y4m"};
     if (named && streams.size() > 1 && o.s(y4m_out ? "output_y4m" : "output_prefix").find("%S") == std::string::npos)
         die(std::string("-streams: -") + (y4m_out ? "output_y4m" : "output_prefix") + " must contain %S (the streams would overwrite each other's frames)");
+    if (named && streams.size() > 1 && !o.s("scene_cut_log").empty() && o.s("scene_cut_log").find("%S") == std::string::npos)
+        die("-streams: -scene_cut_log must contain %S (the streams would overwrite each other's log)");
 
     // ------------------------------------------------------------------------------------------ launcher
     if (rank < 0 && (world > 1 || o.i("force_dist"))) {
@@ -1023,6 +1088,7 @@ int main(int argc, char** argv)
     for (const std::string& name : mine) {
         Opt os = o;
         if (named) for (const char* po : path_opts) os.v[po] = favl::subst_stream(o.s(po), name);
+        if (named) os.v["scene_cut_log"] = favl::subst_stream(o.s("scene_cut_log"), name);
         StreamResult r;
         run_stream(os, flow_opts, net, net_img, nwriters, &r);
         frames += r.frames; seconds += r.seconds; cpu_seconds += r.cpu_s;

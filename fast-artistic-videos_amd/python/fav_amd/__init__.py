@@ -75,6 +75,8 @@ def lib() -> C.CDLL:
     L.fav_flow_pairs_workspace_bytes_ex3.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.fav_yuv_frame_bytes.restype = C.c_size_t
     L.fav_yuv_frame_bytes.argtypes = [C.c_int, C.c_int, C.c_void_p]
+    L.fav_scene_change_workspace_bytes.restype = C.c_size_t
+    L.fav_scene_change_workspace_bytes.argtypes = []
     _lib = L
     return L
 
@@ -107,6 +109,7 @@ EXPORTS = [
     "fav_vr_equi_to_faces_rgb8",
     "fav_yuv_frame_bytes", "fav_yuv_to_rgb8", "fav_rgb8_to_yuv", "fav_rgb_f32_to_yuv", "fav_stream_encode_yuv",
     "fav_y4m_parse_header_host", "fav_y4m_format_header_host",
+    "fav_scene_change_workspace_bytes", "fav_scene_change_rgb8",
 ]
 
 
@@ -443,6 +446,34 @@ def flow_match_check(d_ab, d_ba, want_prior: bool = False):
     prior = torch.empty((3, h, w), dtype=torch.float32, device=d_ab.device)
     _check(lib().fav_flow_match_check(_p(d_ab), _p(d_ba), w, h, _p(prior), _stream()))
     return prior if want_prior else prior[2]
+
+
+def scene_change_workspace_bytes() -> int:
+    return lib().fav_scene_change_workspace_bytes()
+
+
+def scene_change(prev, cur, workspace=None, result=None, workspace_bytes: Optional[int] = None, w: Optional[int] = None, h: Optional[int] = None):
+    """fav_scene_change_rgb8: the block-histogram distance of two u8 [H][W][3] frames -> (total, cells), `cells` the 16 per-cell sums
+    (index cy*4+cx) as a list; the score is total / (2 W H).  workspace: a CUDA tensor of at least scene_change_workspace_bytes() bytes to
+    use (workspace_bytes: the size to declare instead of its own); result: an int32 tensor of 17 elements to write into -- CUDA, or
+    pinned host memory, which the device writes through its mapping; w, h: the size to declare instead of the tensors' own."""
+    torch = _torch()
+    for t in (prev, cur):
+        if not (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 3 and t.shape[2] == 3 and t.shape == prev.shape):
+            raise FavError("scene_change: prev and cur must be contiguous uint8 CUDA tensors [H][W][3] of one size")
+    if workspace is None:
+        workspace = torch.empty((scene_change_workspace_bytes(),), dtype=torch.uint8, device=prev.device)
+    if result is None:
+        result = torch.empty((17,), dtype=torch.int32, device=prev.device)
+    if not (result.dtype == torch.int32 and result.numel() >= 17 and result.is_contiguous() and (result.is_cuda or result.is_pinned())):
+        raise FavError("scene_change: result must be a contiguous int32 tensor of 17 elements, CUDA or pinned")
+    nbytes = workspace.numel() * workspace.element_size() if workspace_bytes is None else workspace_bytes
+    _check(lib().fav_scene_change_rgb8(_p(prev), _p(cur), prev.shape[1] if w is None else w, prev.shape[0] if h is None else h,
+                                       _p(workspace), C.c_size_t(nbytes), _p(result), _stream()))
+    if not result.is_cuda:
+        torch.cuda.current_stream().synchronize()
+    r = result.cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+    return int(r[0]), [int(v) for v in r[1:17]]
 
 
 def flow_coefficients_prior(a_grey, b_grey, flow0, prior, alpha: float, beta: float = 225.0, tau: float = 1.0, smooth_eps: float = 0.0, data_term: int = 0):

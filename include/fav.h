@@ -607,6 +607,24 @@ typedef struct fav_y4m_header { int W, H; int fps_num, fps_den; int aspect_num, 
 int fav_y4m_parse_header_host(const char* line, size_t len, fav_y4m_header* out);
 int fav_y4m_format_header_host(const fav_y4m_header* h, char* buf_host, size_t capacity);
 
+/* ---- scene changes: how much the picture changed between two frames -----------------------------------------------------------------
+ * Not in the reference, which expects a video cut into scenes by hand; a stream on a pipe cannot be (fav_stylize -scene_cut).
+ * A block-histogram distance in integer arithmetic, restated by tests/util/scene_model.py and matched for EQUALITY:
+ *   luma Y = (77 R + 150 G + 29 B + 128) >> 8, bin = Y >> 3 (32 bins); 4 x 4 cells, cell (cx, cy) = x in [cx W/4, (cx+1) W/4),
+ *   y in [cy H/4, (cy+1) H/4) with floor division; cell[cy*4+cx] = sum over bins |hist_prev - hist_cur|; total = sum over cells.
+ * The score is total / (2 W H) in [0, 1]; the caller forms it (in double), the device result is the 17 integers.
+ *   prev / cur     u8 [H][W][3] in device memory, no alignment or padding: nothing outside their W*H*3 bytes is read; prev == cur is
+ *                  allowed (all zeros).  W, H >= 4 and W * H <= 2^28, anything else is FAV_EINVAL.
+ *   workspace      fav_scene_change_workspace_bytes() bytes of device memory, 16-byte aligned, private to the call until the stream has
+ *                  passed it; zeroed by the call itself.  Fewer bytes: FAV_EINVAL and nothing is enqueued.
+ *   result         any device-accessible address, 4-byte aligned: device memory or host-mapped memory (complete when the stream reaches
+ *                  the point after the call).
+ * Asynchronous on `stream`; nothing is allocated. */
+typedef struct fav_scene_change { uint32_t total; uint32_t cell[16]; } fav_scene_change;   /* cell[cy*4+cx] */
+size_t fav_scene_change_workspace_bytes(void);
+int fav_scene_change_rgb8(const uint8_t* prev_rgb_hwc, const uint8_t* cur_rgb_hwc, int W, int H,
+                          void* workspace, size_t workspace_bytes, fav_scene_change* result, fav_hipstream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
