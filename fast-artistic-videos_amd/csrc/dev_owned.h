@@ -1,25 +1,11 @@
-// dev_owned.h -- owning handles for what the host side of libfav keeps on the device: std::unique_ptr with one deleter per kind of
-// resource, and the helpers that fill a handle.  An object whose members are handles needs no destructor that lists them, a function
-// that fails half-way just returns, and std::swap / std::move work as on any unique_ptr.
+// dev_owned.h -- what fills the owning handles of dev_handles.h on the host side of libfav.  A function that fails half-way just
+// returns: the handles it filled free what they hold.
 // Every helper returns FAV_OK or FAV_EHIP (hip_fail: the error text names the call, or `what`), so several chain with ||.
 #pragma once
-#include <memory>
-#include <type_traits>
-
+#include "dev_handles.h"
 #include "fav_internal.h"
 
 namespace fav {
-
-struct DevFree { void operator()(void* p) const { (void)hipFree(p); } };
-struct HostFree { void operator()(void* p) const { (void)hipHostFree(p); } };
-struct EventDestroy { using pointer = hipEvent_t; void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
-// a queue is drained before it goes: what it still holds may read buffers that are freed next
-struct QueueDestroy { using pointer = hipStream_t; void operator()(hipStream_t q) const { (void)hipStreamSynchronize(q); (void)hipStreamDestroy(q); } };
-
-template <class T> using dev_ptr = std::unique_ptr<T, DevFree>;        // hipMalloc
-template <class T> using host_ptr = std::unique_ptr<T, HostFree>;      // hipHostMalloc
-using event_h = std::unique_ptr<std::remove_pointer_t<hipEvent_t>, EventDestroy>;
-using queue_h = std::unique_ptr<std::remove_pointer_t<hipStream_t>, QueueDestroy>;
 
 // n elements of T (dev_ptr<void>: n bytes), uninitialised
 template <class T> int dev_alloc(dev_ptr<T>& out, size_t n, const char* what = "hipMalloc")

@@ -50,6 +50,7 @@
 #include <vector>
 
 #include "../../include/fav.h"
+#include "../csrc/dev_handles.h"
 
 static int fail(const char* what)
 {
@@ -62,14 +63,14 @@ namespace {
 // more than the mask itself: 29 ms per pair against 6)
 struct Batch {
     int W = 0, H = 0;
-    float *d1 = nullptr, *d2 = nullptr; uint8_t *dimg = nullptr, *dout = nullptr; void* ws = nullptr; size_t wsb = 0;
-    float *h1 = nullptr, *h2 = nullptr; uint8_t *himg = nullptr, *hout = nullptr;
-    void release()
-    {
-        hipFree(d1); hipFree(d2); hipFree(dimg); hipFree(dout); hipFree(ws); d1 = d2 = nullptr; dimg = dout = nullptr; ws = nullptr;
-        hipHostFree(h1); hipHostFree(h2); hipHostFree(himg); hipHostFree(hout); h1 = h2 = nullptr; himg = hout = nullptr;
-        W = H = 0;
-    }
+    struct Buffers {
+        fav::dev_ptr<float> d1, d2; fav::dev_ptr<uint8_t> dimg, dout; fav::dev_ptr<void> ws;
+        fav::host_ptr<float> h1, h2; fav::host_ptr<uint8_t> himg, hout;
+    } buf;
+    size_t wsb = 0;
+    void release() { buf = Buffers(); W = H = 0; }
+    template <class H> static bool dev(H& h, size_t bytes) { void* p = nullptr; const bool ok = hipMalloc(&p, bytes) == hipSuccess; h.reset(static_cast<typename H::pointer>(p)); return ok; }
+    template <class H> static bool pinned(H& h, size_t bytes) { void* p = nullptr; const bool ok = hipHostMalloc(&p, bytes, hipHostMallocDefault) == hipSuccess; h.reset(static_cast<typename H::pointer>(p)); return ok; }
     static bool flo_size(const char* path, int* w, int* h)      // the 12-byte header (consistencyChecker.cpp:16-36: tag, width, height)
     {
         FILE* f = fopen(path, "rb");
@@ -94,11 +95,12 @@ struct Batch {
             release();
             W = w1; H = h1s;
             wsb = fav_consistency_workspace_bytes(W, H, 1);
-            if (hipMalloc((void**)&d1, n * 8) || hipMalloc((void**)&d2, n * 8) || hipMalloc((void**)&dout, n) || hipMalloc((void**)&dimg, n * 3) ||
-                (wsb && hipMalloc(&ws, wsb)) || hipHostMalloc((void**)&h1, n * 8, hipHostMallocDefault) || hipHostMalloc((void**)&h2, n * 8, hipHostMallocDefault) ||
-                hipHostMalloc((void**)&himg, n * 3, hipHostMallocDefault) || hipHostMalloc((void**)&hout, n, hipHostMallocDefault)) {
+            if (!dev(buf.d1, n * 8) || !dev(buf.d2, n * 8) || !dev(buf.dout, n) || !dev(buf.dimg, n * 3) || (wsb && !dev(buf.ws, wsb)) ||
+                !pinned(buf.h1, n * 8) || !pinned(buf.h2, n * 8) || !pinned(buf.himg, n * 3) || !pinned(buf.hout, n)) {
                 err = "consistencyChecker: out of memory\n"; release(); return 1; }
         }
+        float *const d1 = buf.d1.get(), *const d2 = buf.d2.get(), *const h1 = buf.h1.get(), *const h2 = buf.h2.get();
+        uint8_t *const dimg = buf.dimg.get(), *const dout = buf.dout.get(), *const himg = buf.himg.get(), *const hout = buf.hout.get(); void* const ws = buf.ws.get();
         int w, h, ch;
         if (fav_read_flo_into_host(a[0].c_str(), h1, n * 2, &w, &h)) return failf(a[0].c_str());
         if (fav_read_flo_into_host(a[1].c_str(), h2, n * 2, &w, &h)) return failf(a[1].c_str());
@@ -140,7 +142,6 @@ int batch_main(const char* list)
         printf("%s\n", a[2].c_str()); fflush(stdout);
     }
     if (f != stdin) fclose(f);
-    b.release();
     return rc;
 }
 
@@ -412,10 +413,11 @@ int main(int argc, char** argv)
     const char* g = getenv("FAV_GPU");
     if (hipSetDevice(g ? atoi(g) : 0) != hipSuccess) { fprintf(stderr, "consistencyChecker: cannot select GPU\n"); return 1; }
     const size_t n = (size_t)w1 * h1;
-    float *d1 = nullptr, *d2 = nullptr; uint8_t *dimg = nullptr, *dout = nullptr; void* ws = nullptr;
+    Batch::Buffers buf;
     const size_t wsb = fav_consistency_workspace_bytes(w1, h1, img != nullptr);
-    if (hipMalloc((void**)&d1, n * 8) || hipMalloc((void**)&d2, n * 8) || hipMalloc((void**)&dout, n) ||
-        (img && hipMalloc((void**)&dimg, n * 3)) || (wsb && hipMalloc(&ws, wsb))) { fprintf(stderr, "consistencyChecker: hipMalloc failed\n"); return 1; }
+    if (!Batch::dev(buf.d1, n * 8) || !Batch::dev(buf.d2, n * 8) || !Batch::dev(buf.dout, n) ||
+        (img && !Batch::dev(buf.dimg, n * 3)) || (wsb && !Batch::dev(buf.ws, wsb))) { fprintf(stderr, "consistencyChecker: hipMalloc failed\n"); return 1; }
+    float *const d1 = buf.d1.get(), *const d2 = buf.d2.get(); uint8_t *const dimg = buf.dimg.get(), *const dout = buf.dout.get(); void* const ws = buf.ws.get();
     lap("context + device buffers");
     hipMemcpy(d1, f1, n * 8, hipMemcpyHostToDevice);
     hipMemcpy(d2, f2, n * 8, hipMemcpyHostToDevice);
@@ -431,6 +433,5 @@ int main(int argc, char** argv)
     lap("write the .pgm");
     printf("%s", argv[3]);   // :166
     fav_free_host(f1); fav_free_host(f2); fav_free_host(img);
-    hipFree(d1); hipFree(d2); hipFree(dimg); hipFree(dout); hipFree(ws);
     return 0;
 }

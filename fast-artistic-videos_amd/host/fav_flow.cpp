@@ -26,10 +26,11 @@
 #include <vector>
 
 #include "../../include/fav.h"
+#include "fav_cli.h"
 
 namespace {
 
-[[noreturn]] void die(const std::string& msg) { fprintf(stderr, "%s\n", msg.c_str()); exit(1); }
+using favl::die; using favl::parse_int;
 
 [[noreturn]] void usage(const std::string& why)
 {
@@ -49,15 +50,6 @@ bool write_flo(const std::string& path, const float* uv, int W, int H)
     const size_t n = (size_t)W * H * 2;
     const bool ok = fwrite(&tag, 4, 1, f) == 1 && fwrite(&W, 4, 1, f) == 1 && fwrite(&H, 4, 1, f) == 1 && fwrite(uv, 4, n, f) == n;
     if (fclose(f) != 0 || !ok || rename(tmp.c_str(), path.c_str()) != 0) { unlink(tmp.c_str()); return false; }
-    return true;
-}
-
-bool parse_int(const char* s, int* out)
-{
-    char* end = nullptr;
-    const long v = strtol(s, &end, 10);
-    if (end == s || *end != '\0' || v < -1000000 || v > 1000000) return false;
-    *out = (int)v;
     return true;
 }
 
@@ -115,7 +107,7 @@ int main(int argc, char** argv)
 
     if (fav_device_count() <= 0) die(std::string("ERROR: ") + fav_last_error());
     if (hipSetDevice(gpu) != hipSuccess) die("cannot select GPU " + std::to_string(gpu));
-    uint8_t *d_a = nullptr, *d_b = nullptr; float* d_flow = nullptr; void* d_ws = nullptr;
+    fav::dev_ptr<uint8_t> d_a, d_b; fav::dev_ptr<float> d_flow; fav::dev_ptr<void> d_ws;
     int cw = 0, ch = 0; size_t ws_bytes = 0;
     std::vector<float> h_flow;
     for (const Job& j : jobs) {
@@ -128,16 +120,15 @@ int main(int argc, char** argv)
         if (W != cw || H != ch) {
             ws_bytes = fav_flow_workspace_bytes_ex3(W, H, &fx3);
             if (!ws_bytes) die(fav_last_error());
-            hipFree(d_a); hipFree(d_b); hipFree(d_flow); hipFree(d_ws);
-            if (hipMalloc((void**)&d_a, n * 3) || hipMalloc((void**)&d_b, n * 3) || hipMalloc((void**)&d_flow, n * 8) || hipMalloc(&d_ws, ws_bytes)) die("hipMalloc failed");
+            d_a.reset(); d_b.reset(); d_flow.reset(); d_ws.reset();      // the old size goes before the new one comes
+            d_a = favl::dev_alloc<uint8_t>(n * 3); d_b = favl::dev_alloc<uint8_t>(n * 3); d_flow = favl::dev_alloc<float>(n * 8); d_ws = favl::dev_alloc<void>(ws_bytes);
             h_flow.resize(n * 2); cw = W; ch = H;
         }
-        if (hipMemcpy(d_a, a, n * 3, hipMemcpyHostToDevice) || hipMemcpy(d_b, b, n * 3, hipMemcpyHostToDevice)) die("upload failed");
+        if (hipMemcpy(d_a.get(), a, n * 3, hipMemcpyHostToDevice) || hipMemcpy(d_b.get(), b, n * 3, hipMemcpyHostToDevice)) die("upload failed");
         fav_free_host(a); fav_free_host(b);
-        if (fav_flow_rgb8_ex3(d_a, d_b, W, H, &fx3, d_flow, d_ws, ws_bytes, nullptr)) die(fav_last_error());
-        if (hipMemcpy(h_flow.data(), d_flow, n * 8, hipMemcpyDeviceToHost) != hipSuccess) die("GPU error while estimating " + j.out);
+        if (fav_flow_rgb8_ex3(d_a.get(), d_b.get(), W, H, &fx3, d_flow.get(), d_ws.get(), ws_bytes, nullptr)) die(fav_last_error());
+        if (hipMemcpy(h_flow.data(), d_flow.get(), n * 8, hipMemcpyDeviceToHost) != hipSuccess) die("GPU error while estimating " + j.out);
         if (!write_flo(j.out, h_flow.data(), W, H)) die("cannot write " + j.out);
     }
-    hipFree(d_a); hipFree(d_b); hipFree(d_flow); hipFree(d_ws);
     return 0;
 }

@@ -33,12 +33,9 @@
 #include <vector>
 
 #include "../../include/fav.h"
+#include "fav_cli.h"
 
 namespace favl {
-
-[[noreturn]] inline void die(const std::string& m) { fprintf(stderr, "%s\n", m.c_str()); exit(1); }
-// where the messages go: stdout, unless the caller's stdout carries data (fav_stylize -output_y4m -)
-inline FILE*& msg() { static FILE* f = stdout; return f; }
 
 inline std::string subst_stream(std::string v, const std::string& name)
 {
@@ -143,18 +140,17 @@ inline void nccl_wait(ncclComm_t comm, ncclResult_t first, const char* what, int
 // checkpoint (6.7 MB, latency-bound) preceded by its 8-byte size.
 inline void broadcast_blob(ncclComm_t comm, int rank, std::vector<uint8_t>& blob, hipStream_t st)
 {
-    unsigned long long n = rank == 0 ? blob.size() : 0, *d_n = nullptr;
-    if (hipMalloc((void**)&d_n, 8) != hipSuccess) die("hipMalloc failed");
-    hipMemcpy(d_n, &n, 8, hipMemcpyHostToDevice);
-    nccl_wait(comm, ncclBroadcast(d_n, d_n, 8, ncclUint8, 0, comm, st), "ncclBroadcast(size)", rank, st, true);
-    hipMemcpy(&n, d_n, 8, hipMemcpyDeviceToHost); hipFree(d_n);
+    unsigned long long n = rank == 0 ? blob.size() : 0;
+    const auto d_n = dev_alloc<unsigned long long>(8);
+    hipMemcpy(d_n.get(), &n, 8, hipMemcpyHostToDevice);
+    nccl_wait(comm, ncclBroadcast(d_n.get(), d_n.get(), 8, ncclUint8, 0, comm, st), "ncclBroadcast(size)", rank, st, true);
+    hipMemcpy(&n, d_n.get(), 8, hipMemcpyDeviceToHost);
     if (n == 0) { blob.clear(); return; }
-    uint8_t* d_b = nullptr;
-    if (hipMalloc((void**)&d_b, n) != hipSuccess) die("hipMalloc failed");
-    if (rank == 0) hipMemcpy(d_b, blob.data(), n, hipMemcpyHostToDevice);
-    nccl_wait(comm, ncclBroadcast(d_b, d_b, n, ncclUint8, 0, comm, st), "ncclBroadcast(blob)", rank, st, true);
+    const auto d_b = dev_alloc<uint8_t>(n);
+    if (rank == 0) hipMemcpy(d_b.get(), blob.data(), n, hipMemcpyHostToDevice);
+    nccl_wait(comm, ncclBroadcast(d_b.get(), d_b.get(), n, ncclUint8, 0, comm, st), "ncclBroadcast(blob)", rank, st, true);
     blob.resize(n);
-    hipMemcpy(blob.data(), d_b, n, hipMemcpyDeviceToHost); hipFree(d_b);
+    hipMemcpy(blob.data(), d_b.get(), n, hipMemcpyDeviceToHost);
 }
 
 inline std::vector<uint8_t> pack_model(const std::string& path)
@@ -360,7 +356,7 @@ inline void load_models_dist(int rank, int world, const std::string& idf, int de
     const ncclResult_t ir = ncclCommInitRankConfig(&comm, world, id, rank, &cfg);      // (sets `comm` before it returns, also when in progress)
     nccl_wait(comm, ir, "ncclCommInitRank", rank);
     const double ims = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ti).count();
-    hipStream_t bst; if (hipStreamCreate(&bst) != hipSuccess) die("hipStreamCreate failed");
+    fav::queue_h bst_h = queue_create(); const hipStream_t bst = bst_h.get();
     const auto tb = std::chrono::steady_clock::now();
     broadcast_blob(comm, rank, blob, bst);
     broadcast_blob(comm, rank, blob_img, bst);
@@ -370,7 +366,7 @@ inline void load_models_dist(int rank, int world, const std::string& idf, int de
     fprintf(msg(), "[rank %d/%d gpu %d] weights: %zu B%s via ncclBroadcast from rank 0 in %.2f ms (communicator up in %.0f ms); %zu stream(s), %d PNG writers\n", rank, world, device,
            blob.size(), blob_img.empty() ? "" : " (+ image model)", bms, ims, nstreams, nwriters);
     if (times) { times->bcast_ms = bms; times->init_ms = ims; }
-    hipStreamDestroy(bst);
+    bst_h.reset();                                              // the queue goes before the communicator that used it
     ncclCommDestroy(comm);
 }
 

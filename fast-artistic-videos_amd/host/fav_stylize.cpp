@@ -91,6 +91,7 @@
 #include <vector>
 
 #include "../../include/fav.h"
+#include "fav_cli.h"
 #include "fav_launcher.h"
 #include "fav_poll.h"
 #include "fav_y4m.h"
@@ -106,7 +107,7 @@ struct Opt {
     bool f(const char* k) const { return b.at(k); }
 };
 
-using favl::die;
+using favl::die; using favl::check; using favl::file_exists; using favl::mkdirs_for; using favl::fmt_int; using favl::flow_name;
 
 // diagnostic switches exist in -DFAV_DIAG builds of this executable only (csrc/fav_internal.h says why)
 const char* diag_env(const char* name)
@@ -119,61 +120,9 @@ const char* diag_env(const char* name)
 #endif
 }
 
-void check(int rc, const char* what)
-{
-    if (rc) die(std::string(what) + ": " + fav_last_error());
-}
-
-bool file_exists(const std::string& p) { struct stat st; return stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode); }
-
-std::string fmt_int(const std::string& pattern, int i)
-{
-    char buf[4096];
-    snprintf(buf, sizeof buf, pattern.c_str(), i);
-    return buf;
-}
-
-// getFormatedFlowFileName (fast_artistic_video.lua:70-77): {fmt} <- fromIndex, [fmt] <- toIndex
-std::string flow_name(const std::string& pattern, int from, int to)
-{
-    std::string out;
-    for (size_t p = 0; p < pattern.size();) {
-        const char c = pattern[p];
-        if (c == '{' || c == '[') {
-            const char close = c == '{' ? '}' : ']';
-            const size_t e = pattern.find(close, p + 1);
-            if (e != std::string::npos) {
-                out += fmt_int(pattern.substr(p + 1, e - p - 1), c == '{' ? from : to);
-                p = e + 1;
-                continue;
-            }
-        }
-        out += c; ++p;
-    }
-    return out;
-}
-
-// utils.wait_for_file (fast_artistic_video/utils.lua:74-80), bounded, with the settle rule of fav_poll.h
-void wait_for_file(const std::string& path, const favp::Poll& p)
-{
-    if (favp::wait_for_file(path, p) != favp::WAIT_OK) die("timed out waiting for " + path);
-}
-
-// wait, read, and poll again while the file reads short under a producer that is still writing it (fav_poll.h)
+// a polled read whose failure names the file
 template <class Reader>
-void read_polled(const std::string& path, const favp::Poll& p, Reader&& reader)
-{
-    bool timed_out = false;
-    const int rc = favp::read_when_complete(path, p, reader, &timed_out);
-    if (timed_out) die("timed out waiting for " + path);
-    check(rc, path.c_str());
-}
-
-void mkdirs_for(const std::string& path)
-{
-    for (size_t p = 1; p < path.size(); ++p)
-        if (path[p] == '/') mkdir(path.substr(0, p).c_str(), 0777);
-}
+void read_polled(const std::string& path, const favp::Poll& p, Reader&& reader) { favl::read_polled(path, p, path.c_str(), reader); }
 
 // minimal PNG reader for -continue_with (8-bit RGB / RGBA / grey, non-interlaced)
 bool read_png_rgb8(const std::string& path, std::vector<uint8_t>& rgb, int& W, int& H)
@@ -322,7 +271,8 @@ double process_cpu_seconds()
     return ru.ru_utime.tv_sec + ru.ru_stime.tv_sec + 1e-6 * (ru.ru_utime.tv_usec + ru.ru_stime.tv_usec);
 }
 
-struct Pinned { uint8_t* frame = nullptr; float* bw = nullptr; float* fw = nullptr; uint8_t* cert = nullptr; uint8_t* yuv = nullptr; };
+// one pinned staging set of the loader pipeline: what frame i's files decode into
+struct Pinned { fav::host_ptr<uint8_t> frame, cert, yuv; fav::host_ptr<float> bw, fw; };
 
 // Everything frame i needs from disk (fast_artistic_video.lua:93-110,153-158): the frame, and for a frame with a predecessor the backward
 // flow plus either the certainty file (the reference's path: polled, fav.lua:102) or the forward flow (fused check).
@@ -335,9 +285,9 @@ FrameIn load_frame_inputs(const Opt& o, const favp::Poll& poll, int i, bool firs
     const bool fused_check = !o.s("forward_flow_pattern").empty();
     FrameIn in; in.index = pd ? -i - 1 : i;              // negative index marks "pinned, do not free"
     if (y4m) {
-        in.yuv = pd ? pd->yuv : static_cast<uint8_t*>(malloc(y4m_bytes));
+        in.yuv = pd ? pd->yuv.get() : static_cast<uint8_t*>(malloc(y4m_bytes));
         if (!in.yuv) die("out of host memory");
-        // anything but a complete frame ends the clip here; run_stream reports a stream that ended inside a frame once the frames
+        // anything but a complete frame ends the clip here; the frame loop reports a stream that ended inside a frame once the frames
         // before it are written
         if (y4m->read_frame(i, in.yuv) != favy::Reader::FRAME) { if (!pd) { free(in.yuv); in.yuv = nullptr; } return in; }
         in.W = y4m->header().W; in.H = y4m->header().H;
@@ -345,7 +295,7 @@ FrameIn load_frame_inputs(const Opt& o, const favp::Poll& poll, int i, bool firs
         const std::string fp = fmt_int(o.s("input_pattern"), i);
         if (!file_exists(fp)) return in;                                                                 // fav.lua:93-97 -> nil -> break
         int ch;
-        if (pd) { check(fav_read_pnm_into_host(fp.c_str(), pd->frame, pin_px * 3, &in.W, &in.H, &ch), fp.c_str()); in.frame = pd->frame; }
+        if (pd) { check(fav_read_pnm_into_host(fp.c_str(), pd->frame.get(), pin_px * 3, &in.W, &in.H, &ch), fp.c_str()); in.frame = pd->frame.get(); }
         else check(fav_read_pnm_host(fp.c_str(), &in.frame, &in.W, &in.H, &ch), fp.c_str());
         if (ch != 3) die(fp + ": expected a colour (P6) frame");
     }
@@ -355,30 +305,22 @@ FrameIn load_frame_inputs(const Opt& o, const favp::Poll& poll, int i, bool firs
         int w, h;
         if (fused_check) {
             const std::string ff = flow_name(o.s("forward_flow_pattern"), i - 1, i);
-            read_polled(ff, poll, [&] { if (pd) { in.fw = pd->fw; return fav_read_flo_into_host(ff.c_str(), pd->fw, pin_px * 2, &w, &h); }
+            read_polled(ff, poll, [&] { if (pd) { in.fw = pd->fw.get(); return fav_read_flo_into_host(ff.c_str(), in.fw, pin_px * 2, &w, &h); }
                                         return fav_read_flo_host(ff.c_str(), &in.fw, &w, &h); });
             if (w != in.W || h != in.H) die(ff + ": size differs from the frame");
         } else {
             const std::string cp = flow_name(o.s("occlusions_pattern"), i - 1, i);
             int cch = 0;
-            read_polled(cp, poll, [&] { if (pd) { in.cert = pd->cert; return fav_read_pnm_into_host(cp.c_str(), pd->cert, pin_px, &w, &h, &cch); }   // fav.lua:102
+            read_polled(cp, poll, [&] { if (pd) { in.cert = pd->cert.get(); return fav_read_pnm_into_host(cp.c_str(), in.cert, pin_px, &w, &h, &cch); }   // fav.lua:102
                                         return fav_read_pnm_host(cp.c_str(), &in.cert, &w, &h, &cch); });
             if (cch != 1 || w != in.W || h != in.H) die(cp + ": expected a P5 mask of the frame's size");
         }
-        read_polled(fl, poll, [&] { if (pd) { in.bw = pd->bw; return fav_read_flo_into_host(fl.c_str(), pd->bw, pin_px * 2, &w, &h); }
+        read_polled(fl, poll, [&] { if (pd) { in.bw = pd->bw.get(); return fav_read_flo_into_host(fl.c_str(), in.bw, pin_px * 2, &w, &h); }
                                     return fav_read_flo_host(fl.c_str(), &in.bw, &w, &h); });
         if (w != in.W || h != in.H) die(fl + ": size differs from the frame");
     }
     in.ok = true;
     return in;
-}
-
-// the estimator's options from the -flow_* flags (main validates them)
-fav_flow_opts_ex3 flow_opts_of(const Opt& o)
-{
-    return {{{{o.i("flow_levels"), o.i("flow_warps"), o.i("flow_iters"), (float)o.d("flow_alpha"), 0, (float)o.d("flow_eps")}, o.i("flow_grad")},
-             o.i("flow_match") ? -1.f : 0.f, 0},
-            o.i("flow_median")};
 }
 
 // The format of a Y4M stream's frames.  from_header: what the input's header says (null: there is no Y4M input -- 4:2:0 with centre
@@ -396,454 +338,651 @@ fav_yuv_format y4m_format_of(const Opt& o, const fav_yuv_format* from_header, in
     return f;
 }
 
-// One video: the loop of run_fast_neural_video (core.lua:189-229) with the video CLI's callbacks (fav.lua:93-172).
-// `net` / `net_img` live on the current device; `nwriters` PNG threads.
-void run_stream(const Opt& o, const fav_flow_opts_ex3& flow_opts, fav_net* net, fav_net* net_img, int nwriters, StreamResult* res)   // nwriters: the budget; adjusted below
-{
-    const bool estimate = o.i("estimate_flow") != 0;       // the flows come from the frames (and go through the fused check)
-    const bool fused_check = estimate || !o.s("forward_flow_pattern").empty();
-    void* d_flow_ws = nullptr; size_t flow_ws_bytes = 0;
-    const int border = o.s("warp_border") == "cpu" ? FAV_BORDER_CPU : FAV_BORDER_STN;
-    const int num_frames = o.i("num_frames");
-    const bool backward = o.f("backward");
-    const int start = backward ? num_frames - 1 : o.i("continue_with"), end = backward ? 1 : num_frames, inc = backward ? -1 : 1;   // core:189-191
-    favp::Poll poll; poll.timeout_s = o.d("poll_timeout"); poll.settle_s = std::max(0.0, o.d("poll_settle")); poll.out = favl::msg();
+struct Counters { std::atomic<long long> png_bytes{0}, cpu_loaders_us{0}, cpu_writers_us{0}, cpu_writer_sync_us{0}; };
 
-    // -input_y4m: one sequential reader behind the loader threads; -output_y4m: planes instead of PNG files, written in order
-    const bool y4m_in = !o.s("input_y4m").empty(), y4m_out = !o.s("output_y4m").empty();
-    favy::Reader y4m_reader; favy::Writer y4m_writer;
-    fav_yuv_format fmt_in{}, fmt_out{};
-    size_t y4m_in_bytes = 0, y4m_out_bytes = 0;
-    if (y4m_in) {
-        const std::string err = y4m_reader.open(o.s("input_y4m"));
-        if (!err.empty()) die(err);
-        const fav_y4m_header& h = y4m_reader.header();
-        fmt_in = y4m_format_of(o, &h.fmt, h.H, false);
-        y4m_in_bytes = fav_yuv_frame_bytes(h.W, h.H, &fmt_in);
-        if (!y4m_in_bytes) die(std::string("-input_y4m: ") + fav_last_error());
-        y4m_reader.set_frame_bytes(y4m_in_bytes);
-    }
+// compute queue; upload queue (the next frame's inputs travel while this frame computes); download queue (the 8-bit frame leaves
+// while the next frame computes: on the compute queue the 2.8 MB copy held back the next frame's kernels for its whole duration)
+// (three queues besides the library's two look-ahead queues: a process gets four hardware queues by default, and the 4-argument
+//  mode lost 20 % when a sixth stream made its side queues share one with the compute queue)
+struct Queues {
+    fav::queue_h compute = favl::queue_create(), upload = favl::queue_create(), download = favl::queue_create();
+    void drain() { for (hipStream_t q : {compute.get(), upload.get(), download.get()}) (void)hipStreamSynchronize(q); }
+};
 
-    size_t pin_px = 0;                       // capacity of a pinned staging set in pixels (0: none yet)
-    auto load = [&](int i, bool first_of_run, const Pinned* pd) {
-        return load_frame_inputs(o, poll, i, first_of_run, pd, pin_px, y4m_in ? &y4m_reader : nullptr, y4m_in_bytes);
-    };
-
-    // -png_encoder gpu (default): the PNG file's bytes are produced on the device (fav_stream_encode_png: Sub filter + fixed-Huffman /
-    // run-length deflate per row + Adler-32 / CRC-32 combine), leave as ONE exact-size DMA and the writer thread only write()s them;
-    // -png_encoder host: the 8-bit frame is downloaded and deflated by zlib on the writer threads (-png_level; ~25 ms per frame and core)
-    // -output_y4m: no PNG at all.  The planes are written by the frame's last kernel straight into a pinned output slot
-    // (fav_stream_encode_yuv), the host learns of them through an event on the compute queue -- the event-ordered path of
-    // -png_encoder host, minus its download -- and ONE writer thread write()s the slots in frame order.
-    const bool gpu_png = !y4m_out && o.s("png_encoder") == "gpu";
-    const bool png_overlap = o.i("png_overlap") != 0;
-    // QUIET synchronisation (gpu_png, no 4-argument look-ahead): nothing but kernels ever enters the compute queue.  On this runtime
-    // a marker behind long-running kernels (hipEventRecord on the compute stream) or a device-side dependency between queues
-    // (hipStreamWaitEvent, a copy in front of kernels in one stream) is resolved by a runtime thread that SPINS until the marker
-    // fires -- one core per process, 1.6 ms of CPU per 1.8 ms frame (scripts/runtime_thread_bench.hip, profiles/r03k_runtime_thread.log:
-    // kernels only 0.03 cores in the background, + one event record per frame 0.70, + a cross-stream dependency 0.74).  So: uploads are
-    // DMA copies on their own queue and the HOST checks (sleeping poll on that queue's event) that frame i's inputs have arrived before
-    // it enqueues frame i's kernels -- they were requested a frame earlier; the frame's last kernel writes the PNG size into host-mapped
-    // memory, which the host polls; the PNG bytes then leave as one DMA on a third queue.  The 4-argument look-ahead (its mask pipeline
-    // runs a frame ahead on the library's side queues) is started after the host has seen that frame's upload finish and is waited
-    // for on the host as well (fav_stream_set_host_ordered): no event there either.
-    const bool quiet = gpu_png;       // (the 4-argument look-ahead runs host-ordered in this mode: fav_stream_set_host_ordered)
-    int cur_device = 0; (void)hipGetDevice(&cur_device);
-    const double cpu0 = process_cpu_seconds();
-    if (gpu_png && o.i("writers") <= 0) nwriters = std::min(nwriters, 4);      // they only write() finished files: 0.5 ms per frame
-    if (y4m_out) nwriters = 1;               // a stream's frames leave in order: the pool's queue is first in, first out
-    Pool writers(nwriters, cur_device);
-    // compute queue; upload queue (the next frame's inputs travel while this frame computes); download queue (the 8-bit frame leaves
-    // while the next frame computes: on the compute queue the 2.8 MB copy held back the next frame's kernels for its whole duration)
-    // gpu_png: the file's bytes must not sit behind the NEXT frame's size word on the download queue (that one waits for the next
-    // frame's kernels: the writer thread then waited a whole frame for a 0.1 ms DMA): finish() enqueues them first
-    // (three queues besides the library's two look-ahead queues: a process gets four hardware queues by default, and the 4-argument
-    //  mode lost 20 % when a sixth stream made its side queues share one with the compute queue)
-    hipStream_t st, st_copy, st_down;
-    if (hipStreamCreate(&st) != hipSuccess || hipStreamCreate(&st_copy) != hipSuccess || hipStreamCreate(&st_down) != hipSuccess) die("hipStreamCreate failed");
-    hipStream_t const st_data = st_down;     // quiet mode: st_down carries nothing else; otherwise finish() enqueues frame i-1's bytes BEFORE frame i's size word
-    constexpr int NDEV = 4;                  // device input sets: frame i (in use) + up to two frames of look-ahead + one being refilled
-    hipEvent_t ev_up[NDEV], ev_done[2], ev_out[2];
-    for (auto& e : ev_out) if (hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess) die("hipEventCreate failed");
-    for (auto& e : ev_up) if (hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess) die("hipEventCreate failed");
-    // events the HOST waits on: blocking (the waiting thread sleeps instead of spinning -- a spinning wait costs one core per waiter,
-    // 1.9 ms of CPU per frame for the main thread alone at 530 frames/s) and with the system-scope fence (the host reads what they cover)
-    for (auto& e : ev_done) if (hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventBlockingSync) != hipSuccess) die("hipEventCreate failed");
-    fav_stream* fs = nullptr;
-    int W = 0, H = 0;                        // frame size
-    int Wo = 0, Ho = 0;                      // size of the stylised frames: the network's output (H x W when both are multiples of 4)
-    struct Dev { uint8_t* frame = nullptr; uint8_t* cert = nullptr; float* bw = nullptr; float* fw = nullptr; uint8_t* yuv = nullptr; };
-    Dev dev[NDEV];
-    uint8_t* d_out8s[2] = {nullptr, nullptr};    // frames alternate: frame i + 2 is enqueued after the host has seen frame i's download complete
-    // gpu_png: device PNG buffers (two, alternating like d_out8s), their sizes on the device and in pinned host memory, and per pinned
-    // output slot the event of the exact-size copy into it
-    uint8_t* d_png[2] = {nullptr, nullptr}; uint32_t* d_png_size[2] = {nullptr, nullptr}; uint32_t* h_png_size = nullptr;
-    hipEvent_t png_copy_ev[2] = {nullptr, nullptr};       // last copy OUT of d_png[k]: the next encode into it waits for this
-    size_t png_cap = 0;
-    std::map<uint8_t*, hipEvent_t> slot_ev;
-    std::atomic<long long> png_bytes_total{0}, cpu_loaders_us{0}, cpu_writers_us{0}, cpu_writer_sync_us{0};
-    const double cpu_main0 = thread_cpu_seconds();
-    float *d_prev = nullptr, *d_cur = nullptr; std::vector<double> temporal;      // -temporal_eval_file
-    // -scene_cut: per device input set one host-mapped record that fav_scene_change_rgb8 fills behind the set's upload.  The host
-    // needs `total` only, which the measure's last kernel stores last: it is set to SCENE_PENDING (no total exceeds 2^29) when the
-    // measure is enqueued and polled when the frame's turn comes, a frame later -- like the PNG's size word, without an event.
-    const double scene_T = o.d("scene_cut");
-    const bool scene = scene_T > 0.0;
-    constexpr uint32_t SCENE_PENDING = 0xFFFFFFFFu;
-    fav_scene_change* h_scene = nullptr; void* d_scene_ws = nullptr;
-    FILE* scene_log = nullptr;
-    if (!o.s("scene_cut_log").empty()) {
-        mkdirs_for(o.s("scene_cut_log"));
-        scene_log = fopen(o.s("scene_cut_log").c_str(), "w");
-        if (!scene_log) die("cannot open " + o.s("scene_cut_log"));
-    }
-    const int nslots = nwriters + 2;   // pinned output slots in flight to the PNG pool (deflate ~55 ms/frame/thread)
-    std::vector<uint8_t*> h_out;       // allocated on demand, at most nslots
-    size_t slot_bytes = 0;
-    Slots slots;
-    auto new_slot = [&]() {
-        uint8_t* p = nullptr;
-        if (hipHostMalloc((void**)&p, slot_bytes, hipHostMallocDefault) != hipSuccess) die("hipHostMalloc failed");
-        if (gpu_png) { hipEvent_t e; if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) die("hipEventCreate failed"); slot_ev[p] = e; }
-        h_out.push_back(p);
-        return p;
-    };
-
-
-    // continue_with > 1: reload the previous stylised PNG as the recurrent state (8-bit; the reference's
-    // video CLI does not reload anything and fails, fast_artistic_video.lua:89,153-156)
-    std::vector<float> resume_state;
-    bool have_resume = false;
-    if (!backward && start > 1 && !o.f("create_inconsistent")) {
-        std::vector<uint8_t> prev; int pw, ph;
-        char nm[4096]; snprintf(nm, sizeof nm, "%s-%05d.png", o.s("output_prefix").c_str(), start - 1);
-        if (read_png_rgb8(nm, prev, pw, ph)) {
-            resume_state.resize((size_t)pw * ph * 3);
-            for (size_t i = 0; i < (size_t)pw * ph; ++i)
-                for (int c = 0; c < 3; ++c) resume_state[(size_t)c * pw * ph + i] = prev[i * 3 + c] / 255.0f;
-            W = -pw; H = -ph; have_resume = true;    // validated against the first frame below
-        } else {
-            fprintf(stderr, "warning: %s not found; frame %d is stylised without a prior\n", nm, start);
-        }
-    }
-
-    // Host pipeline: DEPTH loader threads read + decode frames i+1.. while the GPU works on frame i; decoded
-    // inputs are copied into pinned staging sets so the H2D copies are true async DMA.
-    constexpr int DEPTH = 6;
+// Host pipeline: DEPTH loader threads read + decode frames i+1.. while the GPU works on frame i; decoded
+// inputs are copied into pinned staging sets so the H2D copies are true async DMA.
+struct Loader {
+    static constexpr int DEPTH = 6;
+    const Opt& o; const favp::Poll& poll;
+    favy::Reader* const y4m; const size_t y4m_bytes;       // -input_y4m: one sequential reader behind the loader threads (else null)
+    const int start, end, inc; const bool first_is_single; // the frame range (core:189-191); has frame `start` no prior?
+    std::atomic<long long>* const cpu_us;
+    size_t pin_px = 0;                       // capacity of a pinned staging set in pixels (0: none yet, loads go to malloc'ed memory)
+    double t_wait = 0;
+    int next_to_issue, sets_used = 0;
     Pinned pin[DEPTH + 1];
-    bool pinned_ready = false;
-    auto load_pinned = [&](int i, bool first_of_run, int set) {
-        if (pinned_ready && !pin[set].frame && !pin[set].yuv) {      // first use of this staging set: pinned here, by the loader thread that owns it
-            Pinned& p = pin[set];
-            if (y4m_in ? hipHostMalloc((void**)&p.yuv, y4m_in_bytes, hipHostMallocDefault) : hipHostMalloc((void**)&p.frame, pin_px * 3, hipHostMallocDefault)) die("hipHostMalloc failed");
-            if (!estimate &&                                     // (-estimate_flow: frames only)
-                (hipHostMalloc((void**)&p.bw, pin_px * 8, hipHostMallocDefault) ||
-                 (fused_check ? hipHostMalloc((void**)&p.fw, pin_px * 8, hipHostMallocDefault) : hipHostMalloc((void**)&p.cert, pin_px, hipHostMallocDefault)))) die("hipHostMalloc failed");
-        }
-        return load(i, first_of_run, pinned_ready ? &pin[set] : nullptr);
-    };
-    auto idx_ok = [&](int i) { return backward ? i >= end : i <= end; };
-    // persistent loader threads (a std::thread per frame cost ~0.1 ms of CPU each); no more of them than CPUs to run them on
-    Pool loaders(std::min(DEPTH, std::max(2, favl::effective_cpus())), cur_device);
+    std::vector<FrameIn> ready = std::vector<FrameIn>(DEPTH + 1);
     std::deque<std::pair<int, std::future<void>>> inflight;      // (slot set, completion of its load)
-    std::vector<FrameIn> ready(DEPTH + 1);
-    int next_to_issue = start, sets_used = 0;
-    auto issue = [&]() {
+    // persistent loader threads (a std::thread per frame cost ~0.1 ms of CPU each); no more of them than CPUs to run them on.
+    // Declared last: the threads are gone before the staging sets they fill
+    Pool pool;
+
+    Loader(const Opt& o_, const favp::Poll& poll_, favy::Reader* y4m_, size_t y4m_bytes_, int start_, int end_, int inc_, bool first_is_single_,
+           std::atomic<long long>* cpu_us_, int device)
+        : o(o_), poll(poll_), y4m(y4m_), y4m_bytes(y4m_bytes_), start(start_), end(end_), inc(inc_), first_is_single(first_is_single_), cpu_us(cpu_us_),
+          next_to_issue(start_), pool(std::min(DEPTH, std::max(2, favl::effective_cpus())), device) {}
+
+    bool idx_ok(int i) const { return inc < 0 ? i >= end : i <= end; }
+    FrameIn load(int i, bool first_of_run, const Pinned* pd) { return load_frame_inputs(o, poll, i, first_of_run, pd, pin_px, y4m, y4m_bytes); }
+    FrameIn load_pinned(int i, bool first_of_run, int set)
+    {
+        Pinned& p = pin[set];
+        if (pin_px && !p.frame && !p.yuv) {      // first use of this staging set: pinned here, by the loader thread that owns it
+            if (y4m) p.yuv = favl::host_alloc<uint8_t>(y4m_bytes); else p.frame = favl::host_alloc<uint8_t>(pin_px * 3);
+            if (o.i("estimate_flow") == 0) {                     // (-estimate_flow: frames only)
+                p.bw = favl::host_alloc<float>(pin_px * 8);
+                if (!o.s("forward_flow_pattern").empty()) p.fw = favl::host_alloc<float>(pin_px * 8); else p.cert = favl::host_alloc<uint8_t>(pin_px);
+            }
+        }
+        return load(i, first_of_run, pin_px ? &p : nullptr);
+    }
+    void issue()                                                 // keep DEPTH loads in flight
+    {
         while ((int)inflight.size() < DEPTH && idx_ok(next_to_issue)) {
             const int i = next_to_issue, set = sets_used % (DEPTH + 1);
-            const bool fo = (i == start) && !have_resume && start != 1;
+            const bool fo = (i == start) && first_is_single;
             auto done_p = std::make_shared<std::promise<void>>();
             inflight.emplace_back(set, done_p->get_future());
-            loaders.submit([&, i, fo, set, done_p] {
+            pool.submit([this, i, fo, set, done_p] {
                 const double c0 = thread_cpu_seconds();
                 ready[set] = load_pinned(i, fo, set);
-                cpu_loaders_us += (long long)(1e6 * (thread_cpu_seconds() - c0));
+                *cpu_us += (long long)(1e6 * (thread_cpu_seconds() - c0));
                 done_p->set_value();
             });
             next_to_issue += inc; ++sets_used;
         }
-    };
-
-    bool first = true;
-    const auto t_begin = std::chrono::steady_clock::now();
-    double t_wait_load = 0, t_gpu = 0, t_wait_writer = 0;
-    int done = 0, dset = 0;
-    auto upload = [&](const FrameIn& f, int set) {                // async H2D of one frame's inputs (pinned -> device) on the copy queue
-        const size_t n = (size_t)W * H; const Dev& dv = dev[set];
-        if (f.yuv) {          // -input_y4m: the planes travel, and become the P6 payload on the device, still on the upload queue
-            hipMemcpyAsync(dv.yuv, f.yuv, y4m_in_bytes, hipMemcpyHostToDevice, st_copy);
-            check(fav_yuv_to_rgb8(dv.yuv, W, H, &fmt_in, dv.frame, st_copy), "fav_yuv_to_rgb8");
-        } else hipMemcpyAsync(dv.frame, f.frame, n * 3, hipMemcpyHostToDevice, st_copy);
-        if (f.bw) hipMemcpyAsync(dv.bw, f.bw, n * 8, hipMemcpyHostToDevice, st_copy);
-        if (f.fw) hipMemcpyAsync(dv.fw, f.fw, n * 8, hipMemcpyHostToDevice, st_copy);
-        if (f.cert) hipMemcpyAsync(dv.cert, f.cert, n, hipMemcpyHostToDevice, st_copy);
-        hipEventRecord(ev_up[set], st_copy);
-        if (!quiet) hipStreamWaitEvent(st, ev_up[set], 0);         // everything enqueued on the compute queue from here on sees them
-    };
-    // the host runs one frame ahead of the GPU: frame i is enqueued before frame i-1's completion is awaited
-    struct Pending { bool valid = false; int index = 0; bool single = false; uint8_t* hb = nullptr; int ev = 0;
-                     std::chrono::steady_clock::time_point t0; };
-    Pending pend;
-    auto finish = [&](Pending& pd) {
-        if (!pd.valid) return;
-        if (quiet) {
-            // the frame's last kernel (png_finish_kernel) stores the file size into host-mapped memory behind a system-scope fence
-            volatile uint32_t* sz = &h_png_size[pd.ev];
-            for (int spins = 0; *sz == 0u; ++spins) {
-                usleep(100);
-                if ((spins & 1023) == 1023) {                 // every ~0.1 s: has the GPU faulted? (a query, not a marker)
-                    const hipError_t e = hipStreamQuery(st);
-                    if (e != hipSuccess && e != hipErrorNotReady) die("GPU error while stylising a frame");
-                }
-            }
-        } else if (wait_event_sleeping(ev_done[pd.ev]) != hipSuccess) die("GPU error while stylising a frame");
-        check(fav_net_check(net), "stylising a frame");      // a stream-K hand-off that timed out: fail at THIS frame, before its PNG exists
-        if (net_img) check(fav_net_check(net_img), "stylising a frame");
-        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - pd.t0).count();
-        if (pd.single) fprintf(favl::msg(), "Elapsed time for stylizing frame independently:%g\n", ms / 1000.0);           // core:155
-        else fprintf(favl::msg(), "Elapsed time for stylizing frame:%g\n", ms / 1000.0);                                   // core:177
-        char nm[4096]; snprintf(nm, sizeof nm, "%s-%05d.png", o.s("output_prefix").c_str(), pd.index);       // fav.lua:161
-        if (y4m_out) snprintf(nm, sizeof nm, "%s (frame %d)", o.s("output_y4m").c_str(), pd.index);
-        fprintf(favl::msg(), "Writing output image to %s\n", nm);
-        if (!y4m_out) mkdirs_for(nm);
-        const int lvl = o.i("png_level");
-        const std::string path = nm; uint8_t* hb = pd.hb; const int w_ = Wo, h_ = Ho;
-        Slots* sl = &slots;
-        if (y4m_out) {
-            // the planes are in the pinned slot (the event above covers them): `FRAME` and the payload, behind the frames before it
-            favy::Writer* wr = &y4m_writer; const size_t nbytes = y4m_out_bytes;
-            std::atomic<long long>* cw = &cpu_writers_us;
-            writers.submit([hb, path, nbytes, wr, sl, cw] {
-                const double c0 = thread_cpu_seconds();
-                if (!wr->frame(hb, nbytes)) { fprintf(stderr, "cannot write %s\n", path.c_str()); exit(1); }
-                *cw += (long long)(1e6 * (thread_cpu_seconds() - c0));
-                sl->give(hb);
-            });
-        } else if (gpu_png) {
-            // the size word has arrived (ev_done): ONE DMA of exactly the file's bytes, then the writer thread only write()s
-            const uint32_t nbytes = h_png_size[pd.ev];
-            if (nbytes < 57 || nbytes > png_cap) die("fav_stream_encode_png returned an impossible size");
-            hipEvent_t cev = slot_ev[hb];
-            if (hipMemcpyAsync(hb, d_png[pd.ev], nbytes, hipMemcpyDeviceToHost, st_data) != hipSuccess || hipEventRecord(cev, st_data) != hipSuccess) die("D2H of the PNG failed");
-            png_copy_ev[pd.ev] = cev;
-            png_bytes_total += nbytes;
-            std::atomic<long long>* cw = &cpu_writers_us;
-            std::atomic<long long>* cs = &cpu_writer_sync_us;
-            writers.submit([hb, path, nbytes, cev, sl, cw, cs] {
-                const double c0 = thread_cpu_seconds();
-                if (wait_event_sleeping(cev, 50) != hipSuccess) { fprintf(stderr, "GPU error while downloading %s\n", path.c_str()); exit(1); }
-                *cs += (long long)(1e6 * (thread_cpu_seconds() - c0));
-                const int fd = open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
-                size_t off = 0;
-                while (fd >= 0 && off < nbytes) { const ssize_t k = write(fd, hb + off, nbytes - off); if (k <= 0) break; off += (size_t)k; }
-                if (fd < 0 || off != nbytes || close(fd)) { fprintf(stderr, "cannot write %s\n", path.c_str()); exit(1); }
-                *cw += (long long)(1e6 * (thread_cpu_seconds() - c0));
-                sl->give(hb);
-            });
-        } else {
-            std::atomic<long long>* cw = &cpu_writers_us;
-            writers.submit([hb, path, w_, h_, lvl, sl, cw] {
-                const double c0 = thread_cpu_seconds();
-                if (fav_write_png_rgb8_host(path.c_str(), hb, w_, h_, lvl)) fprintf(stderr, "%s\n", fav_last_error());
-                *cw += (long long)(1e6 * (thread_cpu_seconds() - c0));
-                sl->give(hb);                                     // only now may the slot receive another frame
-            });
-        }
-        pd.valid = false;
-    };
-    auto pop_next = [&](FrameIn& out) {
+    }
+    bool pop_next(FrameIn& out)
+    {
         if (inflight.empty()) return false;
         const auto tl = std::chrono::steady_clock::now();
         const int set = inflight.front().first;
         inflight.front().second.get(); inflight.pop_front();
         out = ready[set];
-        t_wait_load += std::chrono::duration<double>(std::chrono::steady_clock::now() - tl).count();
+        t_wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - tl).count();
         return out.ok;
-    };
-    // the first frame is loaded synchronously (its size sizes every buffer)
-    FrameIn cur = load(start, !have_resume && start != 1, nullptr);
+    }
+    void finish() { for (auto& pr : inflight) pr.second.get(); for (auto& r : ready) if (r.index >= 0) r.release(); }
+};
+
+// Device input sets: frame i (in use) + up to two frames of look-ahead + one being refilled
+struct DevInputs {
+    static constexpr int N = 4;
+    struct Set { fav::dev_ptr<uint8_t> frame, cert, yuv; fav::dev_ptr<float> bw, fw; fav::event_h up; };
+    Set set[N];
+    int W = 0, H = 0; size_t yuv_bytes = 0; fav_yuv_format fmt_in{};        // -input_y4m: a frame's planes and their format
+    DevInputs() { for (Set& s : set) s.up = favl::event_create(hipEventDisableTiming | hipEventDisableSystemFence); }
+    void alloc(int W_, int H_)
+    {
+        W = W_; H = H_;
+        const size_t n = (size_t)W * H;
+        for (Set& s : set) {
+            s.frame = favl::dev_alloc<uint8_t>(n * 3); s.cert = favl::dev_alloc<uint8_t>(n); s.bw = favl::dev_alloc<float>(n * 8); s.fw = favl::dev_alloc<float>(n * 8);
+            if (yuv_bytes) s.yuv = favl::dev_alloc<uint8_t>(yuv_bytes);
+        }
+    }
+    const Set& before(int k) const { return set[(k + N - 1) % N]; }       // the previous frame in processing order
+    // async H2D of one frame's inputs (pinned -> device) on the copy queue; compute != null: everything enqueued on that queue from
+    // here on sees them
+    void upload(const FrameIn& f, int k, hipStream_t copy, hipStream_t compute)
+    {
+        const size_t n = (size_t)W * H; const Set& dv = set[k];
+        if (f.yuv) {          // -input_y4m: the planes travel, and become the P6 payload on the device, still on the upload queue
+            hipMemcpyAsync(dv.yuv.get(), f.yuv, yuv_bytes, hipMemcpyHostToDevice, copy);
+            check(fav_yuv_to_rgb8(dv.yuv.get(), W, H, &fmt_in, dv.frame.get(), copy), "fav_yuv_to_rgb8");
+        } else hipMemcpyAsync(dv.frame.get(), f.frame, n * 3, hipMemcpyHostToDevice, copy);
+        if (f.bw) hipMemcpyAsync(dv.bw.get(), f.bw, n * 8, hipMemcpyHostToDevice, copy);
+        if (f.fw) hipMemcpyAsync(dv.fw.get(), f.fw, n * 8, hipMemcpyHostToDevice, copy);
+        if (f.cert) hipMemcpyAsync(dv.cert.get(), f.cert, n, hipMemcpyHostToDevice, copy);
+        hipEventRecord(dv.up.get(), copy);
+        if (compute) hipStreamWaitEvent(compute, dv.up.get(), 0);
+    }
+};
+
+// -scene_cut: per device input set one host-mapped record that fav_scene_change_rgb8 fills behind the set's upload.  The host
+// needs `total` only, which the measure's last kernel stores last: it is set to PENDING (no total exceeds 2^29) when the
+// measure is enqueued and polled when the frame's turn comes, a frame later -- like the PNG's size word, without an event.
+struct SceneCut {
+    static constexpr uint32_t PENDING = 0xFFFFFFFFu;
+    struct Close { void operator()(FILE* f) const { fclose(f); } };
+    const double T; const bool on;
+    fav::host_ptr<fav_scene_change> h; fav::dev_ptr<void> ws;
+    std::unique_ptr<FILE, Close> log;
+    explicit SceneCut(const Opt& o) : T(o.d("scene_cut")), on(T > 0.0)
+    {
+        if (o.s("scene_cut_log").empty()) return;
+        mkdirs_for(o.s("scene_cut_log"));
+        log.reset(fopen(o.s("scene_cut_log").c_str(), "w"));
+        if (!log) die("cannot open " + o.s("scene_cut_log"));
+    }
+    void alloc()
+    {
+        void* p = nullptr; void* w = nullptr;
+        if (hipHostMalloc(&p, DevInputs::N * sizeof(fav_scene_change), hipHostMallocDefault) != hipSuccess ||
+            hipMalloc(&w, fav_scene_change_workspace_bytes()) != hipSuccess) die("hipMalloc failed");
+        h.reset(static_cast<fav_scene_change*>(p)); ws.reset(w);
+    }
+    // behind the upload of set k, on its queue: the frame before it in processing order is in the set before it
+    void measure(const DevInputs& dev, int k, hipStream_t copy)
+    {
+        h.get()[k].total = PENDING;
+        check(fav_scene_change_rgb8(dev.before(k).frame.get(), dev.set[k].frame.get(), dev.W, dev.H, ws.get(), fav_scene_change_workspace_bytes(),
+                                    &h.get()[k], copy), "fav_scene_change_rgb8");
+    }
+    // is frame i (in set k) a cut?  Its measure was enqueued a frame ago, behind its upload; the first frame has nothing in front of it
+    bool decide(int i, int k, bool has_predecessor, const DevInputs& dev, hipStream_t copy)
+    {
+        uint32_t total = 0; double score = 0.0; bool cut = false;
+        if (has_predecessor) {
+            volatile uint32_t* tw = &h.get()[k].total;
+            for (int spins = 0; *tw == PENDING; ++spins) {
+                usleep(50);
+                if ((spins & 2047) == 2047) {             // every ~0.1 s: has the GPU faulted? (a query, not a marker)
+                    const hipError_t e = hipStreamQuery(copy);
+                    if (e != hipSuccess && e != hipErrorNotReady) die("GPU error while measuring a scene change");
+                }
+            }
+            total = *tw;
+            score = (double)total / (2.0 * (double)dev.W * (double)dev.H);
+            cut = score > T;
+        }
+        if (log) fprintf(log.get(), "%d %u %.6f %d\n", i, total, score, cut ? 1 : 0);
+        return cut;
+    }
+};
+
+// Where a stylised frame goes.  Frames alternate between two sets of what a sink keeps per frame (k = 0 | 1): frame i + 2 is enqueued
+// after the host has seen frame i complete.  Per frame the loop calls, in this order: after_frame (behind the frame's network, with
+// the pinned slot the frame will leave through), hand_off (behind the look-ahead and the wait for the frame before), and a frame
+// later wait, target and writer_task.
+struct SinkEnv { const Opt& o; hipStream_t st, st_down; Slots* slots; Counters* cnt; };
+class Sink {
+public:
+    explicit Sink(const SinkEnv& e) : env(e) {}
+    virtual ~Sink() = default;
+    // QUIET synchronisation: nothing but kernels ever enters the compute queue (DevicePng below says why and how)
+    virtual bool quiet() const { return false; }
+    virtual size_t setup(fav_stream* fs, int Wo, int Ho) = 0;      // at the known output size; returns the bytes of a pinned slot
+    virtual void slot_added(uint8_t*) {}
+    virtual uint8_t* frame_out(int) { return nullptr; }            // where the network is to leave the 8-bit frame, if anywhere
+    virtual void after_frame(int k, uint8_t* hb) = 0;
+    virtual void hand_off(int k, uint8_t* hb) = 0;
+    virtual void wait(int k) = 0;                                  // until frame k is complete where the writer task needs it
+    virtual std::string target(int index) = 0;                     // what "Writing output image to" names
+    virtual std::function<void()> writer_task(int k, uint8_t* hb, const std::string& path) = 0;
+protected:
+    std::string png_target(int index) const
+    {
+        char nm[4096]; snprintf(nm, sizeof nm, "%s-%05d.png", env.o.s("output_prefix").c_str(), index);       // fav.lua:161
+        mkdirs_for(nm);
+        return nm;
+    }
+    // events the HOST waits on: blocking (the waiting thread sleeps instead of spinning -- a spinning wait costs one core per waiter,
+    // 1.9 ms of CPU per frame for the main thread alone at 530 frames/s) and with the system-scope fence (the host reads what they cover)
+    static fav::event_h host_event() { return favl::event_create(hipEventDisableTiming | hipEventBlockingSync); }
+    void wait_host_event(hipEvent_t e) const { if (wait_event_sleeping(e) != hipSuccess) die("GPU error while stylising a frame"); }
+    SinkEnv env; fav_stream* fs = nullptr; int Wo = 0, Ho = 0;
+};
+
+// -png_encoder gpu (default): the PNG file's bytes are produced on the device (fav_stream_encode_png: Sub filter + fixed-Huffman /
+// run-length deflate per row + Adler-32 / CRC-32 combine), leave as ONE exact-size DMA and the writer thread only write()s them.
+// QUIET synchronisation (with the 4-argument look-ahead as well): nothing but kernels ever enters the compute queue.  On this runtime
+// a marker behind long-running kernels (hipEventRecord on the compute stream) or a device-side dependency between queues
+// (hipStreamWaitEvent, a copy in front of kernels in one stream) is resolved by a runtime thread that SPINS until the marker
+// fires -- one core per process, 1.6 ms of CPU per 1.8 ms frame (scripts/runtime_thread_bench.hip, profiles/r03k_runtime_thread.log:
+// kernels only 0.03 cores in the background, + one event record per frame 0.70, + a cross-stream dependency 0.74).  So: uploads are
+// DMA copies on their own queue and the HOST checks (sleeping poll on that queue's event) that frame i's inputs have arrived before
+// it enqueues frame i's kernels -- they were requested a frame earlier; the frame's last kernel writes the PNG size into host-mapped
+// memory, which the host polls; the PNG bytes then leave as one DMA on a third queue.  The 4-argument look-ahead (its mask pipeline
+// runs a frame ahead on the library's side queues) is started after the host has seen that frame's upload finish and is waited
+// for on the host as well (fav_stream_set_host_ordered): no event there either.
+// The download queue carries nothing but the files' bytes: they never sit behind the NEXT frame's size word there (that one would wait
+// for the next frame's kernels: the writer thread then waited a whole frame for a 0.1 ms DMA).
+class DevicePng : public Sink {
+public:
+    explicit DevicePng(const SinkEnv& e) : Sink(e), overlap(e.o.i("png_overlap") != 0) {}
+    bool quiet() const override { return true; }
+    size_t setup(fav_stream* fs_, int Wo_, int Ho_) override
+    {
+        fs = fs_; Wo = Wo_; Ho = Ho_;
+        if (Wo > 9000) die("-png_encoder gpu encodes rows of up to 9000 pixels (one image row lives in a CU's LDS); pass -png_encoder host for " + std::to_string(Wo) + "-wide frames");
+        cap = fav_png_capacity(Wo, Ho);
+        for (auto& d : d_png) d = favl::dev_alloc<uint8_t>(cap);
+        h_size = favl::host_alloc<uint32_t>(64);
+        return cap;
+    }
+    // per pinned output slot the event of the exact-size copy into it
+    void slot_added(uint8_t* p) override { slot_ev[p] = favl::event_create(hipEventDisableTiming); }
+    void after_frame(int k, uint8_t*) override
+    {
+        // two frames ago this buffer's bytes left through the download queue: that copy must have finished (it has, long ago)
+        if (copy_ev[k] && wait_event_sleeping(copy_ev[k], 50) != hipSuccess) die("GPU error while downloading a frame");
+        h_size.get()[k] = 0u;                    // the frame's last kernel overwrites it with the file size (host-mapped)
+        // -png_overlap 1: on the stream's encoder queue, next to frame i + 1's network -- the host learns of the file
+        // through its size word either way
+        if (overlap) check(fav_stream_encode_png_async(fs, d_png[k].get(), cap, &h_size.get()[k], env.st), "fav_stream_encode_png_async");
+        else check(fav_stream_encode_png(fs, d_png[k].get(), cap, &h_size.get()[k], env.st), "fav_stream_encode_png");
+    }
+    void hand_off(int, uint8_t*) override {}     // the bytes leave once their number is known: writer_task
+    void wait(int k) override
+    {
+        // the frame's last kernel (png_finish_kernel) stores the file size into host-mapped memory behind a system-scope fence
+        volatile uint32_t* sz = &h_size.get()[k];
+        for (int spins = 0; *sz == 0u; ++spins) {
+            usleep(100);
+            if ((spins & 1023) == 1023) {                 // every ~0.1 s: has the GPU faulted? (a query, not a marker)
+                const hipError_t e = hipStreamQuery(env.st);
+                if (e != hipSuccess && e != hipErrorNotReady) die("GPU error while stylising a frame");
+            }
+        }
+    }
+    std::string target(int index) override { return png_target(index); }
+    std::function<void()> writer_task(int k, uint8_t* hb, const std::string& path) override
+    {
+        // the size word has arrived: ONE DMA of exactly the file's bytes, then the writer thread only write()s
+        const uint32_t nbytes = h_size.get()[k];
+        if (nbytes < 57 || nbytes > cap) die("fav_stream_encode_png returned an impossible size");
+        hipEvent_t cev = slot_ev[hb].get();
+        if (hipMemcpyAsync(hb, d_png[k].get(), nbytes, hipMemcpyDeviceToHost, env.st_down) != hipSuccess || hipEventRecord(cev, env.st_down) != hipSuccess) die("D2H of the PNG failed");
+        copy_ev[k] = cev;
+        env.cnt->png_bytes += nbytes;
+        Slots* sl = env.slots; Counters* cnt = env.cnt;
+        return [hb, path, nbytes, cev, sl, cnt] {
+            const double c0 = thread_cpu_seconds();
+            if (wait_event_sleeping(cev, 50) != hipSuccess) { fprintf(stderr, "GPU error while downloading %s\n", path.c_str()); exit(1); }
+            cnt->cpu_writer_sync_us += (long long)(1e6 * (thread_cpu_seconds() - c0));
+            const int fd = open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
+            size_t off = 0;
+            while (fd >= 0 && off < nbytes) { const ssize_t n = write(fd, hb + off, nbytes - off); if (n <= 0) break; off += (size_t)n; }
+            if (fd < 0 || off != nbytes || close(fd)) { fprintf(stderr, "cannot write %s\n", path.c_str()); exit(1); }
+            cnt->cpu_writers_us += (long long)(1e6 * (thread_cpu_seconds() - c0));
+            sl->give(hb);
+        };
+    }
+private:
+    const bool overlap;
+    size_t cap = 0;
+    fav::dev_ptr<uint8_t> d_png[2];              // device PNG buffers, alternating
+    fav::host_ptr<uint32_t> h_size;              // their sizes, host-mapped
+    hipEvent_t copy_ev[2] = {nullptr, nullptr};  // last copy OUT of d_png[k]: the next encode into it waits for this
+    std::map<uint8_t*, fav::event_h> slot_ev;
+};
+
+// -png_encoder host: the 8-bit frame is downloaded and deflated by zlib on the writer threads (-png_level; ~25 ms per frame and core).
+// The frame is complete on the compute queue (ev_out) and leaves on the download queue, which tells the host (ev_done).
+class HostPng : public Sink {
+public:
+    using Sink::Sink;
+    size_t setup(fav_stream* fs_, int Wo_, int Ho_) override
+    {
+        fs = fs_; Wo = Wo_; Ho = Ho_;
+        for (auto& d : d_out8) d = favl::dev_alloc<uint8_t>((size_t)Wo * Ho * 3);
+        return (size_t)Wo * Ho * 3;
+    }
+    uint8_t* frame_out(int k) override { return d_out8[k].get(); }
+    void after_frame(int k, uint8_t*) override { hipEventRecord(ev_out[k].get(), env.st); }       // the frame's 8-bit image is complete on the compute queue ...
+    void hand_off(int k, uint8_t* hb) override
+    {
+        hipStreamWaitEvent(env.st_down, ev_out[k].get(), 0);                                       // ... and leaves on the download queue
+        hipMemcpyAsync(hb, d_out8[k].get(), (size_t)Wo * Ho * 3, hipMemcpyDeviceToHost, env.st_down);
+        hipEventRecord(ev_done[k].get(), env.st_down);
+    }
+    void wait(int k) override { wait_host_event(ev_done[k].get()); }
+    std::string target(int index) override { return png_target(index); }
+    std::function<void()> writer_task(int, uint8_t* hb, const std::string& path) override
+    {
+        const int w = Wo, h = Ho, lvl = env.o.i("png_level");
+        Slots* sl = env.slots; Counters* cnt = env.cnt;
+        return [hb, path, w, h, lvl, sl, cnt] {
+            const double c0 = thread_cpu_seconds();
+            if (fav_write_png_rgb8_host(path.c_str(), hb, w, h, lvl)) fprintf(stderr, "%s\n", fav_last_error());
+            cnt->cpu_writers_us += (long long)(1e6 * (thread_cpu_seconds() - c0));
+            sl->give(hb);                                     // only now may the slot receive another frame
+        };
+    }
+private:
+    fav::dev_ptr<uint8_t> d_out8[2];
+    fav::event_h ev_out[2] = {favl::event_create(hipEventDisableTiming | hipEventDisableSystemFence), favl::event_create(hipEventDisableTiming | hipEventDisableSystemFence)};
+    fav::event_h ev_done[2] = {host_event(), host_event()};
+};
+
+// -output_y4m: no PNG at all.  The planes are written by the frame's last kernel straight into a pinned output slot
+// (fav_stream_encode_yuv), the host learns of them through an event on the compute queue -- the event-ordered path of
+// -png_encoder host, minus its download -- and ONE writer thread write()s the slots in frame order.
+class Y4mOut : public Sink {
+public:
+    // in_header, in_fmt: those of -input_y4m, null without it
+    Y4mOut(const SinkEnv& e, const fav_y4m_header* in_header, const fav_yuv_format* in_fmt) : Sink(e), in_header_(in_header), in_fmt_(in_fmt) {}
+    size_t setup(fav_stream* fs_, int Wo_, int Ho_) override
+    {
+        fs = fs_; Wo = Wo_; Ho = Ho_;
+        // the stream's header: the input's (or F25:1 Ip A1:1) with the stylised frames' size and the output's format
+        const std::string path = env.o.s("output_y4m");
+        fav_y4m_header oh;
+        if (in_header_) oh = *in_header_;
+        else { memset(&oh, 0, sizeof oh); oh.fps_num = 25; oh.fps_den = 1; oh.interlace = 'p'; oh.aspect_num = oh.aspect_den = 1; }
+        fmt_out = y4m_format_of(env.o, in_fmt_, Ho, true);
+        oh.W = Wo; oh.H = Ho; oh.fmt = fmt_out;
+        bytes = fav_yuv_frame_bytes(Wo, Ho, &fmt_out);
+        if (!bytes) die(std::string("-output_y4m: ") + fav_last_error());
+        if (path != "-") mkdirs_for(path);
+        if (!writer.open(path)) die("Could not open " + path + " for writing");
+        if (!writer.header(oh)) die("cannot write the stream header to " + path + ": " + fav_last_error());
+        return bytes;
+    }
+    void after_frame(int, uint8_t* hb) override { check(fav_stream_encode_yuv(fs, &fmt_out, hb, bytes, env.st), "fav_stream_encode_yuv"); }      // into the pinned slot
+    void hand_off(int k, uint8_t*) override { hipEventRecord(ev_done[k].get(), env.st); }    // nothing to download: the planes are in host memory when this event fires
+    void wait(int k) override { wait_host_event(ev_done[k].get()); }
+    std::string target(int index) override { return env.o.s("output_y4m") + " (frame " + std::to_string(index) + ")"; }
+    std::function<void()> writer_task(int, uint8_t* hb, const std::string& path) override
+    {
+        // the planes are in the pinned slot (the event covers them): `FRAME` and the payload, behind the frames before it
+        favy::Writer* wr = &writer; const size_t nbytes = bytes;
+        Slots* sl = env.slots; Counters* cnt = env.cnt;
+        return [hb, path, nbytes, wr, sl, cnt] {
+            const double c0 = thread_cpu_seconds();
+            if (!wr->frame(hb, nbytes)) { fprintf(stderr, "cannot write %s\n", path.c_str()); exit(1); }
+            cnt->cpu_writers_us += (long long)(1e6 * (thread_cpu_seconds() - c0));
+            sl->give(hb);
+        };
+    }
+private:
+    const fav_y4m_header* in_header_; const fav_yuv_format* in_fmt_;
+    favy::Writer writer; fav_yuv_format fmt_out{}; size_t bytes = 0;
+    fav::event_h ev_done[2] = {host_event(), host_event()};
+};
+
+struct StreamDestroy { void operator()(fav_stream* s) const { fav_stream_destroy(s); } };
+
+// One video: the loop of run_fast_neural_video (core.lua:189-229) with the video CLI's callbacks (fav.lua:93-172).
+// `net` / `net_img` live on the current device; `nwriters` PNG threads are the budget.
+// The members are destroyed in reverse order of declaration, and that order is meant: the two thread pools (`writers` here, the
+// loader's own) go before the pinned memory their tasks touch, the library's stream before the device buffers its side queues read.
+// The three queues are declared FIRST and so go last; run() drains them itself once the last frame is written, before anything is freed.
+class StreamRun {
+public:
+    StreamRun(const Opt& o, const fav_flow_opts_ex3& flow_opts, fav_net* net, fav_net* net_img, int nwriters);
+    void run(StreamResult* res);
+private:
+    struct Pending { bool valid = false; int index = 0; bool single = false; uint8_t* hb = nullptr; int k = 0; std::chrono::steady_clock::time_point t0; };
+    static int current_device() { int d = 0; (void)hipGetDevice(&d); return d; }
+    static favp::Poll poll_of(const Opt& o) { favp::Poll p; p.timeout_s = o.d("poll_timeout"); p.settle_s = std::max(0.0, o.d("poll_settle")); p.out = favl::msg(); return p; }
+    bool load_resume_state();
+    void setup(const FrameIn& cur, int i);
+    void top_up(int i);
+    void enqueue_network(FrameIn& cur, int i, uint8_t* d_out8);
+    void finish(Pending& pd);
+    uint8_t* new_slot();
+    void write_temporal_eval() const;
+
+    const Opt& o; const fav_flow_opts_ex3& flow_opts; fav_net* const net; fav_net* const net_img;
+    const bool estimate;                     // the flows come from the frames (and go through the fused check)
+    const bool fused_check, teval, backward;
+    const int border, structure;
+    const int start, end, inc;               // core:189-191
+    const favp::Poll poll;
+    const int device = current_device();
+    const double cpu0 = process_cpu_seconds(), cpu_main0 = thread_cpu_seconds();
+    Counters cnt;
+    Queues q;
+    hipStream_t const st = q.compute.get(), st_copy = q.upload.get(), st_down = q.download.get();
+    favy::Reader y4m_reader;                 // -input_y4m: one sequential reader behind the loader threads
+    int W = 0, H = 0;                        // frame size
+    int Wo = 0, Ho = 0;                      // size of the stylised frames: the network's output (H x W when both are multiples of 4)
+    DevInputs dev;
+    fav::dev_ptr<void> d_flow_ws; size_t flow_ws_bytes = 0;
+    fav::dev_ptr<float> d_prev, d_cur; std::vector<double> temporal;      // -temporal_eval_file
+    SceneCut scene;
+    // continue_with > 1: the previous stylised PNG as the recurrent state, rW x rH
+    std::vector<float> resume_state; int rW = 0, rH = 0;
+    const bool have_resume = load_resume_state();
+    // pinned output slots in flight to the PNG pool (deflate ~55 ms/frame/thread), allocated on demand, at most nslots
+    Slots slots; std::vector<fav::host_ptr<uint8_t>> h_out; size_t slot_bytes = 0; int nslots = 0;
+    std::unique_ptr<Sink> sink;
+    bool quiet = false;
+    std::unique_ptr<fav_stream, StreamDestroy> fs;
+    std::unique_ptr<Loader> loader;
+    std::unique_ptr<Pool> writers;
     // Look-ahead: frames i+1 .. i+LA are uploaded (device set of ahead[k] = dset + 1 + k) and, with the checker's 4-argument mode, their
     // masks are under way on the side queues while frame i is enqueued.  That mode needs TWO frames: a mask takes 1.5 ms behind a
     // 0.45 ms upload, a frame 1.9 ms -- one frame ahead, every frame waited 0.1 ms for its mask (period 2.05 ms: 460 frames/s;
     // profiles/r03z_cli_4arg_trace.txt)
-    const int LA = (fused_check && !estimate && o.i("structure") != 0) ? 2 : 1;
-    std::deque<FrameIn> ahead;
-    bool drained = false;
-    next_to_issue = start + inc;
-    for (int i = start; idx_ok(i) && cur.ok; i += inc) {                                                      // core:196-197
-        if (first) {
-            const int rW = -W, rH = -H;          // size of the reloaded PNG (-continue_with), if any
-            W = cur.W; H = cur.H;
-            fav_stream_opts so{border, o.i("occlusions_min_filter"), o.f("invert_occlusion") ? 1 : 0, o.f("fix_occlusions") ? 1 : 0,
-                               o.s("fill_occlusions") == "uniform-random" ? 1 : 0, (unsigned)o.i("seed")};
-            check(fav_stream_create(net, H, W, &so, &fs), "fav_stream_create");
-            check(fav_stream_output_size(fs, &Ho, &Wo), "fav_stream_output_size");
-            if (quiet) check(fav_stream_set_host_ordered(fs, 1), "fav_stream_set_host_ordered");
-            if (have_resume && (rW != Wo || rH != Ho)) die("-continue_with: the previous PNG's size differs from the stylised frames' (" + std::to_string(Wo) + "x" + std::to_string(Ho) + ")");
-            if (!o.s("temporal_eval_file").empty() && (Wo != W || Ho != H))
-                die("-temporal_eval_file: the stylised frames (" + std::to_string(Wo) + "x" + std::to_string(Ho) + ") are larger than the flow; the reference's func_eval fails on such sizes as well (fav.lua:128-151)");
-            if (net_img) check(fav_stream_set_image_net(fs, net_img), "fav_stream_set_image_net");
-            if (o.d("scale_factor") != 1.0) {            // img:view(1, 3, H * f, W * f) (core.lua:130) needs whole numbers
-                const double f = o.d("scale_factor"), hs = H * f, ws = W * f;
-                if (std::fabs(hs - std::round(hs)) > 1e-9 * hs || std::fabs(ws - std::round(ws)) > 1e-9 * ws || hs < 0.5 || ws < 0.5 || hs > 1e6 || ws > 1e6) {
-                    char msg[256];
-                    snprintf(msg, sizeof msg, "-scale_factor %s: %dx%d frames would be stylised at %gx%g; both sides must be whole numbers", o.s("scale_factor").c_str(), W, H, ws, hs);
-                    die(msg);
-                }
-                check(fav_stream_set_single_image_size(fs, (int)std::round(hs), (int)std::round(ws)), "-scale_factor");
-            }
-            const size_t n = (size_t)W * H, no = (size_t)Wo * Ho;
-            if (gpu_png && Wo > 9000) die("-png_encoder gpu encodes rows of up to 9000 pixels (one image row lives in a CU's LDS); pass -png_encoder host for " + std::to_string(Wo) + "-wide frames");
-            if (gpu_png) {
-                png_cap = fav_png_capacity(Wo, Ho);
-                for (int k = 0; k < 2; ++k) if (hipMalloc((void**)&d_png[k], png_cap) || hipMalloc((void**)&d_png_size[k], 16)) die("hipMalloc failed");
-                if (hipHostMalloc((void**)&h_png_size, 64, hipHostMallocDefault) != hipSuccess) die("hipHostMalloc failed");
-            } else if (y4m_out) {
-                // the stream's header: the input's (or F25:1 Ip A1:1) with the stylised frames' size and the output's format
-                fav_y4m_header oh;
-                if (y4m_in) oh = y4m_reader.header();
-                else { memset(&oh, 0, sizeof oh); oh.fps_num = 25; oh.fps_den = 1; oh.interlace = 'p'; oh.aspect_num = oh.aspect_den = 1; }
-                fmt_out = y4m_format_of(o, y4m_in ? &fmt_in : nullptr, Ho, true);
-                oh.W = Wo; oh.H = Ho; oh.fmt = fmt_out;
-                y4m_out_bytes = fav_yuv_frame_bytes(Wo, Ho, &fmt_out);
-                if (!y4m_out_bytes) die(std::string("-output_y4m: ") + fav_last_error());
-                if (o.s("output_y4m") != "-") mkdirs_for(o.s("output_y4m"));
-                if (!y4m_writer.open(o.s("output_y4m"))) die("Could not open " + o.s("output_y4m") + " for writing");
-                if (!y4m_writer.header(oh)) die("cannot write the stream header to " + o.s("output_y4m") + ": " + fav_last_error());
-            } else if (hipMalloc((void**)&d_out8s[0], no * 3) || hipMalloc((void**)&d_out8s[1], no * 3)) die("hipMalloc failed");
-            for (auto& dv : dev)
-                if (hipMalloc((void**)&dv.frame, n * 3) || hipMalloc((void**)&dv.cert, n) || hipMalloc((void**)&dv.bw, n * 8) ||
-                    hipMalloc((void**)&dv.fw, n * 8) || (y4m_in && hipMalloc((void**)&dv.yuv, y4m_in_bytes))) die("hipMalloc failed");
-            // pinned memory is paid for by the page (~0.2 ms per MB): two output slots now, the others when the pool first falls behind;
-            // every loader thread pins its own staging set on first use, in parallel with this thread's set-up
-            slot_bytes = y4m_out ? y4m_out_bytes : gpu_png ? png_cap : no * 3;
-            for (int k = 0; k < std::min(2, nslots); ++k) slots.add(new_slot());
-            pin_px = n; pinned_ready = true;
-            if (have_resume) {
-                float* d_state = nullptr;
-                if (hipMalloc((void**)&d_state, no * 12) != hipSuccess) die("hipMalloc failed");
-                hipMemcpy(d_state, resume_state.data(), no * 12, hipMemcpyHostToDevice);
-                check(fav_stream_set_state(fs, d_state, st), "fav_stream_set_state");
-                hipStreamSynchronize(st); hipFree(d_state);
-            }
-            if (scene) {
-                if (hipHostMalloc((void**)&h_scene, NDEV * sizeof(fav_scene_change), hipHostMallocDefault) != hipSuccess ||
-                    hipMalloc(&d_scene_ws, fav_scene_change_workspace_bytes()) != hipSuccess) die("hipMalloc failed");
-            }
-            if (estimate) {
-                flow_ws_bytes = fav_flow_pairs_workspace_bytes_ex3(W, H, 1, &flow_opts);      // room for both flows at once: the batch of one
-                if (!flow_ws_bytes) die(std::string("-estimate_flow: ") + fav_last_error());
-                if (hipMalloc(&d_flow_ws, flow_ws_bytes) != hipSuccess) die("hipMalloc failed");
-                if (!cur.single) {                       // -continue_with: the frame before the first one is read as well, into the set "before" dset
-                    const std::string pp = fmt_int(o.s("input_pattern"), i - inc);
-                    uint8_t* pf = nullptr; int pw, ph, pch;
-                    check(fav_read_pnm_host(pp.c_str(), &pf, &pw, &ph, &pch), pp.c_str());
-                    if (pch != 3 || pw != W || ph != H) die(pp + ": expected a colour (P6) frame of the sequence's size");
-                    if (hipMemcpy(dev[(dset + NDEV - 1) % NDEV].frame, pf, n * 3, hipMemcpyHostToDevice) != hipSuccess) die("upload failed");
-                    fav_free_host(pf);
-                }
-            }
-            upload(cur, dset);
-            hipStreamSynchronize(st_copy);               // the first frame's host buffers are malloc'ed: release them now
-            first = false;
-            res->setup = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();     // first frame read + every allocation
-        } else if (cur.W != W || cur.H != H) die("frame size changed inside the sequence");
-        issue();                                         // keep DEPTH loads in flight
+    const int LA;
+    std::deque<FrameIn> ahead; bool drained = false;
+    int done = 0, dset = 0;
+    double t_wait_writer = 0;
+    std::chrono::steady_clock::time_point t_begin;
+    double setup_s = 0;
+};
+
+StreamRun::StreamRun(const Opt& o_, const fav_flow_opts_ex3& fo, fav_net* net_, fav_net* net_img_, int nwriters)
+    : o(o_), flow_opts(fo), net(net_), net_img(net_img_), estimate(o.i("estimate_flow") != 0), fused_check(estimate || !o.s("forward_flow_pattern").empty()),
+      teval(!o.s("temporal_eval_file").empty()), backward(o.f("backward")), border(o.s("warp_border") == "cpu" ? FAV_BORDER_CPU : FAV_BORDER_STN),
+      structure(o.i("structure")), start(backward ? o.i("num_frames") - 1 : o.i("continue_with")), end(backward ? 1 : o.i("num_frames")), inc(backward ? -1 : 1),
+      poll(poll_of(o)), scene(o), LA((fused_check && !estimate && structure != 0) ? 2 : 1)
+{
+    const bool y4m_in = !o.s("input_y4m").empty();
+    if (y4m_in) {
+        const std::string err = y4m_reader.open(o.s("input_y4m"));
+        if (!err.empty()) die(err);
+        const fav_y4m_header& h = y4m_reader.header();
+        dev.fmt_in = y4m_format_of(o, &h.fmt, h.H, false);
+        dev.yuv_bytes = fav_yuv_frame_bytes(h.W, h.H, &dev.fmt_in);
+        if (!dev.yuv_bytes) die(std::string("-input_y4m: ") + fav_last_error());
+        y4m_reader.set_frame_bytes(dev.yuv_bytes);
+    }
+    // the output mode is chosen here, once: a sink each (above), and the writer threads it can use
+    const SinkEnv env{o, st, st_down, &slots, &cnt};
+    if (!o.s("output_y4m").empty()) {
+        sink.reset(new Y4mOut(env, y4m_in ? &y4m_reader.header() : nullptr, y4m_in ? &dev.fmt_in : nullptr));
+        nwriters = 1;                        // a stream's frames leave in order: the pool's queue is first in, first out
+    } else if (o.s("png_encoder") == "gpu") {
+        sink.reset(new DevicePng(env));
+        if (o.i("writers") <= 0) nwriters = std::min(nwriters, 4);      // they only write() finished files: 0.5 ms per frame
+    } else sink.reset(new HostPng(env));
+    quiet = sink->quiet();
+    writers.reset(new Pool(nwriters, device));
+    nslots = nwriters + 2;
+    loader.reset(new Loader(o, poll, y4m_in ? &y4m_reader : nullptr, dev.yuv_bytes, start, end, inc, !have_resume && start != 1, &cnt.cpu_loaders_us, device));
+}
+
+// continue_with > 1: reload the previous stylised PNG as the recurrent state (8-bit; the reference's
+// video CLI does not reload anything and fails, fast_artistic_video.lua:89,153-156); its size is validated against the first frame's
+bool StreamRun::load_resume_state()
+{
+    if (backward || start <= 1 || o.f("create_inconsistent")) return false;
+    std::vector<uint8_t> prev;
+    char nm[4096]; snprintf(nm, sizeof nm, "%s-%05d.png", o.s("output_prefix").c_str(), start - 1);
+    if (!read_png_rgb8(nm, prev, rW, rH)) {
+        fprintf(stderr, "warning: %s not found; frame %d is stylised without a prior\n", nm, start);
+        return false;
+    }
+    const size_t n = (size_t)rW * rH;
+    resume_state.resize(n * 3);
+    for (size_t i = 0; i < n; ++i)
+        for (int c = 0; c < 3; ++c) resume_state[(size_t)c * n + i] = prev[i * 3 + c] / 255.0f;
+    return true;
+}
+
+uint8_t* StreamRun::new_slot()
+{
+    h_out.push_back(favl::host_alloc<uint8_t>(slot_bytes));
+    sink->slot_added(h_out.back().get());
+    return h_out.back().get();
+}
+
+// the one-time set-up: the first frame (loaded synchronously) sizes every buffer
+void StreamRun::setup(const FrameIn& cur, int i)
+{
+    W = cur.W; H = cur.H;
+    fav_stream_opts so{border, o.i("occlusions_min_filter"), o.f("invert_occlusion") ? 1 : 0, o.f("fix_occlusions") ? 1 : 0,
+                       o.s("fill_occlusions") == "uniform-random" ? 1 : 0, (unsigned)o.i("seed")};
+    fav_stream* s = nullptr;
+    check(fav_stream_create(net, H, W, &so, &s), "fav_stream_create");
+    fs.reset(s);
+    check(fav_stream_output_size(s, &Ho, &Wo), "fav_stream_output_size");
+    if (quiet) check(fav_stream_set_host_ordered(s, 1), "fav_stream_set_host_ordered");
+    if (have_resume && (rW != Wo || rH != Ho)) die("-continue_with: the previous PNG's size differs from the stylised frames' (" + std::to_string(Wo) + "x" + std::to_string(Ho) + ")");
+    if (teval && (Wo != W || Ho != H))
+        die("-temporal_eval_file: the stylised frames (" + std::to_string(Wo) + "x" + std::to_string(Ho) + ") are larger than the flow; the reference's func_eval fails on such sizes as well (fav.lua:128-151)");
+    if (net_img) check(fav_stream_set_image_net(s, net_img), "fav_stream_set_image_net");
+    if (o.d("scale_factor") != 1.0) {            // img:view(1, 3, H * f, W * f) (core.lua:130) needs whole numbers
+        const double f = o.d("scale_factor"), hs = H * f, ws = W * f;
+        if (std::fabs(hs - std::round(hs)) > 1e-9 * hs || std::fabs(ws - std::round(ws)) > 1e-9 * ws || hs < 0.5 || ws < 0.5 || hs > 1e6 || ws > 1e6) {
+            char msg[256];
+            snprintf(msg, sizeof msg, "-scale_factor %s: %dx%d frames would be stylised at %gx%g; both sides must be whole numbers", o.s("scale_factor").c_str(), W, H, ws, hs);
+            die(msg);
+        }
+        check(fav_stream_set_single_image_size(s, (int)std::round(hs), (int)std::round(ws)), "-scale_factor");
+    }
+    const size_t n = (size_t)W * H, no = (size_t)Wo * Ho;
+    slot_bytes = sink->setup(s, Wo, Ho);
+    dev.alloc(W, H);
+    // pinned memory is paid for by the page (~0.2 ms per MB): two output slots now, the others when the pool first falls behind;
+    // every loader thread pins its own staging set on first use, in parallel with this thread's set-up
+    for (int k = 0; k < std::min(2, nslots); ++k) slots.add(new_slot());
+    loader->pin_px = n;
+    if (have_resume) {
+        const auto d_state = favl::dev_alloc<float>(no * 12);
+        hipMemcpy(d_state.get(), resume_state.data(), no * 12, hipMemcpyHostToDevice);
+        check(fav_stream_set_state(s, d_state.get(), st), "fav_stream_set_state");
+        hipStreamSynchronize(st);
+    }
+    if (scene.on) scene.alloc();
+    if (estimate) {
+        flow_ws_bytes = fav_flow_pairs_workspace_bytes_ex3(W, H, 1, &flow_opts);      // room for both flows at once: the batch of one
+        if (!flow_ws_bytes) die(std::string("-estimate_flow: ") + fav_last_error());
+        d_flow_ws = favl::dev_alloc<void>(flow_ws_bytes);
+        if (!cur.single) {                       // -continue_with: the frame before the first one is read as well, into the set "before" dset
+            const std::string pp = fmt_int(o.s("input_pattern"), i - inc);
+            uint8_t* pf = nullptr; int pw, ph, pch;
+            check(fav_read_pnm_host(pp.c_str(), &pf, &pw, &ph, &pch), pp.c_str());
+            if (pch != 3 || pw != W || ph != H) die(pp + ": expected a colour (P6) frame of the sequence's size");
+            if (hipMemcpy(dev.before(dset).frame.get(), pf, n * 3, hipMemcpyHostToDevice) != hipSuccess) die("upload failed");
+            fav_free_host(pf);
+        }
+    }
+    dev.upload(cur, dset, st_copy, quiet ? nullptr : st);
+    hipStreamSynchronize(st_copy);               // the first frame's host buffers are malloc'ed: release them now
+    setup_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();     // first frame read + every allocation
+}
+
+// frames i+1 (i+2): wait for the loader, upload, and start the consistency mask on the side queues so the (sequential, 1.5 ms)
+// 4-argument structure pass overlaps the network of the frames before it
+void StreamRun::top_up(int i)
+{
+    while ((int)ahead.size() < LA && !drained) {
+        FrameIn nxt;
+        if (!loader->idx_ok(i + inc * ((int)ahead.size() + 1)) || !loader->pop_next(nxt)) { drained = true; break; }
+        if (nxt.W != W || nxt.H != H) die("frame size changed inside the sequence");
+        const int nset = (dset + 1 + (int)ahead.size()) % DevInputs::N;
+        const DevInputs::Set& dn = dev.set[nset];
+        dev.upload(nxt, nset, st_copy, quiet ? nullptr : st);
+        if (scene.on) scene.measure(dev, nset, st_copy);
+        if (fused_check && !estimate && !nxt.single && (!quiet || structure != 0)) {
+            // quiet: the look-ahead may only start on inputs the host has seen arrive (0.35 ms of DMA; the GPU is busy with frame i-1)
+            if (quiet && wait_event_sleeping(dn.up.get(), 50) != hipSuccess) die("GPU error while uploading a frame");
+            check(fav_stream_prefetch_mask(fs.get(), dn.frame.get(), dn.bw.get(), dn.fw.get(), structure, st), "fav_stream_prefetch_mask");
+        }
+        ahead.push_back(nxt);
+    }
+}
+
+// frame i's network, in device set dset, behind its inputs
+void StreamRun::enqueue_network(FrameIn& cur, int i, uint8_t* d_out8)
+{
+    const DevInputs::Set& dc = dev.set[dset];
+    if (quiet && wait_event_sleeping(dc.up.get(), 50) != hipSuccess) die("GPU error while uploading a frame");      // requested a frame ago: already there
+    // a cut takes the path of a frame without a prior: image model, no flow, the recurrence starts afresh
+    if (scene.on && scene.decide(i, dset, done > 0, dev, st_copy)) cur.single = true;
+    if (teval && !d_prev) { d_prev = favl::dev_alloc<float>((size_t)W * H * 12); d_cur = favl::dev_alloc<float>((size_t)W * H * 12); }
+    if (teval && !cur.single) check(fav_stream_get_state(fs.get(), d_prev.get(), st), "fav_stream_get_state");
+    if (cur.single) {
+        check(fav_stream_first_frame(fs.get(), dc.frame.get(), nullptr, d_out8, st), "fav_stream_first_frame");       // core:203-204
+    } else if (estimate) {
+        // the previous frame in processing order is still in the device set before this one: with one frame of look-ahead the
+        // uploads only ever touch the set after it
+        check(fav_stream_next_frame_estimate_ex3(fs.get(), dc.frame.get(), dev.before(dset).frame.get(), &flow_opts, structure, dc.bw.get(), dc.fw.get(),
+                                             d_flow_ws.get(), flow_ws_bytes, nullptr, d_out8, st), "fav_stream_next_frame_estimate");
+    } else if (fused_check) {
+        check(fav_stream_next_frame_flow(fs.get(), dc.frame.get(), dc.bw.get(), dc.fw.get(), structure, nullptr, d_out8, st), "fav_stream_next_frame_flow");
+    } else {
+        check(fav_stream_next_frame_cert(fs.get(), dc.frame.get(), dc.bw.get(), dc.cert.get(), nullptr, d_out8, st), "fav_stream_next_frame_cert");   // core:206-208
+    }
+    if (teval) {                                     // fav.lua:128-151 (third number)
+        double tl = 0.0;
+        if (!cur.single) {
+            check(fav_stream_get_state(fs.get(), d_cur.get(), st), "fav_stream_get_state");
+            check(fav_temporal_loss_host(d_prev.get(), d_cur.get(), dc.bw.get(), fused_check ? fav_stream_last_mask(fs.get()) : dc.cert.get(), H, W, border, &tl, st), "fav_temporal_loss_host");
+        }
+        temporal.push_back(tl);
+    }
+}
+
+// the frame before: wait, report, hand to the writer pool
+void StreamRun::finish(Pending& pd)
+{
+    if (!pd.valid) return;
+    sink->wait(pd.k);
+    check(fav_net_check(net), "stylising a frame");      // a stream-K hand-off that timed out: fail at THIS frame, before its PNG exists
+    if (net_img) check(fav_net_check(net_img), "stylising a frame");
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - pd.t0).count();
+    if (pd.single) fprintf(favl::msg(), "Elapsed time for stylizing frame independently:%g\n", ms / 1000.0);           // core:155
+    else fprintf(favl::msg(), "Elapsed time for stylizing frame:%g\n", ms / 1000.0);                                   // core:177
+    const std::string path = sink->target(pd.index);
+    fprintf(favl::msg(), "Writing output image to %s\n", path.c_str());
+    writers->submit(sink->writer_task(pd.k, pd.hb, path));
+    pd.valid = false;
+}
+
+void StreamRun::write_temporal_eval() const             // core.lua:231-238 layout: values joined by ';', then the mean
+{
+    FILE* f = fopen(o.s("temporal_eval_file").c_str(), "a");
+    if (!f) die("cannot open " + o.s("temporal_eval_file"));
+    double sum = 0.0;
+    for (size_t k = 0; k < temporal.size(); ++k) { fprintf(f, "%s%.9g", k ? ";" : "", temporal[k]); sum += temporal[k]; }
+    fprintf(f, "\n%.9g\n", sum / (double)temporal.size());
+    fclose(f);
+}
+
+void StreamRun::run(StreamResult* res)
+{
+    t_begin = std::chrono::steady_clock::now();
+    double t_gpu = 0;
+    Pending pend;                                // the host runs one frame ahead of the GPU: frame i is enqueued before frame i-1's completion is awaited
+    FrameIn cur = loader->load(start, !have_resume && start != 1, nullptr);      // the first frame is loaded synchronously (its size sizes every buffer)
+    loader->next_to_issue = start + inc;
+    for (int i = start; loader->idx_ok(i) && cur.ok; i += inc) {                                              // core:196-197
+        if (!fs) setup(cur, i);
+        else if (cur.W != W || cur.H != H) die("frame size changed inside the sequence");
+        loader->issue();
         const auto t0 = std::chrono::steady_clock::now();
         static const bool loop_trace = diag_env("FAV_LOOP_TRACE") != nullptr;      // where a loop iteration's host time goes (frames 100-111)
         double tr_ms[6] = {0, 0, 0, 0, 0, 0};
         auto tr_mark = [&](int k) { if (loop_trace) tr_ms[k] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
-        // frames i+1 (i+2): wait for the loader, upload, and start the consistency mask on the side queues so the (sequential, 1.5 ms)
-        // 4-argument structure pass overlaps the network of the frames before it
-        const Dev& dc = dev[dset];
-        auto top_up = [&]() {
-        while ((int)ahead.size() < LA && !drained) {
-            FrameIn nxt;
-            if (!idx_ok(i + inc * ((int)ahead.size() + 1)) || !pop_next(nxt)) { drained = true; break; }
-            if (nxt.W != W || nxt.H != H) die("frame size changed inside the sequence");
-            const int nset = (dset + 1 + (int)ahead.size()) % NDEV;
-            const Dev& dn = dev[nset];
-            upload(nxt, nset);
-            if (scene) {         // behind the upload, on its queue: the frame before `nxt` in processing order is in the set before it
-                h_scene[nset].total = SCENE_PENDING;
-                check(fav_scene_change_rgb8(dev[(nset + NDEV - 1) % NDEV].frame, dn.frame, W, H, d_scene_ws, fav_scene_change_workspace_bytes(),
-                                            &h_scene[nset], st_copy), "fav_scene_change_rgb8");
-            }
-            if (fused_check && !estimate && !nxt.single && (!quiet || o.i("structure") != 0)) {
-                // quiet: the look-ahead may only start on inputs the host has seen arrive (0.35 ms of DMA; the GPU is busy with frame i-1)
-                if (quiet && wait_event_sleeping(ev_up[nset], 50) != hipSuccess) die("GPU error while uploading a frame");
-                check(fav_stream_prefetch_mask(fs, dn.frame, dn.bw, dn.fw, o.i("structure"), st), "fav_stream_prefetch_mask");
-            }
-            ahead.push_back(nxt);
-        }
-        };
         tr_mark(0);      // (the look-ahead is topped up BEHIND the frame's enqueue, also for the first frame: its enqueue is 15 ms of one-time
                          //  work -- activation arena, code objects -- that now runs while the loaders read and pin frames 2, 3, ...)
-        if (quiet && wait_event_sleeping(ev_up[dset], 50) != hipSuccess) die("GPU error while uploading a frame");      // requested a frame ago: already there
-        if (scene) {             // is frame i a cut?  Its measure was enqueued a frame ago, behind its upload
-            uint32_t total = 0; double score = 0.0; bool cut = false;
-            if (done > 0) {          // (the first frame has nothing in front of it)
-                volatile uint32_t* tw = &h_scene[dset].total;
-                for (int spins = 0; *tw == SCENE_PENDING; ++spins) {
-                    usleep(50);
-                    if ((spins & 2047) == 2047) {             // every ~0.1 s: has the GPU faulted? (a query, not a marker)
-                        const hipError_t e = hipStreamQuery(st_copy);
-                        if (e != hipSuccess && e != hipErrorNotReady) die("GPU error while measuring a scene change");
-                    }
-                }
-                total = *tw;
-                score = (double)total / (2.0 * (double)W * (double)H);
-                cut = score > scene_T;
-            }
-            if (cut) cur.single = true;          // the path of a frame without a prior: image model, no flow, the recurrence starts afresh
-            if (scene_log) fprintf(scene_log, "%d %u %.6f %d\n", i, total, score, cut ? 1 : 0);
-        }
-        uint8_t* const d_out8 = (gpu_png || y4m_out) ? nullptr : d_out8s[done & 1];
-        const bool teval = !o.s("temporal_eval_file").empty();
-        if (teval && !d_prev) { if (hipMalloc((void**)&d_prev, (size_t)W * H * 12) || hipMalloc((void**)&d_cur, (size_t)W * H * 12)) die("hipMalloc failed"); }
-        if (teval && !cur.single) check(fav_stream_get_state(fs, d_prev, st), "fav_stream_get_state");
-        if (cur.single) {
-            check(fav_stream_first_frame(fs, dc.frame, nullptr, d_out8, st), "fav_stream_first_frame");       // core:203-204
-        } else if (estimate) {
-            // the previous frame in processing order is still in the device set before this one: with one frame of look-ahead the
-            // uploads only ever touch the set after it
-            check(fav_stream_next_frame_estimate_ex3(fs, dc.frame, dev[(dset + NDEV - 1) % NDEV].frame, &flow_opts, o.i("structure"), dc.bw, dc.fw,
-                                                 d_flow_ws, flow_ws_bytes, nullptr, d_out8, st), "fav_stream_next_frame_estimate");
-        } else if (fused_check) {
-            check(fav_stream_next_frame_flow(fs, dc.frame, dc.bw, dc.fw, o.i("structure"), nullptr, d_out8, st), "fav_stream_next_frame_flow");
-        } else {
-            check(fav_stream_next_frame_cert(fs, dc.frame, dc.bw, dc.cert, nullptr, d_out8, st), "fav_stream_next_frame_cert");   // core:206-208
-        }
-        if (teval) {                                     // fav.lua:128-151 (third number)
-            double tl = 0.0;
-            if (!cur.single) {
-                check(fav_stream_get_state(fs, d_cur, st), "fav_stream_get_state");
-                check(fav_temporal_loss_host(d_prev, d_cur, dc.bw, fused_check ? fav_stream_last_mask(fs) : dc.cert, H, W, border, &tl, st), "fav_temporal_loss_host");
-            }
-            temporal.push_back(tl);
-        }
+        Pending now; now.valid = true; now.index = i; now.k = done & 1; now.t0 = t0;
+        enqueue_network(cur, i, sink->frame_out(now.k));
+        now.single = cur.single;
         tr_mark(1);                                      // frame i enqueued
         const auto tw = std::chrono::steady_clock::now();
-        uint8_t* hb = slots.try_take();                  // a pinned output slot nobody is reading ...
-        if (!hb) hb = (int)h_out.size() < nslots ? new_slot() : slots.take();      // ... a new one while allowed, else wait for the PNG pool
+        now.hb = slots.try_take();                       // a pinned output slot nobody is reading ...
+        if (!now.hb) now.hb = (int)h_out.size() < nslots ? new_slot() : slots.take();      // ... a new one while allowed, else wait for the PNG pool
         t_wait_writer += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw).count();
-        Pending now; now.valid = true; now.index = i; now.single = cur.single; now.hb = hb; now.ev = done & 1; now.t0 = t0;
-        if (gpu_png) {
-            // two frames ago this buffer's bytes left through the download queue: that copy must have finished (it has, long ago)
-            if (png_copy_ev[now.ev]) {
-                if (quiet) { if (wait_event_sleeping(png_copy_ev[now.ev], 50) != hipSuccess) die("GPU error while downloading a frame"); }
-                else hipStreamWaitEvent(st, png_copy_ev[now.ev], 0);
-            }
-            if (quiet) h_png_size[now.ev] = 0u;          // the frame's last kernel overwrites it with the file size (host-mapped)
-            // -png_overlap 1 (quiet mode): on the stream's encoder queue, next to frame i + 1's network -- the host learns of the file
-            // through its size word either way
-            if (quiet && png_overlap) check(fav_stream_encode_png_async(fs, d_png[now.ev], png_cap, &h_png_size[now.ev], st), "fav_stream_encode_png_async");
-            else check(fav_stream_encode_png(fs, d_png[now.ev], png_cap, quiet ? &h_png_size[now.ev] : d_png_size[now.ev], st), "fav_stream_encode_png");
-        }
-        if (y4m_out) check(fav_stream_encode_yuv(fs, &fmt_out, hb, y4m_out_bytes, st), "fav_stream_encode_yuv");      // into the pinned slot
-        if (!quiet && !y4m_out) hipEventRecord(ev_out[now.ev], st);  // the frame's 8-bit image / PNG is complete on the compute queue ...
+        sink->after_frame(now.k, now.hb);
         tr_mark(2);                                      // PNG encode enqueued
-        top_up();                                        // behind frame i's kernels: the 0.45 ms this waits for the upload are not in front of them
+        top_up(i);                                       // behind frame i's kernels: the 0.45 ms this waits for the upload are not in front of them
         const auto tg = std::chrono::steady_clock::now();
         finish(pend);                                    // frame i-1: wait, report, hand to the PNG pool -- frame i's kernels are already queued
         t_gpu += std::chrono::duration<double>(std::chrono::steady_clock::now() - tg).count();
@@ -854,60 +993,32 @@ void run_stream(const Opt& o, const fav_flow_opts_ex3& flow_opts, fav_net* net, 
                     std::chrono::duration<double, std::milli>(t0 - t_begin).count(), tr_ms[0], tr_ms[1], tr_ms[2], tr_ms[3]);
         if (loop_trace && !loop_trace_start && done >= 100 && done < 112)
             fprintf(stderr, "loop trace frame %d: look-ahead %.3f  frame enqueued %.3f  encode enqueued %.3f  previous frame finished %.3f ms\n", i, tr_ms[0], tr_ms[1], tr_ms[2], tr_ms[3]);
-        if (y4m_out) hipEventRecord(ev_done[now.ev], st);    // nothing to download: the planes are in host memory when this event fires
-        else if (!quiet) {
-            hipStreamWaitEvent(st_down, ev_out[now.ev], 0);  // ... and leaves on the download queue
-            if (gpu_png) hipMemcpyAsync(&h_png_size[now.ev], d_png_size[now.ev], 4, hipMemcpyDeviceToHost, st_down);      // (the bytes follow in finish(), exactly `size` of them)
-            else hipMemcpyAsync(hb, d_out8, (size_t)Wo * Ho * 3, hipMemcpyDeviceToHost, st_down);
-            hipEventRecord(ev_done[now.ev], st_down);
-        }
+        sink->hand_off(now.k, now.hb);
         pend = now;
         if (cur.index >= 0) cur.release();               // malloc'ed (first frame); pinned sets are reused
         ++done;
         if (ahead.empty()) break;
-        cur = ahead.front(); ahead.pop_front(); dset = (dset + 1) % NDEV;
+        cur = ahead.front(); ahead.pop_front(); dset = (dset + 1) % DevInputs::N;
     }
     finish(pend);
     const auto t_tail = std::chrono::steady_clock::now();       // the GPU is done: what follows is the PNG pool draining
-    for (auto& pr : inflight) pr.second.get();
-    for (auto& r : ready) if (r.index >= 0) r.release();
+    loader->finish();
     fflush(favl::msg());
-    writers.wait_below(0);
-    if (y4m_in && y4m_reader.failed_at()) {              // the complete frames before it are written: now it is an error
+    writers->wait_below(0);
+    if (y4m_reader.failed_at()) {                        // -input_y4m; the complete frames before it are written: now it is an error
         fflush(favl::msg());
         die(o.s("input_y4m") + (y4m_reader.failure() == favy::Reader::TRUNCATED ? ": the stream ends inside frame " : ": no FRAME marker (or a read error) at frame ") +
             std::to_string(y4m_reader.failed_at()));
     }
-    if (!temporal.empty()) {                             // core.lua:231-238 layout: values joined by ';', then the mean
-        FILE* f = fopen(o.s("temporal_eval_file").c_str(), "a");
-        if (!f) die("cannot open " + o.s("temporal_eval_file"));
-        double sum = 0.0;
-        for (size_t k = 0; k < temporal.size(); ++k) { fprintf(f, "%s%.9g", k ? ";" : "", temporal[k]); sum += temporal[k]; }
-        fprintf(f, "\n%.9g\n", sum / (double)temporal.size());
-        fclose(f);
-    }
-    res->frames = done;
+    if (!temporal.empty()) write_temporal_eval();
+    res->frames = done; res->setup = setup_s;
     res->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
     res->tail = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_tail).count();
-    res->wait_loader = t_wait_load; res->wait_gpu = t_gpu; res->wait_png = t_wait_writer;
-    res->cpu_s = process_cpu_seconds() - cpu0; res->png_bytes = png_bytes_total.load();
-    res->cpu_loaders = 1e-6 * cpu_loaders_us.load(); res->cpu_writers = 1e-6 * cpu_writers_us.load(); res->cpu_main = thread_cpu_seconds() - cpu_main0;
-    res->cpu_writer_sync = 1e-6 * cpu_writer_sync_us.load();
-    for (int k = 0; k < 2; ++k) { hipFree(d_png[k]); hipFree(d_png_size[k]); }
-    if (h_png_size) hipHostFree(h_png_size);
-    for (auto& kv : slot_ev) hipEventDestroy(kv.second);
-    fav_stream_destroy(fs);
-    hipFree(d_prev); hipFree(d_cur); hipFree(d_flow_ws);
-    if (scene_log) fclose(scene_log);
-    if (h_scene) hipHostFree(h_scene);
-    hipFree(d_scene_ws);
-    hipFree(d_out8s[0]); hipFree(d_out8s[1]); for (auto& dv : dev) { hipFree(dv.frame); hipFree(dv.cert); hipFree(dv.bw); hipFree(dv.fw); hipFree(dv.yuv); }
-    for (auto p : h_out) hipHostFree(p);
-    for (auto& p : pin) { hipHostFree(p.frame); hipHostFree(p.bw); hipHostFree(p.fw); hipHostFree(p.cert); hipHostFree(p.yuv); }
-    for (auto& e : ev_up) hipEventDestroy(e);
-    for (auto& e : ev_done) hipEventDestroy(e);
-    for (auto& e : ev_out) hipEventDestroy(e);
-    hipStreamDestroy(st); hipStreamDestroy(st_copy); hipStreamDestroy(st_down);
+    res->wait_loader = loader->t_wait; res->wait_gpu = t_gpu; res->wait_png = t_wait_writer;
+    res->cpu_s = process_cpu_seconds() - cpu0; res->png_bytes = cnt.png_bytes.load();
+    res->cpu_loaders = 1e-6 * cnt.cpu_loaders_us.load(); res->cpu_writers = 1e-6 * cnt.cpu_writers_us.load(); res->cpu_main = thread_cpu_seconds() - cpu_main0;
+    res->cpu_writer_sync = 1e-6 * cnt.cpu_writer_sync_us.load();
+    q.drain();           // every frame has been waited for; nothing may still be queued when the members below `q` free what the queues used
 }
 
 }  // namespace
@@ -929,7 +1040,7 @@ int main(int argc, char** argv)
            {"png_level", "1"}, {"png_encoder", "gpu"}, {"png_overlap", "0"}, {"writers", "0"}, {"timing", "0"}, {"temporal_eval_file", ""}, {"seed", "1"}, {"precision", "fp32"},
            {"input_y4m", ""}, {"output_y4m", ""}, {"y4m_matrix", "auto"}, {"y4m_range", "auto"}, {"y4m_format", ""},
            {"scene_cut", "0"}, {"scene_cut_log", ""},
-           {"estimate_flow", "0"}, {"flow_alpha", "0"}, {"flow_eps", "0"}, {"flow_grad", "0"}, {"flow_match", "0"}, {"flow_median", "0"}, {"flow_iters", "0"}, {"flow_warps", "0"}, {"flow_levels", "0"},
+           {"estimate_flow", "0"}, {"flow_levels", "0"},      // (the other -flow_* flags: favl::add_flow_flags below)
            {"streams", ""}, {"gpus", "1"}, {"force_dist", "0"}, {"dry_run", "0"}, {"shared_gpu", "0"}, {"pin_workers", "1"},
            // internal (set by the launcher for its workers)
            {"worker_rank", "-1"}, {"worker_world", "0"}, {"rccl_id_file", ""},
@@ -938,6 +1049,7 @@ int main(int argc, char** argv)
            {"load_probe", "0"}};
     o.b = {{"invert_occlusion", false}, {"fix_occlusions", false}, {"backward", false}, {"create_inconsistent", false},
            {"evaluate", false}, {"invert_occlusion_eval", false}, {"fix_occlusions_eval", false}, {"backward_eval", false}};
+    favl::add_flow_flags(o.v);
     for (int a = 1; a < argc; ++a) {
         if (argv[a][0] != '-') die(std::string("invalid argument: ") + argv[a]);
         const std::string k = argv[a] + 1;
@@ -972,13 +1084,8 @@ int main(int argc, char** argv)
         if (T > 0.0 && o.f("create_inconsistent")) die("-scene_cut " + sc + " cannot be combined with -create_inconsistent: no frame has a prior there");
         if (!o.s("scene_cut_log").empty() && T == 0.0) die("-scene_cut_log needs -scene_cut: without it no frame is measured");
     }
-    if (o.s("flow_grad") != "0" && o.s("flow_grad") != "1") die("-flow_grad must be 0 or 1, not '" + o.s("flow_grad") + "'");
-    if (o.i("flow_grad") && !estimate) die("-flow_grad 1 selects the data term of the built-in flow estimator: it needs -estimate_flow 1");
-    if (o.s("flow_match") != "0" && o.s("flow_match") != "1") die("-flow_match must be 0 or 1, not '" + o.s("flow_match") + "'");
-    if (o.i("flow_match") && !estimate) die("-flow_match 1 turns on the matching prior of the built-in flow estimator: it needs -estimate_flow 1");
-    if (o.s("flow_median") != "0" && o.s("flow_median") != "3" && o.s("flow_median") != "5") die("-flow_median must be 0, 3 or 5, not '" + o.s("flow_median") + "'");
-    if (o.i("flow_median") && !estimate) die("-flow_median " + o.s("flow_median") + " turns on the median filter of the built-in flow estimator: it needs -estimate_flow 1");
-    const fav_flow_opts_ex3 flow_opts = flow_opts_of(o);
+    favl::validate_flow_flags(o.v, estimate, "-estimate_flow 1");
+    const fav_flow_opts_ex3 flow_opts = favl::flow_opts_of(o.v);
     if (estimate) {
         for (const char* k : {"flow_pattern", "forward_flow_pattern", "occlusions_pattern"})
             if (!o.s(k).empty()) die(std::string("-estimate_flow 1 computes both flows and the certainty from the frames: it cannot be combined with -") + k);
@@ -1090,7 +1197,7 @@ int main(int argc, char** argv)
         if (named) for (const char* po : path_opts) os.v[po] = favl::subst_stream(o.s(po), name);
         if (named) os.v["scene_cut_log"] = favl::subst_stream(o.s("scene_cut_log"), name);
         StreamResult r;
-        run_stream(os, flow_opts, net, net_img, nwriters, &r);
+        StreamRun(os, flow_opts, net, net_img, nwriters).run(&r);
         frames += r.frames; seconds += r.seconds; cpu_seconds += r.cpu_s;
         if (o.i("timing"))
             fprintf(favl::msg(), "{%s\"frames\": %d, \"seconds\": %.4f, \"fps_end_to_end\": %.3f, \"wait_loader_s\": %.3f, \"h2d_gpu_d2h_s\": %.3f, \"wait_png_pool_s\": %.3f, \"setup_s\": %.3f, \"png_tail_s\": %.3f, \"png_writers\": %d, "

@@ -31,47 +31,26 @@
 #include <cstring>
 #include <future>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/fav.h"
+#include "fav_cli.h"
 #include "fav_launcher.h"
 #include "fav_poll.h"
 
 namespace {
 
-using favl::die;
-void check(int rc, const char* what) { if (rc) die(std::string(what) + ": " + fav_last_error()); }
+using favl::die; using favl::check; using favl::file_exists; using favl::mkdirs_for; using favl::fmt_int; using favl::flow_name; using favl::read_polled;
+using Flags = favl::Flags; using Bools = std::map<std::string, bool>;
 void hipc(hipError_t e, const char* what) { if (e != hipSuccess) die(std::string(what) + ": " + hipGetErrorString(e)); }
-bool file_exists(const std::string& p) { struct stat st; return stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode); }
+template <class T> fav::dev_ptr<T> dev_alloc(size_t bytes) { return favl::dev_alloc<T>(bytes, "hipMalloc"); }
 
-std::string fmt1(const std::string& pattern, int a) { char b[4096]; snprintf(b, sizeof b, pattern.c_str(), a); return b; }
-std::string fmt2(const std::string& pattern, int a, int c) { char b[4096]; snprintf(b, sizeof b, pattern.c_str(), a, c); return b; }
+struct VrDestroy { void operator()(fav_vr* p) const { fav_vr_destroy(p); } };
+using vr_h = std::unique_ptr<fav_vr, VrDestroy>;
 
-// getFormatedFlowFileName (fast_artistic_video_vr.lua:105-115): {fmt} <- from, [fmt] <- to, then the remaining %d <- face id
-std::string flow_name(const std::string& pattern, int from, int to, int face)
-{
-    std::string out;
-    for (size_t p = 0; p < pattern.size();) {
-        const char c = pattern[p];
-        if (c == '{' || c == '[') {
-            const size_t e = pattern.find(c == '{' ? '}' : ']', p + 1);
-            if (e != std::string::npos) { out += fmt1(pattern.substr(p + 1, e - p - 1), c == '{' ? from : to); p = e + 1; continue; }
-        }
-        out += c; ++p;
-    }
-    return fmt1(out, face);
-}
-
-// utils.lua:74-80 with the settle rule of fav_poll.h: wait, read, poll again while the file reads short under its producer
-template <class Reader>
-void read_polled(const std::string& path, const favp::Poll& p, const char* what, Reader&& reader)
-{
-    bool timed_out = false;
-    const int rc = favp::read_when_complete(path, p, reader, &timed_out);
-    if (timed_out) die("timed out waiting for " + path);
-    check(rc, what);
-}
+static const int proc_order[6] = {6, 1, 2, 5, 3, 4};                                                               // :103
 
 // a finished input: there, not empty and not modified for -poll_settle seconds (what wait_for_file accepts at its first look)
 bool ready_now(const std::string& path, double settle_s)
@@ -80,38 +59,122 @@ bool ready_now(const std::string& path, double settle_s)
     return stat(path.c_str(), &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0 && favp::wall_age_seconds(st) >= settle_s;
 }
 
-void mkdirs_for(const std::string& path)
+vr_h vr_create(Flags& v, Bools& b, fav_net* vid, fav_net* img, int H, int W)
 {
-    for (size_t p = 1; p < path.size(); ++p) if (path[p] == '/') mkdir(path.substr(0, p).c_str(), 0777);
+    auto I = [&](const char* k) { return atoi(v[k].c_str()); };
+    fav_vr_opts o{};
+    o.overlap_w = I("overlap_pixel_w"); o.overlap_h = I("overlap_pixel_h"); o.occlusions_min_filter = I("occlusions_min_filter");
+    o.median_filter = I("median_filter"); o.fill_random = v["fill_occlusions"] == "uniform-random"; o.seed = (unsigned)I("seed");
+    o.create_inconsistent = b["create_inconsistent"]; o.create_inconsistent_border = b["create_inconsistent_border"];
+    o.out_equi_w = b["out_equi"] ? I("out_equi_w") : 0; o.out_equi_h = b["out_equi"] ? I("out_equi_h") : 0;
+    o.border_mode = v["warp_border"] == "cpu" ? FAV_BORDER_CPU : FAV_BORDER_STN;
+    fav_vr* vr = nullptr;
+    check(fav_vr_create(vid, img, H, W, &o, &vr), "fav_vr_create");
+    return vr_h(vr);
+}
+
+// A finished frame's way out of the device, the same in both input modes (:527-557): the equirectangular and / or cube-map image,
+// -png_encoder gpu (default): as finished PNG files (fav_png_encode_rgb8); host: zlib on the writer thread, -png_level.  One frame is
+// written in the background while the next one computes.
+struct VrOutput {
+    int ew = 0, eh = 0, cw = 0, ch = 0;
+    bool gpu_png = false; int png_level = 1; std::string prefix;
+    fav::dev_ptr<uint8_t> d_equi, d_cube, d_png_e, d_png_c; fav::dev_ptr<uint32_t> d_png_n; fav::dev_ptr<void> d_png_ws;
+    size_t png_ws_bytes = 0, cap_e = 0, cap_c = 0;
+    std::vector<uint8_t> h_equi, h_cube;
+    std::future<void> writer;
+
+    void setup(fav_vr* vr, Flags& v, Bools& b)
+    {
+        gpu_png = v["png_encoder"] == "gpu"; png_level = atoi(v["png_level"].c_str()); prefix = v["output_prefix"];
+        check(fav_vr_output_sizes(vr, &ew, &eh, &cw, &ch, nullptr, nullptr), "fav_vr_output_sizes");
+        if (b["out_cubemap"] && !cw) die("-out_cubemap needs square cropped faces");
+        if (gpu_png && (ew > 9000 || (b["out_cubemap"] && cw > 9000))) die("-png_encoder gpu encodes rows of up to 9000 pixels; pass -png_encoder host for these output sizes");
+        if (ew) { d_equi = dev_alloc<uint8_t>((size_t)ew * eh * 3); h_equi.resize((size_t)ew * eh * 3); }
+        if (b["out_cubemap"]) { d_cube = dev_alloc<uint8_t>((size_t)cw * ch * 3); h_cube.resize((size_t)cw * ch * 3); }
+        if (!gpu_png) return;
+        if (d_equi) { cap_e = fav_png_capacity(ew, eh); d_png_e = dev_alloc<uint8_t>(cap_e); h_equi.resize(cap_e); png_ws_bytes = std::max(png_ws_bytes, fav_png_workspace_bytes(ew, eh)); }
+        if (d_cube) { cap_c = fav_png_capacity(cw, ch); d_png_c = dev_alloc<uint8_t>(cap_c); h_cube.resize(cap_c); png_ws_bytes = std::max(png_ws_bytes, fav_png_workspace_bytes(cw, ch)); }
+        d_png_n = dev_alloc<uint32_t>(16);
+        hipc(hipMemset(d_png_n.get(), 0, 16), "hipMemset");      // (the size word of an output that is not asked for is read back too)
+        if (png_ws_bytes) d_png_ws = dev_alloc<void>(png_ws_bytes);
+    }
+    void wait() { if (writer.valid()) writer.get(); }
+    // the six faces of frame out_idx are through: assemble, encode, download, and write in the background
+    void write_frame(fav_vr* vr, fav_net* vid, int out_idx, hipStream_t st)
+    {
+        wait();
+        check(fav_vr_finish_frame(vr, d_equi.get(), d_cube.get(), st), "fav_vr_finish_frame");
+        uint32_t png_n[2] = {0, 0};
+        if (gpu_png) {
+            if (d_equi) check(fav_png_encode_rgb8(d_equi.get(), ew, eh, d_png_e.get(), cap_e, d_png_n.get(), d_png_ws.get(), png_ws_bytes, st), "fav_png_encode_rgb8");
+            if (d_cube) check(fav_png_encode_rgb8(d_cube.get(), cw, ch, d_png_c.get(), cap_c, d_png_n.get() + 1, d_png_ws.get(), png_ws_bytes, st), "fav_png_encode_rgb8");   // (same stream: the workspace is free again)
+            hipc(hipMemcpyAsync(png_n, d_png_n.get(), 8, hipMemcpyDeviceToHost, st), "D2H");
+            hipc(hipStreamSynchronize(st), "sync");
+            if (png_n[0] > cap_e || png_n[1] > cap_c) die("fav_png_encode_rgb8 returned an impossible size");
+            if (d_equi) hipc(hipMemcpyAsync(h_equi.data(), d_png_e.get(), png_n[0], hipMemcpyDeviceToHost, st), "D2H");
+            if (d_cube) hipc(hipMemcpyAsync(h_cube.data(), d_png_c.get(), png_n[1], hipMemcpyDeviceToHost, st), "D2H");
+        } else {
+            if (d_equi) hipc(hipMemcpyAsync(h_equi.data(), d_equi.get(), h_equi.size(), hipMemcpyDeviceToHost, st), "D2H");
+            if (d_cube) hipc(hipMemcpyAsync(h_cube.data(), d_cube.get(), h_cube.size(), hipMemcpyDeviceToHost, st), "D2H");
+        }
+        hipc(hipStreamSynchronize(st), "sync");
+        check(fav_net_check(vid), "finishing a frame");
+        std::vector<uint8_t> e = h_equi, cb = h_cube;
+        if (gpu_png) { e.resize(d_equi ? png_n[0] : 0); cb.resize(d_cube ? png_n[1] : 0); }
+        writer = std::async(std::launch::async, [e, cb, out_idx, prefix = prefix, gpu = gpu_png, lvl = png_level, ew = ew, eh = eh, cw = cw, ch = ch]() {
+            auto put = [&](const char* kind, const std::vector<uint8_t>& bytes, int pw, int ph) {
+                if (bytes.empty()) return;
+                char name[4096];
+                snprintf(name, sizeof name, "%s-%05d_%s.png", prefix.c_str(), out_idx, kind); mkdirs_for(name);
+                if (gpu) {                                                       // the bytes ARE the file
+                    FILE* f = fopen(name, "wb");
+                    if (!f || fwrite(bytes.data(), 1, bytes.size(), f) != bytes.size() || fclose(f)) die(std::string("writing ") + name + " failed");
+                } else if (fav_write_png_rgb8_host(name, bytes.data(), pw, ph, lvl)) die(std::string("writing ") + name + ": " + fav_last_error());
+            };
+            put("equi", e, ew, eh); put("cubemap", cb, cw, ch);
+        });
+    }
+};
+
+// the end of a video, in the order that matters: the last file, the library's state, the networks' verdict, and the queue -- which
+// the library must not wait on before the next video's first forward.  The caller's buffers go after it, the queue drained.
+double end_video(VrOutput& out, vr_h& vr, fav::queue_h& st, fav_net* vid, fav_net* img, bool timing, int frames_done, std::chrono::steady_clock::time_point t_all)
+{
+    out.wait();
+    if (timing && frames_done) {
+        const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_all).count();
+        printf("%d frames (x6 faces) in %.3f s: %.2f frames/s\n", frames_done, s, frames_done / s);
+    }
+    vr.reset();
+    check(fav_net_check(vid), "stylising the video");
+    if (img) check(fav_net_check(img), "stylising the video (image model)");
+    (void)fav_net_forget_stream(vid, st.get());
+    st.reset();
+    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_all).count();
 }
 
 // one 360-degree video: the loop of run_fast_neural_video with fast_artistic_video_vr.lua's callbacks (:103-302,454-591)
-int run_video(std::map<std::string, std::string>& v, std::map<std::string, bool>& b, fav_net* vid, fav_net* img, double* seconds_out)
+int run_video(Flags& v, Bools& b, fav_net* vid, fav_net* img, double* seconds_out)
 {
     auto I = [&](const char* k) { return atoi(v[k].c_str()); };
     const bool timing = I("timing") != 0;
-    static const int proc_order[6] = {6, 1, 2, 5, 3, 4};                                                           // :103
-    hipStream_t st; hipc(hipStreamCreate(&st), "hipStreamCreate");
-    fav_vr* vr = nullptr;
-    int W = 0, H = 0, ew = 0, eh = 0, cw = 0, ch = 0;
+    fav::queue_h st_h = favl::queue_create("hipStreamCreate"); hipStream_t const st = st_h.get();
+    int W = 0, H = 0;
     // -forward_flow_pattern: the check runs on the device; the six faces of a frame then have their own input buffers (a mask started
     // ahead of its face reads them until that face is through), otherwise set 0 serves every face
     const bool fused = !v["forward_flow_pattern"].empty(); const int use_structure = I("structure");
     const int nset = fused ? 6 : 1;
-    uint8_t* d_frame6[6] = {}; float* d_bw6[6] = {}; float* d_fw6[6] = {}; bool loaded[6] = {};
-    uint8_t *d_cert = nullptr, *d_equi = nullptr, *d_cube = nullptr;
+    fav::dev_ptr<uint8_t> d_frame6[6], d_cert; fav::dev_ptr<float> d_bw6[6], d_fw6[6]; bool loaded[6] = {};
+    VrOutput out;
+    vr_h vr;                                 // declared after the buffers its side stream reads: it goes first
     favp::Poll poll; poll.timeout_s = atof(v["poll_timeout"].c_str()); poll.settle_s = std::max(0.0, atof(v["poll_settle"].c_str()));
-    std::vector<uint8_t> h_equi, h_cube;
-    // -png_encoder gpu (default): the two output images leave the device as finished PNG files (fav_png_encode_rgb8); host: zlib, -png_level
-    const bool gpu_png = v["png_encoder"] == "gpu";
-    uint8_t *d_png_e = nullptr, *d_png_c = nullptr; uint32_t* d_png_n = nullptr; void* d_png_ws = nullptr; size_t png_ws_bytes = 0, cap_e = 0, cap_c = 0;
-    std::future<void> writer;
     const int start = I("start_frame"), total = I("num_frames") * 6;                                              // :571
     const auto t_all = std::chrono::steady_clock::now();
     int frames_done = 0;
     for (int i = 1; i <= total; ++i) {
         const int mode = (i - 1) % 6, file_idx = (i - 1) / 6 + start, face = proc_order[mode];                     // :155-156
-        const std::string img_path = fmt2(v["input_pattern"], file_idx, face);
+        const std::string img_path = fmt_int(v["input_pattern"], file_idx, face);
         if (!file_exists(img_path)) break;                                                                          // :160
         const bool temporal = i >= 7 && !b["create_inconsistent"];
         const int set = fused ? mode : 0;
@@ -121,7 +184,7 @@ int run_video(std::map<std::string, std::string>& v, std::map<std::string, bool>
             std::vector<void*> held;
             for (int k = 0; k < 6; ++k) {
                 loaded[k] = false;
-                const std::string ip = fmt2(v["input_pattern"], file_idx, proc_order[k]);
+                const std::string ip = fmt_int(v["input_pattern"], file_idx, proc_order[k]);
                 const std::string bp = flow_name(v["flow_pattern"], file_idx - 1, file_idx, proc_order[k]);
                 const std::string fp = flow_name(v["forward_flow_pattern"], file_idx - 1, file_idx, proc_order[k]);
                 if (!ready_now(ip, poll.settle_s) || !ready_now(bp, poll.settle_s) || !ready_now(fp, poll.settle_s)) continue;
@@ -130,10 +193,10 @@ int run_video(std::map<std::string, std::string>& v, std::map<std::string, bool>
                                 fav_read_flo_host(fp.c_str(), &ff, &fw_, &fh_) == 0 && ic == 3 && iw == W && ih == H && bw_ == W && bh_ == H && fw_ == W && fh_ == H;
                 held.push_back(r8); held.push_back(bf); held.push_back(ff);
                 if (!ok) continue;                                               // (its own turn reports what is wrong with it)
-                hipc(hipMemcpyAsync(d_frame6[k], r8, (size_t)W * H * 3, hipMemcpyHostToDevice, st), "H2D frame");
-                hipc(hipMemcpyAsync(d_bw6[k], bf, (size_t)W * H * 8, hipMemcpyHostToDevice, st), "H2D flow");
-                hipc(hipMemcpyAsync(d_fw6[k], ff, (size_t)W * H * 8, hipMemcpyHostToDevice, st), "H2D forward flow");
-                check(fav_vr_prefetch_mask(vr, i + k, d_frame6[k], d_bw6[k], d_fw6[k], use_structure, st), "fav_vr_prefetch_mask");
+                hipc(hipMemcpyAsync(d_frame6[k].get(), r8, (size_t)W * H * 3, hipMemcpyHostToDevice, st), "H2D frame");
+                hipc(hipMemcpyAsync(d_bw6[k].get(), bf, (size_t)W * H * 8, hipMemcpyHostToDevice, st), "H2D flow");
+                hipc(hipMemcpyAsync(d_fw6[k].get(), ff, (size_t)W * H * 8, hipMemcpyHostToDevice, st), "H2D forward flow");
+                check(fav_vr_prefetch_mask(vr.get(), i + k, d_frame6[k].get(), d_bw6[k].get(), d_fw6[k].get(), use_structure, st), "fav_vr_prefetch_mask");
                 loaded[k] = true;
             }
             hipc(hipStreamSynchronize(st), "sync");                              // the copies have left the host buffers
@@ -145,33 +208,16 @@ int run_video(std::map<std::string, std::string>& v, std::map<std::string, bool>
         if (c != 3) die(img_path + ": not a P6 image");
         if (!vr) {
             W = w; H = h;
-            fav_vr_opts o{};
-            o.overlap_w = I("overlap_pixel_w"); o.overlap_h = I("overlap_pixel_h"); o.occlusions_min_filter = I("occlusions_min_filter");
-            o.median_filter = I("median_filter"); o.fill_random = v["fill_occlusions"] == "uniform-random"; o.seed = (unsigned)I("seed");
-            o.create_inconsistent = b["create_inconsistent"]; o.create_inconsistent_border = b["create_inconsistent_border"];
-            o.out_equi_w = b["out_equi"] ? I("out_equi_w") : 0; o.out_equi_h = b["out_equi"] ? I("out_equi_h") : 0;
-            o.border_mode = v["warp_border"] == "cpu" ? FAV_BORDER_CPU : FAV_BORDER_STN;
-            check(fav_vr_create(vid, img, H, W, &o, &vr), "fav_vr_create");
-            check(fav_vr_output_sizes(vr, &ew, &eh, &cw, &ch, nullptr, nullptr), "fav_vr_output_sizes");
-            if (b["out_cubemap"] && !cw) die("-out_cubemap needs square cropped faces");
+            vr = vr_create(v, b, vid, img, H, W);
+            out.setup(vr.get(), v, b);
             for (int k = 0; k < nset; ++k) {
-                hipc(hipMalloc(reinterpret_cast<void**>(&d_frame6[k]), (size_t)W * H * 3), "hipMalloc");
-                hipc(hipMalloc(reinterpret_cast<void**>(&d_bw6[k]), (size_t)W * H * 8), "hipMalloc");
-                if (fused) hipc(hipMalloc(reinterpret_cast<void**>(&d_fw6[k]), (size_t)W * H * 8), "hipMalloc");
+                d_frame6[k] = dev_alloc<uint8_t>((size_t)W * H * 3);
+                d_bw6[k] = dev_alloc<float>((size_t)W * H * 8);
+                if (fused) d_fw6[k] = dev_alloc<float>((size_t)W * H * 8);
             }
-            if (!fused) hipc(hipMalloc(reinterpret_cast<void**>(&d_cert), (size_t)W * H), "hipMalloc");
-            if (ew) { hipc(hipMalloc(reinterpret_cast<void**>(&d_equi), (size_t)ew * eh * 3), "hipMalloc"); h_equi.resize((size_t)ew * eh * 3); }
-            if (b["out_cubemap"]) { hipc(hipMalloc(reinterpret_cast<void**>(&d_cube), (size_t)cw * ch * 3), "hipMalloc"); h_cube.resize((size_t)cw * ch * 3); }
-            if (gpu_png && (ew > 9000 || (b["out_cubemap"] && cw > 9000))) die("-png_encoder gpu encodes rows of up to 9000 pixels; pass -png_encoder host for these output sizes");
-            if (gpu_png) {
-                if (ew) { cap_e = fav_png_capacity(ew, eh); hipc(hipMalloc(reinterpret_cast<void**>(&d_png_e), cap_e), "hipMalloc"); h_equi.resize(cap_e); png_ws_bytes = std::max(png_ws_bytes, fav_png_workspace_bytes(ew, eh)); }
-                if (b["out_cubemap"]) { cap_c = fav_png_capacity(cw, ch); hipc(hipMalloc(reinterpret_cast<void**>(&d_png_c), cap_c), "hipMalloc"); h_cube.resize(cap_c); png_ws_bytes = std::max(png_ws_bytes, fav_png_workspace_bytes(cw, ch)); }
-                hipc(hipMalloc(reinterpret_cast<void**>(&d_png_n), 16), "hipMalloc");
-                hipc(hipMemset(d_png_n, 0, 16), "hipMemset");      // (the size word of an output that is not asked for is read back too)
-                if (png_ws_bytes) hipc(hipMalloc(&d_png_ws, png_ws_bytes), "hipMalloc");
-            }
+            if (!fused) d_cert = dev_alloc<uint8_t>((size_t)W * H);
         } else if (w != W || h != H) die(img_path + ": face size changed");
-        uint8_t* d_frame = d_frame6[set]; float* d_flow = d_bw6[set]; float* d_fwd = d_fw6[set];
+        uint8_t* d_frame = d_frame6[set].get(); float* d_flow = d_bw6[set].get(); float* d_fwd = d_fw6[set].get();
         if (!have) hipc(hipMemcpyAsync(d_frame, rgb, (size_t)W * H * 3, hipMemcpyHostToDevice, st), "H2D frame");
         float* flo = nullptr; float* fwd = nullptr; uint8_t* cert = nullptr;
         if (temporal && !have) {                                                                                    // :225-229, :274-278
@@ -186,13 +232,13 @@ int run_video(std::map<std::string, std::string>& v, std::map<std::string, bool>
             }
             read_polled(fp, poll, "reading the flow", [&] { return fav_read_flo_host(fp.c_str(), &flo, &fw, &fh); });
             if (cc != 1 || cw_ != W || ch_ != H || fw != W || fh != H || gw != W || gh != H) die("flow / certainty size does not match the face: " + fp);
-            if (cert) hipc(hipMemcpyAsync(d_cert, cert, (size_t)W * H, hipMemcpyHostToDevice, st), "H2D cert");
+            if (cert) hipc(hipMemcpyAsync(d_cert.get(), cert, (size_t)W * H, hipMemcpyHostToDevice, st), "H2D cert");
             if (fwd) hipc(hipMemcpyAsync(d_fwd, fwd, (size_t)W * H * 8, hipMemcpyHostToDevice, st), "H2D forward flow");
             hipc(hipMemcpyAsync(d_flow, flo, (size_t)W * H * 8, hipMemcpyHostToDevice, st), "H2D flow");
         }
         const auto t0 = std::chrono::steady_clock::now();
-        if (fused) check(fav_vr_face_flow(vr, i, d_frame, temporal ? d_flow : nullptr, temporal ? d_fwd : nullptr, use_structure, nullptr, st), "fav_vr_face_flow");
-        else check(fav_vr_face(vr, i, d_frame, temporal ? d_flow : nullptr, temporal ? d_cert : nullptr, nullptr, st), "fav_vr_face");
+        if (fused) check(fav_vr_face_flow(vr.get(), i, d_frame, temporal ? d_flow : nullptr, temporal ? d_fwd : nullptr, use_structure, nullptr, st), "fav_vr_face_flow");
+        else check(fav_vr_face(vr.get(), i, d_frame, temporal ? d_flow : nullptr, temporal ? d_cert.get() : nullptr, nullptr, st), "fav_vr_face");
         hipc(hipStreamSynchronize(st), "sync");
         // a stream-K hand-off that timed out: fail at THIS face, before any output derived from it is written (fav.h: the check
         // comes before a PNG is queued); the image model stylises the faces without a prior
@@ -200,194 +246,74 @@ int run_video(std::map<std::string, std::string>& v, std::map<std::string, bool>
         if (img) check(fav_net_check(img), "stylising a face (image model)");
         if (timing) printf("Elapsed time for stylizing face %d of frame %d: %.4f\n", face, file_idx, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
         fav_free_host(rgb); fav_free_host(flo); fav_free_host(fwd); fav_free_host(cert);
-        if (mode == 5) {                                                                                            // :527-557
-            if (writer.valid()) writer.get();
-            check(fav_vr_finish_frame(vr, d_equi, b["out_cubemap"] ? d_cube : nullptr, st), "fav_vr_finish_frame");
-            uint32_t png_n[2] = {0, 0};
-            if (gpu_png) {
-                if (d_equi) check(fav_png_encode_rgb8(d_equi, ew, eh, d_png_e, cap_e, d_png_n, d_png_ws, png_ws_bytes, st), "fav_png_encode_rgb8");
-                if (d_cube) check(fav_png_encode_rgb8(d_cube, cw, ch, d_png_c, cap_c, d_png_n + 1, d_png_ws, png_ws_bytes, st), "fav_png_encode_rgb8");   // (same stream: the workspace is free again)
-                hipc(hipMemcpyAsync(png_n, d_png_n, 8, hipMemcpyDeviceToHost, st), "D2H");
-                hipc(hipStreamSynchronize(st), "sync");
-                if (png_n[0] > cap_e || png_n[1] > cap_c) die("fav_png_encode_rgb8 returned an impossible size");
-                if (d_equi) hipc(hipMemcpyAsync(h_equi.data(), d_png_e, png_n[0], hipMemcpyDeviceToHost, st), "D2H");
-                if (d_cube) hipc(hipMemcpyAsync(h_cube.data(), d_png_c, png_n[1], hipMemcpyDeviceToHost, st), "D2H");
-            } else {
-                if (d_equi) hipc(hipMemcpyAsync(h_equi.data(), d_equi, h_equi.size(), hipMemcpyDeviceToHost, st), "D2H");
-                if (d_cube) hipc(hipMemcpyAsync(h_cube.data(), d_cube, h_cube.size(), hipMemcpyDeviceToHost, st), "D2H");
-            }
-            hipc(hipStreamSynchronize(st), "sync");
-            check(fav_net_check(vid), "finishing a frame");
-            const int out_idx = (i - 1) / 6 + 1;                                                                    // :517 (not offset by -start_frame)
-            const std::string prefix = v["output_prefix"]; const int lvl = I("png_level");
-            std::vector<uint8_t> e = h_equi, cb = h_cube;
-            if (gpu_png) { e.resize(d_equi ? png_n[0] : 0); cb.resize(d_cube ? png_n[1] : 0); }
-            writer = std::async(std::launch::async, [=]() {
-                char name[4096];
-                auto put = [&](const char* nm, const std::vector<uint8_t>& bytes) {          // the bytes ARE the file (GPU encoder)
-                    FILE* f = fopen(nm, "wb");
-                    if (!f || fwrite(bytes.data(), 1, bytes.size(), f) != bytes.size() || fclose(f)) die(std::string("writing ") + nm + " failed");
-                };
-                if (!e.empty()) {
-                    snprintf(name, sizeof name, "%s-%05d_equi.png", prefix.c_str(), out_idx); mkdirs_for(name);
-                    if (gpu_png) put(name, e);
-                    else if (fav_write_png_rgb8_host(name, e.data(), ew, eh, lvl)) die(std::string("writing ") + name + ": " + fav_last_error());
-                }
-                if (!cb.empty()) {
-                    snprintf(name, sizeof name, "%s-%05d_cubemap.png", prefix.c_str(), out_idx); mkdirs_for(name);
-                    if (gpu_png) put(name, cb);
-                    else if (fav_write_png_rgb8_host(name, cb.data(), cw, ch, lvl)) die(std::string("writing ") + name + ": " + fav_last_error());
-                }
-            });
-            ++frames_done;
-        }
+        if (mode == 5) { out.write_frame(vr.get(), vid, (i - 1) / 6 + 1, st); ++frames_done; }                      // :517 (not offset by -start_frame)
     }
-    if (writer.valid()) writer.get();
-    if (timing && frames_done) {
-        const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_all).count();
-        printf("%d frames (x6 faces) in %.3f s: %.2f frames/s\n", frames_done, s, frames_done / s);
-    }
-    if (vr) fav_vr_destroy(vr);
-    check(fav_net_check(vid), "stylising the video");
-    if (img) check(fav_net_check(img), "stylising the video (image model)");
-    for (int k = 0; k < 6; ++k) { (void)hipFree(d_frame6[k]); (void)hipFree(d_bw6[k]); (void)hipFree(d_fw6[k]); }
-    (void)hipFree(d_cert); (void)hipFree(d_equi); (void)hipFree(d_cube);
-    (void)hipFree(d_png_e); (void)hipFree(d_png_c); (void)hipFree(d_png_n); (void)hipFree(d_png_ws);
-    (void)fav_net_forget_stream(vid, st);      // the library must not wait on this handle before the next video's first forward
-    hipStreamDestroy(st);
-    *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_all).count();
+    *seconds_out = end_video(out, vr, st_h, vid, img, timing, frames_done, t_all);
     return frames_done;
 }
 
 // -input_equi_pattern: the same video from its equirectangular frames alone.  Per frame one PPM goes to the device, one launch makes the
 // six faces (fav_vr_equi_to_faces_rgb8), one batched call estimates the twelve flows between the previous faces and these
 // (fav_flow_pairs_rgb8), the six masks start on the library's side stream and the faces run through fav_vr_face_flow as in the file
-// mode with -forward_flow_pattern; no face, flow or certainty file exists.  Everything is enqueued on one stream.  (run_video above is
-// the reference's file contract and stays as it is; the frame's way out of the device is restated here.)
-int run_video_equi(std::map<std::string, std::string>& v, std::map<std::string, bool>& b, const fav_flow_opts_ex3& fo, fav_net* vid, fav_net* img, double* seconds_out)
+// mode with -forward_flow_pattern; no face, flow or certainty file exists.  Everything is enqueued on one stream.
+int run_video_equi(Flags& v, Bools& b, const fav_flow_opts_ex3& fo, fav_net* vid, fav_net* img, double* seconds_out)
 {
     auto I = [&](const char* k) { return atoi(v[k].c_str()); };
-    const bool timing = I("timing") != 0, gpu_png = v["png_encoder"] == "gpu", inconsistent = b["create_inconsistent"];
-    static const int proc_order[6] = {6, 1, 2, 5, 3, 4};                                                           // :103
+    const bool timing = I("timing") != 0, inconsistent = b["create_inconsistent"];
     const int W = I("cube_edge_length"), H = W, use_structure = I("structure"), start = I("start_frame"), count = I("num_frames");
-    hipStream_t st; hipc(hipStreamCreate(&st), "hipStreamCreate");
-    fav_vr* vr = nullptr;
-    fav_vr_opts o{};
-    o.overlap_w = I("overlap_pixel_w"); o.overlap_h = I("overlap_pixel_h"); o.occlusions_min_filter = I("occlusions_min_filter");
-    o.median_filter = I("median_filter"); o.fill_random = v["fill_occlusions"] == "uniform-random"; o.seed = (unsigned)I("seed");
-    o.create_inconsistent = inconsistent; o.create_inconsistent_border = b["create_inconsistent_border"];
-    o.out_equi_w = b["out_equi"] ? I("out_equi_w") : 0; o.out_equi_h = b["out_equi"] ? I("out_equi_h") : 0;
-    o.border_mode = v["warp_border"] == "cpu" ? FAV_BORDER_CPU : FAV_BORDER_STN;
-    check(fav_vr_create(vid, img, H, W, &o, &vr), "fav_vr_create");
-    int ew = 0, eh = 0, cw = 0, ch = 0;
-    check(fav_vr_output_sizes(vr, &ew, &eh, &cw, &ch, nullptr, nullptr), "fav_vr_output_sizes");
-    if (b["out_cubemap"] && !cw) die("-out_cubemap needs square cropped faces");
-    if (gpu_png && (ew > 9000 || (b["out_cubemap"] && cw > 9000))) die("-png_encoder gpu encodes rows of up to 9000 pixels; pass -png_encoder host for these output sizes");
+    fav::queue_h st_h = favl::queue_create("hipStreamCreate"); hipStream_t const st = st_h.get();
     // two sets of six faces (previous, current), the twelve flows, the estimator's workspace, the source frame
+    fav::dev_ptr<uint8_t> faces_h[2][6], d_src; fav::dev_ptr<float> bw_h[6], fw_h[6]; fav::dev_ptr<void> d_flow_ws;
+    uint8_t* d_faces[2][6] = {}; float* d_bw[6] = {}; float* d_fw[6] = {};      // what the library's calls take: arrays of plain pointers
+    VrOutput out;
+    vr_h vr = vr_create(v, b, vid, img, H, W);        // declared after the buffers its side stream reads: it goes first
+    out.setup(vr.get(), v, b);
     const size_t face_bytes = (size_t)W * H * 3, flow_bytes = (size_t)W * H * 8;
-    uint8_t* d_faces[2][6] = {}; float* d_bw[6] = {}; float* d_fw[6] = {};
     for (int k = 0; k < 6; ++k) {
-        hipc(hipMalloc(reinterpret_cast<void**>(&d_faces[0][k]), face_bytes), "hipMalloc");
-        hipc(hipMalloc(reinterpret_cast<void**>(&d_faces[1][k]), face_bytes), "hipMalloc");
-        if (!inconsistent) { hipc(hipMalloc(reinterpret_cast<void**>(&d_bw[k]), flow_bytes), "hipMalloc"); hipc(hipMalloc(reinterpret_cast<void**>(&d_fw[k]), flow_bytes), "hipMalloc"); }
+        d_faces[0][k] = (faces_h[0][k] = dev_alloc<uint8_t>(face_bytes)).get();
+        d_faces[1][k] = (faces_h[1][k] = dev_alloc<uint8_t>(face_bytes)).get();
+        if (!inconsistent) { d_bw[k] = (bw_h[k] = dev_alloc<float>(flow_bytes)).get(); d_fw[k] = (fw_h[k] = dev_alloc<float>(flow_bytes)).get(); }
     }
-    void* d_flow_ws = nullptr; size_t flow_ws_bytes = 0;
+    size_t flow_ws_bytes = 0;
     if (!inconsistent) {
         flow_ws_bytes = fav_flow_pairs_workspace_bytes_ex3(W, H, 6, &fo);
         if (!flow_ws_bytes) die(std::string("-input_equi_pattern: ") + fav_last_error());
-        hipc(hipMalloc(&d_flow_ws, flow_ws_bytes), "hipMalloc");
+        d_flow_ws = dev_alloc<void>(flow_ws_bytes);
     }
-    uint8_t *d_src = nullptr, *d_equi = nullptr, *d_cube = nullptr; int sw = 0, sh = 0;
-    std::vector<uint8_t> h_equi, h_cube;
-    uint8_t *d_png_e = nullptr, *d_png_c = nullptr; uint32_t* d_png_n = nullptr; void* d_png_ws = nullptr; size_t png_ws_bytes = 0, cap_e = 0, cap_c = 0;
-    if (ew) { hipc(hipMalloc(reinterpret_cast<void**>(&d_equi), (size_t)ew * eh * 3), "hipMalloc"); h_equi.resize((size_t)ew * eh * 3); }
-    if (b["out_cubemap"]) { hipc(hipMalloc(reinterpret_cast<void**>(&d_cube), (size_t)cw * ch * 3), "hipMalloc"); h_cube.resize((size_t)cw * ch * 3); }
-    if (gpu_png) {
-        if (ew) { cap_e = fav_png_capacity(ew, eh); hipc(hipMalloc(reinterpret_cast<void**>(&d_png_e), cap_e), "hipMalloc"); h_equi.resize(cap_e); png_ws_bytes = std::max(png_ws_bytes, fav_png_workspace_bytes(ew, eh)); }
-        if (b["out_cubemap"]) { cap_c = fav_png_capacity(cw, ch); hipc(hipMalloc(reinterpret_cast<void**>(&d_png_c), cap_c), "hipMalloc"); h_cube.resize(cap_c); png_ws_bytes = std::max(png_ws_bytes, fav_png_workspace_bytes(cw, ch)); }
-        hipc(hipMalloc(reinterpret_cast<void**>(&d_png_n), 16), "hipMalloc");
-        hipc(hipMemset(d_png_n, 0, 16), "hipMemset");
-        if (png_ws_bytes) hipc(hipMalloc(&d_png_ws, png_ws_bytes), "hipMalloc");
-    }
-    std::future<void> writer;
+    int sw = 0, sh = 0;
     const auto t_all = std::chrono::steady_clock::now();
     int frames_done = 0;
     for (int n = 0; n < count; ++n) {
         const int file_idx = start + n, cur = n & 1, prev = cur ^ 1;
-        const std::string path = fmt1(v["input_equi_pattern"], file_idx);
+        const std::string path = fmt_int(v["input_equi_pattern"], file_idx);
         if (!file_exists(path)) break;
         uint8_t* rgb = nullptr; int w = 0, h = 0, c = 0;
         check(fav_read_pnm_host(path.c_str(), &rgb, &w, &h, &c), "reading the equirectangular frame");
         if (c != 3) die(path + ": not a P6 image");
-        if (!d_src) { sw = w; sh = h; hipc(hipMalloc(reinterpret_cast<void**>(&d_src), (size_t)w * h * 3), "hipMalloc"); }
+        if (!d_src) { sw = w; sh = h; d_src = dev_alloc<uint8_t>((size_t)w * h * 3); }
         else if (w != sw || h != sh) die(path + ": frame size changed");
-        hipc(hipMemcpyAsync(d_src, rgb, (size_t)sw * sh * 3, hipMemcpyHostToDevice, st), "H2D frame");
-        check(fav_vr_equi_to_faces_rgb8(d_src, sw, sh, H, W, o.overlap_w, o.overlap_h, I("supersample"), d_faces[cur], nullptr, st), "fav_vr_equi_to_faces_rgb8");
+        hipc(hipMemcpyAsync(d_src.get(), rgb, (size_t)sw * sh * 3, hipMemcpyHostToDevice, st), "H2D frame");
+        check(fav_vr_equi_to_faces_rgb8(d_src.get(), sw, sh, H, W, I("overlap_pixel_w"), I("overlap_pixel_h"), I("supersample"), d_faces[cur], nullptr, st), "fav_vr_equi_to_faces_rgb8");
         const bool temporal = n > 0 && !inconsistent;
         const int i0 = n * 6 + 1;                                              // the frame's first face, 1-based and frame-major
         if (temporal) {
-            check(fav_flow_pairs_rgb8_ex3(d_faces[prev], d_faces[cur], 6, W, H, &fo, d_bw, d_fw, d_flow_ws, flow_ws_bytes, st), "fav_flow_pairs_rgb8_ex3");
-            for (int k = 0; k < 6; ++k) check(fav_vr_prefetch_mask(vr, i0 + k, d_faces[cur][k], d_bw[k], d_fw[k], use_structure, st), "fav_vr_prefetch_mask");
+            check(fav_flow_pairs_rgb8_ex3(d_faces[prev], d_faces[cur], 6, W, H, &fo, d_bw, d_fw, d_flow_ws.get(), flow_ws_bytes, st), "fav_flow_pairs_rgb8_ex3");
+            for (int k = 0; k < 6; ++k) check(fav_vr_prefetch_mask(vr.get(), i0 + k, d_faces[cur][k], d_bw[k], d_fw[k], use_structure, st), "fav_vr_prefetch_mask");
         }
         hipc(hipStreamSynchronize(st), "sync");                                // the copy has left the host buffer
         fav_free_host(rgb);
         for (int k = 0; k < 6; ++k) {
             const auto t0 = std::chrono::steady_clock::now();
-            check(fav_vr_face_flow(vr, i0 + k, d_faces[cur][k], temporal ? d_bw[k] : nullptr, temporal ? d_fw[k] : nullptr, use_structure, nullptr, st), "fav_vr_face_flow");
+            check(fav_vr_face_flow(vr.get(), i0 + k, d_faces[cur][k], temporal ? d_bw[k] : nullptr, temporal ? d_fw[k] : nullptr, use_structure, nullptr, st), "fav_vr_face_flow");
             hipc(hipStreamSynchronize(st), "sync");
             check(fav_net_check(vid), "stylising a face");                       // before any output derived from the face is written
             if (img) check(fav_net_check(img), "stylising a face (image model)");
             if (timing) printf("Elapsed time for stylizing face %d of frame %d: %.4f\n", proc_order[k], file_idx, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
         }
-        if (writer.valid()) writer.get();
-        check(fav_vr_finish_frame(vr, d_equi, d_cube, st), "fav_vr_finish_frame");
-        uint32_t png_n[2] = {0, 0};
-        if (gpu_png) {
-            if (d_equi) check(fav_png_encode_rgb8(d_equi, ew, eh, d_png_e, cap_e, d_png_n, d_png_ws, png_ws_bytes, st), "fav_png_encode_rgb8");
-            if (d_cube) check(fav_png_encode_rgb8(d_cube, cw, ch, d_png_c, cap_c, d_png_n + 1, d_png_ws, png_ws_bytes, st), "fav_png_encode_rgb8");
-            hipc(hipMemcpyAsync(png_n, d_png_n, 8, hipMemcpyDeviceToHost, st), "D2H");
-            hipc(hipStreamSynchronize(st), "sync");
-            if (png_n[0] > cap_e || png_n[1] > cap_c) die("fav_png_encode_rgb8 returned an impossible size");
-            if (d_equi) hipc(hipMemcpyAsync(h_equi.data(), d_png_e, png_n[0], hipMemcpyDeviceToHost, st), "D2H");
-            if (d_cube) hipc(hipMemcpyAsync(h_cube.data(), d_png_c, png_n[1], hipMemcpyDeviceToHost, st), "D2H");
-        } else {
-            if (d_equi) hipc(hipMemcpyAsync(h_equi.data(), d_equi, h_equi.size(), hipMemcpyDeviceToHost, st), "D2H");
-            if (d_cube) hipc(hipMemcpyAsync(h_cube.data(), d_cube, h_cube.size(), hipMemcpyDeviceToHost, st), "D2H");
-        }
-        hipc(hipStreamSynchronize(st), "sync");
-        check(fav_net_check(vid), "finishing a frame");
-        const int out_idx = n + 1;                                              // :517 (not offset by -start_frame)
-        const std::string prefix = v["output_prefix"]; const int lvl = I("png_level");
-        std::vector<uint8_t> e = h_equi, cb = h_cube;
-        if (gpu_png) { e.resize(d_equi ? png_n[0] : 0); cb.resize(d_cube ? png_n[1] : 0); }
-        writer = std::async(std::launch::async, [=]() {
-            auto put = [&](const char* kind, const std::vector<uint8_t>& bytes, int pw, int ph) {
-                if (bytes.empty()) return;
-                char name[4096];
-                snprintf(name, sizeof name, "%s-%05d_%s.png", prefix.c_str(), out_idx, kind); mkdirs_for(name);
-                if (gpu_png) {                                                   // the bytes ARE the file
-                    FILE* f = fopen(name, "wb");
-                    if (!f || fwrite(bytes.data(), 1, bytes.size(), f) != bytes.size() || fclose(f)) die(std::string("writing ") + name + " failed");
-                } else if (fav_write_png_rgb8_host(name, bytes.data(), pw, ph, lvl)) die(std::string("writing ") + name + ": " + fav_last_error());
-            };
-            put("equi", e, ew, eh); put("cubemap", cb, cw, ch);
-        });
+        out.write_frame(vr.get(), vid, n + 1, st);                              // :517 (not offset by -start_frame)
         ++frames_done;
     }
-    if (writer.valid()) writer.get();
-    if (timing && frames_done) {
-        const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_all).count();
-        printf("%d frames (x6 faces) in %.3f s: %.2f frames/s\n", frames_done, s, frames_done / s);
-    }
-    fav_vr_destroy(vr);
-    check(fav_net_check(vid), "stylising the video");
-    if (img) check(fav_net_check(img), "stylising the video (image model)");
-    for (int k = 0; k < 6; ++k) { (void)hipFree(d_faces[0][k]); (void)hipFree(d_faces[1][k]); (void)hipFree(d_bw[k]); (void)hipFree(d_fw[k]); }
-    (void)hipFree(d_flow_ws); (void)hipFree(d_src); (void)hipFree(d_equi); (void)hipFree(d_cube);
-    (void)hipFree(d_png_e); (void)hipFree(d_png_c); (void)hipFree(d_png_n); (void)hipFree(d_png_ws);
-    (void)fav_net_forget_stream(vid, st);
-    hipStreamDestroy(st);
-    *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_all).count();
+    *seconds_out = end_video(out, vr, st_h, vid, img, timing, frames_done, t_all);
     return frames_done;
 }
 
@@ -396,7 +322,7 @@ int run_video_equi(std::map<std::string, std::string>& v, std::map<std::string, 
 int main(int argc, char** argv)
 {
     std::map<std::string, std::string> v = {
-        {"input_pattern", ""}, {"input_equi_pattern", ""}, {"cube_edge_length", "768"}, {"supersample", "2"}, {"flow_alpha", "0"}, {"flow_eps", "0"}, {"flow_grad", "0"}, {"flow_match", "0"}, {"flow_median", "0"}, {"flow_warps", "0"}, {"flow_iters", "0"},
+        {"input_pattern", ""}, {"input_equi_pattern", ""}, {"cube_edge_length", "768"}, {"supersample", "2"},
         {"flow_pattern", ""}, {"occlusions_pattern", ""}, {"forward_flow_pattern", ""}, {"structure", "1"}, {"model_img", ""}, {"model_vid", ""},
         {"start_frame", "1"}, {"continue_with", "1"}, {"num_frames", "9999"}, {"occlusions_min_filter", "7"},
         {"fill_occlusions", "vgg-mean"}, {"overlap_pixel_w", "20"}, {"overlap_pixel_h", "20"}, {"output_prefix", "out"},
@@ -410,6 +336,7 @@ int main(int argc, char** argv)
         {"invert_occlusions", false}, {"fix_occlusions", false}, {"smooth_certainty", false}, {"create_inconsistent", false},
         {"create_inconsistent_border", false}, {"backward", false}, {"out_equi", false}, {"out_cubemap", false}, {"evaluate", false},
         {"no_consistency_eval", false}, {"invert_occlusions_eval", false}, {"backward_eval", false}, {"fix_occlusions_eval", false}};
+    favl::add_flow_flags(v);
     for (int a = 1; a < argc; ++a) {                       // torch.CmdLine: -flag value | -boolflag
         std::string k = argv[a];
         if (k.size() < 2 || k[0] != '-') die("unknown argument " + k);
@@ -423,16 +350,8 @@ int main(int argc, char** argv)
     // -input_equi_pattern: the faces are made from the equirectangular frames and both flows of every face are estimated from them, so
     // no face, flow or certainty file exists and none may be named
     const bool from_equi = !v["input_equi_pattern"].empty();
-    if (v["flow_grad"] != "0" && v["flow_grad"] != "1") die("-flow_grad must be 0 or 1, not '" + v["flow_grad"] + "'");
-    if (I("flow_grad") && !from_equi) die("-flow_grad 1 selects the data term of the built-in flow estimator: it needs -input_equi_pattern");
-    // the estimator's options from the -flow_* flags: validated here, used by run_video_equi
-    if (v["flow_match"] != "0" && v["flow_match"] != "1") die("-flow_match must be 0 or 1, not '" + v["flow_match"] + "'");
-    if (I("flow_match") && !from_equi) die("-flow_match 1 turns on the matching prior of the built-in flow estimator: it needs -input_equi_pattern");
-    if (v["flow_median"] != "0" && v["flow_median"] != "3" && v["flow_median"] != "5") die("-flow_median must be 0, 3 or 5, not '" + v["flow_median"] + "'");
-    if (I("flow_median") && !from_equi) die("-flow_median " + v["flow_median"] + " turns on the median filter of the built-in flow estimator: it needs -input_equi_pattern");
-    const fav_flow_opts_ex3 fo{{{{0, I("flow_warps"), I("flow_iters"), (float)atof(v["flow_alpha"].c_str()), 0, (float)atof(v["flow_eps"].c_str())}, I("flow_grad")},
-                                I("flow_match") ? -1.f : 0.f, 0},
-                               I("flow_median")};
+    favl::validate_flow_flags(v, from_equi, "-input_equi_pattern");
+    const fav_flow_opts_ex3 fo = favl::flow_opts_of(v);      // used by run_video_equi
     if (from_equi) {
         for (const char* k : {"input_pattern", "flow_pattern", "forward_flow_pattern", "occlusions_pattern"})
             if (!v[k].empty()) die(std::string("-input_equi_pattern makes the faces and their flows from the equirectangular frames: it cannot be combined with -") + k);

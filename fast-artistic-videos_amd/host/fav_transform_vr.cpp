@@ -21,21 +21,11 @@
 #include <vector>
 
 #include "../../include/fav.h"
+#include "fav_cli.h"
 
 namespace {
 
-[[noreturn]] void die(const std::string& msg) { fprintf(stderr, "%s\n", msg.c_str()); exit(1); }
-bool file_exists(const std::string& p) { struct stat st; return stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode); }
-void mkdirs_for(const std::string& path) { for (size_t p = 1; p < path.size(); ++p) if (path[p] == '/') mkdir(path.substr(0, p).c_str(), 0777); }
-
-bool parse_int(const std::string& s, int* out)
-{
-    char* end = nullptr;
-    const long v = strtol(s.c_str(), &end, 10);
-    if (end == s.c_str() || *end != '\0' || v < -1000000 || v > 1000000) return false;
-    *out = (int)v;
-    return true;
-}
+using favl::die; using favl::file_exists; using favl::mkdirs_for; using favl::parse_int;
 
 bool write_ppm(const std::string& path, const uint8_t* rgb, int W, int H)
 {
@@ -67,7 +57,7 @@ int main(int argc, char** argv)
     for (auto kv : {std::make_pair("cube_edge_length", &edge), std::make_pair("overlap_pixel_w", &ovw), std::make_pair("overlap_pixel_h", &ovh),
                     std::make_pair("supersample", &ss), std::make_pair("start_frame", &start), std::make_pair("num_frames", &count),
                     std::make_pair("gpu", &gpu), std::make_pair("dry_run", &dry)})
-        if (!parse_int(v[kv.first], kv.second)) die(std::string("bad value for -") + kv.first + ": '" + v[kv.first] + "'");
+        if (!parse_int(v[kv.first].c_str(), kv.second)) die(std::string("bad value for -") + kv.first + ": '" + v[kv.first] + "'");
     if (v["input_equi_pattern"].empty()) die("Must give -input_equi_pattern");
     if (v["output_pattern"].empty()) die("Must give -output_pattern");
     if (edge < 16 || edge > 16384) die("-cube_edge_length must be 16 .. 16384, not " + v["cube_edge_length"]);
@@ -85,9 +75,8 @@ int main(int argc, char** argv)
     if (hipSetDevice(gpu) != hipSuccess) die("cannot select GPU " + v["gpu"]);
     static const int proc_order[6] = {6, 1, 2, 5, 3, 4};                      // fast_artistic_video_vr.lua:103
     const size_t face_bytes = (size_t)edge * edge * 3;
-    uint8_t* d_equi = nullptr; uint8_t* d_faces = nullptr; uint8_t* faces[6];
-    if (hipMalloc((void**)&d_faces, 6 * face_bytes) != hipSuccess) die("hipMalloc failed");
-    for (int k = 0; k < 6; ++k) faces[k] = d_faces + k * face_bytes;
+    fav::dev_ptr<uint8_t> d_equi; const fav::dev_ptr<uint8_t> d_faces = favl::dev_alloc<uint8_t>(6 * face_bytes); uint8_t* faces[6];
+    for (int k = 0; k < 6; ++k) faces[k] = d_faces.get() + k * face_bytes;
     std::vector<uint8_t> h_faces(6 * face_bytes);
     int ew = 0, eh = 0, done = 0;
     char name[4096];
@@ -97,12 +86,12 @@ int main(int argc, char** argv)
         uint8_t* rgb = nullptr; int w, h, c;
         if (fav_read_pnm_host(name, &rgb, &w, &h, &c)) die(fav_last_error());
         if (c != 3) die(std::string(name) + ": not a P6 image");
-        if (!d_equi) { ew = w; eh = h; if (hipMalloc((void**)&d_equi, (size_t)w * h * 3) != hipSuccess) die("hipMalloc failed"); }
+        if (!d_equi) { ew = w; eh = h; d_equi = favl::dev_alloc<uint8_t>((size_t)w * h * 3); }
         else if (w != ew || h != eh) die(std::string(name) + ": frame size changed");
-        if (hipMemcpy(d_equi, rgb, (size_t)w * h * 3, hipMemcpyHostToDevice) != hipSuccess) die("upload failed");
+        if (hipMemcpy(d_equi.get(), rgb, (size_t)w * h * 3, hipMemcpyHostToDevice) != hipSuccess) die("upload failed");
         fav_free_host(rgb);
-        if (fav_vr_equi_to_faces_rgb8(d_equi, ew, eh, edge, edge, ovw, ovh, ss, faces, nullptr, nullptr)) die(fav_last_error());
-        if (hipMemcpy(h_faces.data(), d_faces, 6 * face_bytes, hipMemcpyDeviceToHost) != hipSuccess) die(std::string("GPU error while transforming ") + name);
+        if (fav_vr_equi_to_faces_rgb8(d_equi.get(), ew, eh, edge, edge, ovw, ovh, ss, faces, nullptr, nullptr)) die(fav_last_error());
+        if (hipMemcpy(h_faces.data(), d_faces.get(), 6 * face_bytes, hipMemcpyDeviceToHost) != hipSuccess) die(std::string("GPU error while transforming ") + name);
         for (int k = 0; k < 6; ++k) {
             snprintf(name, sizeof name, v["output_pattern"].c_str(), fr, proc_order[k]);
             mkdirs_for(name);
@@ -111,6 +100,5 @@ int main(int argc, char** argv)
         ++done;
     }
     printf("%d frames transformed\n", done);
-    hipFree(d_equi); hipFree(d_faces);
     return 0;
 }
