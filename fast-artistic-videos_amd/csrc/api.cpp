@@ -191,6 +191,26 @@ extern "C" int fav_rgb_f32_to_yuv(const float* rgb_planar, int W, int H, const f
     return launch_rgb_to_yuv(nullptr, rgb_planar, W, H, *fmt_host, yuv, static_cast<hipStream_t>(stream));
 }
 
+// ---- original colours: the stylised frame's luminance on the original frame's colours (kernels_color.hip)
+extern "C" int fav_color_transfer_rgb8(const float* stylised_rgb_planar, const uint8_t* original_rgb_hwc, int W, int H, int matrix,
+                                       uint8_t* out_rgb_hwc, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(stylised_rgb_planar && original_rgb_hwc && out_rgb_hwc, "fav_color_transfer_rgb8: null pointer");
+    const fav_yuv_format f{FAV_YUV_444, FAV_YUV_SITING_CENTER, matrix, 1};      // (size and matrix: the YUV operators' rules)
+    int rc = yuv_format_check("fav_color_transfer_rgb8", W, H, &f); if (rc) return rc;
+    rc = ensure_device(); if (rc) return rc;
+    return launch_color_transfer_rgb8(stylised_rgb_planar, original_rgb_hwc, W, H, matrix, out_rgb_hwc, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int fav_color_transfer_yuv(const float* stylised_rgb_planar, const uint8_t* original_rgb_hwc, int W, int H,
+                                      const fav_yuv_format* fmt_host, uint8_t* yuv, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(stylised_rgb_planar && original_rgb_hwc && yuv, "fav_color_transfer_yuv: null pointer");
+    int rc = yuv_format_check("fav_color_transfer_yuv", W, H, fmt_host); if (rc) return rc;
+    rc = ensure_device(); if (rc) return rc;
+    return launch_color_transfer_yuv(stylised_rgb_planar, original_rgb_hwc, W, H, *fmt_host, yuv, static_cast<hipStream_t>(stream));
+}
+
 // ---- scene changes: the block-histogram distance of two frames (kernels_scene.hip)
 extern "C" size_t fav_scene_change_workspace_bytes(void) { return scene_change_workspace_bytes(); }
 

@@ -368,6 +368,10 @@ size_t yuv_frame_bytes(int W, int H, const fav_yuv_format& f);
 int yuv_format_check(const char* who, int W, int H, const fav_yuv_format* f);
 int launch_yuv_to_rgb8(const uint8_t* yuv, int W, int H, const fav_yuv_format& f, uint8_t* rgb_hwc, hipStream_t st);
 int launch_rgb_to_yuv(const uint8_t* rgb_hwc, const float* rgb_planar, int W, int H, const fav_yuv_format& f, uint8_t* yuv, hipStream_t st);
+// the stylised frame's luminance on the original frame's colours (kernels_color.hip; tests/util/color_model.py), as an RGB8 image or as
+// the planes of that image; sizes, matrix and format have been validated (api.cpp)
+int launch_color_transfer_rgb8(const float* state, const uint8_t* orig_hwc, int W, int H, int matrix, uint8_t* out_hwc, hipStream_t st);
+int launch_color_transfer_yuv(const float* state, const uint8_t* orig_hwc, int W, int H, const fav_yuv_format& f, uint8_t* yuv, hipStream_t st);
 // the block-histogram distance of two RGB8 frames (kernels_scene.hip; tests/util/scene_model.py): the workspace is zeroed by the call,
 // the 17 integers go to `result` (device or host-mapped memory); W, H >= 4 and W * H <= 2^28 have been checked (api.cpp)
 size_t scene_change_workspace_bytes();

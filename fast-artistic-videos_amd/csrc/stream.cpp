@@ -38,6 +38,7 @@ struct fav_stream {
     dev_ptr<int> q0_main;        // the XCD the caller's queue deals block 0 of a launch to (written by prep_input_kernel, read by the look-ahead mask's long-lived kernels)
     dev_ptr<void> ws; size_t ws_bytes = 0;
     dev_ptr<void> png_ws; size_t png_ws_bytes = 0;        // workspace of fav_stream_encode_png (allocated on first use)
+    dev_ptr<uint8_t> color_rgb8;                          // fav_stream_encode_png_colors: the image [Ho][Wo][3] it encodes (allocated on first use)
     // fav_stream_encode_png_async: the encoder's kernels run on a queue of their own, next to the NEXT frame's network (they fill the
     // tails of its grids instead of standing in front of it).  The state is double-buffered from then on: frame i + 1 is written into
     // the other buffer while frame i's is being encoded, and the frame that comes back to a buffer waits for that buffer's encoder
@@ -490,6 +491,45 @@ extern "C" int fav_stream_encode_yuv(fav_stream* s, const fav_yuv_format* fmt_ho
     FAV_REQUIRE(capacity >= need, "fav_stream_encode_yuv: a %dx%d frame takes %zu bytes, the buffer holds %zu", s->Wo, s->Ho, need, capacity);
     FAV_HIP(hipSetDevice(net_device(s->net)));
     return launch_rgb_to_yuv(nullptr, s->state.get(), s->Wo, s->Ho, *fmt_host, yuv_out, static_cast<hipStream_t>(stream));
+}
+
+// -original_colors: the current stylised frame's luminance on the colours of `frame_rgb_hwc` (kernels_color.hip).  The state is read only.
+// The frame and the stylised frame must be one size: a network that pads its output to a multiple of 4 has no original pixel there
+static int colors_size_check(const char* who, const fav_stream* s)
+{
+    if (s->Wo == s->W && s->Ho == s->H) return FAV_OK;
+    set_error("%s: the stylised frames are %dx%d, the original frames %dx%d: the colours of one cannot be laid over the other", who, s->Wo, s->Ho, s->W, s->H);
+    return FAV_EUNSUPPORTED;
+}
+
+extern "C" int fav_stream_encode_png_colors(fav_stream* s, const uint8_t* frame_rgb_hwc, int matrix, void* png_out, size_t capacity,
+                                            uint32_t* png_bytes_out, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(s && s->has_state, "fav_stream_encode_png_colors: no stylised frame yet");
+    FAV_REQUIRE(frame_rgb_hwc && png_out && png_bytes_out, "fav_stream_encode_png_colors: null pointer");
+    FAV_REQUIRE(matrix == FAV_YUV_BT601 || matrix == FAV_YUV_BT709, "fav_stream_encode_png_colors: matrix must be 0 (BT.601) or 1 (BT.709), not %d", matrix);
+    { int rc = colors_size_check("fav_stream_encode_png_colors", s); if (rc) return rc; }
+    FAV_REQUIRE(capacity >= png_capacity(s->Wo, s->Ho), "fav_stream_encode_png_colors: output capacity %zu < fav_png_capacity = %zu", capacity, png_capacity(s->Wo, s->Ho));
+    FAV_HIP(hipSetDevice(net_device(s->net)));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    { int rc = ensure_png_ws(s); if (rc) return rc; }
+    if (!s->color_rgb8) { int rc = dev_alloc(s->color_rgb8, (size_t)3 * s->Ho * s->Wo, "fav_stream_encode_png_colors: image buffer"); if (rc) return rc; }
+    if (s->png_q) { int rc = fav_stream_wait_png(s, stream); if (rc) return rc; }      // (one workspace: behind the asynchronous encodes)
+    int rc = launch_color_transfer_rgb8(s->state.get(), frame_rgb_hwc, s->Wo, s->Ho, matrix, s->color_rgb8.get(), st); if (rc) return rc;
+    return launch_png_encode(s->color_rgb8.get(), nullptr, s->Wo, s->Ho, png_out, capacity, png_bytes_out, s->png_ws.get(), s->png_ws_bytes, st);
+}
+
+extern "C" int fav_stream_encode_yuv_colors(fav_stream* s, const uint8_t* frame_rgb_hwc, const fav_yuv_format* fmt_host, uint8_t* yuv_out,
+                                            size_t capacity, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(s && s->has_state, "fav_stream_encode_yuv_colors: no stylised frame yet");
+    FAV_REQUIRE(frame_rgb_hwc && yuv_out, "fav_stream_encode_yuv_colors: null pointer");
+    { int rc = yuv_format_check("fav_stream_encode_yuv_colors", s->Wo, s->Ho, fmt_host); if (rc) return rc; }
+    { int rc = colors_size_check("fav_stream_encode_yuv_colors", s); if (rc) return rc; }
+    const size_t need = yuv_frame_bytes(s->Wo, s->Ho, *fmt_host);
+    FAV_REQUIRE(capacity >= need, "fav_stream_encode_yuv_colors: a %dx%d frame takes %zu bytes, the buffer holds %zu", s->Wo, s->Ho, need, capacity);
+    FAV_HIP(hipSetDevice(net_device(s->net)));
+    return launch_color_transfer_yuv(s->state.get(), frame_rgb_hwc, s->Wo, s->Ho, *fmt_host, yuv_out, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int fav_stream_encode_png_async(fav_stream* s, void* png_out, size_t capacity, uint32_t* png_bytes_out, fav_hipstream_t stream)

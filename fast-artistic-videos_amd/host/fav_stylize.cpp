@@ -52,6 +52,15 @@
 //   -create_inconsistent, a value outside [0, 1].
 // -scene_cut_log <path> (only with -scene_cut): one line per frame, `index total score cut` (cut = 0 | 1; the first frame is
 //   `index 0 0 0`), written when the frame is decided.
+// -original_colors <0|1> (0, default): 1 keeps the INPUT frame's colours and takes only the luminance of the stylised frame (Gatys et al.,
+//   "Preserving color in neural artistic style transfer"; the arithmetic is in include/fav.h and DESIGN.md, "Original colours").  Only what
+//   leaves through the sink changes: the state that is warped into the next frame stays the network's full-colour output, and
+//   -temporal_eval_file keeps measuring that state.  The matrix of the luminance is the output format's with -output_y4m, else BT.709 from
+//   720 rows on and BT.601 below; -y4m_matrix bt601|bt709 overrides either.  Works through all three sinks (-png_encoder gpu | host,
+//   -output_y4m); with -png_encoder gpu the encode is the synchronous one whatever -png_overlap says.
+//   Refused: a value other than 0 / 1; -continue_with above 1 (it reloads the previous PNG as the recurrent state, and with this flag the
+//   PNG is not the state); at the first frame, stylised frames whose size is not the input's (sizes that are no multiples of 4).
+//   fav_stylize_vr and the `th` shim do not take the flag.
 //
 // Several videos on several GPUs (BASELINE config 4; the reference runs one `th` process per video, stylizeVideo_deepflow.sh:87-96,
 // and its only device hook is utils.setup_gpu, fast_artistic_video/utils.lua:43-66):
@@ -505,17 +514,19 @@ struct SceneCut {
 // after the host has seen frame i complete.  Per frame the loop calls, in this order: after_frame (behind the frame's network, with
 // the pinned slot the frame will leave through), hand_off (behind the look-ahead and the wait for the frame before), and a frame
 // later wait, target and writer_task.
+// -original_colors 1: after_frame also gets the device RGB8 frame the network has just consumed, and what it enqueues is the stylised
+// frame's luminance on that frame's colours (fav_stream_encode_*_colors, fav_color_transfer_rgb8) instead of the state itself.
 struct SinkEnv { const Opt& o; hipStream_t st, st_down; Slots* slots; Counters* cnt; };
 class Sink {
 public:
-    explicit Sink(const SinkEnv& e) : env(e) {}
+    explicit Sink(const SinkEnv& e) : env(e), colors(e.o.i("original_colors") != 0) {}
     virtual ~Sink() = default;
     // QUIET synchronisation: nothing but kernels ever enters the compute queue (DevicePng below says why and how)
     virtual bool quiet() const { return false; }
     virtual size_t setup(fav_stream* fs, int Wo, int Ho) = 0;      // at the known output size; returns the bytes of a pinned slot
     virtual void slot_added(uint8_t*) {}
     virtual uint8_t* frame_out(int) { return nullptr; }            // where the network is to leave the 8-bit frame, if anywhere
-    virtual void after_frame(int k, uint8_t* hb) = 0;
+    virtual void after_frame(int k, uint8_t* hb, const uint8_t* frame) = 0;
     virtual void hand_off(int k, uint8_t* hb) = 0;
     virtual void wait(int k) = 0;                                  // until frame k is complete where the writer task needs it
     virtual std::string target(int index) = 0;                     // what "Writing output image to" names
@@ -531,7 +542,10 @@ protected:
     // 1.9 ms of CPU per frame for the main thread alone at 530 frames/s) and with the system-scope fence (the host reads what they cover)
     static fav::event_h host_event() { return favl::event_create(hipEventDisableTiming | hipEventBlockingSync); }
     void wait_host_event(hipEvent_t e) const { if (wait_event_sleeping(e) != hipSuccess) die("GPU error while stylising a frame"); }
-    SinkEnv env; fav_stream* fs = nullptr; int Wo = 0, Ho = 0;
+    // -original_colors into a PNG: no stream format names the matrix, so it is the Y4M header parser's rule for the frame's height
+    // (-y4m_matrix overrides)
+    int png_colors_matrix() const { return y4m_format_of(env.o, nullptr, Ho, false).matrix; }
+    SinkEnv env; const bool colors; fav_stream* fs = nullptr; int Wo = 0, Ho = 0;
 };
 
 // -png_encoder gpu (default): the PNG file's bytes are produced on the device (fav_stream_encode_png: Sub filter + fixed-Huffman /
@@ -563,14 +577,17 @@ public:
     }
     // per pinned output slot the event of the exact-size copy into it
     void slot_added(uint8_t* p) override { slot_ev[p] = favl::event_create(hipEventDisableTiming); }
-    void after_frame(int k, uint8_t*) override
+    void after_frame(int k, uint8_t*, const uint8_t* frame) override
     {
         // two frames ago this buffer's bytes left through the download queue: that copy must have finished (it has, long ago)
         if (copy_ev[k] && wait_event_sleeping(copy_ev[k], 50) != hipSuccess) die("GPU error while downloading a frame");
         h_size.get()[k] = 0u;                    // the frame's last kernel overwrites it with the file size (host-mapped)
+        // -original_colors 1: one kernel in front of the encoder's, still nothing but kernels on the compute queue; the synchronous
+        // encode whatever -png_overlap says (the asynchronous one reads the state on another queue, and has measured no gain)
+        if (colors) check(fav_stream_encode_png_colors(fs, frame, png_colors_matrix(), d_png[k].get(), cap, &h_size.get()[k], env.st), "fav_stream_encode_png_colors");
         // -png_overlap 1: on the stream's encoder queue, next to frame i + 1's network -- the host learns of the file
         // through its size word either way
-        if (overlap) check(fav_stream_encode_png_async(fs, d_png[k].get(), cap, &h_size.get()[k], env.st), "fav_stream_encode_png_async");
+        else if (overlap) check(fav_stream_encode_png_async(fs, d_png[k].get(), cap, &h_size.get()[k], env.st), "fav_stream_encode_png_async");
         else check(fav_stream_encode_png(fs, d_png[k].get(), cap, &h_size.get()[k], env.st), "fav_stream_encode_png");
     }
     void hand_off(int, uint8_t*) override {}     // the bytes leave once their number is known: writer_task
@@ -627,10 +644,19 @@ public:
     {
         fs = fs_; Wo = Wo_; Ho = Ho_;
         for (auto& d : d_out8) d = favl::dev_alloc<uint8_t>((size_t)Wo * Ho * 3);
+        if (colors) d_state = favl::dev_alloc<float>((size_t)Wo * Ho * 12);
         return (size_t)Wo * Ho * 3;
     }
-    uint8_t* frame_out(int k) override { return d_out8[k].get(); }
-    void after_frame(int k, uint8_t*) override { hipEventRecord(ev_out[k].get(), env.st); }       // the frame's 8-bit image is complete on the compute queue ...
+    // -original_colors 1: the network is not asked for its own 8-bit frame; the buffer is filled from the state behind it
+    uint8_t* frame_out(int k) override { return colors ? nullptr : d_out8[k].get(); }
+    void after_frame(int k, uint8_t*, const uint8_t* frame) override
+    {
+        if (colors) {         // the operator takes planes the caller owns: a copy of the state (this sink's queue carries copies and events anyway)
+            check(fav_stream_get_state(fs, d_state.get(), env.st), "fav_stream_get_state");
+            check(fav_color_transfer_rgb8(d_state.get(), frame, Wo, Ho, png_colors_matrix(), d_out8[k].get(), env.st), "fav_color_transfer_rgb8");
+        }
+        hipEventRecord(ev_out[k].get(), env.st);       // the frame's 8-bit image is complete on the compute queue ...
+    }
     void hand_off(int k, uint8_t* hb) override
     {
         hipStreamWaitEvent(env.st_down, ev_out[k].get(), 0);                                       // ... and leaves on the download queue
@@ -652,6 +678,7 @@ public:
     }
 private:
     fav::dev_ptr<uint8_t> d_out8[2];
+    fav::dev_ptr<float> d_state;                 // -original_colors 1: the state's planes for fav_color_transfer_rgb8
     fav::event_h ev_out[2] = {favl::event_create(hipEventDisableTiming | hipEventDisableSystemFence), favl::event_create(hipEventDisableTiming | hipEventDisableSystemFence)};
     fav::event_h ev_done[2] = {host_event(), host_event()};
 };
@@ -680,7 +707,11 @@ public:
         if (!writer.header(oh)) die("cannot write the stream header to " + path + ": " + fav_last_error());
         return bytes;
     }
-    void after_frame(int, uint8_t* hb) override { check(fav_stream_encode_yuv(fs, &fmt_out, hb, bytes, env.st), "fav_stream_encode_yuv"); }      // into the pinned slot
+    void after_frame(int, uint8_t* hb, const uint8_t* frame) override      // into the pinned slot
+    {
+        if (colors) check(fav_stream_encode_yuv_colors(fs, frame, &fmt_out, hb, bytes, env.st), "fav_stream_encode_yuv_colors");      // the output format's matrix
+        else check(fav_stream_encode_yuv(fs, &fmt_out, hb, bytes, env.st), "fav_stream_encode_yuv");
+    }
     void hand_off(int k, uint8_t*) override { hipEventRecord(ev_done[k].get(), env.st); }    // nothing to download: the planes are in host memory when this event fires
     void wait(int k) override { wait_host_event(ev_done[k].get()); }
     std::string target(int index) override { return env.o.s("output_y4m") + " (frame " + std::to_string(index) + ")"; }
@@ -835,8 +866,11 @@ void StreamRun::setup(const FrameIn& cur, int i)
     if (have_resume && (rW != Wo || rH != Ho)) die("-continue_with: the previous PNG's size differs from the stylised frames' (" + std::to_string(Wo) + "x" + std::to_string(Ho) + ")");
     if (teval && (Wo != W || Ho != H))
         die("-temporal_eval_file: the stylised frames (" + std::to_string(Wo) + "x" + std::to_string(Ho) + ") are larger than the flow; the reference's func_eval fails on such sizes as well (fav.lua:128-151)");
+    if (o.i("original_colors") != 0 && (Wo != W || Ho != H))
+        die("-original_colors 1: the stylised frames (" + std::to_string(Wo) + "x" + std::to_string(Ho) + ") are larger than the input frames (" + std::to_string(W) + "x" +
+            std::to_string(H) + "): there are no original colours for the added pixels; use a size whose sides are multiples of 4");
     if (net_img) check(fav_stream_set_image_net(s, net_img), "fav_stream_set_image_net");
-    if (o.d("scale_factor") != 1.0) {            // img:view(1, 3, H * f, W * f) (core.lua:130) needs whole numbers
+    if (o.d("scale_factor") != 1.0) {          // img:view(1, 3, H * f, W * f) (core.lua:130) needs whole numbers
         const double f = o.d("scale_factor"), hs = H * f, ws = W * f;
         if (std::fabs(hs - std::round(hs)) > 1e-9 * hs || std::fabs(ws - std::round(ws)) > 1e-9 * ws || hs < 0.5 || ws < 0.5 || hs > 1e6 || ws > 1e6) {
             char msg[256];
@@ -980,7 +1014,12 @@ void StreamRun::run(StreamResult* res)
         now.hb = slots.try_take();                       // a pinned output slot nobody is reading ...
         if (!now.hb) now.hb = (int)h_out.size() < nslots ? new_slot() : slots.take();      // ... a new one while allowed, else wait for the PNG pool
         t_wait_writer += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw).count();
-        sink->after_frame(now.k, now.hb);
+        // -original_colors 1 reads the frame the network has just consumed, dev.set[dset].frame (with -input_y4m: what fav_yuv_to_rgb8
+        // left there).  It still holds frame i when the sink's kernels run: they are enqueued here, on the compute queue, behind frame
+        // i's network, whose inputs the queue (or, quiet, the host) has seen arrive; and the set is refilled by top_up of the iteration
+        // of frame i + N - LA >= i + 2 at the earliest, after finish() in the iteration of frame i + 1 has SEEN frame i complete where
+        // the writer needs it -- the size word, the download or the planes, all behind the sink's kernels.
+        sink->after_frame(now.k, now.hb, dev.set[dset].frame.get());
         tr_mark(2);                                      // PNG encode enqueued
         top_up(i);                                       // behind frame i's kernels: the 0.45 ms this waits for the upload are not in front of them
         const auto tg = std::chrono::steady_clock::now();
@@ -1039,7 +1078,7 @@ int main(int argc, char** argv)
            {"forward_flow_pattern", ""}, {"structure", "1"}, {"warp_border", "stn"}, {"poll_timeout", "3600"}, {"poll_settle", "1.0"},
            {"png_level", "1"}, {"png_encoder", "gpu"}, {"png_overlap", "0"}, {"writers", "0"}, {"timing", "0"}, {"temporal_eval_file", ""}, {"seed", "1"}, {"precision", "fp32"},
            {"input_y4m", ""}, {"output_y4m", ""}, {"y4m_matrix", "auto"}, {"y4m_range", "auto"}, {"y4m_format", ""},
-           {"scene_cut", "0"}, {"scene_cut_log", ""},
+           {"scene_cut", "0"}, {"scene_cut_log", ""}, {"original_colors", "0"},
            {"estimate_flow", "0"}, {"flow_levels", "0"},      // (the other -flow_* flags: favl::add_flow_flags below)
            {"streams", ""}, {"gpus", "1"}, {"force_dist", "0"}, {"dry_run", "0"}, {"shared_gpu", "0"}, {"pin_workers", "1"},
            // internal (set by the launcher for its workers)
@@ -1071,7 +1110,12 @@ int main(int argc, char** argv)
     if (o.s("y4m_range") != "auto" && o.s("y4m_range") != "limited" && o.s("y4m_range") != "full") die("-y4m_range must be auto, limited or full, not '" + o.s("y4m_range") + "'");
     if (!o.s("y4m_format").empty() && o.s("y4m_format") != "420jpeg" && o.s("y4m_format") != "420mpeg2" && o.s("y4m_format") != "444")
         die("-y4m_format must be 420jpeg, 420mpeg2 or 444, not '" + o.s("y4m_format") + "'");
-    if (!y4m_in && o.s("input_pattern").empty()) die("Must give -input_pattern");                           // fav.lua:177-179
+    // -original_colors: refused here, before any device is opened
+    if (o.s("original_colors") != "0" && o.s("original_colors") != "1") die("-original_colors must be 0 or 1, not '" + o.s("original_colors") + "'");
+    if (o.s("original_colors") == "1" && o.i("continue_with") > 1)
+        die("-original_colors 1 cannot be combined with -continue_with " + o.s("continue_with") +
+            ": -continue_with reloads the previous PNG as the recurrent state, and with -original_colors 1 the PNG is not the state");
+    if (!y4m_in && o.s("input_pattern").empty()) die("Must give -input_pattern");                         // fav.lua:177-179
     if (o.s("estimate_flow") != "0" && o.s("estimate_flow") != "1") die("-estimate_flow must be 0 or 1, not '" + o.s("estimate_flow") + "'");
     const bool estimate = o.i("estimate_flow") != 0;
     {   // -scene_cut: the recurrence restarts where the picture changes by more than T (0: off)

@@ -110,6 +110,7 @@ EXPORTS = [
     "fav_yuv_frame_bytes", "fav_yuv_to_rgb8", "fav_rgb8_to_yuv", "fav_rgb_f32_to_yuv", "fav_stream_encode_yuv",
     "fav_y4m_parse_header_host", "fav_y4m_format_header_host",
     "fav_scene_change_workspace_bytes", "fav_scene_change_rgb8",
+    "fav_color_transfer_rgb8", "fav_color_transfer_yuv", "fav_stream_encode_png_colors", "fav_stream_encode_yuv_colors",
 ]
 
 
@@ -745,6 +746,15 @@ class Stream:
         """fav_stream_encode_yuv: the current stylised frame as the planes of a Y4M frame, enqueued on the current stream (no sync)"""
         _check(lib().fav_stream_encode_yuv(self.h, C.byref(fmt), _p(out), C.c_size_t(out.numel() if capacity is None else capacity), _stream()))
 
+    def encode_png_colors_into(self, frame_u8_hwc, matrix: int, out, nbytes):
+        """fav_stream_encode_png_colors: the current stylised frame's luminance on the colours of frame_u8_hwc, as the bytes of a PNG file"""
+        _check(lib().fav_stream_encode_png_colors(self.h, _p(frame_u8_hwc), matrix, _p(out), C.c_size_t(out.numel()), _p(nbytes), _stream()))
+
+    def encode_yuv_colors_into(self, frame_u8_hwc, out, fmt: "YuvFormat", capacity: Optional[int] = None):
+        """fav_stream_encode_yuv_colors: the planes of that image (the transfer takes fmt's matrix), enqueued on the current stream (no sync)"""
+        _check(lib().fav_stream_encode_yuv_colors(self.h, _p(frame_u8_hwc), C.byref(fmt), _p(out),
+                                                  C.c_size_t(out.numel() if capacity is None else capacity), _stream()))
+
     def last_input(self):
         """[7][H][W] network input of the last frame (content | prior | certainty), un-padded copy of the fused kernel's output"""
         torch = _torch()
@@ -846,6 +856,26 @@ def rgb_to_yuv(img, fmt: YuvFormat, out=None):
     if not u8:
         _chk_f32(img, "img")
     _check((lib().fav_rgb8_to_yuv if u8 else lib().fav_rgb_f32_to_yuv)(_p(img), w, h, C.byref(fmt), _p(out), _stream()))
+    return out
+
+
+def color_transfer(stylised, original, matrix_or_fmt, out=None):
+    """-original_colors: the luminance of `stylised` (float [3][H][W], image.save's quantisation in front) on the colours of `original`
+    (u8 [H][W][3]).  An int matrix (YUV_BT601 | YUV_BT709): fav_color_transfer_rgb8 -> [H][W][3] u8; a YuvFormat: fav_color_transfer_yuv
+    -> the planes of that image, flat u8.  out: a u8 tensor of at least H*W*3 / fav_yuv_frame_bytes elements to write into"""
+    torch = _torch()
+    _chk_f32(stylised, "stylised")
+    h, w = stylised.shape[1], stylised.shape[2]
+    assert original.dtype == torch.uint8 and original.is_contiguous() and original.numel() >= h * w * 3
+    planes = isinstance(matrix_or_fmt, YuvFormat)
+    n = yuv_frame_bytes(w, h, matrix_or_fmt) if planes else h * w * 3
+    if out is None:
+        out = torch.empty(n if planes else (h, w, 3), dtype=torch.uint8, device=stylised.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= n
+    if planes:
+        _check(lib().fav_color_transfer_yuv(_p(stylised), _p(original), w, h, C.byref(matrix_or_fmt), _p(out), _stream()))
+    else:
+        _check(lib().fav_color_transfer_rgb8(_p(stylised), _p(original), w, h, int(matrix_or_fmt), _p(out), _stream()))
     return out
 
 

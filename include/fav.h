@@ -588,6 +588,33 @@ int fav_rgb_f32_to_yuv(const float* rgb_planar, int W, int H, const fav_yuv_form
  * (complete when the stream reaches the point after the call -- use an event WITH the system-scope fence) of `capacity` >=
  * fav_yuv_frame_bytes(Wo, Ho, fmt) bytes; a smaller capacity is FAV_EINVAL and nothing is written. */
 int fav_stream_encode_yuv(fav_stream* s, const fav_yuv_format* fmt_host, uint8_t* yuv_out, size_t capacity, fav_hipstream_t stream);
+/* ---- original colours: the stylised frame's luminance on the input frame's colours -------------------------------------------------
+ * Not in the reference: the luminance transfer of Gatys et al., "Preserving color in neural artistic style transfer", where a frame
+ * leaves (fav_stylize -original_colors 1).  S = image.save's bytes of the stylised planes (clamp to [0, 1], x255, truncate: those of
+ * fav_png_encode_f32), O = the original frame's bytes.  Per pixel, fp32, in this order:
+ *   ys = (Kr Sr + Kg Sg) + Kb Sb;  yo = (Kr Or + Kg Og) + Kb Ob;  d = ys - yo;  Pc = clamp(floor((Oc + d) + 0.5), 0, 255) for c = R, G, B
+ * with (Kr, Kb) of `matrix` (FAV_YUV_BT601 | FAV_YUV_BT709), Kg = 1 - Kr - Kb; no range scaling enters.  Restated by
+ * tests/util/color_model.py and matched byte for byte ("Original colours").
+ * fav_color_transfer_rgb8 writes the image P, [H][W][3] u8; fav_color_transfer_yuv writes the planes of P -- the bytes of
+ * fav_rgb8_to_yuv(P, fmt), whose matrix is also the transfer's -- without P ever existing in memory.
+ * The conventions of the YUV operators above: device pointers, caller-owned buffers (3*W*H floats, W*H*3 bytes, fav_yuv_frame_bytes), no
+ * alignment requirement, nothing allocated, no synchronisation, nothing outside the buffers read or written; a null pointer, a size below
+ * 1 x 1 or above 2^28 pixels, a matrix or a field of the format outside its values: FAV_EINVAL. */
+int fav_color_transfer_rgb8(const float* stylised_rgb_planar, const uint8_t* original_rgb_hwc, int W, int H, int matrix,
+                            uint8_t* out_rgb_hwc, fav_hipstream_t stream);
+int fav_color_transfer_yuv(const float* stylised_rgb_planar, const uint8_t* original_rgb_hwc, int W, int H,
+                           const fav_yuv_format* fmt_host, uint8_t* yuv, fav_hipstream_t stream);
+/* the same for a stream's current stylised frame (the recurrent state, which is only read: fav_stream_get_state gives the same bits
+ * before and after) and `frame_rgb_hwc`, normally the frame the stream has just consumed.  The stream's output size must be the frame's
+ * (fav_stream_output_size == H x W, i.e. both multiples of 4 for the canonical network): otherwise FAV_EUNSUPPORTED with a message that
+ * names both sizes, and nothing is written.
+ * fav_stream_encode_png_colors writes P into a buffer the stream owns (allocated at first use, freed with the stream) and runs the RGB8
+ * encoder of fav_png_encode_rgb8 on it with the stream's own workspace: png_out / capacity / png_bytes_out as for fav_stream_encode_png
+ * (png_bytes_out may be host-mapped memory).  fav_stream_encode_yuv_colors is one launch: yuv_out / capacity as for fav_stream_encode_yuv. */
+int fav_stream_encode_png_colors(fav_stream* s, const uint8_t* frame_rgb_hwc, int matrix, void* png_out, size_t capacity,
+                                 uint32_t* png_bytes_out, fav_hipstream_t stream);
+int fav_stream_encode_yuv_colors(fav_stream* s, const uint8_t* frame_rgb_hwc, const fav_yuv_format* fmt_host, uint8_t* yuv_out,
+                                 size_t capacity, fav_hipstream_t stream);
 /* The stream header of YUV4MPEG2, host-only (no device needed): the magic `YUV4MPEG2`, then space-separated tags in any order, ended by
  * '\n'; at most FAV_Y4M_MAX_HEADER bytes.  `line` holds the header up to or including the newline (len bytes).
  *   W, H   required;  F<num>:<den> and A<num>:<den> are kept (fps_den 0 / aspect_num -1: the tag was absent and is not written back)
