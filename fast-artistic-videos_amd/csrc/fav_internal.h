@@ -285,6 +285,7 @@ __device__ __forceinline__ float fill_uniform(unsigned seed, unsigned index, uns
 #endif
 
 // frame-level kernels (kernels_frame.hip / kernels_consistency.hip)
+constexpr int MIN_FILTER_RMAX = 15;      // largest -occlusions_min_filter window: the erosion kernels' LDS tiles are sized for it
 int launch_warp(const float* img, const float* flow, float* out, int B, int C, int H, int W, int Ho, int Wo,
                 int border, hipStream_t st);
 int launch_min_filter_f32(const float* cert, float* out, int H, int W, int r, hipStream_t st);

@@ -146,7 +146,7 @@ __device__ __forceinline__ float cert_from_mask(const uint8_t* mask, const float
 // utils.min_filter (utils.lua:161-169): 1 - maxpool_{r x r, stride 1, pad r/2}(1 - cert); max-pooling pads with -inf, i.e. the
 // windows are truncated at the borders.  max is exact and order-free, so the r x r window is evaluated separably on an LDS
 // tile (rows, then columns): 2r instead of r*r taps, each input element read from memory once per tile.
-constexpr int MF_TX = 64, MF_TY = 16, MF_RMAX = 15;
+constexpr int MF_TX = 64, MF_TY = 16, MF_RMAX = MIN_FILTER_RMAX;
 // FROM_MASK: the tile is filled from the checker's mask byte with the certainty options applied on the way in (cert_from_mask; 1.5x of that cheap work is repeated in the tiles' halos) -- one launch and one 3.7 MB plane less per frame
 // FROM_MASK == 2: the tile is filled from the two FLOWS -- the forward-backward check itself (consistency_pixel, bit-exact) runs on
 // every tile position, the mask byte of the tile's own pixels is written out (tests, -temporal_eval_file, the VR path read it), the

@@ -116,6 +116,8 @@ extern "C" int fav_stream_create(fav_net* net, int H, int W, const fav_stream_op
     s->net = net; s->H = H; s->W = W; s->Ho = Ho; s->Wo = Wo;
     if (o) s->opts = *o; else { s->opts.border_mode = FAV_BORDER_STN; s->opts.occlusions_min_filter = 7; s->opts.invert_occlusion = 0; s->opts.fix_occlusions = 0; s->opts.fill_random = 0; s->opts.seed = 0; }
     if (s->opts.occlusions_min_filter < 1) s->opts.occlusions_min_filter = 1;
+    FAV_REQUIRE(s->opts.occlusions_min_filter <= MIN_FILTER_RMAX, "fav_stream_create: -occlusions_min_filter %d is larger than the supported maximum of %d",
+                s->opts.occlusions_min_filter, MIN_FILTER_RMAX);
     const size_t n = (size_t)H * W;
     s->ws_bytes = structure_workspace_bytes(W, H);
     const unsigned ef = hipEventDisableTiming | hipEventDisableSystemFence;
@@ -587,6 +589,17 @@ extern "C" int fav_stream_get_input_f32(const fav_stream* s, float* in7, fav_hip
     FAV_REQUIRE(!s->last_scaled, "fav_stream_get_input_f32: the last frame ran at the scaled single-image size (this view is the H x W input)");
     FAV_HIP(hipSetDevice(net_device(s->net)));
     return launch_unpad_input(s->in8.get(), s->H, s->W, net_pad(s->net), in7, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int fav_stream_get_padded_input_f32(const fav_stream* s, float* out, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(s && out && s->frame_counter > 0, "fav_stream_get_padded_input_f32: no frame has been assembled yet");
+    FAV_REQUIRE(!s->last_scaled, "fav_stream_get_padded_input_f32: the last frame ran at the scaled single-image size (this view is the H x W input)");
+    FAV_HIP(hipSetDevice(net_device(s->net)));
+    const int pad = net_pad(s->net);
+    FAV_HIP(hipMemcpyAsync(out, s->in8.get(), (size_t)(s->H + 2 * pad) * (s->W + 2 * pad) * 8 * sizeof(float), hipMemcpyDeviceToDevice,
+                           static_cast<hipStream_t>(stream)));
+    return FAV_OK;
 }
 
 extern "C" const uint8_t* fav_stream_last_mask(const fav_stream* s) { return s ? s->mask.get() : nullptr; }

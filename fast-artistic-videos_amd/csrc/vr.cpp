@@ -217,6 +217,8 @@ extern "C" int fav_vr_create(fav_net* video_net, fav_net* image_net_or_null, int
     FAV_REQUIRE(o.overlap_w > 10 && o.overlap_h > 10 && o.overlap_w < wplus && o.overlap_h < hplus && !(o.overlap_w & 1) && !(o.overlap_h & 1),
                 "fav_vr_create: overlap %dx%d must be even, > 10 (gradient width = overlap - 10) and smaller than the face", o.overlap_w, o.overlap_h);
     FAV_REQUIRE(o.median_filter == 0 || (o.median_filter >= 3 && o.median_filter <= 5 && (o.median_filter & 1)), "fav_vr_create: -median_filter %d (0, 3 or 5)", o.median_filter);
+    FAV_REQUIRE(o.occlusions_min_filter <= MIN_FILTER_RMAX, "fav_vr_create: -occlusions_min_filter %d is larger than the supported maximum of %d",
+                o.occlusions_min_filter, MIN_FILTER_RMAX);
     FAV_REQUIRE(net_in_channels(video_net) == 7, "fav_vr_create: the video model must take 7 input channels");
     int Ho, Wo; net_out_size(video_net, hplus, wplus, &Ho, &Wo);
     FAV_REQUIRE(Ho == hplus && Wo == wplus, "fav_vr_create: a %dx%d face gives a %dx%d output (sizes must be multiples of 4)", wplus, hplus, Wo, Ho);

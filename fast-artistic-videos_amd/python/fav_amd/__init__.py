@@ -89,7 +89,7 @@ EXPORTS = [
     "fav_conv2d_nchw_f32", "fav_conv_transpose2d_nchw_f32", "fav_stream_create", "fav_stream_destroy",
     "fav_stream_set_image_net", "fav_stream_first_frame", "fav_stream_next_frame_cert", "fav_stream_next_frame_flow", "fav_stream_prefetch_mask",
     "fav_stream_get_state",
-    "fav_stream_set_state", "fav_stream_last_mask", "fav_stream_get_input_f32", "fav_stream_output_size", "fav_stream_set_host_ordered",
+    "fav_stream_set_state", "fav_stream_last_mask", "fav_stream_get_input_f32", "fav_stream_get_padded_input_f32", "fav_stream_output_size", "fav_stream_set_host_ordered",
     "fav_png_capacity", "fav_png_workspace_bytes", "fav_png_encode_rgb8", "fav_png_encode_f32", "fav_stream_encode_png", "fav_stream_encode_png_async", "fav_stream_wait_png", "fav_png_tables_host", "fav_png_crc32_combine_host", "fav_read_flo_host", "fav_read_pnm_host", "fav_write_pgm_host",
     "fav_write_png_rgb8_host", "fav_free_host",
     "fav_vr_create", "fav_vr_destroy", "fav_vr_face", "fav_vr_finish_frame", "fav_vr_output_sizes", "fav_vr_get_f32",
@@ -550,6 +550,11 @@ class Net:
         _check(lib().fav_net_describe_host(self.h, buf, C.c_size_t(len(buf))))
         return buf.value.decode()
 
+    def input_pad(self) -> int:
+        """the leading reflection padding the input assembly writes itself (fav_net::upload: a first layer `pad p p p p`), else 0"""
+        first = self.describe().split("\n", 1)[0].split()
+        return int(first[1]) if first[:1] == ["pad"] and len(set(first[1:])) == 1 else 0
+
     def param_count(self) -> int:
         return int(lib().fav_net_param_count(self.h))
 
@@ -760,6 +765,15 @@ class Stream:
         torch = _torch()
         out = torch.empty((7, self.H, self.W), dtype=torch.float32, device=f"cuda:{self.net.device}")
         _check(lib().fav_stream_get_input_f32(self.h, _p(out), _stream()))
+        return out
+
+    def last_padded_input(self):
+        """[H + 2p][W + 2p][8] network input of the last frame as the network reads it: the stream's own buffer with the leading reflection
+        padding p (Net.input_pad) and the zero eighth channel, copied device to device"""
+        torch = _torch()
+        p = self.net.input_pad()
+        out = torch.empty((self.H + 2 * p, self.W + 2 * p, 8), dtype=torch.float32, device=f"cuda:{self.net.device}")
+        _check(lib().fav_stream_get_padded_input_f32(self.h, _p(out), _stream()))
         return out
 
     def last_mask(self):

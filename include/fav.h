@@ -319,7 +319,7 @@ typedef struct fav_stream fav_stream;
 
 typedef struct fav_stream_opts {
     int border_mode;           /* enum fav_border */
-    int occlusions_min_filter; /* -occlusions_min_filter (default 7) */
+    int occlusions_min_filter; /* -occlusions_min_filter (default 7): 1..15, below 1 runs as 1, above 15 is FAV_EINVAL at create */
     int invert_occlusion;      /* -invert_occlusion */
     int fix_occlusions;        /* -fix_occlusions */
     int fill_random;           /* -fill_occlusions uniform-random (1) | vgg-mean (0): core.lua:108-117.  The reference's
@@ -419,6 +419,10 @@ int fav_stream_set_state(fav_stream* s, const float* state_rgb_f32, fav_hipstrea
  * content | masked warped prior + fill | certainty), [7][H][W] fp32, copied out of the fused kernel's padded buffer (FAV_EINVAL
  * right after a frame that ran at the scaled single-image size) */
 int fav_stream_get_input_f32(const fav_stream* s, float* in7, fav_hipstream_t stream);
+/* test view: the same frame's input as the network reads it, with the leading reflection padding p the input assembly writes
+ * (0 when the model starts without a symmetric reflection padding): [H + 2p][W + 2p][8] fp32, channel 7 zero -- a device-to-device
+ * copy of the stream's buffer.  Same preconditions and errors as fav_stream_get_input_f32 */
+int fav_stream_get_padded_input_f32(const fav_stream* s, float* out, fav_hipstream_t stream);
 /* device pointer of the last certainty mask used (u8 [H][W], before the min filter) -- tests */
 const uint8_t* fav_stream_last_mask(const fav_stream* s);
 
@@ -445,7 +449,7 @@ int fav_temporal_loss_host(const float* prev_rgb, const float* cur_rgb, const fl
 typedef struct fav_vr fav_vr;
 typedef struct fav_vr_opts {
     int overlap_w, overlap_h;        /* -overlap_pixel_w / _h (fast_artistic_video_vr.lua:42-43); even, > 10 */
-    int occlusions_min_filter;       /* :36 */
+    int occlusions_min_filter;       /* :36; 1..15, below 1 runs as 1, above 15 is FAV_EINVAL at create */
     int median_filter;               /* :50; 0, 3 or 5 */
     int fill_random;                 /* -fill_occlusions uniform-random (1) | vgg-mean (0) */
     unsigned seed;                   /* of the documented RNG */

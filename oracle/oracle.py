@@ -351,11 +351,21 @@ class Stylizer:
     callbacks (fast_artistic_video.lua:93-172); fill_occlusions = vgg-mean."""
 
     def __init__(self, layers, border="stn", min_filter_r=7, invert_occlusion=False, fix_occlusions=False,
-                 fill_random=False, seed=1):
+                 fill_random=False, seed=1, stn_f32=False):
         self.layers, self.border, self.r = layers, border, min_filter_r
         self.invert, self.fix = invert_occlusion, fix_occlusions
-        self.fill_random, self.seed, self.count = fill_random, seed, 0      # -fill_occlusions uniform-random (core.lua:108-117)
+        # the uniform-random fill (core.lua:108-117) is keyed by `count`, the product's fav_stream::frame_counter: the 1-based number of
+        # frames this stream has ASSEMBLED, incremented just before each assembly.  A stream that starts with first() fills frame 1 with
+        # index 1 and its first next() with index 2; one that starts with set_state() has assembled nothing, so its first next() uses 1
+        self.fill_random, self.seed, self.count = fill_random, seed, 0
+        # stn_f32: the "stn" warps (prior, all-ones warp of -fix_occlusions) in fp32 exactly as the reference kernel is written
+        # (warp(..., "stn_f32"): bit-identical to the GPU kernels) instead of the sum rounded once from double
+        self.warp_mode = "stn_f32" if (stn_f32 and border == "stn") else border
         self.last = None        # last_frame_stylized: float RGB [3][H][W], unclamped (fav.lua:169)
+
+    def set_state(self, rgb):
+        """fav_stream_set_state (-continue_with): the recurrent state from outside; the frame counter does not move."""
+        self.last = np.ascontiguousarray(rgb, np.float32)
 
     def _fill(self, cert):
         """generate_fill with the documented counter RNG (vr_oracle.fill_uniform) instead of the unseeded torch.rand."""
@@ -364,33 +374,49 @@ class Stylizer:
         return preprocess(fill_uniform(self.seed, self.count, h, w)) * ((cert + np.float32(-1)) * np.float32(-1))
 
     def first(self, frame_rgb01, image_layers=None):
-        self.count += 1
         if image_layers is not None:       # model_img:forward(pre) -- core.lua:146
+            self.count += 1
             out = deprocess(net_forward(image_layers, preprocess(frame_rgb01)))
             self.last = out
             return out
-        x = assemble(frame_rgb01, None, None)
-        if self.fill_random:
-            x[3:6] = self._fill(np.zeros((1,) + x.shape[1:], np.float32))
+        x = self.first_input7(frame_rgb01)
         out = deprocess(net_forward(self.layers, x))
         self.last = out
         return out
 
-    def next(self, frame_rgb01, backward_flow_uv, cert01):
+    def first_input7(self, frame_rgb01):
+        """the 7-channel network input of a frame without a prior (core.lua:133-138): fill only, zero certainty.  Advances the counter."""
         self.count += 1
+        x = assemble(frame_rgb01, None, None)
+        if self.fill_random:
+            x[3:6] = self._fill(np.zeros((1,) + x.shape[1:], np.float32))
+        return x
+
+    def certainty(self, backward_flow_uv, cert01):
+        """func_load_cert (fav.lua:99-112): the certainty after -invert_occlusion and -fix_occlusions, before the erosion"""
         cert01 = np.ascontiguousarray(cert01, np.float32)
         if self.invert:                                                       # fav.lua:104-106: cert:add(-1):mul(-1)
             cert01 = (cert01 + np.float32(-1)) * np.float32(-1)
         if self.fix:                                                          # fav.lua:79-86,107-110
             ones = np.ones((1,) + cert01.shape, np.float32)
-            tmp = warp(ones, flo_to_lua(backward_flow_uv), self.border)[0]
-            tmp = np.maximum(np.sign(tmp + np.float32(-0.5)), 0).astype(np.float32)
+            tmp = warp(ones, flo_to_lua(backward_flow_uv), self.warp_mode)[0] + np.float32(-0.5)
+            # Tensor:sign() is (x > 0) - (x < 0): 0 for a NaN (a non-finite flow), where numpy's sign would hand the NaN on
+            tmp = np.maximum((tmp > 0).astype(np.float32) - (tmp < 0).astype(np.float32), 0).astype(np.float32)
             cert01 = cert01 * tmp
-        cert = min_filter(cert01, self.r)                                     # core:207
-        warped = warp(self.last, flo_to_lua(backward_flow_uv), self.border)  # fav.lua:153-158
+        return cert01
+
+    def input7(self, frame_rgb01, backward_flow_uv, cert01):
+        """the 7-channel network input of a frame with a prior (core.lua:161-171), without running the network.  Advances the counter."""
+        self.count += 1
+        cert = min_filter(self.certainty(backward_flow_uv, cert01), self.r)   # core:207
+        warped = warp(self.last, flo_to_lua(backward_flow_uv), self.warp_mode)  # fav.lua:153-158
         x = assemble(frame_rgb01, warped, cert)
         if self.fill_random:
             x[3:6] = self._fill(cert[None]) + x[3:6]
+        return x
+
+    def next(self, frame_rgb01, backward_flow_uv, cert01):
+        x = self.input7(frame_rgb01, backward_flow_uv, cert01)
         out = deprocess(net_forward(self.layers, x))
         self.last = out
         return out

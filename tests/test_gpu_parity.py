@@ -216,6 +216,17 @@ def test_min_filter_and_assemble(favlib, oracle, cuda):
         assert np.abs(got - oracle.assemble(fr, wp, cert)).max() <= 1e-5 * 255
         got0 = favlib.assemble(T(fr, cuda)).cpu().numpy()
         assert np.abs(got0 - oracle.assemble(fr, None, None)).max() <= 1e-5 * 255
+    # every window the kernel accepts (its LDS tiles are sized for exactly 15), even ones included (the asymmetric window
+    # -r/2 .. r-1-r/2 that tests/test_cpu_min_filter_windows.py pins), on grey certainties byte / 255: one pixel, less than a tile,
+    # exactly one 64 x 16 tile, one-pixel ragged tiles, interior seams on both axes
+    for (h, w) in [(1, 1), (7, 5), (16, 64), (17, 65), (33, 130)]:
+        grey = rng.integers(0, 256, (h, w)).astype(np.float32) / np.float32(255)
+        tg = T(grey, cuda)
+        for r in range(1, 16):
+            got = favlib.min_filter(tg, r).cpu().numpy()
+            assert np.array_equal(got, oracle.min_filter(grey, r)), (h, w, r)
+        with pytest.raises(favlib.FavError, match=r"window 16 unsupported \(1\.\.15\)"):
+            favlib.min_filter(tg, 16)
 
 
 # ---------------------------------------------------------------------------------------------- A8 layers
@@ -1147,6 +1158,22 @@ def test_temporal_loss_vs_oracle(favlib, oracle, cuda):
     got = favlib.temporal_loss(T(prev, cuda), T(cur, cuda), T(bw, cuda), T(cert, cuda))
     assert want > 1e-5 and abs(got - want) <= 1e-5 * want
     assert favlib.temporal_loss(T(prev, cuda), T(oracle.warp(prev, oracle.flo_to_lua(bw)), cuda), T(bw, cuda), T(cert, cuda)) <= 1e-12
+    # both borders, grey certainties (byte / 255 over 0..255), a frame of several blocks and the two smallest ones
+    for (h, w) in [(90, 130), (1, 1), (5, 3)]:
+        prev = rng.random((3, h, w)).astype(np.float32) * 1.2 - 0.1
+        bw = synth.backward_flow(h, w, 6) if h > 8 else synth.random_flow(h, w, 6, 0.5)
+        if h == 1:
+            bw[:] = 0          # a 1 x 1 frame has one place to sample
+        grey = rng.integers(0, 256, (h, w), dtype=np.uint8)
+        grey.reshape(-1)[0] = 200
+        for border, mode in ((favlib.BORDER_STN, "stn"), (favlib.BORDER_CPU, "cpu")):
+            warped = oracle.warp(prev, oracle.flo_to_lua(bw), mode)
+            cur = warped + rng.normal(0, 0.1, (3, h, w)).astype(np.float32)
+            want = oracle.temporal_loss(prev, cur, bw, grey.astype(np.float32) / np.float32(255), mode)
+            got = favlib.temporal_loss(T(prev, cuda), T(cur, cuda), T(bw, cuda), T(grey, cuda), border)
+            assert want > 1e-5 and abs(got - want) <= 1e-5 * want, (h, w, mode, got, want)
+            # zero by construction: no certainty anywhere
+            assert favlib.temporal_loss(T(prev, cuda), T(cur, cuda), T(bw, cuda), T(np.zeros((h, w), np.uint8), cuda), border) <= 1e-12
 
 
 @pytest.mark.parametrize("arch,size", [
