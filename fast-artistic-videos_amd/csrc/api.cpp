@@ -113,6 +113,20 @@ extern "C" int fav_consistency_u8(const float* flow1_flo, const float* flow2_flo
     return launch_consistency(flow1_flo, flow2_flo, structure, avg, out, W, H, st);
 }
 
+// test / tool entry: the structure map of the 4-argument mode itself, in either launch form (see include/fav.h)
+extern "C" int fav_structure_f32(const uint8_t* rgb_hwc, int W, int H, void* workspace, size_t workspace_bytes, float* structure_out,
+                                 float* avg_out, int pack_cus, int q0, int* form_ran, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(rgb_hwc && workspace && structure_out && avg_out && form_ran, "fav_structure_f32: null pointer");
+    FAV_REQUIRE(W >= 2 && H >= 2 && (long long)W * H <= (1ll << 28), "fav_structure_f32: bad frame size %dx%d (both sides at least 2, at most 2^28 pixels)", W, H);
+    FAV_REQUIRE(pack_cus >= 0 && pack_cus <= 4, "fav_structure_f32: pack_cus must be 0 (wide form) .. 4, not %d", pack_cus);
+    FAV_REQUIRE(q0 >= 0 && q0 <= 7, "fav_structure_f32: q0 must be 0 .. 7, not %d", q0);
+    FAV_REQUIRE(workspace_bytes >= structure_workspace_bytes(W, H), "fav_structure_f32: the workspace holds %zu bytes, fav_consistency_workspace_bytes(W, H, 1) is %zu",
+                workspace_bytes, structure_workspace_bytes(W, H));
+    int rc = ensure_device(); if (rc) return rc;
+    return launch_structure_map(rgb_hwc, W, H, workspace, workspace_bytes, structure_out, avg_out, pack_cus, q0, form_ran, static_cast<hipStream_t>(stream));
+}
+
 extern "C" int fav_min_filter_f32(const float* cert, float* out, int H, int W, int r, fav_hipstream_t stream)
 {
     FAV_REQUIRE(cert && out && H > 0 && W > 0 && r >= 1, "fav_min_filter_f32: bad argument");

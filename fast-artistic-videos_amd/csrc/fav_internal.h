@@ -390,7 +390,10 @@ int launch_temporal_loss(const float* prev_rgb, const float* cur_rgb, const floa
 
 size_t structure_workspace_bytes(int W, int H);
 int launch_structure(const uint8_t* rgb_hwc, int W, int H, void* ws, size_t ws_bytes,
-                     const float** structure_out, const float** avg_out, hipStream_t st, int pack_cus = 0, const int* q0_main = nullptr);
+                     const float** structure_out, const float** avg_out, hipStream_t st, int pack_cus = 0, const int* q0_main = nullptr,
+                     int* form_ran = nullptr);
+int launch_structure_map(const uint8_t* rgb_hwc, int W, int H, void* ws, size_t ws_bytes, float* structure_out, float* avg_out,
+                         int pack_cus, int q0, int* form_ran, hipStream_t st);
 int launch_sequential_sum(const float* x, size_t n, float* sum_out, hipStream_t st);
 int launch_consistency(const float* f1_flo, const float* f2_flo, const float* structure, const float* avg,
                        uint8_t* out, int W, int H, hipStream_t st);

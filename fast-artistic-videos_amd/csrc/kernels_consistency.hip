@@ -923,8 +923,9 @@ static void iir_constants(float sigma, IIR& c)
 // passes run as pack_cus blocks of eight waves instead of one block per wave (see iir_rows_kernel) -- together with the one-block scans
 // they are the mask's only long-lived blocks, and they then hold at most pack_cus CUs at any time.  The wide kernels stay wide: their
 // blocks live for microseconds (measured: all of them together cost the network 4 us per frame).  0: the widest form (stand-alone mask).
+// form_ran (optional, host): which form was LAUNCHED -- FAV_STRUCTURE_PACKED, or FAV_STRUCTURE_WIDE (asked for, or the fall-back below)
 int launch_structure(const uint8_t* rgb_hwc, int W, int H, void* ws, size_t ws_bytes, const float** structure_out,
-                     const float** avg_out, hipStream_t st, int pack_cus, const int* q0_main)
+                     const float** avg_out, hipStream_t st, int pack_cus, const int* q0_main, int* form_ran)
 {
     if (!q0_main) pack_cus = 0;
     if (pack_cus > 0) {
@@ -1000,6 +1001,31 @@ int launch_structure(const uint8_t* rgb_hwc, int W, int H, void* ws, size_t ws_b
     FAV_LAUNCH_CHECK("structure kernels");
     *structure_out = corners;
     *avg_out = mm + 2;
+    if (form_ran) *form_ran = pack_cus > 0 ? FAV_STRUCTURE_PACKED : FAV_STRUCTURE_WIDE;
+    return FAV_OK;
+}
+
+// fav_structure_f32: the map and its average in the caller's buffers, in either launch form.  The packed form's "where the network's
+// queue starts" word is written here, in stream order, into a word of the workspace no kernel uses (the 256 bytes of cmax / cmin / avg
+// hold three floats: word 4); the copies out of the workspace are stream-ordered too.
+int launch_structure_map(const uint8_t* rgb_hwc, int W, int H, void* ws, size_t ws_bytes, float* structure_out, float* avg_out,
+                         int pack_cus, int q0, int* form_ran, hipStream_t st)
+{
+    const size_t n = (size_t)W * H;
+    const size_t nb = (n + NB - 1) / NB;
+    // (launch_structure's layout: ten planes, then bmax / bpre / bmin, then the 256 bytes of cmax / cmin / avg)
+    float* mm = static_cast<float*>(ws) + 10 * structure_plane_floats(W, H) + 3 * (align_up(nb * 4, 256) / 4);
+    int* q0_word = nullptr;
+    if (pack_cus > 0) {
+        q0_word = reinterpret_cast<int*>(mm + 4);
+        FAV_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(q0_word), q0, 1, st));
+    }
+    const float* structure = nullptr; const float* avg = nullptr;
+    int rc = launch_structure(rgb_hwc, W, H, ws, ws_bytes, &structure, &avg, st, pack_cus, q0_word, form_ran);
+    if (rc) return rc;
+    FAV_REQUIRE(avg == mm + 2, "fav_structure_f32: the workspace layout moved under the q0 word");
+    FAV_HIP(hipMemcpyAsync(structure_out, structure, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    FAV_HIP(hipMemcpyAsync(avg_out, avg, sizeof(float), hipMemcpyDeviceToDevice, st));
     return FAV_OK;
 }
 

@@ -111,6 +111,7 @@ EXPORTS = [
     "fav_y4m_parse_header_host", "fav_y4m_format_header_host",
     "fav_scene_change_workspace_bytes", "fav_scene_change_rgb8",
     "fav_color_transfer_rgb8", "fav_color_transfer_yuv", "fav_stream_encode_png_colors", "fav_stream_encode_yuv_colors",
+    "fav_structure_f32",
 ]
 
 
@@ -173,6 +174,32 @@ def consistency(flow1_flo, flow2_flo, rgb_hwc=None):
     _check(lib().fav_consistency_u8(_p(flow1_flo), _p(flow2_flo), _p(rgb_hwc), _p(out), w, h, _p(ws),
                                     C.c_size_t(ws_bytes), _stream()))
     return out
+
+
+STRUCTURE_WIDE, STRUCTURE_PACKED = 0, 1
+
+
+def structure(rgb_hwc, pack_cus: int = 0, q0: int = 0, ws=None, out=None, avg=None):
+    """fav_structure_f32: the structure map of the 4-argument check of a u8 [H][W][3] frame -> (map [H][W] f32, avg [1] f32, form_ran).
+    pack_cus = 0: the wide launch form (what consistency() runs); 1..4: the packed form of the look-ahead path, q0 (0..7) its placement
+    word.  form_ran: STRUCTURE_WIDE | STRUCTURE_PACKED, the form that was launched.  ws / out / avg: the caller's workspace (u8, at least
+    fav_consistency_workspace_bytes(W, H, 1) elements) and output tensors (tests hand them in pre-filled)."""
+    torch = _torch()
+    if not (rgb_hwc.is_cuda and rgb_hwc.dtype == torch.uint8 and rgb_hwc.dim() == 3 and rgb_hwc.shape[2] == 3 and rgb_hwc.is_contiguous()):
+        raise FavError("structure: the frame must be a contiguous uint8 CUDA tensor [H][W][3]")
+    h, w = rgb_hwc.shape[0], rgb_hwc.shape[1]
+    if ws is None:
+        ws = torch.empty((max(lib().fav_consistency_workspace_bytes(w, h, 1), 1),), dtype=torch.uint8, device=rgb_hwc.device)
+    if out is None:
+        out = torch.empty((h, w), dtype=torch.float32, device=rgb_hwc.device)
+    if avg is None:
+        avg = torch.empty(1, dtype=torch.float32, device=rgb_hwc.device)
+    _chk_f32(out, "out"); _chk_f32(avg, "avg")
+    assert ws.dtype == torch.uint8 and ws.is_contiguous() and out.numel() >= h * w
+    form = C.c_int(-1)
+    _check(lib().fav_structure_f32(_p(rgb_hwc), w, h, _p(ws), C.c_size_t(ws.numel()), _p(out), _p(avg), int(pack_cus), int(q0),
+                                   C.byref(form), _stream()))
+    return out, avg, form.value
 
 
 def min_filter(cert, r: int = 7):

@@ -84,6 +84,21 @@ int fav_consistency_u8(const float* flow1_flo, const float* flow2_flo, const uin
                        uint8_t* out, int W, int H, void* workspace, size_t workspace_bytes,
                        fav_hipstream_t stream);
 
+/* test / tool entry: the structure map of the 4-argument mode itself -- computeCorners(image, 3.0f) + CMatrix::normalize(0, 1)
+ * (consistencyChecker.cpp:39-78,158-159) into structure_out [H][W] fp32 and its CMatrix::avg() into avg_out [1], both device memory,
+ * bit-exact with the reference binary.  rgb_hwc, workspace (fav_consistency_workspace_bytes(W, H, 1) bytes): as for fav_consistency_u8.
+ * pack_cus == 0: the wide launch form, as fav_consistency_u8 runs it.  pack_cus 1..4: the packed form of the look-ahead path
+ * (fav_stream_prefetch_mask) with that many working blocks; q0 (0..7) is written, in stream order, into the device word the packed
+ * kernels read as "the XCD the network's queue deals block 0 to".  Called stand-alone the eight blocks of each launch land one per
+ * XCD, so every q0 is a valid placement and gives the same bits.  *form_ran (host) receives the form that was launched: a device that
+ * does not present eight XCDs runs the wide form whatever pack_cus says.  Enqueues on `stream` and returns; the first packed call on
+ * a device synchronises `stream` once (the XCD probe).  FAV_EINVAL (nothing written) for a null pointer, W < 2, H < 2, a short
+ * workspace, pack_cus or q0 out of range. */
+enum fav_structure_form { FAV_STRUCTURE_WIDE = 0, FAV_STRUCTURE_PACKED = 1 };
+int fav_structure_f32(const uint8_t* rgb_hwc, int W, int H, void* workspace, size_t workspace_bytes,
+                      float* structure_out, float* avg_out, int pack_cus, int q0, int* form_ran,
+                      fav_hipstream_t stream);
+
 /* ---- A5: certainty erosion -------------------------------------------------------------------
  * Replaces utils.min_filter(cert, r) (fast_artistic_video/utils.lua:161-169):
  * 1 - maxpool_{r x r, stride 1, pad r/2}(1 - cert), window truncated at the borders. cert [H][W]. */

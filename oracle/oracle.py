@@ -22,6 +22,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 REF_CHECKER = os.path.join(_HERE, "_ref", "consistencyChecker")
+STRUCTURE_REF = os.path.join(_HERE, "_ref", "libstructure_ref.so")
 
 
 def build(force: bool = False) -> None:
@@ -31,6 +32,8 @@ def build(force: bool = False) -> None:
         subprocess.check_call(["make", "-C", _HERE, "libfav_oracle.so"], stdout=subprocess.DEVNULL)
     if os.path.isdir("/root/reference/consistencyChecker") and (force or not os.path.exists(REF_CHECKER)):
         subprocess.check_call(["make", "-C", _HERE, "ref"], stdout=subprocess.DEVNULL)
+    if force or not structure_ref_available():      # (the target itself looks for the reference tree and leaves things as they are without it)
+        subprocess.check_call(["make", "-C", _HERE, "structure_ref"], stdout=subprocess.DEVNULL)
     if os.path.isdir("/root/reference/stnbdhw") and (force or not warp_ref_available()):
         subprocess.check_call(["make", "-C", _HERE, "warp_ref"], stdout=subprocess.DEVNULL)
 
@@ -160,12 +163,54 @@ def corners(rgb_hwc_u8: np.ndarray) -> np.ndarray:
     return out
 
 
-def consistency(flow1_uv: np.ndarray, flow2_uv: np.ndarray, rgb_hwc_u8: Optional[np.ndarray] = None) -> np.ndarray:
-    """flow*_uv: [H][W][2] as read from .flo.  Returns the PGM payload [H][W] u8 in {0,255}."""
+def structure(rgb_hwc_u8: np.ndarray):
+    """The structure map of the 4-argument mode as the checker uses it: (computeCorners + normalize(0, 1) [H][W] f32, its
+    CMatrix::avg() as a numpy float32), fp32 operations in the reference's order."""
+    m = corners(rgb_hwc_u8)
+    h, w = m.shape
+    return m, np.float32(lib().orc_avg(m.ctypes.data_as(C.POINTER(C.c_float)), w, h))
+
+
+_STRUCTURE_REF = None
+
+
+def structure_ref_available() -> bool:
+    return os.path.exists(STRUCTURE_REF)
+
+
+def structure_ref(rgb_hwc_u8: np.ndarray):
+    """The same pair from the reference's OWN compiled code (oracle/_ref/libstructure_ref.so = structure_ref_shim.cpp around the
+    reference's consistencyChecker.cpp, built by oracle/Makefile with the reference's flags); the image travels through a
+    temporary PPM and the reference's own readFromPPM."""
+    import tempfile
+    global _STRUCTURE_REF
+    if _STRUCTURE_REF is None:
+        _STRUCTURE_REF = C.CDLL(STRUCTURE_REF)
+        _STRUCTURE_REF.structure_ref.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_float),
+                                                 C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    h, w, _ = rgb_hwc_u8.shape
+    out = np.full((h, w), np.nan, np.float32)
+    avg, rw, rh = C.c_float(float("nan")), C.c_int(0), C.c_int(0)
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "i.ppm")
+        write_pnm(path, rgb_hwc_u8)
+        rc = _STRUCTURE_REF.structure_ref(path.encode(), out.ctypes.data_as(C.POINTER(C.c_float)), out.size, C.byref(avg),
+                                          C.byref(rw), C.byref(rh))
+    assert rc == 0 and (rw.value, rh.value) == (w, h), (rc, rw.value, rh.value, w, h)
+    return out, np.float32(avg.value)
+
+
+def consistency(flow1_uv: np.ndarray, flow2_uv: np.ndarray, rgb_hwc_u8: Optional[np.ndarray] = None,
+                structure: Optional[np.ndarray] = None) -> np.ndarray:
+    """flow*_uv: [H][W][2] as read from .flo.  Returns the PGM payload [H][W] u8 in {0,255}.
+    structure: a normalised structure map [H][W] f32 to use instead of the one computed from rgb_hwc_u8 (tests)."""
     h, w, _ = flow1_uv.shape
     f1, p1 = _f(flo_to_planar_uv(flow1_uv)); f2, p2 = _f(flo_to_planar_uv(flow2_uv))
     out = np.empty((h, w), np.uint8)
-    if rgb_hwc_u8 is not None:
+    if structure is not None:
+        assert structure.shape == (h, w)
+        st, ps = _f(structure)
+    elif rgb_hwc_u8 is not None:
         st, ps = _f(corners(rgb_hwc_u8))
     else:
         st, ps = None, None

@@ -6,6 +6,7 @@ is not a reference output.
 
     python tests/golden/make_golden.py
     python tests/golden/make_golden.py --live      (only the stored reference-checker cases of tests/test_cpu_oracle.py)
+    python tests/golden/make_golden.py --structure (only structure_ref_cases.npz: structure maps of the reference's compiled code)
     python tests/golden/make_golden.py --warp --out gpurun_out/golden      (ON THE GPU BOX: warp fixtures)
 
 The warp fixtures (warp_*.npz) are outputs of the reference's OWN warp kernel (stnbdhw/BilinearSamplerBDHW.cu:1-109 compiled for
@@ -72,6 +73,23 @@ def live_mask_fixtures():
         bw[y, x, c] = np.float32(v); hit.append((y, x))
     np.savez_compressed(os.path.join(HERE, "mask_extreme_flows_24x40.npz"), bw=bw, fw=fw, hit=np.array(hit, dtype=np.int32),
                         mask3=_ref_mask(d, bw, fw))
+
+
+def structure_fixture():
+    """structure_ref_cases.npz: for every case of tests/util/structure_cases.FIXTURE_CASES the u8 image, the normalised structure map
+    and its CMatrix::avg() as the reference's own compiled code gives them (oracle/_ref/libstructure_ref.so: oracle/structure_ref_shim.cpp
+    around the reference's consistencyChecker.cpp, g++ -O3 -fPIC -w -shared) -- recorded results, for machines without the reference"""
+    sys.path.insert(0, os.path.join(ROOT, "tests", "util"))
+    import structure_cases as SC
+    assert O.structure_ref_available(), "oracle/_ref/libstructure_ref.so missing (needs the reference tree)"
+    out = {}
+    for (h, w, kind) in SC.FIXTURE_CASES:
+        img = SC.image(kind, h, w)
+        m, avg = O.structure_ref(img)
+        out[f"img_{h}x{w}_{kind}"] = img; out[f"map_{h}x{w}_{kind}"] = m; out[f"avg_{h}x{w}_{kind}"] = np.float32(avg)
+    path = os.path.join(HERE, "structure_ref_cases.npz")
+    np.savez_compressed(path, **out)
+    print("structure_ref_cases.npz", len(SC.FIXTURE_CASES), "cases", os.path.getsize(path), "bytes")
 
 
 def net_fixture():
@@ -148,10 +166,14 @@ if __name__ == "__main__":
         sys.exit(0)
     O.build()
     assert os.path.exists(O.REF_CHECKER), "oracle/_ref/consistencyChecker missing (needs /root/reference)"
+    if "--structure" in sys.argv:
+        structure_fixture()
+        sys.exit(0)
     if "--live" in sys.argv:
         live_mask_fixtures()
         sys.exit(0)
     mask_fixture("mask_smooth_64x96.npz", 64, 96, "smooth", 100)
     mask_fixture("mask_rand_120x160.npz", 120, 160, "rand", 200)
     mask_fixture("mask_smooth_180x320.npz", 180, 320, "smooth", 300)
+    structure_fixture()
     net_fixture()
