@@ -205,6 +205,51 @@ extern "C" int fav_rgb_f32_to_yuv(const float* rgb_planar, int W, int H, const f
     return launch_rgb_to_yuv(nullptr, rgb_planar, W, H, *fmt_host, yuv, static_cast<hipStream_t>(stream));
 }
 
+// ---- every layout of include/fav_yuv.h: 4:2:0, 4:2:2, 4:4:4 at 8 .. 16 bits (kernels_yuv_layout.hip)
+static bool yuv_depth_ok(int d) { return d == 8 || d == 9 || d == 10 || d == 12 || d == 14 || d == 16; }
+
+int fav::yuv_layout_check(const char* who, int W, int H, const fav_yuv_layout* l)
+{
+    FAV_REQUIRE(l, "%s: null layout", who);
+    FAV_REQUIRE(l->struct_bytes == sizeof(fav_yuv_layout), "%s: struct_bytes must be %zu (sizeof(fav_yuv_layout)), not %u", who, sizeof(fav_yuv_layout), l->struct_bytes);
+    FAV_REQUIRE(W > 0 && H > 0 && (long long)W * H <= (1ll << 28), "%s: bad frame size %dx%d", who, W, H);
+    FAV_REQUIRE(l->chroma == FAV_YUV_420 || l->chroma == FAV_YUV_444 || l->chroma == FAV_YUV_422, "%s: chroma must be 0 (4:2:0), 1 (4:4:4) or 2 (4:2:2), not %d", who, l->chroma);
+    FAV_REQUIRE(l->chroma == FAV_YUV_444 || l->siting == FAV_YUV_SITING_CENTER || l->siting == FAV_YUV_SITING_LEFT,
+                "%s: siting must be 0 (centre) or 1 (left), not %d", who, l->siting);
+    FAV_REQUIRE(l->matrix == FAV_YUV_BT601 || l->matrix == FAV_YUV_BT709, "%s: matrix must be 0 (BT.601) or 1 (BT.709), not %d", who, l->matrix);
+    FAV_REQUIRE(yuv_depth_ok(l->depth), "%s: depth must be 8, 9, 10, 12, 14 or 16, not %d", who, l->depth);
+    return FAV_OK;
+}
+
+extern "C" size_t fav_yuv_layout_frame_bytes(int W, int H, const fav_yuv_layout* layout_host)
+{
+    return yuv_layout_check("fav_yuv_layout_frame_bytes", W, H, layout_host) ? 0 : yuv_layout_frame_bytes(W, H, *layout_host);
+}
+
+extern "C" int fav_yuv_layout_to_rgb8(const void* yuv, int W, int H, const fav_yuv_layout* layout_host, uint8_t* rgb_hwc, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(yuv && rgb_hwc, "fav_yuv_layout_to_rgb8: null pointer");
+    int rc = yuv_layout_check("fav_yuv_layout_to_rgb8", W, H, layout_host); if (rc) return rc;
+    rc = ensure_device(); if (rc) return rc;
+    return launch_yuv_layout_to_rgb8(yuv, W, H, *layout_host, rgb_hwc, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int fav_rgb8_to_yuv_layout(const uint8_t* rgb_hwc, int W, int H, const fav_yuv_layout* layout_host, void* yuv, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(rgb_hwc && yuv, "fav_rgb8_to_yuv_layout: null pointer");
+    int rc = yuv_layout_check("fav_rgb8_to_yuv_layout", W, H, layout_host); if (rc) return rc;
+    rc = ensure_device(); if (rc) return rc;
+    return launch_rgb_to_yuv_layout(rgb_hwc, nullptr, W, H, *layout_host, yuv, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int fav_rgb_f32_to_yuv_layout(const float* rgb_planar, int W, int H, const fav_yuv_layout* layout_host, void* yuv, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(rgb_planar && yuv, "fav_rgb_f32_to_yuv_layout: null pointer");
+    int rc = yuv_layout_check("fav_rgb_f32_to_yuv_layout", W, H, layout_host); if (rc) return rc;
+    rc = ensure_device(); if (rc) return rc;
+    return launch_rgb_to_yuv_layout(nullptr, rgb_planar, W, H, *layout_host, yuv, static_cast<hipStream_t>(stream));
+}
+
 // ---- original colours: the stylised frame's luminance on the original frame's colours (kernels_color.hip)
 extern "C" int fav_color_transfer_rgb8(const float* stylised_rgb_planar, const uint8_t* original_rgb_hwc, int W, int H, int matrix,
                                        uint8_t* out_rgb_hwc, fav_hipstream_t stream)
@@ -462,16 +507,57 @@ static bool y4m_ratio(const std::string& tag, int* num, int* den)   // "<letter>
     return c != std::string::npos && y4m_int(tag.data() + 1, tag.data() + c, num) && y4m_int(tag.data() + c + 1, tag.data() + tag.size(), den);
 }
 
+// the C tag of include/fav_yuv.h: "420", "420jpeg", "420mpeg2", "422", "444", "4xxpN"
+static bool y4m_colour_space(const std::string& name, fav_yuv_layout* l)
+{
+    l->depth = 8;
+    if (name == "420" || name == "420jpeg") { l->chroma = FAV_YUV_420; l->siting = FAV_YUV_SITING_CENTER; return true; }
+    if (name == "420mpeg2") { l->chroma = FAV_YUV_420; l->siting = FAV_YUV_SITING_LEFT; return true; }
+    if (name == "444") { l->chroma = FAV_YUV_444; l->siting = FAV_YUV_SITING_CENTER; return true; }
+    if (name == "422") { l->chroma = FAV_YUV_422; l->siting = FAV_YUV_SITING_LEFT; return true; }
+    if (name.size() < 5 || name[3] != 'p') return false;
+    const std::string base = name.substr(0, 3), bits = name.substr(4);
+    if (bits != "9" && bits != "10" && bits != "12" && bits != "14" && bits != "16") return false;
+    if (base == "420") { l->chroma = FAV_YUV_420; l->siting = FAV_YUV_SITING_CENTER; }
+    else if (base == "422") { l->chroma = FAV_YUV_422; l->siting = FAV_YUV_SITING_LEFT; }
+    else if (base == "444") { l->chroma = FAV_YUV_444; l->siting = FAV_YUV_SITING_CENTER; }
+    else return false;
+    l->depth = atoi(bits.c_str());
+    return true;
+}
+
+// one grammar behind both parsers; every_layout: the C tags of fav_yuv.h, else those of fav.h (h.layout is then 8-bit 4:2:0 / 4:4:4)
+static int y4m_parse(const char* line, size_t len, fav_y4m_stream_header* out, bool every_layout);
+
 extern "C" int fav_y4m_parse_header_host(const char* line, size_t len, fav_y4m_header* out)
 {
     FAV_REQUIRE(line && out, "fav_y4m_parse_header_host: null argument");
+    fav_y4m_stream_header h;
+    int rc = y4m_parse(line, len, &h, false); if (rc) return rc;
+    memset(out, 0, sizeof *out);
+    out->W = h.W; out->H = h.H; out->fps_num = h.fps_num; out->fps_den = h.fps_den; out->aspect_num = h.aspect_num; out->aspect_den = h.aspect_den;
+    out->interlace = h.interlace;
+    out->fmt = fav_yuv_format{h.layout.chroma, h.layout.siting, h.layout.matrix, h.layout.full_range};
+    memcpy(out->xtags, h.xtags, sizeof out->xtags);
+    return FAV_OK;
+}
+
+extern "C" int fav_y4m_parse_stream_header_host(const char* line, size_t len, fav_y4m_stream_header* out)
+{
+    FAV_REQUIRE(line && out, "fav_y4m_parse_stream_header_host: null argument");
+    return y4m_parse(line, len, out, true);
+}
+
+static int y4m_parse(const char* line, size_t len, fav_y4m_stream_header* out, bool every_layout)
+{
     size_t n = 0;
     while (n < len && n < FAV_Y4M_MAX_HEADER && line[n] != '\n') ++n;
     FAV_REQUIRE(n < FAV_Y4M_MAX_HEADER, "Y4M header: longer than %d bytes", FAV_Y4M_MAX_HEADER);
     FAV_REQUIRE(n >= 9 && !memcmp(line, "YUV4MPEG2", 9) && (n == 9 || line[9] == ' '), "Y4M header: the stream does not start with YUV4MPEG2");
-    fav_y4m_header h;
+    fav_y4m_stream_header h;
     memset(&h, 0, sizeof h);
     h.aspect_num = -1;
+    h.layout.struct_bytes = sizeof(fav_yuv_layout); h.layout.depth = 8;
     bool have_w = false, have_h = false;
     std::string xt;
     for (size_t p = 9; p < n;) {
@@ -491,15 +577,16 @@ extern "C" int fav_y4m_parse_header_host(const char* line, size_t len, fav_y4m_h
             h.interlace = tag[1];
             break;
         case 'C':
-            if (tag == "C420" || tag == "C420jpeg") { h.fmt.chroma = FAV_YUV_420; h.fmt.siting = FAV_YUV_SITING_CENTER; }
-            else if (tag == "C420mpeg2") { h.fmt.chroma = FAV_YUV_420; h.fmt.siting = FAV_YUV_SITING_LEFT; }
-            else if (tag == "C444") { h.fmt.chroma = FAV_YUV_444; h.fmt.siting = FAV_YUV_SITING_CENTER; }
-            else { set_error("Y4M header: colour space %s is not supported (8-bit C420, C420jpeg, C420mpeg2 and C444 are)", tag.c_str()); return FAV_EUNSUPPORTED; }
+            if (!y4m_colour_space(tag.substr(1), &h.layout) || (!every_layout && (h.layout.depth != 8 || h.layout.chroma == FAV_YUV_422))) {
+                if (every_layout) set_error("Y4M header: colour space %s is not supported (C420, C420jpeg, C420mpeg2, C422, C444 and C420pN, C422pN, C444pN with N in 9, 10, 12, 14, 16 are)", tag.c_str());
+                else set_error("Y4M header: colour space %s is not supported (8-bit C420, C420jpeg, C420mpeg2 and C444 are)", tag.c_str());
+                return FAV_EUNSUPPORTED;
+            }
             break;
         case 'X':
             if (tag.compare(0, 12, "XCOLORRANGE=") == 0) {
                 FAV_REQUIRE(tag == "XCOLORRANGE=FULL" || tag == "XCOLORRANGE=LIMITED", "Y4M header: bad tag %s", tag.c_str());
-                h.fmt.full_range = tag == "XCOLORRANGE=FULL";
+                h.layout.full_range = tag == "XCOLORRANGE=FULL";
             }
             xt += (xt.empty() ? "" : " ") + tag;
             break;
@@ -508,24 +595,54 @@ extern "C" int fav_y4m_parse_header_host(const char* line, size_t len, fav_y4m_h
     }
     FAV_REQUIRE(have_w && have_h, "Y4M header: the %s tag is missing", have_w ? "H" : "W");
     FAV_REQUIRE((long long)h.W * h.H <= (1ll << 28), "Y4M header: %dx%d frames are too large", h.W, h.H);
-    h.fmt.matrix = h.H >= 720 ? FAV_YUV_BT709 : FAV_YUV_BT601;      // the stream carries none: the usual player heuristic
+    h.layout.matrix = h.H >= 720 ? FAV_YUV_BT709 : FAV_YUV_BT601;      // the stream carries none: the usual player heuristic
     memcpy(h.xtags, xt.c_str(), xt.size() + 1);                     // (shorter than the line, which is shorter than the array)
     *out = h;
     return FAV_OK;
 }
 
+// one formatter behind both entry points (`who` names the one called); the layout has been checked
+static int y4m_format(const char* who, const fav_y4m_stream_header* h, char* buf_host, size_t capacity);
+
 extern "C" int fav_y4m_format_header_host(const fav_y4m_header* h, char* buf_host, size_t capacity)
 {
     FAV_REQUIRE(h && buf_host, "fav_y4m_format_header_host: null argument");
     int rc = yuv_format_check("fav_y4m_format_header_host", h->W, h->H, &h->fmt); if (rc) return rc;
-    FAV_REQUIRE(h->interlace == 0 || h->interlace == 'p' || h->interlace == '?', "fav_y4m_format_header_host: interlace must be 0, 'p' or '?'");
-    FAV_REQUIRE(memchr(h->xtags, 0, sizeof h->xtags) != nullptr, "fav_y4m_format_header_host: xtags is not terminated");
+    fav_y4m_stream_header s;
+    s.W = h->W; s.H = h->H; s.fps_num = h->fps_num; s.fps_den = h->fps_den; s.aspect_num = h->aspect_num; s.aspect_den = h->aspect_den;
+    s.interlace = h->interlace;
+    s.layout = fav_yuv_layout{(uint32_t)sizeof(fav_yuv_layout), h->fmt.chroma, h->fmt.chroma == FAV_YUV_444 ? FAV_YUV_SITING_CENTER : h->fmt.siting,
+                              h->fmt.matrix, h->fmt.full_range, 8};
+    memcpy(s.xtags, h->xtags, sizeof s.xtags);
+    return y4m_format("fav_y4m_format_header_host", &s, buf_host, capacity);
+}
+
+extern "C" int fav_y4m_format_stream_header_host(const fav_y4m_stream_header* h, char* buf_host, size_t capacity)
+{
+    FAV_REQUIRE(h && buf_host, "fav_y4m_format_stream_header_host: null argument");
+    int rc = yuv_layout_check("fav_y4m_format_stream_header_host", h->W, h->H, &h->layout); if (rc) return rc;
+    return y4m_format("fav_y4m_format_stream_header_host", h, buf_host, capacity);
+}
+
+static int y4m_format(const char* who, const fav_y4m_stream_header* h, char* buf_host, size_t capacity)
+{
+    const fav_yuv_layout& l = h->layout;
+    const bool left = l.chroma != FAV_YUV_444 && l.siting == FAV_YUV_SITING_LEFT;
+    std::string ctag = l.chroma == FAV_YUV_444 ? "C444" : l.chroma == FAV_YUV_422 ? "C422" : l.depth > 8 ? "C420" : left ? "C420mpeg2" : "C420jpeg";
+    if (l.depth > 8) ctag += "p" + std::to_string(l.depth);
+    if ((l.chroma == FAV_YUV_422 && !left) || (l.chroma == FAV_YUV_420 && left && l.depth > 8)) {
+        set_error("%s: YUV4MPEG2 has no colour-space tag for %s: %s is %s-sited", who, l.chroma == FAV_YUV_422 ? "4:2:2 with centre siting" : "left-sited 4:2:0 above 8 bits",
+                  ctag.c_str(), l.chroma == FAV_YUV_422 ? "left" : "centre");
+        return FAV_EUNSUPPORTED;
+    }
+    FAV_REQUIRE(h->interlace == 0 || h->interlace == 'p' || h->interlace == '?', "%s: interlace must be 0, 'p' or '?'", who);
+    FAV_REQUIRE(memchr(h->xtags, 0, sizeof h->xtags) != nullptr, "%s: xtags is not terminated", who);
     std::string s = "YUV4MPEG2 W" + std::to_string(h->W) + " H" + std::to_string(h->H);
     if (h->fps_den > 0) s += " F" + std::to_string(h->fps_num) + ":" + std::to_string(h->fps_den);
     if (h->interlace) s += std::string(" I") + (char)h->interlace;
     if (h->aspect_num >= 0) s += " A" + std::to_string(h->aspect_num) + ":" + std::to_string(h->aspect_den);
-    s += h->fmt.chroma == FAV_YUV_444 ? " C444" : h->fmt.siting == FAV_YUV_SITING_LEFT ? " C420mpeg2" : " C420jpeg";
-    const char* const range = h->fmt.full_range ? "XCOLORRANGE=FULL" : "XCOLORRANGE=LIMITED";
+    s += " " + ctag;
+    const char* const range = l.full_range ? "XCOLORRANGE=FULL" : "XCOLORRANGE=LIMITED";
     bool range_written = false;
     const std::string xt = h->xtags;
     for (size_t p = 0; p < xt.size();) {
@@ -534,14 +651,14 @@ extern "C" int fav_y4m_format_header_host(const fav_y4m_header* h, char* buf_hos
         if (e == std::string::npos) e = xt.size();
         const std::string tag = xt.substr(p, e - p);
         p = e;
-        FAV_REQUIRE(tag[0] == 'X' && tag.find('\n') == std::string::npos, "fav_y4m_format_header_host: '%s' in xtags is no X tag", tag.c_str());
+        FAV_REQUIRE(tag[0] == 'X' && tag.find('\n') == std::string::npos, "%s: '%s' in xtags is no X tag", who, tag.c_str());
         if (tag.compare(0, 12, "XCOLORRANGE=") == 0) { if (!range_written) s += std::string(" ") + range; range_written = true; }
         else s += " " + tag;
     }
-    if (!range_written && h->fmt.full_range) s += std::string(" ") + range;
+    if (!range_written && l.full_range) s += std::string(" ") + range;
     s += "\n";
-    FAV_REQUIRE(s.size() <= FAV_Y4M_MAX_HEADER, "fav_y4m_format_header_host: the header would be longer than %d bytes", FAV_Y4M_MAX_HEADER);
-    FAV_REQUIRE(s.size() < capacity, "fav_y4m_format_header_host: %zu bytes do not fit the caller's buffer", s.size() + 1);
+    FAV_REQUIRE(s.size() <= FAV_Y4M_MAX_HEADER, "%s: the header would be longer than %d bytes", who, FAV_Y4M_MAX_HEADER);
+    FAV_REQUIRE(s.size() < capacity, "%s: %zu bytes do not fit the caller's buffer", who, s.size() + 1);
     memcpy(buf_host, s.c_str(), s.size() + 1);
     return (int)s.size();
 }

@@ -369,6 +369,12 @@ size_t yuv_frame_bytes(int W, int H, const fav_yuv_format& f);
 int yuv_format_check(const char* who, int W, int H, const fav_yuv_format* f);
 int launch_yuv_to_rgb8(const uint8_t* yuv, int W, int H, const fav_yuv_format& f, uint8_t* rgb_hwc, hipStream_t st);
 int launch_rgb_to_yuv(const uint8_t* rgb_hwc, const float* rgb_planar, int W, int H, const fav_yuv_format& f, uint8_t* yuv, hipStream_t st);
+// the same for every layout of include/fav_yuv.h (kernels_yuv_layout.hip: 4:2:2, 9 .. 16 bits; depth 8 in 4:2:0 / 4:4:4 goes to the
+// launchers above); the layout has been validated (yuv_layout_check, api.cpp)
+size_t yuv_layout_frame_bytes(int W, int H, const fav_yuv_layout& l);
+int yuv_layout_check(const char* who, int W, int H, const fav_yuv_layout* l);
+int launch_yuv_layout_to_rgb8(const void* yuv, int W, int H, const fav_yuv_layout& l, uint8_t* rgb_hwc, hipStream_t st);
+int launch_rgb_to_yuv_layout(const uint8_t* rgb_hwc, const float* rgb_planar, int W, int H, const fav_yuv_layout& l, void* yuv, hipStream_t st);
 // the stylised frame's luminance on the original frame's colours (kernels_color.hip; tests/util/color_model.py), as an RGB8 image or as
 // the planes of that image; sizes, matrix and format have been validated (api.cpp)
 int launch_color_transfer_rgb8(const float* state, const uint8_t* orig_hwc, int W, int H, int matrix, uint8_t* out_hwc, hipStream_t st);

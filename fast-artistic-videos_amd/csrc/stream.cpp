@@ -495,6 +495,18 @@ extern "C" int fav_stream_encode_yuv(fav_stream* s, const fav_yuv_format* fmt_ho
     return launch_rgb_to_yuv(nullptr, s->state.get(), s->Wo, s->Ho, *fmt_host, yuv_out, static_cast<hipStream_t>(stream));
 }
 
+// the same for every layout of include/fav_yuv.h (kernels_yuv_layout.hip): above 8 bits the state's floats enter unquantised
+extern "C" int fav_stream_encode_yuv_layout(fav_stream* s, const fav_yuv_layout* layout_host, void* yuv_out, size_t capacity, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(s && s->has_state, "fav_stream_encode_yuv_layout: no stylised frame yet");
+    FAV_REQUIRE(yuv_out, "fav_stream_encode_yuv_layout: null output");
+    { int rc = yuv_layout_check("fav_stream_encode_yuv_layout", s->Wo, s->Ho, layout_host); if (rc) return rc; }
+    const size_t need = yuv_layout_frame_bytes(s->Wo, s->Ho, *layout_host);
+    FAV_REQUIRE(capacity >= need, "fav_stream_encode_yuv_layout: a %dx%d frame takes %zu bytes, the buffer holds %zu", s->Wo, s->Ho, need, capacity);
+    FAV_HIP(hipSetDevice(net_device(s->net)));
+    return launch_rgb_to_yuv_layout(nullptr, s->state.get(), s->Wo, s->Ho, *layout_host, yuv_out, static_cast<hipStream_t>(stream));
+}
+
 // -original_colors: the current stylised frame's luminance on the colours of `frame_rgb_hwc` (kernels_color.hip).  The state is read only.
 // The frame and the stylised frame must be one size: a network that pads its output to a multiple of 4 has no original pixel there
 static int colors_size_check(const char* who, const fav_stream* s)

@@ -42,6 +42,9 @@
 // -y4m_matrix <auto|bt601|bt709>, -y4m_range <auto|limited|full>: override what the input's header says or lacks (auto: XCOLORRANGE,
 //   else limited; BT.709 from 720 rows on, else BT.601 -- Y4M carries no matrix); -y4m_format <420jpeg|420mpeg2|444>: the output's
 //   sampling when it is not to be the input's (without -input_y4m the default is 420jpeg).
+//   -y4m_pixel_format <tag> sets the output's whole layout instead, by Y4M's own C value: 420jpeg, 420mpeg2, 422, 444, and 420pN, 422pN,
+//   444pN with N in 9, 10, 12, 14, 16 (include/fav_yuv.h).  The input may be any of these: a 10-bit 4:2:2 video in is a 10-bit 4:2:2 video
+//   out.  Above 8 bits the stylised frame's floats reach the samples unquantised.  Not both of -y4m_format and -y4m_pixel_format.
 //   Refused: -backward with -input_y4m, -continue_with other than 1 with either, `-` with more than one -streams entry.
 // -scene_cut <T> (0, default: off; T in (0, 1]; only with -estimate_flow 1): restart the recurrence at scene changes.  Frame i, in
 //   processing order, is a CUT when score(frame i-1, frame i) > T, the score being fav_scene_change_rgb8's block-histogram distance
@@ -57,7 +60,8 @@
 //   leaves through the sink changes: the state that is warped into the next frame stays the network's full-colour output, and
 //   -temporal_eval_file keeps measuring that state.  The matrix of the luminance is the output format's with -output_y4m, else BT.709 from
 //   720 rows on and BT.601 below; -y4m_matrix bt601|bt709 overrides either.  Works through all three sinks (-png_encoder gpu | host,
-//   -output_y4m); with -png_encoder gpu the encode is the synchronous one whatever -png_overlap says.
+//   -output_y4m); with -png_encoder gpu the encode is the synchronous one whatever -png_overlap says.  Refused with a Y4M output that is
+//   4:2:2 or deeper than 8 bits: the colour transfer writes 8-bit 4:2:0 / 4:4:4 planes only.
 //   Refused: a value other than 0 / 1; -continue_with above 1 (it reloads the previous PNG as the recurrent state, and with this flag the
 //   PNG is not the state); at the first frame, stylised frames whose size is not the input's (sizes that are no multiples of 4).
 //   fav_stylize_vr and the `th` shim do not take the flag.
@@ -334,17 +338,51 @@ FrameIn load_frame_inputs(const Opt& o, const favp::Poll& poll, int i, bool firs
 
 // The format of a Y4M stream's frames.  from_header: what the input's header says (null: there is no Y4M input -- 4:2:0 with centre
 // siting, limited range, BT.709 from 720 rows on, else BT.601: the heuristic players use, Y4M carries no matrix); -y4m_matrix and
-// -y4m_range override either; -y4m_format sets the OUTPUT's sampling.  main has validated the three options.
-fav_yuv_format y4m_format_of(const Opt& o, const fav_yuv_format* from_header, int H, bool output)
+// -y4m_range override either; -y4m_format sets the OUTPUT's sampling, -y4m_pixel_format its sampling, siting and depth.  main has
+// validated the four options.
+bool y4m_pixel_format_layout(const std::string& tag, fav_yuv_layout* out);
+fav_yuv_layout y4m_layout_of(const Opt& o, const fav_yuv_layout* from_header, int H, bool output)
 {
-    fav_yuv_format f = from_header ? *from_header : fav_yuv_format{FAV_YUV_420, FAV_YUV_SITING_CENTER, H >= 720 ? FAV_YUV_BT709 : FAV_YUV_BT601, 0};
+    fav_yuv_layout f = from_header ? *from_header
+                                   : fav_yuv_layout{(uint32_t)sizeof(fav_yuv_layout), FAV_YUV_420, FAV_YUV_SITING_CENTER, H >= 720 ? FAV_YUV_BT709 : FAV_YUV_BT601, 0, 8};
     if (o.s("y4m_matrix") != "auto") f.matrix = o.s("y4m_matrix") == "bt709" ? FAV_YUV_BT709 : FAV_YUV_BT601;
     if (o.s("y4m_range") != "auto") f.full_range = o.s("y4m_range") == "full";
     if (output && !o.s("y4m_format").empty()) {
         f.chroma = o.s("y4m_format") == "444" ? FAV_YUV_444 : FAV_YUV_420;
         f.siting = o.s("y4m_format") == "420mpeg2" ? FAV_YUV_SITING_LEFT : FAV_YUV_SITING_CENTER;
+        f.depth = 8;
+    }
+    if (output && !o.s("y4m_pixel_format").empty()) {
+        fav_yuv_layout t;
+        y4m_pixel_format_layout(o.s("y4m_pixel_format"), &t);
+        f.chroma = t.chroma; f.siting = t.siting; f.depth = t.depth;
     }
     return f;
+}
+
+// -y4m_pixel_format: the C value of a Y4M header, read by the library's own header parser; false: not one of the accepted values
+const char* const Y4M_PIXEL_FORMATS = "420jpeg, 420mpeg2, 422, 444, or 420pN, 422pN, 444pN with N in 9, 10, 12, 14, 16";
+bool y4m_pixel_format_layout(const std::string& tag, fav_yuv_layout* out)
+{
+    if (tag.empty() || tag == "420" || tag.find(' ') != std::string::npos) return false;
+    const std::string line = "YUV4MPEG2 W2 H2 C" + tag + "\n";
+    fav_y4m_stream_header h;
+    if (fav_y4m_parse_stream_header_host(line.c_str(), line.size(), &h)) return false;
+    *out = h.layout;
+    return true;
+}
+
+// the C value of a layout, as the header will carry it
+std::string y4m_tag_of(const fav_yuv_layout& l)
+{
+    std::string t = l.chroma == FAV_YUV_444 ? "444" : l.chroma == FAV_YUV_422 ? "422" : l.depth > 8 ? "420" : l.siting == FAV_YUV_SITING_LEFT ? "420mpeg2" : "420jpeg";
+    return l.depth > 8 ? t + "p" + std::to_string(l.depth) : t;
+}
+// -original_colors 1 writes the planes of fav_stream_encode_yuv_colors: 8-bit 4:2:0 / 4:4:4
+bool y4m_colors_can_write(const fav_yuv_layout& l) { return l.depth == 8 && l.chroma != FAV_YUV_422; }
+std::string y4m_colors_refusal(const fav_yuv_layout& l)
+{
+    return "-original_colors 1 cannot be combined with the output format " + y4m_tag_of(l) + ": the colour transfer writes 8-bit 4:2:0 / 4:4:4 planes only";
 }
 
 struct Counters { std::atomic<long long> png_bytes{0}, cpu_loaders_us{0}, cpu_writers_us{0}, cpu_writer_sync_us{0}; };
@@ -429,7 +467,7 @@ struct DevInputs {
     static constexpr int N = 4;
     struct Set { fav::dev_ptr<uint8_t> frame, cert, yuv; fav::dev_ptr<float> bw, fw; fav::event_h up; };
     Set set[N];
-    int W = 0, H = 0; size_t yuv_bytes = 0; fav_yuv_format fmt_in{};        // -input_y4m: a frame's planes and their format
+    int W = 0, H = 0; size_t yuv_bytes = 0; fav_yuv_layout fmt_in{};        // -input_y4m: a frame's planes and their format
     DevInputs() { for (Set& s : set) s.up = favl::event_create(hipEventDisableTiming | hipEventDisableSystemFence); }
     void alloc(int W_, int H_)
     {
@@ -448,7 +486,7 @@ struct DevInputs {
         const size_t n = (size_t)W * H; const Set& dv = set[k];
         if (f.yuv) {          // -input_y4m: the planes travel, and become the P6 payload on the device, still on the upload queue
             hipMemcpyAsync(dv.yuv.get(), f.yuv, yuv_bytes, hipMemcpyHostToDevice, copy);
-            check(fav_yuv_to_rgb8(dv.yuv.get(), W, H, &fmt_in, dv.frame.get(), copy), "fav_yuv_to_rgb8");
+            check(fav_yuv_layout_to_rgb8(dv.yuv.get(), W, H, &fmt_in, dv.frame.get(), copy), "fav_yuv_layout_to_rgb8");
         } else hipMemcpyAsync(dv.frame.get(), f.frame, n * 3, hipMemcpyHostToDevice, copy);
         if (f.bw) hipMemcpyAsync(dv.bw.get(), f.bw, n * 8, hipMemcpyHostToDevice, copy);
         if (f.fw) hipMemcpyAsync(dv.fw.get(), f.fw, n * 8, hipMemcpyHostToDevice, copy);
@@ -544,7 +582,7 @@ protected:
     void wait_host_event(hipEvent_t e) const { if (wait_event_sleeping(e) != hipSuccess) die("GPU error while stylising a frame"); }
     // -original_colors into a PNG: no stream format names the matrix, so it is the Y4M header parser's rule for the frame's height
     // (-y4m_matrix overrides)
-    int png_colors_matrix() const { return y4m_format_of(env.o, nullptr, Ho, false).matrix; }
+    int png_colors_matrix() const { return y4m_layout_of(env.o, nullptr, Ho, false).matrix; }
     SinkEnv env; const bool colors; fav_stream* fs = nullptr; int Wo = 0, Ho = 0;
 };
 
@@ -684,23 +722,25 @@ private:
 };
 
 // -output_y4m: no PNG at all.  The planes are written by the frame's last kernel straight into a pinned output slot
-// (fav_stream_encode_yuv), the host learns of them through an event on the compute queue -- the event-ordered path of
+// (fav_stream_encode_yuv_layout), the host learns of them through an event on the compute queue -- the event-ordered path of
 // -png_encoder host, minus its download -- and ONE writer thread write()s the slots in frame order.
 class Y4mOut : public Sink {
 public:
     // in_header, in_fmt: those of -input_y4m, null without it
-    Y4mOut(const SinkEnv& e, const fav_y4m_header* in_header, const fav_yuv_format* in_fmt) : Sink(e), in_header_(in_header), in_fmt_(in_fmt) {}
+    Y4mOut(const SinkEnv& e, const fav_y4m_stream_header* in_header, const fav_yuv_layout* in_fmt) : Sink(e), in_header_(in_header), in_fmt_(in_fmt) {}
     size_t setup(fav_stream* fs_, int Wo_, int Ho_) override
     {
         fs = fs_; Wo = Wo_; Ho = Ho_;
         // the stream's header: the input's (or F25:1 Ip A1:1) with the stylised frames' size and the output's format
         const std::string path = env.o.s("output_y4m");
-        fav_y4m_header oh;
+        fav_y4m_stream_header oh;
         if (in_header_) oh = *in_header_;
         else { memset(&oh, 0, sizeof oh); oh.fps_num = 25; oh.fps_den = 1; oh.interlace = 'p'; oh.aspect_num = oh.aspect_den = 1; }
-        fmt_out = y4m_format_of(env.o, in_fmt_, Ho, true);
-        oh.W = Wo; oh.H = Ho; oh.fmt = fmt_out;
-        bytes = fav_yuv_frame_bytes(Wo, Ho, &fmt_out);
+        fmt_out = y4m_layout_of(env.o, in_fmt_, Ho, true);
+        if (colors && !y4m_colors_can_write(fmt_out)) die(y4m_colors_refusal(fmt_out));      // (the input's format: known only now)
+        fmt_colors = fav_yuv_format{fmt_out.chroma, fmt_out.siting, fmt_out.matrix, fmt_out.full_range};
+        oh.W = Wo; oh.H = Ho; oh.layout = fmt_out;
+        bytes = fav_yuv_layout_frame_bytes(Wo, Ho, &fmt_out);
         if (!bytes) die(std::string("-output_y4m: ") + fav_last_error());
         if (path != "-") mkdirs_for(path);
         if (!writer.open(path)) die("Could not open " + path + " for writing");
@@ -709,8 +749,8 @@ public:
     }
     void after_frame(int, uint8_t* hb, const uint8_t* frame) override      // into the pinned slot
     {
-        if (colors) check(fav_stream_encode_yuv_colors(fs, frame, &fmt_out, hb, bytes, env.st), "fav_stream_encode_yuv_colors");      // the output format's matrix
-        else check(fav_stream_encode_yuv(fs, &fmt_out, hb, bytes, env.st), "fav_stream_encode_yuv");
+        if (colors) check(fav_stream_encode_yuv_colors(fs, frame, &fmt_colors, hb, bytes, env.st), "fav_stream_encode_yuv_colors");      // the output format's matrix
+        else check(fav_stream_encode_yuv_layout(fs, &fmt_out, hb, bytes, env.st), "fav_stream_encode_yuv_layout");
     }
     void hand_off(int k, uint8_t*) override { hipEventRecord(ev_done[k].get(), env.st); }    // nothing to download: the planes are in host memory when this event fires
     void wait(int k) override { wait_host_event(ev_done[k].get()); }
@@ -728,8 +768,8 @@ public:
         };
     }
 private:
-    const fav_y4m_header* in_header_; const fav_yuv_format* in_fmt_;
-    favy::Writer writer; fav_yuv_format fmt_out{}; size_t bytes = 0;
+    const fav_y4m_stream_header* in_header_; const fav_yuv_layout* in_fmt_;
+    favy::Writer writer; fav_yuv_layout fmt_out{}; fav_yuv_format fmt_colors{}; size_t bytes = 0;
     fav::event_h ev_done[2] = {host_event(), host_event()};
 };
 
@@ -806,9 +846,9 @@ StreamRun::StreamRun(const Opt& o_, const fav_flow_opts_ex3& fo, fav_net* net_, 
     if (y4m_in) {
         const std::string err = y4m_reader.open(o.s("input_y4m"));
         if (!err.empty()) die(err);
-        const fav_y4m_header& h = y4m_reader.header();
-        dev.fmt_in = y4m_format_of(o, &h.fmt, h.H, false);
-        dev.yuv_bytes = fav_yuv_frame_bytes(h.W, h.H, &dev.fmt_in);
+        const fav_y4m_stream_header& h = y4m_reader.header();
+        dev.fmt_in = y4m_layout_of(o, &h.layout, h.H, false);
+        dev.yuv_bytes = fav_yuv_layout_frame_bytes(h.W, h.H, &dev.fmt_in);
         if (!dev.yuv_bytes) die(std::string("-input_y4m: ") + fav_last_error());
         y4m_reader.set_frame_bytes(dev.yuv_bytes);
     }
@@ -1077,7 +1117,7 @@ int main(int argc, char** argv)
            // additive
            {"forward_flow_pattern", ""}, {"structure", "1"}, {"warp_border", "stn"}, {"poll_timeout", "3600"}, {"poll_settle", "1.0"},
            {"png_level", "1"}, {"png_encoder", "gpu"}, {"png_overlap", "0"}, {"writers", "0"}, {"timing", "0"}, {"temporal_eval_file", ""}, {"seed", "1"}, {"precision", "fp32"},
-           {"input_y4m", ""}, {"output_y4m", ""}, {"y4m_matrix", "auto"}, {"y4m_range", "auto"}, {"y4m_format", ""},
+           {"input_y4m", ""}, {"output_y4m", ""}, {"y4m_matrix", "auto"}, {"y4m_range", "auto"}, {"y4m_format", ""}, {"y4m_pixel_format", ""},
            {"scene_cut", "0"}, {"scene_cut_log", ""}, {"original_colors", "0"},
            {"estimate_flow", "0"}, {"flow_levels", "0"},      // (the other -flow_* flags: favl::add_flow_flags below)
            {"streams", ""}, {"gpus", "1"}, {"force_dist", "0"}, {"dry_run", "0"}, {"shared_gpu", "0"}, {"pin_workers", "1"},
@@ -1110,8 +1150,15 @@ int main(int argc, char** argv)
     if (o.s("y4m_range") != "auto" && o.s("y4m_range") != "limited" && o.s("y4m_range") != "full") die("-y4m_range must be auto, limited or full, not '" + o.s("y4m_range") + "'");
     if (!o.s("y4m_format").empty() && o.s("y4m_format") != "420jpeg" && o.s("y4m_format") != "420mpeg2" && o.s("y4m_format") != "444")
         die("-y4m_format must be 420jpeg, 420mpeg2 or 444, not '" + o.s("y4m_format") + "'");
+    fav_yuv_layout asked{};                                                                                  // -y4m_pixel_format: what it names
+    if (!o.s("y4m_pixel_format").empty()) {
+        if (!o.s("y4m_format").empty()) die("-y4m_format and -y4m_pixel_format both set the output's format: give one of them");
+        if (!y4m_pixel_format_layout(o.s("y4m_pixel_format"), &asked))
+            die(std::string("-y4m_pixel_format must be ") + Y4M_PIXEL_FORMATS + ", not '" + o.s("y4m_pixel_format") + "'");
+    }
     // -original_colors: refused here, before any device is opened
     if (o.s("original_colors") != "0" && o.s("original_colors") != "1") die("-original_colors must be 0 or 1, not '" + o.s("original_colors") + "'");
+    if (o.s("original_colors") == "1" && y4m_out && !o.s("y4m_pixel_format").empty() && !y4m_colors_can_write(asked)) die(y4m_colors_refusal(asked));
     if (o.s("original_colors") == "1" && o.i("continue_with") > 1)
         die("-original_colors 1 cannot be combined with -continue_with " + o.s("continue_with") +
             ": -continue_with reloads the previous PNG as the recurrent state, and with -original_colors 1 the PNG is not the state");
@@ -1211,6 +1258,9 @@ int main(int argc, char** argv)
         for (size_t k = 0; k < mine.size(); ++k) {
             js += std::string(k ? ", " : "") + "{\"name\": " + favl::json_str(mine[k]);
             for (const char* po : path_opts) js += std::string(", \"") + po + "\": " + favl::json_str(named ? favl::subst_stream(o.s(po), mine[k]) : o.s(po));
+            // the output stream's C tag; with a Y4M input and neither format option it is the input's, which only its header says
+            if (y4m_out) js += ", \"output_y4m_tag\": " + favl::json_str(y4m_in && o.s("y4m_format").empty() && o.s("y4m_pixel_format").empty()
+                                                                            ? std::string("input") : y4m_tag_of(y4m_layout_of(o, nullptr, 0, true)));
             js += "}";
         }
         fprintf(favl::msg(), "%s]}\n", js.c_str());

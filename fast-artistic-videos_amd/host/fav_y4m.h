@@ -1,6 +1,7 @@
 // fav_y4m.h -- the YUV4MPEG2 streams of fav_stylize (-input_y4m / -output_y4m): a sequential reader that several loader threads may
-// share, and a writer.  The header grammar is libfav's (fav_y4m_parse_header_host / fav_y4m_format_header_host, include/fav.h); this file
-// only moves bytes: `YUV4MPEG2 ...\n`, then per frame `FRAME[ params]\n` and fav_yuv_frame_bytes bytes.  PATH `-` is stdin / stdout.
+// share, and a writer.  The header grammar is libfav's (fav_y4m_parse_stream_header_host / fav_y4m_format_stream_header_host,
+// include/fav_yuv.h: every layout); this file only moves bytes: `YUV4MPEG2 ...\n`, then per frame `FRAME[ params]\n` and
+// fav_yuv_layout_frame_bytes bytes.  PATH `-` is stdin / stdout.
 #pragma once
 #include <fcntl.h>
 #include <unistd.h>
@@ -57,10 +58,10 @@ public:
             if (k == 0) return path + ": the stream ends inside its header";
             if (line[n] == '\n') break;
         }
-        if (fav_y4m_parse_header_host(line, n, &hdr_)) return path + ": " + fav_last_error();
+        if (fav_y4m_parse_stream_header_host(line, n, &hdr_)) return path + ": " + fav_last_error();
         return "";
     }
-    const fav_y4m_header& header() const { return hdr_; }
+    const fav_y4m_stream_header& header() const { return hdr_; }
     void set_frame_bytes(size_t n) { frame_bytes_ = n; }
     // Frame `index` (1, 2, ...) into dst.  Callers on several threads each wait for their turn, so the indices must be asked for without
     // gaps.  END: the stream ended at a frame boundary (also for every later index); TRUNCATED: it ended inside this frame.
@@ -95,7 +96,7 @@ public:
     Status failure() const { std::lock_guard<std::mutex> l(m_); return failure_; }
 private:
     int fd_ = -1;
-    fav_y4m_header hdr_{};
+    fav_y4m_stream_header hdr_{};
     size_t frame_bytes_ = 0;
     mutable std::mutex m_;
     std::condition_variable turn_;
@@ -112,10 +113,10 @@ public:
         fd_ = path == "-" ? 1 : ::open(path.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0666);
         return fd_ >= 0;
     }
-    bool header(const fav_y4m_header& h)
+    bool header(const fav_y4m_stream_header& h)
     {
         char buf[FAV_Y4M_MAX_HEADER + 1];
-        const int n = fav_y4m_format_header_host(&h, buf, sizeof buf);
+        const int n = fav_y4m_format_stream_header_host(&h, buf, sizeof buf);
         return n > 0 && write_full(fd_, buf, (size_t)n);
     }
     bool frame(const uint8_t* planes, size_t n) { return write_full(fd_, "FRAME\n", 6) && write_full(fd_, planes, n); }

@@ -75,6 +75,8 @@ def lib() -> C.CDLL:
     L.fav_flow_pairs_workspace_bytes_ex3.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.fav_yuv_frame_bytes.restype = C.c_size_t
     L.fav_yuv_frame_bytes.argtypes = [C.c_int, C.c_int, C.c_void_p]
+    L.fav_yuv_layout_frame_bytes.restype = C.c_size_t
+    L.fav_yuv_layout_frame_bytes.argtypes = [C.c_int, C.c_int, C.c_void_p]
     L.fav_scene_change_workspace_bytes.restype = C.c_size_t
     L.fav_scene_change_workspace_bytes.argtypes = []
     _lib = L
@@ -112,6 +114,11 @@ EXPORTS = [
     "fav_scene_change_workspace_bytes", "fav_scene_change_rgb8",
     "fav_color_transfer_rgb8", "fav_color_transfer_yuv", "fav_stream_encode_png_colors", "fav_stream_encode_yuv_colors",
     "fav_structure_f32",
+]
+# include/fav_yuv.h: 4:2:2 and 9- to 16-bit Y4M frames
+EXPORTS_YUV = [
+    "fav_yuv_layout_frame_bytes", "fav_yuv_layout_to_rgb8", "fav_rgb8_to_yuv_layout", "fav_rgb_f32_to_yuv_layout",
+    "fav_stream_encode_yuv_layout", "fav_y4m_parse_stream_header_host", "fav_y4m_format_stream_header_host",
 ]
 
 
@@ -782,6 +789,11 @@ class Stream:
         """fav_stream_encode_png_colors: the current stylised frame's luminance on the colours of frame_u8_hwc, as the bytes of a PNG file"""
         _check(lib().fav_stream_encode_png_colors(self.h, _p(frame_u8_hwc), matrix, _p(out), C.c_size_t(out.numel()), _p(nbytes), _stream()))
 
+    def encode_yuv_layout_into(self, out, layout: "YuvLayout", capacity: Optional[int] = None):
+        """fav_stream_encode_yuv_layout: the current stylised frame as planes of any layout (above 8 bits: unquantised floats in),
+        enqueued on the current stream (no sync).  out: a u8 tensor; capacity in bytes"""
+        _check(lib().fav_stream_encode_yuv_layout(self.h, C.byref(layout), _p(out), C.c_size_t(out.numel() if capacity is None else capacity), _stream()))
+
     def encode_yuv_colors_into(self, frame_u8_hwc, out, fmt: "YuvFormat", capacity: Optional[int] = None):
         """fav_stream_encode_yuv_colors: the planes of that image (the transfer takes fmt's matrix), enqueued on the current stream (no sync)"""
         _check(lib().fav_stream_encode_yuv_colors(self.h, _p(frame_u8_hwc), C.byref(fmt), _p(out),
@@ -931,6 +943,84 @@ def y4m_format_header(h: Y4mHeader) -> bytes:
     """fav_y4m_format_header_host (no device needed): the header line, newline included"""
     buf = C.create_string_buffer(1100)
     n = lib().fav_y4m_format_header_host(C.byref(h), buf, C.c_size_t(len(buf)))
+    if n <= 0:
+        _check(n if n else -1)
+    return buf.raw[:n]
+
+
+# ---- include/fav_yuv.h: every layout (4:2:0, 4:2:2, 4:4:4 at 8, 9, 10, 12, 14, 16 bits); planes travel as flat u8 tensors of
+# fav_yuv_layout_frame_bytes BYTES (a sample above 8 bits is two of them, little-endian) at any byte offset
+YUV_422 = 2
+
+
+class YuvLayout(C.Structure):
+    """fav_yuv_layout"""
+    _fields_ = [("struct_bytes", C.c_uint32), ("chroma", C.c_int), ("siting", C.c_int), ("matrix", C.c_int), ("full_range", C.c_int),
+                ("depth", C.c_int)]
+
+    def __repr__(self):
+        return (f"YuvLayout(chroma={self.chroma}, siting={self.siting}, matrix={self.matrix}, full_range={self.full_range}, "
+                f"depth={self.depth})")
+
+
+class Y4mStreamHeader(C.Structure):
+    """fav_y4m_stream_header"""
+    _fields_ = [("W", C.c_int), ("H", C.c_int), ("fps_num", C.c_int), ("fps_den", C.c_int), ("aspect_num", C.c_int),
+                ("aspect_den", C.c_int), ("interlace", C.c_int), ("layout", YuvLayout), ("xtags", C.c_char * 1024)]
+
+
+def yuv_layout(chroma: int = YUV_420, siting: int = YUV_SITING_CENTER, matrix: int = YUV_BT601, full_range: bool = False, depth: int = 8,
+               struct_bytes: Optional[int] = None) -> YuvLayout:
+    return YuvLayout(C.sizeof(YuvLayout) if struct_bytes is None else struct_bytes, chroma, siting, matrix, int(full_range), depth)
+
+
+def yuv_layout_frame_bytes(w: int, h: int, layout: YuvLayout) -> int:
+    """bytes of one frame's payload; raises on a bad size or field"""
+    n = lib().fav_yuv_layout_frame_bytes(w, h, C.byref(layout))
+    if n == 0:
+        raise FavError(lib().fav_last_error().decode(errors="replace"))
+    return n
+
+
+def yuv_layout_to_rgb8(yuv, w: int, h: int, layout: YuvLayout, out=None):
+    """fav_yuv_layout_to_rgb8: a frame's planes (flat u8 tensor of its bytes) -> [H][W][3] u8.  out: a u8 tensor of at least H*W*3 elements"""
+    torch = _torch()
+    assert yuv.dtype == torch.uint8 and yuv.is_contiguous() and yuv.numel() >= yuv_layout_frame_bytes(w, h, layout)
+    if out is None:
+        out = torch.empty((h, w, 3), dtype=torch.uint8, device=yuv.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= h * w * 3
+    _check(lib().fav_yuv_layout_to_rgb8(_p(yuv), w, h, C.byref(layout), _p(out), _stream()))
+    return out
+
+
+def rgb_to_yuv_layout(img, layout: YuvLayout, out=None):
+    """fav_rgb8_to_yuv_layout for a u8 [H][W][3] tensor, fav_rgb_f32_to_yuv_layout for a float [3][H][W] tensor (depth 8: image.save's
+    quantisation in front; deeper: unquantised) -> the frame's planes, flat u8 of fav_yuv_layout_frame_bytes bytes"""
+    torch = _torch()
+    assert img.is_contiguous()
+    u8 = img.dtype == torch.uint8
+    h, w = (img.shape[0], img.shape[1]) if u8 else (img.shape[1], img.shape[2])
+    n = yuv_layout_frame_bytes(w, h, layout)
+    if out is None:
+        out = torch.empty(n, dtype=torch.uint8, device=img.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= n
+    if not u8:
+        _chk_f32(img, "img")
+    _check((lib().fav_rgb8_to_yuv_layout if u8 else lib().fav_rgb_f32_to_yuv_layout)(_p(img), w, h, C.byref(layout), _p(out), _stream()))
+    return out
+
+
+def y4m_parse_stream_header(line: bytes) -> Y4mStreamHeader:
+    """fav_y4m_parse_stream_header_host (no device needed); raises FavError with the library's message"""
+    h = Y4mStreamHeader()
+    _check(lib().fav_y4m_parse_stream_header_host(line, C.c_size_t(len(line)), C.byref(h)))
+    return h
+
+
+def y4m_format_stream_header(h: Y4mStreamHeader) -> bytes:
+    """fav_y4m_format_stream_header_host (no device needed): the header line, newline included"""
+    buf = C.create_string_buffer(1100)
+    n = lib().fav_y4m_format_stream_header_host(C.byref(h), buf, C.c_size_t(len(buf)))
     if n <= 0:
         _check(n if n else -1)
     return buf.raw[:n]

@@ -674,4 +674,6 @@ int fav_scene_change_rgb8(const uint8_t* prev_rgb_hwc, const uint8_t* cur_rgb_hw
 #ifdef __cplusplus
 }
 #endif
+/* 4:2:2 and 9- to 16-bit Y4M frames: one more record (fav_yuv_layout) and the entry points that take it */
+#include "fav_yuv.h"
 #endif /* FAV_H */
