@@ -294,6 +294,22 @@ extern "C" int fav_assemble_input_f32(const float* frame_rgb, const float* warpe
     return launch_assemble(frame_rgb, warped_rgb, cert, in7, H, W, static_cast<hipStream_t>(stream));
 }
 
+// the merged input assembly of the long-term priors on its own (kernels_longterm.hip)
+extern "C" int fav_long_term_input_f32(const uint8_t* frame_rgb_hwc, int n, const float* const* states, int Hs, int Ws,
+                                       const float* const* backward_flo, const float* const* cert, int border, int H, int W, int pad,
+                                       int fill_random, unsigned seed, unsigned index, float* in8_out, float* cert_out, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(n >= 1 && n <= FAV_LONG_TERM_MAX, "fav_long_term_input_f32: %d priors (1..%d)", n, FAV_LONG_TERM_MAX);
+    FAV_REQUIRE(frame_rgb_hwc && states && backward_flo && cert && in8_out, "fav_long_term_input_f32: null pointer");
+    FAV_REQUIRE(H > 0 && W > 0 && Hs > 0 && Ws > 0 && pad >= 0 && pad < H && pad < W, "fav_long_term_input_f32: needs H, W, Hs, Ws > 0 and 0 <= pad < H, W (pad %d, %dx%d)", pad, W, H);
+    FAV_REQUIRE(border == FAV_BORDER_STN || border == FAV_BORDER_CPU, "fav_long_term_input_f32: border mode %d", border);
+    for (int k = 0; k < n; ++k)
+        FAV_REQUIRE(states[k] && backward_flo[k] && cert[k], "fav_long_term_input_f32: null pointer for prior %d", k);
+    int rc = ensure_device(); if (rc) return rc;
+    return launch_longterm_prep(frame_rgb_hwc, n, states, Hs, Ws, backward_flo, cert, border, H, W, pad, in8_out, cert_out,
+                                static_cast<hipStream_t>(stream), fill_random, seed, index);
+}
+
 // left-to-right fp32 sum, bit-identical to `float s = 0; for (i) s += x[i];` (CMatrix::avg, CMatrix.h:1245-1251), evaluated
 // with the parallel parity-transducer scan of kernels_consistency.hip
 extern "C" int fav_sequential_sum_f32(const float* x, size_t n, float* sum_out, fav_hipstream_t stream)

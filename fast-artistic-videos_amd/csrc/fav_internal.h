@@ -300,6 +300,11 @@ int launch_prep_input(const uint8_t* frame_hwc, const float* prev_rgb, int Hs, i
                       const float* cert, int border, int H, int W, int pad, float* in8, hipStream_t st,
                       int fill_random = 0, unsigned seed = 0, unsigned index = 0, int* q0_out = nullptr);
 int launch_quantize_rgb8(const float* rgb_planar, uint8_t* out_hwc, int H, int W, hipStream_t st);
+// long-term priors (kernels_longterm.hip): launch_prep_input with K = 1..FAV_LONG_TERM_MAX priors merged per pixel; the three arrays are
+// HOST arrays of K device pointers (they travel in the kernel arguments); cert_out: the merged certainty [H][W] or null
+int launch_longterm_prep(const uint8_t* frame_hwc, int K, const float* const* states, int Hs, int Ws, const float* const* backward_flo,
+                         const float* const* cert, int border, int H, int W, int pad, float* in8, float* cert_out, hipStream_t st,
+                         int fill_random = 0, unsigned seed = 0, unsigned index = 0);
 // -scale_factor (kernels_scale.hip): image.scale(.., 'bicubic') [recalled].  launch_scale_prep: launch_prep_input for a frame without a
 // prior, resampled H x W -> Hs x Ws on the way (in8: [Hs+2*pad][Ws+2*pad][8]; the fill is keyed by the scaled grid);
 // launch_scale_planar: [C][Hs][Ws] -> [C][Hd][Wd] fp32

@@ -66,6 +66,12 @@ struct fav_stream {
     // host-mapped memory (everything enqueued before it has then finished), and a look-ahead into a slot waits ON THE HOST for the
     // sequence number of the buffers it holds (with NPREF slots and two frames of look-ahead that frame finished long ago: no wait)
     uint32_t* retired_host = nullptr; uint32_t retire_counter = 0;      // (a view into done_host's allocation, on its own 64-byte line)
+    // long-term priors (fav_stream_set_long_term): the configured distances (ascending, lt_dist[0] == 1) and the HISTORY, a ring of the
+    // last lt_dist[lt_n - 1] stylised frames and input frames -- entry of distance d: hist[(hist_head - (d - 1)) mod size], d <= hist_count
+    int lt_n = 0; int lt_dist[FAV_LONG_TERM_MAX] = {0, 0, 0, 0};
+    struct Hist { dev_ptr<float> state; dev_ptr<uint8_t> frame; bool has_frame = false; };      // (a state set from outside has no frame)
+    std::vector<Hist> hist; int hist_head = 0, hist_count = 0;
+    dev_ptr<uint8_t> lt_mask[FAV_LONG_TERM_MAX]; dev_ptr<float> lt_cert[FAV_LONG_TERM_MAX];      // per distance beyond the first (that one: mask, cert)
     hipStream_t last_st = nullptr; bool ran = false;       // the HIP stream of the last forward (forgotten by the destructor)
     ~fav_stream()
     {
@@ -163,10 +169,38 @@ static void state_writing_failed(fav_stream* s)
     swap_state_buffers(s);
 }
 
-static int stream_finish(fav_stream* s, float* out_rgb_f32, uint8_t* out_rgb8_hwc, hipStream_t st)
+// long-term priors: the current state, and the frame it was stylised from (null: a state set from outside), become the history's newest entry
+static int history_push(fav_stream* s, const uint8_t* frame, hipStream_t st)
+{
+    const int size = (int)s->hist.size();
+    s->hist_head = s->hist_count ? (s->hist_head + 1) % size : 0;
+    fav_stream::Hist& h = s->hist[s->hist_head];
+    FAV_HIP(hipMemcpyAsync(h.state.get(), s->state.get(), (size_t)3 * s->Ho * s->Wo * 4, hipMemcpyDeviceToDevice, st));
+    if (frame) FAV_HIP(hipMemcpyAsync(h.frame.get(), frame, (size_t)3 * s->H * s->W, hipMemcpyDeviceToDevice, st));
+    h.has_frame = frame != nullptr;
+    s->hist_count = std::min(s->hist_count + 1, size);
+    return FAV_OK;
+}
+
+static const fav_stream::Hist& history_at(const fav_stream* s, int distance)
+{
+    const int size = (int)s->hist.size();
+    return s->hist[((s->hist_head - (distance - 1)) % size + size) % size];
+}
+
+// how many of the configured distances, from the first, the history serves (with_frames: ... and holds the input frame of)
+static int history_available(const fav_stream* s, bool with_frames)
+{
+    int m = 0;
+    while (m < s->lt_n && s->lt_dist[m] <= s->hist_count && (!with_frames || history_at(s, s->lt_dist[m]).has_frame)) ++m;
+    return m;
+}
+
+static int stream_finish(fav_stream* s, const uint8_t* frame, float* out_rgb_f32, uint8_t* out_rgb8_hwc, hipStream_t st)
 {
     const size_t n = (size_t)s->Ho * s->Wo;
     s->has_state = true;
+    if (s->lt_n) { int rc = history_push(s, frame, st); if (rc) return rc; }
     if (out_rgb_f32) FAV_HIP(hipMemcpyAsync(out_rgb_f32, s->state.get(), 3 * n * 4, hipMemcpyDeviceToDevice, st));
     if (out_rgb8_hwc) return launch_quantize_rgb8(s->state.get(), out_rgb8_hwc, s->Ho, s->Wo, st);
     return FAV_OK;
@@ -179,6 +213,7 @@ extern "C" int fav_stream_first_frame(fav_stream* s, const uint8_t* frame_rgb_hw
     FAV_HIP(hipSetDevice(net_device(s->net)));
     hipStream_t st = static_cast<hipStream_t>(stream);
     ++s->frame_counter;
+    s->hist_count = 0;                                   // long-term priors: nothing from before a frame without a prior is warped in
     fav_net* fn = s->img_net ? s->img_net : s->net;      // image model: 3 content channels (the zero prior / mask planes meet zero weights)
     if (s->sHs) {      // core.lua:127-130,150-152: resampled before the model, the result resampled back to H x W (= Ho x Wo) into the state
         int rc = launch_scale_prep(frame_rgb_hwc, s->H, s->W, s->sHs, s->sWs, net_pad(s->net), s->scaled_in8.get(), st,
@@ -189,7 +224,7 @@ extern "C" int fav_stream_first_frame(fav_stream* s, const uint8_t* frame_rgb_hw
         rc = net_forward_padded(fn, s->scaled_in8.get(), s->sHs, s->sWs, s->scaled_out.get(), st);
         if (!rc) rc = launch_scale_planar(s->scaled_out.get(), s->state.get(), 3, s->sHo, s->sWo, s->Ho, s->Wo, st);
         if (rc) { state_writing_failed(s); return rc; }
-        return stream_finish(s, out_rgb_f32, out_rgb8_hwc, st);
+        return stream_finish(s, frame_rgb_hwc, out_rgb_f32, out_rgb8_hwc, st);
     }
     // the image model sees only the three content channels (core.lua:146): no fill there
     int rc = launch_prep_input(frame_rgb_hwc, nullptr, 0, 0, nullptr, nullptr, s->opts.border_mode, s->H, s->W, net_pad(s->net), s->in8.get(), st,
@@ -198,7 +233,7 @@ extern "C" int fav_stream_first_frame(fav_stream* s, const uint8_t* frame_rgb_hw
     s->last_st = st; s->ran = true; s->last_scaled = false;
     rc = state_for_writing(s, st); if (rc) return rc;
     rc = net_forward_padded(fn, s->in8.get(), s->H, s->W, s->state.get(), st); if (rc) { state_writing_failed(s); return rc; }
-    return stream_finish(s, out_rgb_f32, out_rgb8_hwc, st);
+    return stream_finish(s, frame_rgb_hwc, out_rgb_f32, out_rgb8_hwc, st);
 }
 
 extern "C" int fav_stream_set_image_net(fav_stream* s, fav_net* image_net)
@@ -280,7 +315,7 @@ static int stream_next(fav_stream* s, const uint8_t* frame, const float* bw, con
     rc = state_for_writing(s, st); if (rc) return rc;       // (the prior was read from the previous state above)
     { TraceRange tr_net("fav:network"); rc = net_forward_padded(s->net, s->in8.get(), s->H, s->W, s->state.get(), st); }
     if (rc) { state_writing_failed(s); return rc; }
-    return stream_finish(s, out_f32, out_u8, st);
+    return stream_finish(s, frame, out_f32, out_u8, st);
 }
 
 extern "C" int fav_stream_next_frame_cert(fav_stream* s, const uint8_t* frame_rgb_hwc, const float* backward_flo,
@@ -453,6 +488,8 @@ extern "C" int fav_stream_set_state(fav_stream* s, const float* state_rgb_f32, f
     if (s->png_pending) { FAV_HIP(hipStreamWaitEvent(static_cast<hipStream_t>(stream), s->png_done.get(), 0)); s->png_pending = false; }
     FAV_HIP(hipMemcpyAsync(s->state.get(), state_rgb_f32, (size_t)3 * s->Ho * s->Wo * 4, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
     s->has_state = true;
+    s->hist_count = 0;                                   // long-term priors: the history restarts with this state (it has no frame)
+    if (s->lt_n) return history_push(s, nullptr, static_cast<hipStream_t>(stream));
     return FAV_OK;
 }
 
@@ -615,3 +652,115 @@ extern "C" int fav_stream_get_padded_input_f32(const fav_stream* s, float* out, 
 }
 
 extern "C" const uint8_t* fav_stream_last_mask(const fav_stream* s) { return s ? s->mask.get() : nullptr; }
+
+// ================================================================================================
+// long-term priors (include/fav_long_term.h; DESIGN.md, "Long-term priors")
+// ================================================================================================
+extern "C" int fav_stream_set_long_term(fav_stream* s, const int* distances_host, int n)
+{
+    FAV_REQUIRE(s, "fav_stream_set_long_term: null stream");
+    FAV_REQUIRE(n >= 0 && n <= FAV_LONG_TERM_MAX, "fav_stream_set_long_term: %d distances (0 = off, at most %d, distance 1 included)", n, FAV_LONG_TERM_MAX);
+    FAV_REQUIRE(n == 0 || distances_host, "fav_stream_set_long_term: null distances");
+    for (int k = 0; k < n; ++k) {
+        if (k == 0) FAV_REQUIRE(distances_host[0] == 1, "fav_stream_set_long_term: the first distance is %d, it must be 1", distances_host[0]);
+        else FAV_REQUIRE(distances_host[k] > distances_host[k - 1], "fav_stream_set_long_term: distance %d follows %d (strictly ascending)", distances_host[k], distances_host[k - 1]);
+        FAV_REQUIRE(distances_host[k] <= FAV_LONG_TERM_MAX_DISTANCE, "fav_stream_set_long_term: distance %d is larger than the supported maximum of %d", distances_host[k], FAV_LONG_TERM_MAX_DISTANCE);
+    }
+    FAV_HIP(hipSetDevice(net_device(s->net)));
+    // everything new first: the stream keeps what it has when an allocation fails
+    std::vector<fav_stream::Hist> hist(n ? distances_host[n - 1] : 0);
+    dev_ptr<uint8_t> mask[FAV_LONG_TERM_MAX]; dev_ptr<float> cert[FAV_LONG_TERM_MAX];
+    const size_t px = (size_t)s->H * s->W;
+    const char* what = "fav_stream_set_long_term: history";
+    for (auto& h : hist)
+        if (dev_alloc(h.state, (size_t)3 * s->Ho * s->Wo, what) || dev_alloc(h.frame, 3 * px, what)) return FAV_EHIP;
+    for (int k = 1; k < n; ++k)
+        if (dev_alloc(mask[k], px, what) || dev_alloc(cert[k], px, what)) return FAV_EHIP;
+    s->hist = std::move(hist);                          // (freeing the old buffers waits for the frames that still read them)
+    for (int k = 0; k < FAV_LONG_TERM_MAX; ++k) { s->lt_mask[k] = std::move(mask[k]); s->lt_cert[k] = std::move(cert[k]); s->lt_dist[k] = k < n ? distances_host[k] : 0; }
+    s->lt_n = n; s->hist_head = 0; s->hist_count = 0;
+    // the state the stream already has starts the history, as fav_stream_set_state would (no queue is given here: behind everything the device has been given)
+    if (n && s->has_state) {
+        FAV_HIP(hipDeviceSynchronize());
+        FAV_HIP(hipMemcpy(s->hist[0].state.get(), s->state.get(), (size_t)3 * s->Ho * s->Wo * 4, hipMemcpyDeviceToDevice));
+        s->hist[0].has_frame = false; s->hist_count = 1;
+    }
+    return FAV_OK;
+}
+
+extern "C" int fav_stream_long_term_available(const fav_stream* s) { return s ? history_available(s, false) : 0; }
+
+extern "C" int fav_stream_next_frame_flows_lt(fav_stream* s, const uint8_t* frame_rgb_hwc, int m, const float* const* backward_flo,
+                                              const float* const* forward_flo, int use_structure, float* out_rgb_f32, uint8_t* out_rgb8_hwc,
+                                              fav_hipstream_t stream)
+{
+    FAV_REQUIRE(s && frame_rgb_hwc && backward_flo && forward_flo, "fav_stream_next_frame_flows_lt: null argument");
+    FAV_REQUIRE(s->lt_n > 0, "fav_stream_next_frame_flows_lt: long-term priors are off (fav_stream_set_long_term)");
+    const int avail = history_available(s, false);
+    FAV_REQUIRE(m >= 1 && m <= avail, "fav_stream_next_frame_flows_lt: flows of %d distances, the history serves %d of the %d configured", m, avail, s->lt_n);
+    for (int k = 0; k < m; ++k)
+        FAV_REQUIRE(backward_flo[k] && forward_flo[k], "fav_stream_next_frame_flows_lt: null flow for distance %d", s->lt_dist[k]);
+    for (auto& pf : s->pref)
+        FAV_REQUIRE(!pf.valid, "fav_stream_next_frame_flows_lt: a look-ahead mask (fav_stream_prefetch_mask) is pending; the long-term path does not consume it");
+    FAV_REQUIRE(s->has_state, "fav_stream_next_frame_flows_lt: no previous stylised frame");
+    FAV_REQUIRE(s->opts.occlusions_min_filter <= MIN_FILTER_RMAX, "fav_stream_next_frame_flows_lt: window %d unsupported", s->opts.occlusions_min_filter);
+    FAV_HIP(hipSetDevice(net_device(s->net)));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    {
+        TraceRange tr_mask("fav:long-term masks + assemble");
+        // the 4-argument structure map depends on THIS frame alone (launch_structure reads nothing else): once for all distances
+        const float* structure = nullptr; const float* avg = nullptr;
+        if (use_structure) { int rc = launch_structure(frame_rgb_hwc, s->W, s->H, s->ws.get(), s->ws_bytes, &structure, &avg, st); if (rc) return rc; }
+        const float* states[FAV_LONG_TERM_MAX]; const float* certs[FAV_LONG_TERM_MAX];
+        for (int k = 0; k < m; ++k) {
+            uint8_t* mask = k ? s->lt_mask[k].get() : s->mask.get();        // (fav_stream_last_mask stays the distance-1 mask)
+            float* cert = k ? s->lt_cert[k].get() : s->cert.get();
+            int rc = launch_check_cert(backward_flo[k], forward_flo[k], structure, avg, mask, s->opts.invert_occlusion, s->opts.fix_occlusions,
+                                       s->opts.border_mode, s->opts.occlusions_min_filter, cert, s->H, s->W, st);
+            if (rc) return rc;
+            states[k] = history_at(s, s->lt_dist[k]).state.get(); certs[k] = cert;
+        }
+        ++s->frame_counter;
+        int rc = launch_longterm_prep(frame_rgb_hwc, m, states, s->Ho, s->Wo, backward_flo, certs, s->opts.border_mode, s->H, s->W, net_pad(s->net),
+                                      s->in8.get(), nullptr, st, s->opts.fill_random, s->opts.seed, s->frame_counter);
+        if (rc) return rc;
+    }
+    return stream_next(s, frame_rgb_hwc, backward_flo[0], s->mask.get(), out_rgb_f32, out_rgb8_hwc, st, true, true);
+}
+
+static size_t lt_flow_bytes(const fav_stream* s) { return ((size_t)s->H * s->W * 8 + 255) / 256 * 256; }
+
+extern "C" size_t fav_stream_long_term_workspace_bytes(const fav_stream* s, const fav_flow_opts_ex3* opts_host)
+{
+    if (!s || s->lt_n == 0) { set_error("fav_stream_long_term_workspace_bytes: long-term priors are off (fav_stream_set_long_term)"); return 0; }
+    const size_t pairs = fav_flow_pairs_workspace_bytes_ex3(s->W, s->H, s->lt_n, opts_host);      // (0: a bad option or size, with its message)
+    return pairs ? (size_t)2 * s->lt_n * lt_flow_bytes(s) + pairs : 0;
+}
+
+extern "C" int fav_stream_next_frame_estimate_lt(fav_stream* s, const uint8_t* frame_rgb_hwc, const fav_flow_opts_ex3* opts_host, int use_structure,
+                                                 void* workspace, size_t workspace_bytes, float* out_rgb_f32, uint8_t* out_rgb8_hwc,
+                                                 fav_hipstream_t stream)
+{
+    FAV_REQUIRE(s && frame_rgb_hwc && workspace, "fav_stream_next_frame_estimate_lt: null argument");
+    FAV_REQUIRE(s->lt_n > 0, "fav_stream_next_frame_estimate_lt: long-term priors are off (fav_stream_set_long_term)");
+    const int m = history_available(s, true);
+    FAV_REQUIRE(m >= 1, "fav_stream_next_frame_estimate_lt: the history holds no previous frame (after fav_stream_set_state the first frame takes "
+                        "fav_stream_next_frame_estimate_ex3, which is given one)");
+    for (auto& pf : s->pref)
+        FAV_REQUIRE(!pf.valid, "fav_stream_next_frame_estimate_lt: a look-ahead mask (fav_stream_prefetch_mask) is pending; the long-term path does not consume it");
+    const size_t need = fav_stream_long_term_workspace_bytes(s, opts_host);
+    if (!need) return FAV_EINVAL;
+    FAV_REQUIRE(workspace_bytes >= need, "fav_stream_next_frame_estimate_lt: the workspace holds %zu bytes, fav_stream_long_term_workspace_bytes = %zu", workspace_bytes, need);
+    FAV_REQUIRE(((uintptr_t)workspace & 255) == 0, "fav_stream_next_frame_estimate_lt: the workspace is not 256-byte aligned");
+    const size_t F = lt_flow_bytes(s);
+    char* base = static_cast<char*>(workspace);
+    const uint8_t* prev[FAV_LONG_TERM_MAX]; const uint8_t* cur[FAV_LONG_TERM_MAX]; float* bw[FAV_LONG_TERM_MAX]; float* fw[FAV_LONG_TERM_MAX];
+    for (int k = 0; k < m; ++k) {
+        prev[k] = history_at(s, s->lt_dist[k]).frame.get(); cur[k] = frame_rgb_hwc;
+        bw[k] = reinterpret_cast<float*>(base + (size_t)2 * k * F); fw[k] = reinterpret_cast<float*>(base + (size_t)(2 * k + 1) * F);
+    }
+    const size_t off = (size_t)2 * s->lt_n * F;
+    int rc = fav_flow_pairs_rgb8_ex3(prev, cur, m, s->W, s->H, opts_host, bw, fw, base + off, workspace_bytes - off, stream);
+    if (rc) return rc;
+    return fav_stream_next_frame_flows_lt(s, frame_rgb_hwc, m, bw, fw, use_structure, out_rgb_f32, out_rgb8_hwc, stream);
+}

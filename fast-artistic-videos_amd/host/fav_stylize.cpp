@@ -55,6 +55,14 @@
 //   -create_inconsistent, a value outside [0, 1].
 // -scene_cut_log <path> (only with -scene_cut): one line per frame, `index total score cut` (cut = 0 | 1; the first frame is
 //   `index 0 0 0`), written when the frame is decided.
+// -long_term <d[,d...]> (empty, default: off; only with -estimate_flow 1): LONG-TERM PRIORS.  The list names the distances beyond 1,
+//   ascending, each in 2..16, at most three: -long_term 2,4 warps the stylised frames i-1, i-2 and i-4 to frame i, and every pixel takes
+//   the nearest of them in which it was visible (Ruder et al. 2016, section 4.2; include/fav_long_term.h, DESIGN.md "Long-term priors"): what a
+//   moving object uncovers continues from before it was covered.  The frames and stylised frames further back live in the library's
+//   history (fav_stream_set_long_term); each distance costs one more pair of flows per frame, estimated in the same batched call, and the
+//   -flow_* flags, the certainty options and -structure apply to every distance alike.  A frame without a prior (the first one, a
+//   -scene_cut) restarts the history: frame i after a restart at r uses the distances d <= i - r.  -temporal_eval_file keeps measuring
+//   distance 1.  Refused: without -estimate_flow 1 (flows from files exist for distance 1 only), with -create_inconsistent, a malformed list.
 // -original_colors <0|1> (0, default): 1 keeps the INPUT frame's colours and takes only the luminance of the stylised frame (Gatys et al.,
 //   "Preserving color in neural artistic style transfer"; the arithmetic is in include/fav.h and DESIGN.md, "Original colours").  Only what
 //   leaves through the sink changes: the state that is warped into the next frame stays the network's full-colour output, and
@@ -812,6 +820,7 @@ private:
     int Wo = 0, Ho = 0;                      // size of the stylised frames: the network's output (H x W when both are multiples of 4)
     DevInputs dev;
     fav::dev_ptr<void> d_flow_ws; size_t flow_ws_bytes = 0;
+    std::vector<int> long_term; bool lt_frame_seen = false;      // -long_term: {1, d...} (empty: off) | the library's history holds the previous FRAME
     fav::dev_ptr<float> d_prev, d_cur; std::vector<double> temporal;      // -temporal_eval_file
     SceneCut scene;
     // continue_with > 1: the previous stylised PNG as the recurrent state, rW x rH
@@ -835,6 +844,23 @@ private:
     std::chrono::steady_clock::time_point t_begin;
     double setup_s = 0;
 };
+
+// -long_term: the list of distances beyond 1 -> {1, d...}; false: malformed (not ascending integers in 2..16, more than three, empty items)
+static bool parse_long_term(const std::string& v, std::vector<int>& out)
+{
+    out.assign(1, 1);
+    if (v.empty()) { out.clear(); return true; }
+    for (size_t a = 0; a <= v.size();) {
+        const size_t b = std::min(v.find(',', a), v.size());
+        const std::string item = v.substr(a, b - a);
+        if (item.empty() || item.size() > 2 || item.find_first_not_of("0123456789") != std::string::npos) return false;
+        const int d = atoi(item.c_str());
+        if (d <= out.back() || d > FAV_LONG_TERM_MAX_DISTANCE || (int)out.size() >= FAV_LONG_TERM_MAX) return false;
+        out.push_back(d);
+        a = b + 1;
+    }
+    return true;
+}
 
 StreamRun::StreamRun(const Opt& o_, const fav_flow_opts_ex3& fo, fav_net* net_, fav_net* net_img_, int nwriters)
     : o(o_), flow_opts(fo), net(net_), net_img(net_img_), estimate(o.i("estimate_flow") != 0), fused_check(estimate || !o.s("forward_flow_pattern").empty()),
@@ -910,6 +936,8 @@ void StreamRun::setup(const FrameIn& cur, int i)
         die("-original_colors 1: the stylised frames (" + std::to_string(Wo) + "x" + std::to_string(Ho) + ") are larger than the input frames (" + std::to_string(W) + "x" +
             std::to_string(H) + "): there are no original colours for the added pixels; use a size whose sides are multiples of 4");
     if (net_img) check(fav_stream_set_image_net(s, net_img), "fav_stream_set_image_net");
+    parse_long_term(o.s("long_term"), long_term);      // (validated in main)
+    if (!long_term.empty()) check(fav_stream_set_long_term(s, long_term.data(), (int)long_term.size()), "-long_term");
     if (o.d("scale_factor") != 1.0) {          // img:view(1, 3, H * f, W * f) (core.lua:130) needs whole numbers
         const double f = o.d("scale_factor"), hs = H * f, ws = W * f;
         if (std::fabs(hs - std::round(hs)) > 1e-9 * hs || std::fabs(ws - std::round(ws)) > 1e-9 * ws || hs < 0.5 || ws < 0.5 || hs > 1e6 || ws > 1e6) {
@@ -935,6 +963,8 @@ void StreamRun::setup(const FrameIn& cur, int i)
     if (scene.on) scene.alloc();
     if (estimate) {
         flow_ws_bytes = fav_flow_pairs_workspace_bytes_ex3(W, H, 1, &flow_opts);      // room for both flows at once: the batch of one
+        // -long_term: the flows of every distance and the batch of as many pairs; it also serves the batch of one after -continue_with
+        if (flow_ws_bytes && !long_term.empty()) flow_ws_bytes = std::max(flow_ws_bytes, fav_stream_long_term_workspace_bytes(s, &flow_opts));
         if (!flow_ws_bytes) die(std::string("-estimate_flow: ") + fav_last_error());
         d_flow_ws = favl::dev_alloc<void>(flow_ws_bytes);
         if (!cur.single) {                       // -continue_with: the frame before the first one is read as well, into the set "before" dset
@@ -983,6 +1013,10 @@ void StreamRun::enqueue_network(FrameIn& cur, int i, uint8_t* d_out8)
     if (teval && !cur.single) check(fav_stream_get_state(fs.get(), d_prev.get(), st), "fav_stream_get_state");
     if (cur.single) {
         check(fav_stream_first_frame(fs.get(), dc.frame.get(), nullptr, d_out8, st), "fav_stream_first_frame");       // core:203-204
+    } else if (estimate && lt_frame_seen) {
+        // -long_term: the previous frames are in the library's history; the flows of every distance land at the head of the workspace
+        check(fav_stream_next_frame_estimate_lt(fs.get(), dc.frame.get(), &flow_opts, structure, d_flow_ws.get(), flow_ws_bytes, nullptr, d_out8, st),
+              "fav_stream_next_frame_estimate_lt");
     } else if (estimate) {
         // the previous frame in processing order is still in the device set before this one: with one frame of look-ahead the
         // uploads only ever touch the set after it
@@ -993,11 +1027,13 @@ void StreamRun::enqueue_network(FrameIn& cur, int i, uint8_t* d_out8)
     } else {
         check(fav_stream_next_frame_cert(fs.get(), dc.frame.get(), dc.bw.get(), dc.cert.get(), nullptr, d_out8, st), "fav_stream_next_frame_cert");   // core:206-208
     }
+    const bool lt_ran = estimate && lt_frame_seen && !cur.single;      // (distance 1's backward flow is then the workspace's first field)
+    lt_frame_seen = !long_term.empty();
     if (teval) {                                     // fav.lua:128-151 (third number)
         double tl = 0.0;
         if (!cur.single) {
             check(fav_stream_get_state(fs.get(), d_cur.get(), st), "fav_stream_get_state");
-            check(fav_temporal_loss_host(d_prev.get(), d_cur.get(), dc.bw.get(), fused_check ? fav_stream_last_mask(fs.get()) : dc.cert.get(), H, W, border, &tl, st), "fav_temporal_loss_host");
+            check(fav_temporal_loss_host(d_prev.get(), d_cur.get(), lt_ran ? static_cast<const float*>(d_flow_ws.get()) : dc.bw.get(), fused_check ? fav_stream_last_mask(fs.get()) : dc.cert.get(), H, W, border, &tl, st), "fav_temporal_loss_host");
         }
         temporal.push_back(tl);
     }
@@ -1118,7 +1154,7 @@ int main(int argc, char** argv)
            {"forward_flow_pattern", ""}, {"structure", "1"}, {"warp_border", "stn"}, {"poll_timeout", "3600"}, {"poll_settle", "1.0"},
            {"png_level", "1"}, {"png_encoder", "gpu"}, {"png_overlap", "0"}, {"writers", "0"}, {"timing", "0"}, {"temporal_eval_file", ""}, {"seed", "1"}, {"precision", "fp32"},
            {"input_y4m", ""}, {"output_y4m", ""}, {"y4m_matrix", "auto"}, {"y4m_range", "auto"}, {"y4m_format", ""}, {"y4m_pixel_format", ""},
-           {"scene_cut", "0"}, {"scene_cut_log", ""}, {"original_colors", "0"},
+           {"scene_cut", "0"}, {"scene_cut_log", ""}, {"original_colors", "0"}, {"long_term", ""},
            {"estimate_flow", "0"}, {"flow_levels", "0"},      // (the other -flow_* flags: favl::add_flow_flags below)
            {"streams", ""}, {"gpus", "1"}, {"force_dist", "0"}, {"dry_run", "0"}, {"shared_gpu", "0"}, {"pin_workers", "1"},
            // internal (set by the launcher for its workers)
@@ -1174,6 +1210,15 @@ int main(int argc, char** argv)
             die("-scene_cut " + sc + " needs -estimate_flow 1: with flows from files the look-ahead has already started a frame's mask when the cut is known");
         if (T > 0.0 && o.f("create_inconsistent")) die("-scene_cut " + sc + " cannot be combined with -create_inconsistent: no frame has a prior there");
         if (!o.s("scene_cut_log").empty() && T == 0.0) die("-scene_cut_log needs -scene_cut: without it no frame is measured");
+    }
+    if (!o.s("long_term").empty()) {      // -long_term: priors from frames further back than the last
+        const std::string lt = o.s("long_term");
+        std::vector<int> d;
+        if (!parse_long_term(lt, d))
+            die("-long_term must list the distances beyond 1: ascending whole numbers in 2.." + std::to_string(FAV_LONG_TERM_MAX_DISTANCE) + ", at most " +
+                std::to_string(FAV_LONG_TERM_MAX - 1) + ", separated by commas (e.g. 2,4), not '" + lt + "'");
+        if (!estimate) die("-long_term " + lt + " needs -estimate_flow 1: flows from files exist for distance 1 only");
+        if (o.f("create_inconsistent")) die("-long_term " + lt + " cannot be combined with -create_inconsistent: no frame has a prior there");
     }
     favl::validate_flow_flags(o.v, estimate, "-estimate_flow 1");
     const fav_flow_opts_ex3 flow_opts = favl::flow_opts_of(o.v);

@@ -79,6 +79,15 @@ def lib() -> C.CDLL:
     L.fav_yuv_layout_frame_bytes.argtypes = [C.c_int, C.c_int, C.c_void_p]
     L.fav_scene_change_workspace_bytes.restype = C.c_size_t
     L.fav_scene_change_workspace_bytes.argtypes = []
+    L.fav_stream_long_term_workspace_bytes.restype = C.c_size_t
+    L.fav_stream_long_term_workspace_bytes.argtypes = [C.c_void_p, C.c_void_p]
+    L.fav_stream_long_term_available.restype = C.c_int
+    L.fav_stream_long_term_available.argtypes = [C.c_void_p]
+    L.fav_stream_set_long_term.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    L.fav_long_term_input_f32.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.fav_stream_next_frame_flows_lt.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.fav_stream_next_frame_estimate_lt.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -119,6 +128,13 @@ EXPORTS = [
 EXPORTS_YUV = [
     "fav_yuv_layout_frame_bytes", "fav_yuv_layout_to_rgb8", "fav_rgb8_to_yuv_layout", "fav_rgb_f32_to_yuv_layout",
     "fav_stream_encode_yuv_layout", "fav_y4m_parse_stream_header_host", "fav_y4m_format_stream_header_host",
+]
+
+
+# include/fav_long_term.h: long-term priors
+EXPORTS_LONG_TERM = [
+    "fav_long_term_input_f32", "fav_stream_set_long_term", "fav_stream_long_term_available", "fav_stream_next_frame_flows_lt",
+    "fav_stream_long_term_workspace_bytes", "fav_stream_next_frame_estimate_lt",
 ]
 
 
@@ -222,6 +238,33 @@ def assemble(frame_rgb, warped_rgb=None, cert=None):
     out = torch.empty((7, h, w), dtype=torch.float32, device=frame_rgb.device)
     _check(lib().fav_assemble_input_f32(_p(frame_rgb), _p(warped_rgb), _p(cert), _p(out), h, w, _stream()))
     return out
+
+
+LONG_TERM_MAX, LONG_TERM_MAX_DISTANCE = 4, 16
+
+
+def _ptr_array(ts):
+    """a HOST array of device pointers, one per tensor"""
+    return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def long_term_input(frame_u8_hwc, states, backward_flos, certs, border: int = BORDER_STN, pad: int = 0, fill_random: bool = False,
+                    seed: int = 0, index: int = 0, want_cert: bool = True):
+    """fav_long_term_input_f32: the network input of a frame from K = len(states) priors in ascending distance (states [3][Hs][Ws],
+    backward_flos [H][W][2], certs [H][W] eroded certainty) -> (padded input [H + 2 pad][W + 2 pad][8], merged certainty [H][W] | None)"""
+    torch = _torch()
+    h, w = frame_u8_hwc.shape[0], frame_u8_hwc.shape[1]
+    for t in list(states) + list(backward_flos) + list(certs):
+        _chk_f32(t, "long_term_input: every state, flow and certainty")
+    if not (len(states) == len(backward_flos) == len(certs)) or any(t.shape != states[0].shape for t in states) or \
+            any(tuple(t.shape) != (h, w, 2) for t in backward_flos) or any(tuple(t.shape) != (h, w) for t in certs):
+        raise FavError("long_term_input: K states of one size, K flows [H][W][2] and K certainties [H][W]")
+    hs, ws = (states[0].shape[1], states[0].shape[2]) if states else (0, 0)
+    out = torch.empty((h + 2 * pad, w + 2 * pad, 8) if 0 <= pad else (0,), dtype=torch.float32, device=frame_u8_hwc.device)
+    cert = torch.empty((h, w), dtype=torch.float32, device=frame_u8_hwc.device) if want_cert else None
+    _check(lib().fav_long_term_input_f32(_p(frame_u8_hwc), len(states), _ptr_array(states), hs, ws, _ptr_array(backward_flos), _ptr_array(certs),
+                                         border, h, w, pad, 1 if fill_random else 0, seed, index, _p(out), _p(cert), _stream()))
+    return out, cert
 
 
 def conv2d(x, weight, bias=None, stride=1, pad=0, gamma=None, beta=None, eps=1e-5, relu=False):
@@ -743,6 +786,43 @@ class Stream:
         _check(lib().fav_stream_next_frame_estimate_ex3(self.h, _p(frame_u8_hwc), _p(prev_frame_u8_hwc), C.byref(o), 1 if use_structure else 0,
                                                        _p(bw), _p(fw), _p(ws), C.c_size_t(nb), _p(f), _p(u), _stream()))
         return f, u, bw, fw
+
+    def set_long_term(self, distances):
+        """fav_stream_set_long_term: long-term priors from the stylised frames at these distances (ascending, the first one 1; () = off)"""
+        d = [int(x) for x in distances]
+        _check(lib().fav_stream_set_long_term(self.h, (C.c_int * max(len(d), 1))(*d), len(d)))
+
+    def long_term_available(self) -> int:
+        return lib().fav_stream_long_term_available(self.h)
+
+    def next_frame_flows_lt(self, frame_u8_hwc, backward_flos, forward_flos, use_structure=False, want_f32=True, want_u8=False):
+        """fav_stream_next_frame_flows_lt: the next frame from the flows of the first len(backward_flos) configured distances"""
+        f, u = self._outs(frame_u8_hwc.device, want_f32, want_u8)
+        _check(lib().fav_stream_next_frame_flows_lt(self.h, _p(frame_u8_hwc), len(backward_flos), _ptr_array(backward_flos), _ptr_array(forward_flos),
+                                                    1 if use_structure else 0, _p(f), _p(u), _stream()))
+        return f, u
+
+    def long_term_workspace_bytes(self, **flow_opts) -> int:
+        o = _flow_opts_ex3(flow_opts)
+        n = lib().fav_stream_long_term_workspace_bytes(self.h, C.cast(C.pointer(o), C.c_void_p))
+        if n == 0:
+            _check(-1)
+        return n
+
+    def next_frame_estimate_lt(self, frame_u8_hwc, use_structure=False, want_f32=True, want_u8=False, workspace=None, **flow_opts):
+        """fav_stream_next_frame_estimate_lt: the next frame from the frames alone, flows to every distance the history serves.
+        Returns (f32, u8, backward_flos, forward_flos): the flows are views into the workspace, one pair per distance used."""
+        torch = _torch()
+        f, u = self._outs(frame_u8_hwc.device, want_f32, want_u8)
+        o = _flow_opts_ex3(flow_opts)
+        nb = self.long_term_workspace_bytes(**flow_opts)
+        ws = workspace if workspace is not None else torch.empty(nb, dtype=torch.uint8, device=frame_u8_hwc.device)
+        m = self.long_term_available()      # (right after set_state fewer distances hold a frame: their views are not written)
+        _check(lib().fav_stream_next_frame_estimate_lt(self.h, _p(frame_u8_hwc), C.byref(o), 1 if use_structure else 0, _p(ws), C.c_size_t(ws.numel()),
+                                                       _p(f), _p(u), _stream()))
+        fb = (self.H * self.W * 8 + 255) // 256 * 256
+        view = lambda j: ws[j * fb:j * fb + self.H * self.W * 8].view(torch.float32).view(self.H, self.W, 2)
+        return f, u, [view(2 * k) for k in range(m)], [view(2 * k + 1) for k in range(m)]
 
     def prefetch_mask(self, frame_u8_hwc, backward_flo, forward_flo, use_structure=False):
         _check(lib().fav_stream_prefetch_mask(self.h, _p(frame_u8_hwc), _p(backward_flo), _p(forward_flo),

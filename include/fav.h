@@ -441,6 +441,7 @@ int fav_stream_get_padded_input_f32(const fav_stream* s, float* out, fav_hipstre
 /* device pointer of the last certainty mask used (u8 [H][W], before the min filter) -- tests */
 const uint8_t* fav_stream_last_mask(const fav_stream* s);
 
+
 /* fp32 sum in index order with the rounding of every partial sum: bit-identical to `float s = 0; for (i) s += x[i];`, the
  * arithmetic of CMatrix::avg (consistencyChecker/CMatrix.h:1245-1251) that the 4-argument checker depends on.  Evaluated in
  * parallel (exact parity-transducer scan; kernels_consistency.hip).  x, sum_out: device pointers. */
@@ -676,4 +677,6 @@ int fav_scene_change_rgb8(const uint8_t* prev_rgb_hwc, const uint8_t* cur_rgb_hw
 #endif
 /* 4:2:2 and 9- to 16-bit Y4M frames: one more record (fav_yuv_layout) and the entry points that take it */
 #include "fav_yuv.h"
+/* long-term priors: a stream's history and the entries that merge the priors of several distances (fav_stylize -long_term) */
+#include "fav_long_term.h"
 #endif /* FAV_H */
