@@ -152,6 +152,7 @@ struct fav_vr {
     dev_ptr<float> equi_map;
     dev_ptr<float> last[6], prev[6], filt[6];
     bool have_last[6] = {}; bool have_prev = false;
+    bool set_prev[6] = {};                // blended faces written by fav_vr_set_f32 since create / the last finished frame
     dev_ptr<float> tmp_rot, tmp_warp, border, lfw, prior;
     dev_ptr<float> flow_lua, cert_tmp, cert, in8;
     dev_ptr<float> strip, equi, cube;
@@ -503,7 +504,7 @@ extern "C" int fav_vr_finish_frame(fav_vr* v, uint8_t* equi_rgb8_hwc, uint8_t* c
         rc = launch_vr_blend(S[f].get(), v->border.get(), v->grad[5].get(), v->anti_all.get(), v->prev[f].get(), v->n, st); if (rc) return rc;
     }
     v->have_prev = true;
-    for (int k = 0; k < 6; ++k) v->have_last[k] = false;
+    for (int k = 0; k < 6; ++k) v->have_last[k] = v->set_prev[k] = false;
     // :529-536 median filter of every blended face
     for (int f = 0; f < 6; ++f) {
         if (v->o.median_filter > 0) { rc = launch_vr_median(v->prev[f].get(), v->filt[f].get(), v->H, v->W, v->o.median_filter, st); if (rc) return rc; }
@@ -556,5 +557,25 @@ extern "C" int fav_vr_get_f32(const fav_vr* v, int which, int k, float* out_dev,
     else if (which == 5) { src = v->cert.get(); cnt = v->n; }
     FAV_REQUIRE(src && cnt, "fav_vr_get_f32: nothing of kind %d", which);
     FAV_HIP(hipMemcpyAsync(out_dev, src, cnt * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return FAV_OK;
+}
+
+// include/fav_vr_state.h.  which: 0 last_segments[k] (marked present, as a face the network wrote), 1 prev_last_segments[k] (six of them
+// since create / the last finished frame make a previous frame)
+extern "C" int fav_vr_set_f32(fav_vr* v, int which, int k, const float* in_dev, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(v && in_dev, "fav_vr_set_f32: null %s", v ? "pointer" : "handle");
+    FAV_REQUIRE(which == 0 || which == 1, "fav_vr_set_f32: kind %d cannot be written (0 raw face, 1 blended face)", which);
+    FAV_REQUIRE(k >= 0 && k < 6, "fav_vr_set_f32: face %d (0 .. 5)", k);
+    FAV_HIP(hipSetDevice(net_device(v->vid)));
+    float* dst = which == 0 ? v->last[k].get() : v->prev[k].get();
+    FAV_HIP(hipMemcpyAsync(dst, in_dev, 3 * v->n * sizeof(float), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    if (which == 0) v->have_last[k] = true;
+    else {
+        v->set_prev[k] = true;
+        bool all = true;
+        for (int f = 0; f < 6; ++f) all = all && v->set_prev[f];
+        if (all) v->have_prev = true;
+    }
     return FAV_OK;
 }

@@ -88,6 +88,7 @@ def lib() -> C.CDLL:
                                           C.c_int, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
     L.fav_stream_next_frame_flows_lt.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.fav_stream_next_frame_estimate_lt.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.fav_vr_set_f32.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -136,6 +137,8 @@ EXPORTS_LONG_TERM = [
     "fav_long_term_input_f32", "fav_stream_set_long_term", "fav_stream_long_term_available", "fav_stream_next_frame_flows_lt",
     "fav_stream_long_term_workspace_bytes", "fav_stream_next_frame_estimate_lt",
 ]
+# include/fav_vr_state.h: writing a VR object's faces
+EXPORTS_VR_STATE = ["fav_vr_set_f32"]
 
 
 def _check(rc: int) -> None:
@@ -1247,6 +1250,15 @@ class VR:
         out = torch.empty(shape, dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
         _check(lib().fav_vr_get_f32(self.h, which, k, _p(out), _stream()))
         return out
+
+    def set(self, which: int, k: int, tensor):
+        """fav_vr_set_f32: write raw face k of this frame (which = 0; six of them and finish_frame runs) or blended face k of the finished
+        frame (which = 1; six of them make a previous frame) from a contiguous f32 CUDA tensor [3][hplus][wplus]"""
+        torch = _torch()
+        if tensor is not None and not (tensor.is_cuda and tensor.dtype == torch.float32 and tensor.is_contiguous() and
+                                       tuple(tensor.shape) == (3, self.H, self.W)):
+            raise FavError(f"VR.set: the face must be a contiguous float32 CUDA tensor [3][{self.H}][{self.W}]")
+        _check(lib().fav_vr_set_f32(self.h, which, k, _p(tensor), _stream()))
 
 
 def _from_ptr_u8(ptr: int, n: int, device: int):

@@ -679,4 +679,6 @@ int fav_scene_change_rgb8(const uint8_t* prev_rgb_hwc, const uint8_t* cur_rgb_hw
 #include "fav_yuv.h"
 /* long-term priors: a stream's history and the entries that merge the priors of several distances (fav_stylize -long_term) */
 #include "fav_long_term.h"
+/* writing a fav_vr's faces (the counterpart of fav_vr_get_f32): tests of the post-processing, resuming a 360-degree run */
+#include "fav_vr_state.h"
 #endif /* FAV_H */

@@ -19,6 +19,16 @@ import numpy as np
 import oracle as O
 
 F = np.float32
+
+
+def warp(img, flow_lua):
+    """Every warp of this file is the reference's GPU kernel (utils.lua:141-145 -> stnbdhw/BilinearSamplerBDHW.cu), whose sum :103-106 is
+    an fp32 expression: oracle.warp "stn_f32", bit-identical to the reference's own kernel in both of its builds (tests/golden/warp_*.npz,
+    tests/test_cpu_oracle.py).  The sum in double rounded once ("stn") differs from it by one ulp in places -- also in the static masks,
+    warps of ones, that the certainty planes are selected from (tests/test_gpu_vr_post.py holds those planes to the bit)."""
+    return O.warp(img, flow_lua, "stn_f32")
+
+
 PROC_ORDER = [6, 1, 2, 5, 3, 4]          # fast_artistic_video_vr.lua:103 (file ids of modes 0..5)
 
 
@@ -207,10 +217,10 @@ class VRStylizer:
         hp, wp = hplus, wplus
         ones = np.ones((1, hp, wp), F)
         # fast_artistic_video_vr.lua:164-198
-        self.map_left = warp_map_left(hp, overlap_w, wp);   self.mask_left = O.warp(ones, self.map_left)
-        self.map_top = warp_map_top(wp, overlap_h, hp);     self.mask_top = O.warp(ones, self.map_top)
-        self.map_bottom = warp_map_bottom(wp, overlap_h, hp); self.mask_bottom = O.warp(ones, self.map_bottom)
-        self.map_right = warp_map_right(hp, overlap_w, wp); self.mask_right = O.warp(ones, self.map_right)
+        self.map_left = warp_map_left(hp, overlap_w, wp);   self.mask_left = warp(ones, self.map_left)
+        self.map_top = warp_map_top(wp, overlap_h, hp);     self.mask_top = warp(ones, self.map_top)
+        self.map_bottom = warp_map_bottom(wp, overlap_h, hp); self.mask_bottom = warp(ones, self.map_bottom)
+        self.map_right = warp_map_right(hp, overlap_w, wp); self.mask_right = warp(ones, self.map_right)
         s = ((self.mask_left + self.mask_right) + self.mask_top) + self.mask_bottom
         self.mask_all_div = np.maximum(s, F(1)); self.mask_all = np.minimum(s, F(1))
         gh, gw = overlap_h - 10, overlap_w - 10
@@ -245,7 +255,7 @@ class VRStylizer:
 
     # :239-302
     def _prior(self, i, mode, cert, flow_uv):
-        L, w = self.last, O.warp
+        L, w = self.last, warp
         d = self.mask_all_div
         border = np.zeros((3, self.hp, self.wp), F)
         if not self.inconsistent_border:
@@ -311,7 +321,7 @@ class VRStylizer:
 
     # blend_other_sides :454-509
     def _blend(self):
-        L, w, d = self.last, O.warp, self.mask_all_div
+        L, w, d = self.last, warp, self.mask_all_div
         g = self.g_all.astype(F); anti = (1.0 - self.g_all).astype(F)      # csub in double, then :type(dtype)
 
         def comb(a, b, c, e):
@@ -339,7 +349,7 @@ class VRStylizer:
         ovw = self.ow // 2 - rr; ovh = self.oh // 2 - rr
         if self.equi_map is not None:
             cat = np.concatenate([fs[0], fs[1], fs[2], fs[3], rotate180(fs[4]), rotate180(fs[5])], 2)
-            self.equi = O.warp(np.ascontiguousarray(cat), self.equi_map)
+            self.equi = warp(np.ascontiguousarray(cat), self.equi_map)
         crop = lambda t: t[:, ovh:self.hp - ovh, ovw:self.wp - ovw]
         self.cubemap = np.ascontiguousarray(np.concatenate(
             [crop(fs[3]), crop(fs[0]), rotate90(crop(fs[4])), rotate_minus90(crop(fs[5])), crop(fs[2]), crop(fs[1])], 2))
