@@ -154,6 +154,9 @@ struct fav_vr {
     bool have_last[6] = {}; bool have_prev = false;
     bool set_prev[6] = {};                // blended faces written by fav_vr_set_f32 since create / the last finished frame
     dev_ptr<float> tmp_rot, tmp_warp, border, lfw, prior;
+    // what the last face left for fav_vr_get_f32 kinds 6 and 7 and fav_vr_get_padded_input_f32 (include/fav_vr_state.h): `border` holds
+    // that face's border sum until fav_vr_finish_frame reuses it; last_prior is what went to launch_vr_prep (border, lfw or prior)
+    bool border_is_face = false, have_in8 = false; const float* last_prior = nullptr;
     dev_ptr<float> flow_lua, cert_tmp, cert, in8;
     dev_ptr<float> strip, equi, cube;
     int FH = 0, FW = 0;                   // filtered face size
@@ -369,9 +372,11 @@ static int vr_face(fav_vr* v, int i, const uint8_t* frame_rgb_hwc, const float* 
     int rc;
     if (temporal && cs.flow) FAV_REQUIRE(cs.fw, "%s: face %d needs the forward flow (forward_flo is NULL)", cs.who, i);
     fav_vr::Pending* ahead = take_pending(v, i, frame_rgb_hwc, backward_flo, cs.fw, temporal && cs.flow, cs.structure);
+    v->border_is_face = false; v->last_prior = nullptr;                          // (set again below once this face's are enqueued)
     if (single) {
         rc = launch_vr_prep(frame_rgb_hwc, nullptr, nullptr, v->img ? 0 : v->o.fill_random, v->o.seed, (unsigned)i, H, W, pad, v->in8.get(), st);
         if (rc) return rc;
+        v->have_in8 = true;
         rc = net_forward_padded(v->img ? v->img : v->vid, v->in8.get(), H, W, v->last[mode].get(), st); if (rc) return rc;
     } else {
         if (temporal) FAV_REQUIRE(backward_flo && (cs.flow || cs.cert_pgm) && v->have_prev, "%s: face %d needs the flow, the certainty and a finished previous frame", cs.who, i);
@@ -431,6 +436,7 @@ static int vr_face(fav_vr* v, int i, const uint8_t* frame_rgb_hwc, const float* 
         }
         // ---- run_next_image (core.lua:161-180)
         rc = launch_vr_prep(frame_rgb_hwc, prior, v->cert.get(), v->o.fill_random, v->o.seed, (unsigned)i, H, W, pad, v->in8.get(), st); if (rc) return rc;
+        v->border_is_face = true; v->last_prior = prior; v->have_in8 = true;
         rc = net_forward_padded(v->vid, v->in8.get(), H, W, v->last[mode].get(), st); if (rc) return rc;
     }
     v->have_last[mode] = true;
@@ -499,6 +505,8 @@ extern "C" int fav_vr_finish_frame(fav_vr* v, uint8_t* equi_rgb8_hwc, uint8_t* c
         {{0, 3, T}, {1, 2, L}, {2, 1, R}, {3, 0, B}},
     };
     int rc;
+    v->border_is_face = false;                                                   // the post-blend sums its borders in the same buffer
+    if (v->last_prior == v->border.get()) v->last_prior = nullptr;
     for (int f = 0; f < 6; ++f) {
         for (int q = 0; q < 4; ++q) { rc = add_border(v, S[plan[f][q].face].get(), plan[f][q].rot, plan[f][q].map, true, q == 0, st); if (rc) return rc; }
         rc = launch_vr_blend(S[f].get(), v->border.get(), v->grad[5].get(), v->anti_all.get(), v->prev[f].get(), v->n, st); if (rc) return rc;
@@ -544,6 +552,7 @@ extern "C" int fav_vr_output_sizes(const fav_vr* v, int* equi_w, int* equi_h, in
 // which: 0 last_segments[k] (this frame's raw faces), 1 prev_last_segments[k] (blended faces of the finished frame),
 //        2 median-filtered faces ([3][filt_h][filt_w]), 3 equirectangular float image, 4 cube-map float strip,
 //        5 the last face's certainty plane after border max and erosion ([H][W])
+//        6 the last face's border sum, 7 the prior its input was assembled from ([3][H][W]; include/fav_vr_state.h)
 extern "C" int fav_vr_get_f32(const fav_vr* v, int which, int k, float* out_dev, fav_hipstream_t stream)
 {
     FAV_REQUIRE(v && out_dev && k >= 0 && k < 6, "fav_vr_get_f32: bad argument");
@@ -555,6 +564,13 @@ extern "C" int fav_vr_get_f32(const fav_vr* v, int which, int k, float* out_dev,
     else if (which == 3) { src = v->equi.get(); cnt = v->equi ? 3 * (size_t)v->o.out_equi_w * v->o.out_equi_h : 0; }
     else if (which == 4) { src = v->cube.get(); cnt = v->cube ? 3 * (size_t)v->cube_h * v->cube_w : 0; }
     else if (which == 5) { src = v->cert.get(); cnt = v->n; }
+    else if (which == 6) {
+        FAV_REQUIRE(v->border_is_face, "fav_vr_get_f32: kind 6 (border sum): the last call on this handle was not a face with a prior");
+        src = v->border.get(); cnt = 3 * v->n;
+    } else if (which == 7) {
+        FAV_REQUIRE(v->last_prior, "fav_vr_get_f32: kind 7 (prior): the last call on this handle was not a face with a prior");
+        src = v->last_prior; cnt = 3 * v->n;
+    }
     FAV_REQUIRE(src && cnt, "fav_vr_get_f32: nothing of kind %d", which);
     FAV_HIP(hipMemcpyAsync(out_dev, src, cnt * sizeof(float), hipMemcpyDeviceToDevice, st));
     return FAV_OK;
@@ -577,5 +593,16 @@ extern "C" int fav_vr_set_f32(fav_vr* v, int which, int k, const float* in_dev, 
         for (int f = 0; f < 6; ++f) all = all && v->set_prev[f];
         if (all) v->have_prev = true;
     }
+    return FAV_OK;
+}
+
+// include/fav_vr_state.h: the input the network read for the last face, as it lies in the handle's own buffer
+extern "C" int fav_vr_get_padded_input_f32(const fav_vr* v, float* out_dev, fav_hipstream_t stream)
+{
+    FAV_REQUIRE(v && out_dev, "fav_vr_get_padded_input_f32: null %s", v ? "pointer" : "handle");
+    FAV_REQUIRE(v->have_in8, "fav_vr_get_padded_input_f32: no face has been assembled yet");
+    const int pad = net_pad(v->vid);
+    const size_t cnt = (size_t)(v->H + 2 * pad) * (v->W + 2 * pad) * 8;
+    FAV_HIP(hipMemcpyAsync(out_dev, v->in8.get(), cnt * sizeof(float), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
     return FAV_OK;
 }

@@ -89,6 +89,7 @@ def lib() -> C.CDLL:
     L.fav_stream_next_frame_flows_lt.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.fav_stream_next_frame_estimate_lt.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
     L.fav_vr_set_f32.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.fav_vr_get_padded_input_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -138,7 +139,7 @@ EXPORTS_LONG_TERM = [
     "fav_stream_long_term_workspace_bytes", "fav_stream_next_frame_estimate_lt",
 ]
 # include/fav_vr_state.h: writing a VR object's faces
-EXPORTS_VR_STATE = ["fav_vr_set_f32"]
+EXPORTS_VR_STATE = ["fav_vr_set_f32", "fav_vr_get_padded_input_f32"]
 
 
 def _check(rc: int) -> None:
@@ -1243,12 +1244,31 @@ class VR:
         _check(lib().fav_vr_finish_frame(self.h, _p(e), _p(c), _stream()))
         return e, c
 
-    def get(self, which: int, k: int = 0):
+    def get(self, which: int, k: int = 0, out=None):
+        """fav_vr_get_f32 into a new tensor, or into `out` (a contiguous float32 CUDA tensor of the kind's shape; a refusal leaves it as
+        it was)"""
         torch = _torch()
         shape = {0: (3, self.H, self.W), 1: (3, self.H, self.W), 2: (3, self.filt_h, self.filt_w),
-                 3: (3, self.equi_h, self.equi_w), 4: (3, self.cube_h, self.cube_w), 5: (self.H, self.W)}[which]
-        out = torch.empty(shape, dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
+                 3: (3, self.equi_h, self.equi_w), 4: (3, self.cube_h, self.cube_w), 5: (self.H, self.W),
+                 6: (3, self.H, self.W), 7: (3, self.H, self.W)}[which]       # 6: the last face's border sum, 7: its prior
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape):
+            raise FavError(f"VR.get: out must be a contiguous float32 CUDA tensor {list(shape)}")
         _check(lib().fav_vr_get_f32(self.h, which, k, _p(out), _stream()))
+        return out
+
+    def last_padded_input(self, out=None):
+        """fav_vr_get_padded_input_f32: [H + 2p][W + 2p][8] network input of the last face as the network read it (p = Net.input_pad,
+        eighth channel zero), copied device to device"""
+        torch = _torch()
+        p = self.net.input_pad()
+        shape = (self.H + 2 * p, self.W + 2 * p, 8)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=f"cuda:{self.net.device}")
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == shape):
+            raise FavError(f"VR.last_padded_input: out must be a contiguous float32 CUDA tensor {list(shape)}")
+        _check(lib().fav_vr_get_padded_input_f32(self.h, _p(out), _stream()))
         return out
 
     def set(self, which: int, k: int, tensor):

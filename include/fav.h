@@ -499,7 +499,7 @@ int fav_vr_finish_frame(fav_vr* v, uint8_t* equi_rgb8_hwc, uint8_t* cubemap_rgb8
 int fav_vr_output_sizes(const fav_vr* v, int* equi_w, int* equi_h, int* cube_w, int* cube_h, int* filtered_w, int* filtered_h);
 /* float views for tests: which = 0 this frame's raw face k, 1 blended face k, 2 median-filtered face k, 3 equirectangular
  * image, 4 cube-map strip, 5 the certainty plane of the last face after border max and erosion ([hplus][wplus]; k ignored)
- * (device to device copy) */
+ * (device to device copy); 6 the border sum and 7 the prior of the last face ([3][hplus][wplus]; k ignored): fav_vr_state.h */
 int fav_vr_get_f32(const fav_vr* v, int which, int k, float* out_dev, fav_hipstream_t stream);
 /* the static maps, computed on the host (no device needed): kind 0..3 = perspective map left/right/top/bottom
  * ([2][hplus][wplus], `overlap` = the crop along that axis), 4 = cube->equirectangular map ([2][out_h][out_w]) */
