@@ -413,7 +413,10 @@ int fav_stream_next_frame_estimate_ex3(fav_stream* s, const uint8_t* frame_rgb_h
 /* optional look-ahead: start computing the consistency mask of a FUTURE frame on an internal side stream (the mask
  * depends only on that frame and its two flows, not on the recurrent state), so the order-preserving 4-argument
  * structure pass overlaps the network of the current frame.  The inputs must already be complete on `stream`.  The next
- * fav_stream_next_frame_flow call with the same three pointers and mode consumes the prefetched mask. */
+ * fav_stream_next_frame_flow call with the same three pointers and mode consumes the prefetched mask.
+ * A look-ahead stays pending -- across fav_stream_first_frame, fav_stream_set_state and frames that do not match it, whose results it
+ * does not touch -- until it is consumed, until the fourth look-ahead after it takes its slot (four slots, dealt in turn), or until
+ * fav_stream_set_host_ordered drops it; the three buffers must stay unchanged for as long. */
 int fav_stream_prefetch_mask(fav_stream* s, const uint8_t* frame_rgb_hwc, const float* backward_flo,
                              const float* forward_flo, int use_structure, fav_hipstream_t stream);
 /* Host-ordered look-ahead (on != 0): fav_stream_prefetch_mask then records nothing on `stream` and nothing waits on it -- the CALLER
@@ -425,6 +428,8 @@ int fav_stream_prefetch_mask(fav_stream* s, const uint8_t* frame_rgb_hwc, const 
  * library's business in both modes: host-ordered, a look-ahead that would rewrite a mask / certainty buffer which frames still in the
  * caller's queue read waits on the host until those frames are through (a retire sequence number stored by a one-thread kernel in the
  * caller's queue; with up to two frames of look-ahead that is never a wait), so a caller may run any number of frames ahead.
+ * Every call, in either direction, drops all pending look-aheads (the frames they were for compute their masks inline) and must be made
+ * with the caller's queue drained: the retire bookkeeping starts anew, and knows nothing of frames enqueued in the other mode.
  * Default: off (event-ordered, fully asynchronous). */
 int fav_stream_set_host_ordered(fav_stream* s, int on);
 /* read / overwrite the recurrent state ([3][Ho][Wo] float RGB) -- for -continue_with */
@@ -438,7 +443,8 @@ int fav_stream_get_input_f32(const fav_stream* s, float* in7, fav_hipstream_t st
  * (0 when the model starts without a symmetric reflection padding): [H + 2p][W + 2p][8] fp32, channel 7 zero -- a device-to-device
  * copy of the stream's buffer.  Same preconditions and errors as fav_stream_get_input_f32 */
 int fav_stream_get_padded_input_f32(const fav_stream* s, float* out, fav_hipstream_t stream);
-/* device pointer of the last certainty mask used (u8 [H][W], before the min filter) -- tests */
+/* device pointer of the last certainty mask used (u8 [H][W], before the min filter) -- tests.  fav_stream_first_frame uses none and
+ * leaves the buffer as it was: its content is defined after a fav_stream_next_frame_* call only */
 const uint8_t* fav_stream_last_mask(const fav_stream* s);
 
 
